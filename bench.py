@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the path-tracing hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3|C2|C4|C5] [--no-secondary]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3|C2|C4|C5] [--dump-outputs DIR] [--full [--no-secondary]]
+
+A plain run sets up, warms up, times the K steps and prints the headline figures (value, ms_per_step, dtype, config); with
+--dump-outputs DIR it also writes the frame of the last timed step.  Everything else below -- one step alone, the frame on the
+host, the exchange check, the counters pass, roofline and issue figures, the CPU baselines and the `secondary` workloads --
+is measured only with --full.
 
 One "step" = one pass of the hot path over the whole workload: Renderer::sample of the
 lampshade scene in fog (BASELINE config C3, examples/volumetric_pathtrace_lampshade.rs) at
@@ -12,7 +17,7 @@ scaling is "strong".  `python bench.py --gpus N` starts its N ranks itself (fres
 torch.distributed.run, before this process has touched a GPU); under torch.distributed.run it is one of the
 ranks.  Rank 0 prints ONE JSON line.
 
-The headline (`value`, `config`, `roofline`, `cpu_baseline`) is C3.  At N = 1 the same line carries a `secondary`
+The headline (`value`, `config`, `roofline`, `cpu_baseline`) is C3.  With --full at N = 1 the same line carries a `secondary`
 array with the other BASELINE configurations (C2 cornell 512x512x64, C4 beam x point photon map 1024x1024x256 with
 1 M photons, C5 100k-triangle mesh in fog 2048x2048x1024) at 2 steps each, every entry with its own value, ms_per_step,
 roofline, issue figures and cpu_baseline.
@@ -287,9 +292,16 @@ def parse_args(argv):
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--spp", type=int, default=0)
     ap.add_argument("--photons", type=int, default=0, help="C4 only: photons shot per step (default: the config's 1,000,000)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline: one step alone, frame on the host, exchange check, counters pass, "
+                         "roofline / issue figures, CPU baselines and (N = 1, default workload and size) the `secondary` workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the frame of the last timed step to DIR/frame.npy ((h*w, 3) fp64 per-pixel means, as "
+                         "Renderer.sample_array returns them); a frame of more than 2^21 pixels as DIR/frame_sample.npy, a fixed "
+                         "seeded sample of 2^21 pixels in ascending pixel order")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline workload only (default at N = 1 with the default workload and "
-                                                               "size: C2, C4 and C5 follow at 2 steps each in `secondary`)")
+    ap.add_argument("--no-secondary", action="store_true", help="headline workload only (default with --full at N = 1 with the default "
+                                                               "workload and size: C2, C4 and C5 follow at 2 steps each in `secondary`)")
     ap.add_argument("--streams", type=int, default=0, choices=(0, 1, 2),
                     help="HIP streams the consecutive steps alternate between (2, the default: the start of a step overlaps the tail "
                          "of the previous one, as consecutive batches of an iterative render do; 1: strictly one launch at a time)")
@@ -362,8 +374,24 @@ class Exchange:
             self.comm.close()
 
 
-def measure(workload, args, steps, warmup, streams_opt, torch, dist, rank, local_rank, world, headline):
-    """Run one workload and return its fields of the JSON line (rank 0; None elsewhere)."""
+DUMP_MAX_PIXELS = 1 << 21   # 48 MiB of fp64 RGB: --dump-outputs writes larger frames as a seeded sample of this many pixels
+
+
+def dump_frame(out_dir, frame, width, height):
+    """--dump-outputs: what a caller of the timed path receives, the (h*w, 3) fp64 per-pixel means of the last timed step."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = frame.cpu().numpy().reshape(width * height, 3)
+    if width * height <= DUMP_MAX_PIXELS:
+        np.save(os.path.join(out_dir, "frame.npy"), img)
+    else:
+        pix = np.sort(np.random.default_rng(0).choice(width * height, size=DUMP_MAX_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "frame_sample.npy"), img[pix])
+
+
+def measure(workload, args, steps, warmup, streams_opt, torch, dist, rank, local_rank, world, headline, full=True):
+    """Run one workload and return its fields of the JSON line (rank 0; None elsewhere).  Without `full`: the timed steps and
+    the figures they give, nothing else."""
     import rpt_amd
     from rpt_amd import Renderer, scenes
     from rpt_amd.dist import photon_map_build_sharded
@@ -466,6 +494,30 @@ def measure(workload, args, steps, warmup, streams_opt, torch, dist, rank, local
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if headline and args.dump_outputs and rank == 0:
+        dump_frame(args.dump_outputs, frames[(step_no[0] - 1) % n_frames], width, height)   # before any later step reuses it
+
+    samples_per_step = width * height * spp
+    ms_per_step = elapsed / steps * 1e3
+    value = samples_per_step * steps / elapsed / 1e6
+    parallelism = f"tile-shard x{world}" + (f", frame {xchg.mode} on rank 0" if xchg is not None else "")
+    value_is = ("pipelined: consecutive steps alternate between two HIP streams and overlap (an iterative render's batches)"
+                if n_streams == 2 else "one stream, one launch at a time")
+    if not full:
+        if xchg is not None:
+            xchg.close()
+        if rank != 0:
+            return None
+        out = {"value": round(value, 3), "unit": "Msamples/s", "steps": steps, "warmup": warmup, "ms_per_step": round(ms_per_step, 3),
+               "ms_per_step_is": "pipelined over two HIP streams" if n_streams == 2 else "one stream", "dtype": "f64" if eps else "f32",
+               "config": {"workload": f"{WORKLOAD_NAMES[workload]} {width}x{height}x{spp}spp"
+                                      + (f", {n_photons} photons shot + map build + camera pass per step" if photon else ""),
+                          "scene": SCENE_FILES[workload], "parallelism": parallelism, "streams": n_streams, "value_is": value_is,
+                          "full_figures": "not measured in a plain run: --full adds wall_clock_s, the host-resident figures, roofline, "
+                                          "issue figures, cpu_baseline and the secondary workloads"}}
+        if xchg is not None and xchg.fallback:
+            out["exchange_fallback"] = f"rpt_gather_frame_device unavailable ({xchg.fallback}): torch.distributed sum-reduce used instead"
+        return out
 
     # ---- N > 1: is the assembled frame the frame?  Rank 0 renders the whole image alone (same seed: the render is a function of
     # scene, seed and pixel) and compares it with the last frame the exchange delivered, bit for bit (the exchange carries the
@@ -530,9 +582,6 @@ def measure(workload, args, steps, warmup, streams_opt, torch, dist, rank, local
         host_elapsed = (time.perf_counter() - t0) / n_host
         r.timing_mean()
 
-    samples_per_step = width * height * spp
-    ms_per_step = elapsed / steps * 1e3
-    value = samples_per_step * steps / elapsed / 1e6
     local_samples = samples_per_step / world          # tiles are sharded evenly over ranks
     n_owned_px = width * height / world
     pmc, pmc_path, pmc_current = pmc_profile(workload, width, height, spp, world, n_photons)
@@ -551,7 +600,6 @@ def measure(workload, args, steps, warmup, streams_opt, torch, dist, rank, local
     if host_elapsed is not None:
         out["value_host_resident"] = round(samples_per_step / host_elapsed / 1e6, 3)
         out["ms_per_step_host_resident"] = round(host_elapsed * 1e3, 3)
-    parallelism = f"tile-shard x{world}" + (f", frame {xchg.mode} on rank 0" if xchg is not None else "")
     if exchange_verified is not None:
         out["exchange_verified"] = exchange_verified   # rank 0's own render of the whole frame == the frame assembled from the ranks' tiles
     if xchg is not None and xchg.fallback:
@@ -626,8 +674,7 @@ def measure(workload, args, steps, warmup, streams_opt, torch, dist, rank, local
                      "parallelism": parallelism, "streams": n_streams, "rays_per_sample": round(rays_ps, 3),
                      "Mrays_per_s": round(value * rays_ps, 1), "chunk_spp": chunk_spp,
                      # the contract's `value` / `ms_per_step` are the pipelined figures; the walls SURVEY.md 8d defines are here too
-                     "value_is": ("pipelined: consecutive steps alternate between two HIP streams and overlap (an iterative render's batches)"
-                                  if n_streams == 2 else "one stream, one launch at a time"),
+                     "value_is": value_is,
                      "wall_clock_s": round(single_s, 5), "wall_clock_is": "one step alone, launch -> frame in HBM, one stream, synchronised"}
     if host_elapsed is not None:
         out["config"]["value_host_resident"] = out["value_host_resident"]
@@ -707,7 +754,7 @@ def main(argv=None):
         return dryrun_cpu(args, dist, rank, world, json_fd)
     torch.cuda.set_device(local_rank)
 
-    head = measure(args.workload, args, args.steps, args.warmup, args.streams, torch, dist, rank, local_rank, world, True)
+    head = measure(args.workload, args, args.steps, args.warmup, args.streams, torch, dist, rank, local_rank, world, True, args.full)
     out = None
     if rank == 0:
         out = {"metric": "Msamples/sec", "value": head.pop("value"), "unit": head.pop("unit"), "n_gpus": world,
@@ -715,7 +762,7 @@ def main(argv=None):
                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": head.pop("dtype"), "data": "synthetic"}
         out.update(head)
     default_run = args.workload == "C3" and not (args.width or args.height or args.spp or args.chunk_spp or args.emulate_shard)
-    if world == 1 and dist is None and default_run and not args.no_secondary:
+    if args.full and world == 1 and dist is None and default_run and not args.no_secondary:
         secondary = []
         for wl in ("C3eps", "C2", "C2eps", "C4", "C4eps", "C5", "C5G"):
             entry = measure(wl, args, 2, 1, 1, torch, None, rank, local_rank, world, False)

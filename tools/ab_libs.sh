@@ -4,7 +4,7 @@
 libs=$1; wls=$2; shift 2
 for l in $libs; do
   for w in $wls; do
-    RPT_LIB=$l timeout -k 10 300 python bench.py --workload $w --steps 3 --warmup 1 --streams 1 --no-cpu-baseline --no-secondary "$@" 2>/dev/null | python -c "
+    RPT_LIB=$l timeout -k 10 300 python bench.py --full --workload $w --steps 3 --warmup 1 --streams 1 --no-cpu-baseline --no-secondary "$@" 2>/dev/null | python -c "
 import json,sys
 for line in sys.stdin:
     try: d=json.loads(line)

@@ -8,7 +8,7 @@ import sys
 chunks = [int(v) for v in sys.argv[1:]] or [4, 8, 16, 32]
 for shard in (0, 8):
     for c in chunks:
-        out = subprocess.run([sys.executable, "bench.py", "--steps", "40", "--warmup", "4", "--no-cpu-baseline", "--no-secondary",
+        out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "40", "--warmup", "4", "--no-cpu-baseline", "--no-secondary",
                               "--chunk-spp", str(c), "--emulate-shard", str(shard)], capture_output=True, text=True)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:
