@@ -98,7 +98,7 @@ struct Mat4 {
     }
 };
 
-// ---- shapes (shape.rs, shape/*.rs).  One value type covers Sphere / Cube / Plane / Mesh and
+// ---- shapes (shape.rs, shape/*.rs).  One value type covers Sphere / Cube / Plane / Mesh / MonomialSurface and
 //      `Transformed<T>`; chained transforms left-multiply and never nest (shape.rs:232-285).
 struct Triangle {
     Vec3 v1, v2, v3, n1, n2, n3;
@@ -162,6 +162,12 @@ inline Shape plane(Vec3 normal, double value) {
     s.kind = RPT_SHAPE_PLANE;
     s.plane_normal = normal;
     s.plane_value = value;
+    return s;
+}
+inline Shape monomial_surface(double height, double exp) {  // shape.rs:292-295; y = height (x^2 + z^2)^2, x^2 + z^2 <= 1
+    Shape s;                                                 // (intersection hard-codes the exponent 4, as the reference does)
+    s.kind = RPT_SHAPE_MONOMIAL;
+    s.plane_normal = {height, exp, 0};
     return s;
 }
 inline Shape mesh(const std::vector<Triangle>& ts) {  // Mesh::new

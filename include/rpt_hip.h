@@ -33,10 +33,15 @@ extern "C" {
 typedef struct rpt_scene rpt_scene;
 
 /* Shape kinds: the closed set of `impl Shape` on the hot path
- * (src/shape/sphere.rs, cube.rs, plane.rs, mesh.rs; `Mesh = KdTree<Triangle>`). */
+ * (src/shape/sphere.rs, cube.rs, plane.rs, mesh.rs, monomial_surface.rs; `Mesh = KdTree<Triangle>`). */
 enum { RPT_SHAPE_SPHERE = 0, RPT_SHAPE_CUBE = 1, RPT_SHAPE_PLANE = 2, RPT_SHAPE_MESH = 3,
-       RPT_SHAPE_GROUP = 4 /* KdTree<Box<dyn Bounded>> of other shapes (src/kdtree.rs:103-146,
-                              examples/fractal_spheres.rs:45); children must be Bounded (no planes) */ };
+       RPT_SHAPE_GROUP = 4, /* KdTree<Box<dyn Bounded>> of other shapes (src/kdtree.rs:103-146,
+                              examples/fractal_spheres.rs:45); children must be Bounded (no planes) */
+       RPT_SHAPE_MONOMIAL = 5 /* MonomialSurface { height, exp } (src/shape/monomial_surface.rs, monomial_surface(height, exp)
+                                 src/shape.rs:292-295): y = height (x^2 + z^2)^2 for x^2 + z^2 <= 1, two-sided.  height is carried
+                                 in plane_normal[0], exp in plane_normal[1]; as in the reference, intersection hard-codes the
+                                 exponent 4 and ignores exp.  Bounded (a KdTree child may be one).  Not supported as a
+                                 Light::Object (MonomialSurface::sample) nor in scenes that are photon-mapped: RPT_ERR_UNSUPPORTED. */ };
 
 /* One `Box<dyn Shape>`: a unit primitive or mesh, optionally wrapped in `Transformed<T>`
  * (src/shape.rs:102-152).  `transform` is the composed homogeneous matrix M, row-major;
@@ -46,7 +51,7 @@ typedef struct rpt_shape_desc {
     int32_t kind;            /* RPT_SHAPE_*                                              */
     int32_t has_transform;   /* 0: bare shape, 1: Transformed<shape>                     */
     double transform[16];    /* row-major 4x4, used iff has_transform                    */
-    double plane_normal[3];  /* Plane { normal, value } (src/shape/plane.rs:7-13)        */
+    double plane_normal[3];  /* Plane { normal, value } (src/shape/plane.rs:7-13); RPT_SHAPE_MONOMIAL: height, exp, - */
     double plane_value;
     const double* tris;      /* n_tris * 18 doubles: v1 v2 v3 n1 n2 n3 (src/shape/mesh.rs:9-23) */
     uint64_t n_tris;
@@ -136,6 +141,11 @@ int rpt_render_sample_device(rpt_scene*, const rpt_camera*, const rpt_render_par
  * t = +inf, object = -1 on a miss.  normal may be NULL. */
 int rpt_intersect_batch(rpt_scene*, uint64_t n, const float* origins, const float* dirs, float* t,
                         int32_t* object, float* normal);
+/* The same query in the reference-epsilon mode (a scene committed with epsilon_policy = 1, else RPT_ERR_STATE): the fp64
+ * closest hit of that mode's kernels, t_min = 1e-12, over n rays given in fp64.  t = +inf, object = -1 on a miss; a hit may
+ * carry t = NaN where the reference's own test produces one (MonomialSurface).  normal may be NULL. */
+int rpt_intersect_batch_f64(rpt_scene*, uint64_t n, const double* origins, const double* dirs, double* t,
+                            int32_t* object, double* normal);
 
 /* Flattened-layout statistics of a committed scene: [0] spheres, [1] general (rotated) cubes,
  * [2] planes, [3] linearly scanned triangles, [4] axis-aligned boxes, [5] axis-aligned
@@ -321,7 +331,7 @@ int rpt_frame_unpack_device(uint32_t width, uint32_t height, uint32_t rank, uint
  * colours, no fused multiply-adds (only the objects a ray's padded fp32 box test keeps are evaluated -- the result is that of
  * the full scan bit for bit; option "f64_cull" = 0 runs the full scan).  Same entry points (rpt_render_sample*,
  * rpt_render_into_buffer), same RNG streams, same sharding; 4-5 times slower than the fp32 path (C3: 2.9 Gsamples/s).
- * Supported: spheres, cubes, planes, meshes (scanned triangle by triangle), KdTree groups of them as objects and as
+ * Supported: spheres, cubes, planes, meshes (scanned triangle by triangle), monomial surfaces, KdTree groups of them as objects and as
  * Light::Objects (nested at most three deep), all materials, lights and media, Environment::Color and Environment::Hdri.
  * Photon mapping (rpt_photon_map_build, rpt_photon_render_sample*): the shooting pass and the surface estimate's visibility rays run in
  * fp64 with the reference's tests (t_min = 1e-12; a gathered photon counts unless len > hit.time, src/photon.rs:357-361); the maps, the

@@ -23,7 +23,7 @@ ShapeDesc._fields_ = [
     ("kind", C.c_int32),
     ("has_transform", C.c_int32),
     ("transform", C.c_double * 16),
-    ("plane_normal", C.c_double * 3),
+    ("plane_normal", C.c_double * 3),     # Plane normal; kind 5 (MonomialSurface): height, exp, -
     ("plane_value", C.c_double),
     ("tris", C.POINTER(C.c_double)),
     ("n_tris", C.c_uint64),
@@ -88,6 +88,7 @@ SYMBOLS = [
     ("rpt_render_sample_device", C.c_int,
      [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P, _P]),
     ("rpt_intersect_batch", C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P]),
+    ("rpt_intersect_batch_f64", C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("rpt_scene_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("rpt_get_counters", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("rpt_debug_section_counters", C.c_int, [_P, C.POINTER(C.c_uint64)]),

@@ -59,7 +59,7 @@ def set_option(name, value):
 __all__ = [
     "set_option", "shard_pixels",
     "vec3", "hex_color", "color_bytes", "Sphere", "Cube", "Plane", "Triangle", "Mesh", "KdTree", "Transformed",
-    "sphere", "cube", "plane", "polygon", "Material", "Object", "Light", "Medium", "Environment",
+    "MonomialSurface", "sphere", "cube", "plane", "polygon", "monomial_surface", "Material", "Object", "Light", "Medium", "Environment",
     "Scene", "Camera", "Filter", "Buffer", "DeviceBuffer", "Renderer", "RptError",
 ]
 
@@ -177,6 +177,17 @@ class Plane(Shape):
         self.value = float(value)
 
 
+class MonomialSurface(Shape):
+    """y = height * (x^2 + z^2)^2 for x^2 + z^2 <= 1, two-sided (shape/monomial_surface.rs:8-19).  `exp` is stored but, as in
+    the reference, intersection hard-codes the exponent 4.  Bounded: it may sit in a KdTree.  Not a Light::Object, and scenes that
+    hold one are not photon-mapped (the library refuses both)."""
+    KIND = 5
+
+    def __init__(self, height, exp):
+        self.height = float(height)
+        self.exp = float(exp)
+
+
 class Triangle:
     """shape/mesh.rs:9-39."""
 
@@ -259,6 +270,11 @@ def cube():
 
 def plane(normal, value):
     return Plane(normal, value)
+
+
+def monomial_surface(height, exp):
+    """shape.rs:292-295."""
+    return MonomialSurface(height, exp)
 
 
 def polygon(verts):
@@ -502,6 +518,9 @@ def shape_desc(shape, cls):
         for i in range(3):
             d.plane_normal[i] = float(base.normal[i])
         d.plane_value = base.value
+    elif isinstance(base, MonomialSurface):
+        d.plane_normal[0] = base.height
+        d.plane_normal[1] = base.exp
     elif isinstance(base, Mesh):
         keep = np.ascontiguousarray(base.tris, dtype=np.float64)
         d.tris = keep.ctypes.data_as(C.POINTER(C.c_double))
@@ -941,4 +960,20 @@ class Renderer:
         _lib.check(lib.rpt_intersect_batch(h, n, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
                                            t.ctypes.data_as(C.c_void_p), obj.ctypes.data_as(C.c_void_p),
                                            nrm.ctypes.data_as(C.c_void_p)))
+        return t, obj, nrm
+
+    def get_closest_hit_f64(self, origins, dirs):
+        """The same query in the reference-epsilon mode (a scene with set_option("epsilon_policy", 1)): fp64 rays, t_min = 1e-12,
+        the mode's own closest hit -> (t, object index, normal), fp64; t = inf and object -1 on a miss."""
+        lib = _lib.load()
+        h = self.scene._commit(self.device_)
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        n = o.shape[0]
+        t = np.empty(n, dtype=np.float64)
+        obj = np.empty(n, dtype=np.int32)
+        nrm = np.empty((n, 3), dtype=np.float64)
+        _lib.check(lib.rpt_intersect_batch_f64(h, n, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
+                                               t.ctypes.data_as(C.c_void_p), obj.ctypes.data_as(C.c_void_p),
+                                               nrm.ctypes.data_as(C.c_void_p)))
         return t, obj, nrm

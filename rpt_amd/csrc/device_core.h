@@ -258,6 +258,60 @@ RPT_DEV void to_local(const XfScan& x, V o, V d, V& ol, V& dl) {
     ol = mk(dot3w(x.r0, o), dot3w(x.r1, o), dot3w(x.r2, o));
     dl = mk(dot3(x.r0, d), dot3(x.r1, d), dot3(x.r2, d));
 }
+// MonomialSurface::intersect, src/shape/monomial_surface.rs:22-107, in the surface's local space (t is shared), step for step:
+// the box test against [-1, 0, -1]..[1, h, 1] (min / max per axis, so h <= 0 works), maximize = dist(t_min) < 0, Newton from
+// the box's midpoint (at most 10 steps, leaving as soon as dist > 0) for the end of the bracket -- or 10000 --, the sign check,
+// exactly 60 bisection steps, then `r > tbest` (an equal time replaces the record) and the x^2 + z^2 > 1 rejection.  The fp32
+// policy's one addition: a NaN or infinite root is a miss.  The quartic costs ~700 flops per ray, so a
+// wave leaves before the solve when none of its lanes passes the box test; the lanes that do run the 60 steps together.
+// Compiled without contraction (fmas written out), as sphere_closer: the scan and the tree walks get the same bits.
+RPT_DEV bool mono_closer(V ol, V dl, const F4& hb, float tmin, float tbest, float& t) {
+#pragma clang fp contract(off)
+    const float ix = rcp(dl.x), iy = rcp(dl.y), iz = rcp(dl.z);
+    const float x1 = (-1.f - ol.x) * ix, x2 = (1.f - ol.x) * ix;
+    const float y1 = (hb.y - ol.y) * iy, y2 = (hb.z - ol.y) * iy;
+    const float z1 = (-1.f - ol.z) * iz, z2 = (1.f - ol.z) * iz;
+    const float b_min = max3(fminf(x1, x2), fminf(y1, y2), fminf(z1, z2));
+    const float b_max = min3(fmaxf(x1, x2), fmaxf(y1, y2), fmaxf(z1, z2));
+    const bool in_box = !(fmaxf(b_min, tmin) > fminf(b_max, tbest));
+    if (__ballot(in_box) == 0ull) return false;   // (wave-uniform: nobody solves)
+    if (!in_box) return false;
+    const float h = hb.x;
+    auto dist = [&](float s) {   // :27-32
+        const float x = fmaf(s, dl.x, ol.x), y = fmaf(s, dl.y, ol.y), z = fmaf(s, dl.z, ol.z);
+        const float r2 = fmaf(x, x, z * z);
+        return fmaf(-h, r2 * r2, y);
+    };
+    // :33-48, in Horner form: deriv = d.y - h (A + s (B + s (C + s D))), deriv2 = -h (B + s (2 C + s 3 D))
+    const float c0 = fmaf(ol.x, ol.x, ol.z * ol.z), c1 = 2.f * fmaf(ol.x, dl.x, ol.z * dl.z), c2 = fmaf(dl.x, dl.x, dl.z * dl.z);
+    const float A = 2.f * c0 * c1, B = 2.f * fmaf(c1, c1, 2.f * c0 * c2), Cq = 6.f * c1 * c2, Dq = 4.f * c2 * c2;
+    const float d_tmin = dist(tmin);
+    const bool maximize = d_tmin < 0.f;   // :50
+    float t_max = 10000.f;                // :70
+    if (maximize) {                       // :51-68
+        float cur = 0.5f * (b_min + b_max);
+        for (int k = 0; k < 10; k++) {
+            if (dist(cur) > 0.f) break;
+            const float der = fmaf(-h, fmaf(cur, fmaf(cur, fmaf(cur, Dq, Cq), B), A), dl.y);
+            const float der2 = -h * fmaf(cur, fmaf(cur, 3.f * Dq, 2.f * Cq), B);
+            cur -= der / der2;
+        }
+        t_max = cur;
+        if (t_max < tmin) return false;
+    }
+    if (maximize == (dist(t_max) < 0.f)) return false;   // :72-74
+    float l = tmin, r = t_max;
+    for (int k = 0; k < 60; k++) {        // :75-84
+        const float m = (l + r) * 0.5f;
+        if ((dist(m) >= 0.f) == maximize) r = m;
+        else l = m;
+    }
+    if (r > tbest || !(fabsf(r) < __builtin_huge_valf())) return false;   // :85-87; NaN / inf: a miss (fp32 policy)
+    const float px = fmaf(r, dl.x, ol.x), pz = fmaf(r, dl.z, ol.z);
+    if (fmaf(px, px, pz * pz) > 1.f) return false;   // :88-92
+    t = r;
+    return true;
+}
 
 // ------------------------------------------------------------------ closest hit
 // Renderer::get_closest_hit, src/renderer.rs:416-425: every object is tested, the closest
@@ -279,20 +333,28 @@ struct AnyHit {
     uint32_t tw_lo, tw_hi;
     RPT_DEV bool blocks(float t, uint32_t code) const { return t < t_block && !(code >= tw_lo && code <= tw_hi); }
 };
-template <bool COUNT, bool PRIMS, bool ANY = false>
+template <bool COUNT, bool PRIMS, bool ANY = false, bool MONO = false>
 RPT_DEV void bvh_traverse(const SceneView& sc, uint32_t root, V o, V d, float tmin, float& tbest, uint32_t& code,
                           uint32_t& inst, uint32_t* stk, uint32_t stride, uint32_t cap, uint32_t& c_nodes,
                           uint32_t& c_tris, AnyHit any = AnyHit{-kInf, 1u, 0u});
 
 // One primitive of a BVH_PRIMS leaf (per lane: kinds may differ between lanes).  `stk`/`cap`:
 // the part of the lane's stack column above the caller's entries, for the nested walk of an instance.
-template <bool COUNT>
+// MONO: the scene holds monomial surfaces (K_MONO leaf items; an instantiation of its own).
+template <bool COUNT, bool MONO = false>
 RPT_DEV void hit_prim(const SceneView& scene_, uint32_t pc, V o, V d, V inv, float tmin, float& tbest, uint32_t& code,
                       uint32_t& inst, uint32_t* stk, uint32_t stride, uint32_t cap, uint32_t& c_nodes,
                       uint32_t& c_tris) {
     const auto& sc = *kernarg_scene();   // (see kernarg_scene)
     const uint32_t kind = pc >> 28, i = pc & 0x0FFFFFFFu;
     float t = -1.f;
+    if (MONO && kind == K_MONO) {
+        const MonoScan m = sc.mono[i];
+        V ol, dl;
+        to_local(XfScan{m.r0, m.r1, m.r2}, o, d, ol, dl);
+        if (mono_closer(ol, dl, m.h, tmin, tbest, t)) { tbest = t; code = pc; }
+        return;
+    }
     if (kind == K_INST) {
         const InstRec r = sc.inst[i];
         const V ol = mk(dot3w(r.r0, o), dot3w(r.r1, o), dot3w(r.r2, o));
@@ -329,7 +391,7 @@ RPT_DEV void hit_prim(const SceneView& scene_, uint32_t pc, V o, V d, V inv, flo
     if (t >= 0.f && t < tbest) { tbest = t; code = pc; }
 }
 
-template <bool COUNT, bool PRIMS, bool ANY>
+template <bool COUNT, bool PRIMS, bool ANY, bool MONO>
 RPT_DEV void bvh_traverse(const SceneView& scene_, uint32_t root, V o, V d, float tmin, float& tbest, uint32_t& code,
                           uint32_t& inst, uint32_t* stk, uint32_t stride, uint32_t cap, uint32_t& c_nodes,
                           uint32_t& c_tris, AnyHit any) {
@@ -368,7 +430,7 @@ RPT_DEV void bvh_traverse(const SceneView& scene_, uint32_t root, V o, V d, floa
             if (PRIMS && (cur & BVH_PRIMS)) {
                 for (uint32_t i = 0; i < count; i++) {
                     if (COUNT) c_tris++;
-                    hit_prim<COUNT>(scene_, sc.pleaf[first + i], o, d, inv, tmin, tbest, code, inst, stk + sp * stride, stride,
+                    hit_prim<COUNT, MONO>(scene_, sc.pleaf[first + i], o, d, inv, tmin, tbest, code, inst, stk + sp * stride, stride,
                                     cap - sp, c_nodes, c_tris);
                 }
             } else {
@@ -393,7 +455,9 @@ RPT_DEV void bvh_traverse(const SceneView& scene_, uint32_t root, V o, V d, floa
 // The linear scan over the wave-uniform primitive records (everything that is not in a tree).
 // MASKED: bit i of `mask` (wave-uniform) says whether bounded record i -- numbered in scan order: spheres, cubes,
 // boxes, rectangles, triangles, as in SceneView::pbox -- can be hit at all; planes and the shell are always tested.
-template <bool MASKED = false>
+// MONO: ... and then the monomial surfaces; an instantiation of its own.  Not with MASKED: scan_mask_for_ball numbers only the
+// records up to the triangles (only photon mapping masks its scans, and it refuses scenes with monomial surfaces).
+template <bool MASKED = false, bool MONO = false>
 RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbest, uint32_t& code, uint64_t mask = ~0ull) {
     // The scene view is a kernel argument (every caller passes its kernarg struct): its fields are read HERE, through the
     // constant address space, behind an opaque copy of the pointer.  Read as plain kernel arguments they are all hoisted to
@@ -489,10 +553,21 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
         float t = hit_tri(tr.pn, tr.A, tr.B, o, d, tmin, tbest);
         if (t >= 0.f) { tbest = t; code = (K_TRI << 28) | i; }
     }
+    if constexpr (MONO) {
+        static_assert(!MASKED, "scan_mask_for_ball does not cover the monomial surfaces");
+        for (uint32_t i = 0; i < sc.n_mono; i++) {
+            const MonoScan m = uload(&sc.mono[i]);
+            V ol, dl;
+            to_local(XfScan{m.r0, m.r1, m.r2}, o, d, ol, dl);
+            float t;
+            if (mono_closer(ol, dl, m.h, tmin, tbest, t)) { tbest = t; code = (K_MONO << 28) | i; }
+        }
+    }
 }
 // Which scanned records can a query touch that stays inside the ball (c, r) of each live lane?  Wave-uniform mask
 // for scan_prims<true> (the union over the lanes: one lane's ball reaching a box keeps that record for all of them).
-// Scenes with more than 64 bounded scan records do not occur (from 64 on, the scene-level tree takes over).
+// Scenes with more than 64 bounded scan records do not occur (from 64 on, the scene-level tree takes over).  The monomial surfaces'
+// boxes follow the triangles' in pbox but are not counted here: scan_prims<true, true> does not exist (static_assert there).
 // `touched` (optional): does any record's box reach THIS lane's ball?
 RPT_DEV uint64_t scan_mask_for_ball(const SceneView& scene_, bool live, V c, float r, bool* touched = nullptr) {
     const auto& sc = *kernarg_scene();   // (see kernarg_scene)
@@ -636,7 +711,7 @@ RPT_DEV void walk_meshes_resumable(const SceneView& scene_, V o, V d, float tmin
 }
 
 // BVH: 0 = no tree in the scene, 1 = per-mesh trees only, 2 = scene-level tree possible.
-template <int BVH, bool COUNT, bool ANY = false>
+template <int BVH, bool COUNT, bool ANY = false, bool MONO = false>
 RPT_DEV void closest_hit(const SceneView& scene_, V o, V d, float tmin, float& tbest, uint32_t& code, uint32_t& inst,
                          uint32_t* stk, uint32_t stride, uint32_t& c_nodes, uint32_t& c_tris,
                          AnyHit any = AnyHit{-kInf, 1u, 0u}) {
@@ -647,17 +722,17 @@ RPT_DEV void closest_hit(const SceneView& scene_, V o, V d, float tmin, float& t
             float t = hit_plane(nv, o, d, tmin);
             if (t >= 0.f && t < tbest) { tbest = t; code = (K_PLANE << 28) | i; }
         }
-        bvh_traverse<COUNT, true, ANY>(scene_, sc.top_root, o, d, tmin, tbest, code, inst, stk, stride, 32u, c_nodes, c_tris, any);
+        bvh_traverse<COUNT, true, ANY, MONO>(scene_, sc.top_root, o, d, tmin, tbest, code, inst, stk, stride, 32u, c_nodes, c_tris, any);
         if (sc.mesh_deferred) walk_meshes<COUNT, ANY>(scene_, o, d, tmin, tbest, code, inst, stk, stride, c_nodes, c_tris, any);   // (wave-uniform)
         return;
     }
-    scan_prims(scene_, o, d, tmin, tbest, code);
+    scan_prims<false, MONO>(scene_, o, d, tmin, tbest, code);
     if (BVH) walk_meshes<COUNT, ANY>(scene_, o, d, tmin, tbest, code, inst, stk, stride, c_nodes, c_tris, any);
 }
 
 // Everything of a query except the per-mesh trees: the linear scan, or -- BVH = 3: a scene tree whose meshes are walked
 // separately (SceneView::mesh_deferred) -- the planes and the scene tree.
-template <int BVH, bool COUNT>
+template <int BVH, bool COUNT, bool MONO = false>
 RPT_DEV void scan_or_tree(const SceneView& scene_, V o, V d, float tmin, float& tbest, uint32_t& code, uint32_t& inst, uint32_t* stk,
                           uint32_t stride, uint32_t& c_nodes, uint32_t& c_tris) {
     if constexpr (BVH == 3) {
@@ -667,9 +742,9 @@ RPT_DEV void scan_or_tree(const SceneView& scene_, V o, V d, float tmin, float& 
             float t = hit_plane(nv, o, d, tmin);
             if (t >= 0.f && t < tbest) { tbest = t; code = (K_PLANE << 28) | i; }
         }
-        bvh_traverse<COUNT, true, false>(scene_, sc.top_root, o, d, tmin, tbest, code, inst, stk, stride, 32u, c_nodes, c_tris);
+        bvh_traverse<COUNT, true, false, MONO>(scene_, sc.top_root, o, d, tmin, tbest, code, inst, stk, stride, 32u, c_nodes, c_tris);
     } else {
-        scan_prims(scene_, o, d, tmin, tbest, code);
+        scan_prims<false, MONO>(scene_, o, d, tmin, tbest, code);
     }
 }
 
@@ -683,10 +758,24 @@ RPT_DEV V box_face_normal(V p, V lo, V hi) {
     return mk(ax0 ? (xh < xl ? 1.f : -1.f) : 0.f, ax1 ? (yh < yl ? 1.f : -1.f) : 0.f, (!ax0 && !ax1) ? (zh < zl ? 1.f : -1.f) : 0.f);
 }
 // Normal and object of the winning primitive (per lane).
+template <bool MONO = false>
 RPT_DEV void finalize_hit(const SceneView& scene_, V o, V d, float tmin, float t, uint32_t code, uint32_t inst, V& n,
                           uint32_t& obj) {
     const auto& sc = *kernarg_scene();   // (see kernarg_scene)
     uint32_t kind = code >> 28, idx = code & 0x0FFFFFFFu;
+    if (MONO && kind == K_MONO) {   // src/shape/monomial_surface.rs:88-104 (flipped against the local ray), then src/shape.rs:131-134
+        const MonoScan m = sc.mono[idx];
+        const XfShade s = sc.mono_sh[idx];
+        V ol, dl;
+        to_local(XfScan{m.r0, m.r1, m.r2}, o, d, ol, dl);
+        const V p = fma3(t, dl, ol);
+        const float k = m.h.x * 4.f * fmaf(p.x, p.x, p.z * p.z);
+        V nl = normalize(mk(k * p.x, -1.f, k * p.z));
+        if (dot(nl, dl) > 0.f) nl = -nl;
+        n = (s.r1.w != 0.f) ? normalize(mk(dot3(s.r0, nl), dot3(s.r1, nl), dot3(s.r2, nl))) : nl;
+        obj = __float_as_uint(s.r0.w);
+        return;
+    }
     if (kind == K_INSTTRI) {  // src/shape/mesh.rs:78 in the instance's space, then src/shape.rs:131-134
         const InstRec r = sc.inst[inst];
         const TriShade s = sc.btri_sh[idx];

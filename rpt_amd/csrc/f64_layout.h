@@ -17,7 +17,8 @@
 
 namespace rpt64 {
 
-enum : int32_t { SH_SPHERE = 0, SH_CUBE = 1, SH_PLANE = 2, SH_MESH = 3, SH_GROUP = 4 };   // (SH_GROUP: in a light's shape tree only)
+enum : int32_t { SH_SPHERE = 0, SH_CUBE = 1, SH_PLANE = 2, SH_MESH = 3, SH_GROUP = 4,   // (SH_GROUP: in a light's shape tree only)
+                 SH_MONO = 5 };   // MonomialSurface (scene objects only: the MONO kernel instantiations)
 enum : int32_t { LT_POINT = 0, LT_AMBIENT = 1, LT_DIRECTIONAL = 2, LT_OBJECT = 3 };
 
 // One `Box<dyn Shape>`: unit primitive / plane / mesh, optionally under Transformed<T> (src/shape.rs:102-152).  The full
@@ -31,7 +32,7 @@ struct Shape {
     double lin[9];      // linear part of M                Transformed::linear
     double nrm[9];      // (linear)^-T                     Transformed::normal_transform
     double det;         // det(linear)                     Transformed::scale
-    double plane[4];    // SH_PLANE: normal, value
+    double plane[4];    // SH_PLANE: normal, value; SH_MONO: height, exp
     double bmin[3], bmax[3];   // SH_MESH: KdTree::bounds (src/kdtree.rs:108-113)
 };
 struct Tri {   // src/shape/mesh.rs:9-23
@@ -66,7 +67,8 @@ struct ObjRec {
     uint32_t tri_first, tri_count;
     uint32_t n_frames, frame[kMaxFrames];
     double inv[12];   // rows of M^-1 (3 x 4)
-    double b[6];      // SH_MESH: KdTree::bounds min, max; SH_CUBE: -0.5 x 3, 0.5 x 3 (src/shape/cube.rs:25-26); SH_PLANE: normal, value
+    double b[6];      // SH_MESH: KdTree::bounds min, max; SH_CUBE: -0.5 x 3, 0.5 x 3 (src/shape/cube.rs:25-26); SH_PLANE: normal, value;
+                      // SH_MONO: the bounding box (-1, 0, -1), (1, height, 1) (src/shape/monomial_surface.rs:181-187): b[4] is the height
 };
 struct FrameRec {     // one group level: 144 bytes
     double inv[12];   // rows of the group's own M^-1 (has_xf)
@@ -138,6 +140,18 @@ struct Args {
     double* slab;                   // [n_chunks][n_owned][4]: partial sums of (pixel, chunk) items
     unsigned long long* counters;   // [0] rays [1] accepted hits [2] self hits [3] shadow tests [4] passed [5] near misses [6] samples [7] vertices
                                     // [8] objects evaluated [9] evaluation rounds (wave-level) [10] trips (wave-level) [11] live lanes summed over trips; or null
+    uint32_t mono;            // some object is a MonomialSurface (its own kernel instantiation; last: the fields above keep their offsets)
+};
+
+// rpt_intersect_batch_f64 (kernels_f64.hip, intersect_f64_kernel): the closest-hit query of this mode over n rays.
+struct IsectArgs64 {
+    Args a;                     // scene, a.cull
+    uint64_t n;
+    const double* o;            // [3 n] origins, fp64
+    const double* d;            // [3 n] directions
+    double* t;                  // [n] HitRecord::time (+inf: none)
+    int32_t* obj;               // [n] object index, -1: none
+    double* nrm;                // [3 n] normal, or null
 };
 
 // ---- photon mapping in the reference-epsilon mode (kernels_f64.hip; the maps, the k-nearest selection and the volume estimates are

@@ -19,7 +19,8 @@ struct alignas(16) F4 {
 // Primitive code = (kind << 28) | index-within-kind.  0xFFFFFFFF = miss.
 enum : uint32_t { K_SPHERE = 0, K_CUBE = 1, K_PLANE = 2, K_TRI = 3, K_BVHTRI = 4, K_AABB = 5, K_RECT = 6,
                   K_INST = 7,      // scene-BVH leaf item: one instance of a shared local-space mesh
-                  K_INSTTRI = 8 }; // hit code: triangle of an instanced mesh (the instance travels beside the code)
+                  K_INSTTRI = 8,   // hit code: triangle of an instanced mesh (the instance travels beside the code)
+                  K_MONO = 9 };    // MonomialSurface (scenes that hold one only: the MONO kernel instantiations)
 static const uint32_t CODE_MISS = 0xFFFFFFFFu;
 
 // Sphere / cube scan record: rows of the inverse affine map (world -> unit primitive).
@@ -36,6 +37,12 @@ struct alignas(16) XfShade {
 // holds the unit normal and the object id.
 struct alignas(16) PlaneScan {
     F4 nv;
+};
+// MonomialSurface (src/shape/monomial_surface.rs): rows of the inverse affine map (world -> local, as XfScan) and the
+// height with the local box's y range [min(0, h), max(0, h)] (h.y, h.z).  Its shade record is an XfShade.
+struct alignas(16) MonoScan {
+    F4 r0, r1, r2;
+    F4 h;   // height, y lo, y hi, -
 };
 struct alignas(16) PlaneShade {
     F4 unit_n_obj;
@@ -185,6 +192,9 @@ struct SceneView {
     // Counters builds only: bumped when a tree walk finds its stack full (bvh_traverse then drops the far child -- the commit-
     // time depth check is what rules that out; this is where a violation would show).  rpt_get_counters()[7].
     unsigned long long* stack_overflows;
+    // Monomial surfaces (K_MONO), scanned after the triangles (their pbox entries follow the triangles'); n_mono != 0 selects
+    // the kernel instantiations that test them.  (Kept last: the fields above keep their offsets in the kernel arguments.)
+    const MonoScan* mono;  const XfShade* mono_sh;  uint32_t n_mono;
 };
 
 struct CameraG {

@@ -19,6 +19,7 @@ struct SceneDev {
     rptg::SceneView view;
     int first_object_light;  // index into scene.lights of the first Light::Object, or -1
     bool epsilon64;          // committed in the reference-epsilon mode (epsilon_policy = 1)
+    bool has_monomial;       // some object is (or holds) a MonomialSurface: photon mapping refuses such scenes
 };
 SceneDev scene_dev(rpt_scene* s);
 void*& photon_slot(rpt_scene* s);  // owned by photon.hip (PhotonMapDev*), released through photon_release

@@ -24,10 +24,12 @@ namespace rptg {
 RPT_DEV uint32_t mbcnt64(uint64_t m) {
     return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
 }
+template <bool MONO = false>
 RPT_DEV uint32_t code_object(const SceneView& sc, uint32_t code, uint32_t inst) {
     uint32_t kind = code >> 28, idx = code & 0x0FFFFFFFu;
     float w;
-    if (kind == K_INSTTRI) w = sc.inst[inst].n0.w;
+    if (MONO && kind == K_MONO) w = sc.mono_sh[idx].r0.w;
+    else if (kind == K_INSTTRI) w = sc.inst[inst].n0.w;
     else if (kind == K_SPHERE) w = sc.sph_sh[idx].r0.w;
     else if (kind == K_CUBE) w = sc.cub_sh[idx].r0.w;
     else if (kind == K_PLANE) w = sc.pln_sh[idx].unit_n_obj.w;
@@ -70,7 +72,7 @@ RPT_DEV void item_pixel(const RenderArgs& a, uint32_t p, uint32_t& x, uint32_t& 
                               // the medium flavour spilled 84 B/lane at 6 waves -- 32 GB of HBM writes per C3 launch -- and 5 was the setting.)
 #endif
 #ifndef RPT_MIN_WAVES_SCAN_GROUPS
-#define RPT_MIN_WAVES_SCAN_GROUPS 5  // ... with group lights or counters (GROUPS / COUNT): 64 / 48 B of scratch at 6 waves, none at 5
+#define RPT_MIN_WAVES_SCAN_GROUPS 5  // ... with group lights, counters or monomial surfaces (GROUPS / COUNT / MONO): 64 / 48 B of scratch at 6 waves, none at 5
 #endif
 // LDS of the per-mesh-tree kernel with detached shadow queries (render_kernel<true, 1, *, false, true>), in dwords per block
 // of 256 lanes: [stack rows][5 state rows][staged tables][pend: 256][acc: 3 x 256 u64][4 wave queues].  40,320 B: four
@@ -169,7 +171,7 @@ RPT_DEV void stage_distance(Rng& rng, float inv_sigma_t, float& dmed, float& t) 
 }
 // The event at a medium point or a surface hit: position, what shading needs, emission (src/renderer.rs:207-216,
 // 243-255, 289-299).
-template <bool COUNT>
+template <bool COUNT, bool MONO = false>
 RPT_DEV void stage_event(const RenderArgs& a, const LdsTables& tab, V ro, V rd, uint32_t depth, bool medium, float dmed, float t,
                          uint32_t code, uint32_t inst, V& x, V& n, V& mcol, Mat& mat, V& E) {
     const SceneView& sc = a.sc;
@@ -183,7 +185,7 @@ RPT_DEV void stage_event(const RenderArgs& a, const LdsTables& tab, V ro, V rd, 
     } else {
         uint32_t obj;
         SECT(6);
-        finalize_hit(sc, ro, rd, ray_tmin(ro), t, code, inst, n, obj);
+        finalize_hit<MONO>(sc, ro, rd, ray_tmin(ro), t, code, inst, n, obj);
         mat = load_mat(sc, obj, tab);
         x = fma3(t, rd, ro);
         E = (depth == 0) ? mat_emit(mat) * mat_color(mat) : mk(0, 0, 0);
@@ -192,10 +194,11 @@ RPT_DEV void stage_event(const RenderArgs& a, const LdsTables& tab, V ro, V rd, 
 // The shadow test of an object light and its term of E (src/renderer.rs:347-353, 395-404).  Reference: contributes
 // iff the closest hit along wi lies at dist_to_light (|hit - dist| < 1e-12).  fp32 equivalent: the closest hit
 // belongs to the scene object that IS this light, at the sampled distance (rel. tol 1e-3).
+template <bool MONO = false>
 RPT_DEV void stage_light_term(const SceneView& sc, const Light& L, float albedo_med, V rd, bool medium, float ts, uint32_t cs,
                               uint32_t is, float dist, V I, V wi, V n, V mcol, const Mat& mat, V& E) {
     const bool twin = (L.twin_lo <= L.twin_hi) ? (cs >= L.twin_lo && cs <= L.twin_hi)   // wave-uniform choice
-                                               : (cs != CODE_MISS && code_object(sc, cs, is) == uint32_t(L.twin_object));
+                                               : (cs != CODE_MISS && code_object<MONO>(sc, cs, is) == uint32_t(L.twin_object));
     if (cs != CODE_MISS && ts >= dist * (1.f - 1e-3f) && twin) {
         if (medium) {
             E = fma3(albedo_med * sc.medium_phase, I * mcol, E);
@@ -241,8 +244,10 @@ RPT_DEV bool stage_bounce(const RenderArgs& a, float albedo_med, V rd, uint32_t 
 // sampler copy costs the plain kernels 6 % through register allocation alone, and a call costs 6x.
 // DETACH (per-mesh-tree kernels in a medium): shadow queries that need a tree walk leave their path (see the loop body).
 // DETACH = 2: primary queries leave as well -- their paths wait in memory and the lane goes on with another one.
-template <bool MEDIUM, int BVH, bool COUNT, bool GROUPS = false, int DETACH = 0>
-__global__ __launch_bounds__(256, BVH == 0 ? ((GROUPS || COUNT) ? RPT_MIN_WAVES_SCAN_GROUPS : RPT_MIN_WAVES_SCAN) : BVH == 3 ? RPT_MIN_WAVES_SCENE_MESH : BVH == 1 ? (DETACH == 2 ? RPT_MIN_WAVES_STREAM : RPT_MIN_WAVES_MESH) : RPT_MIN_WAVES)
+// MONO: the scene holds monomial surfaces (K_MONO records, ~700 flops per ray and surface): a separate instantiation, chosen
+// at commit only for such scenes, so that the others run exactly the code they ran before.
+template <bool MEDIUM, int BVH, bool COUNT, bool GROUPS = false, int DETACH = 0, bool MONO = false>
+__global__ __launch_bounds__(256, BVH == 0 ? ((GROUPS || COUNT || MONO) ? RPT_MIN_WAVES_SCAN_GROUPS : RPT_MIN_WAVES_SCAN) : BVH == 3 ? RPT_MIN_WAVES_SCENE_MESH : BVH == 1 ? (DETACH == 2 ? RPT_MIN_WAVES_STREAM : RPT_MIN_WAVES_MESH) : RPT_MIN_WAVES)
 void render_kernel(const RenderArgs a) {
 #ifdef RPT_SECT_CLOCKS
     __shared__ unsigned long long sect_lds_[4][56];   // per wave: [2k] visits of section k, [2k + 1] its ticks
@@ -251,6 +256,7 @@ void render_kernel(const RenderArgs a) {
     uint32_t sect_prev_ = 27u;   // (time before the first section point)
 #endif
     static_assert(DETACH == 0 || (MEDIUM && BVH == 1 && !GROUPS), "detached tree walks: per-mesh-tree kernels in a medium only");
+    static_assert(DETACH == 0 || !MONO, "no detached tree walks in scenes with monomial surfaces");
     extern __shared__ uint32_t dyn_lds[];
     const SceneView& sc = a.sc;
     uint32_t* stk = BVH ? (dyn_lds + threadIdx.x) : nullptr;
@@ -535,7 +541,7 @@ void render_kernel(const RenderArgs a) {
                 stage_distance<MEDIUM>(rng, inv_sigma_t, v_dmed, q_t);
                 const float tmin = ray_tmin(ro);
                 q_code = CODE_MISS;
-                scan_prims(sc, ro, rd, tmin, q_t, q_code);
+                scan_prims<false, MONO>(sc, ro, rd, tmin, q_t, q_code);
                 if (COUNT) c_rays++;
                 phase = PH_HAVEP;
                 if (mesh_roots_hit(sc, ro, rd, tmin, q_t)) {
@@ -579,7 +585,7 @@ void render_kernel(const RenderArgs a) {
                 } else {
                     V x, n = mk(0, 1, 0), mcol = mk(0, 0, 0), E;
                     Mat mat = Mat{mk(0, 0, 0), 0.f, 0u, 0.f, 0.f};
-                    stage_event<COUNT>(a, tab, ro, rd, depth, ev_medium, v_dmed, q_t, q_code, 0u, x, n, mcol, mat, E);
+                    stage_event<COUNT, MONO>(a, tab, ro, rd, depth, ev_medium, v_dmed, q_t, q_code, 0u, x, n, mcol, mat, E);
                     for (uint32_t li = 0; li < sc.n_lights; li++) {
                         const Light L = uload(&sc.lights[li]);
                         if (L.kind == L_AMBIENT) {
@@ -594,10 +600,10 @@ void render_kernel(const RenderArgs a) {
                                 const float tm = ray_tmin(x);
                                 float ts = dist * (1.f + 1e-3f);
                                 uint32_t cs = CODE_MISS;
-                                scan_prims(sc, x, wi, tm, ts, cs);
+                                scan_prims<false, MONO>(sc, x, wi, tm, ts, cs);
                                 if (COUNT) c_rays++;
                                 const bool twin = (L.twin_lo <= L.twin_hi) ? (cs >= L.twin_lo && cs <= L.twin_hi)
-                                                                           : (cs != CODE_MISS && code_object(sc, cs, 0u) == uint32_t(L.twin_object));
+                                                                           : (cs != CODE_MISS && code_object<MONO>(sc, cs, 0u) == uint32_t(L.twin_object));
                                 if (cs != CODE_MISS && ts >= dist * (1.f - 1e-3f) && twin) {   // (see DETACH = 1)
                                     SECTK(9);
                                     V T;
@@ -826,7 +832,7 @@ void render_kernel(const RenderArgs a) {
                 stage_distance<MEDIUM>(rng, inv_sigma_t, v_dmed, q_t);
                 const float tmin = ray_tmin(ro);
                 q_code = CODE_MISS;
-                scan_prims(sc, ro, rd, tmin, q_t, q_code);
+                scan_prims<false, MONO>(sc, ro, rd, tmin, q_t, q_code);
                 if (COUNT) c_rays++;
                 phase = mesh_roots_hit(sc, ro, rd, tmin, q_t) ? PH_WAITP : PH_HAVEP;
                 if (h_e == kNoEntry) walk = walk_begin(sc);   // (else `walk` is the entry's walk; this query begins at the root when that one is through)
@@ -844,7 +850,7 @@ void render_kernel(const RenderArgs a) {
                 } else {
                     V x, n = mk(0, 1, 0), mcol = mk(0, 0, 0), E;
                     Mat mat = Mat{mk(0, 0, 0), 0.f, 0u, 0.f, 0.f};
-                    stage_event<COUNT>(a, tab, ro, rd, depth, ev_medium, v_dmed, q_t, q_code, 0u, x, n, mcol, mat, E);
+                    stage_event<COUNT, MONO>(a, tab, ro, rd, depth, ev_medium, v_dmed, q_t, q_code, 0u, x, n, mcol, mat, E);
                     for (uint32_t li = 0; li < sc.n_lights; li++) {
                         const Light L = uload(&sc.lights[li]);
                         if (L.kind == L_AMBIENT) {
@@ -859,13 +865,13 @@ void render_kernel(const RenderArgs a) {
                                 const float tm = ray_tmin(x);
                                 float ts = dist * (1.f + 1e-3f);
                                 uint32_t cs = CODE_MISS;
-                                scan_prims(sc, x, wi, tm, ts, cs);
+                                scan_prims<false, MONO>(sc, x, wi, tm, ts, cs);
                                 if (COUNT) c_rays++;
                                 // the light's twin lies among the scanned records (the host selects this kernel only then): the
                                 // light can be visible only if the scan's closest hit is the twin at the sampled distance, and
                                 // then it is visible unless a tree holds a triangle in front of that hit
                                 const bool twin = (L.twin_lo <= L.twin_hi) ? (cs >= L.twin_lo && cs <= L.twin_hi)
-                                                                           : (cs != CODE_MISS && code_object(sc, cs, 0u) == uint32_t(L.twin_object));
+                                                                           : (cs != CODE_MISS && code_object<MONO>(sc, cs, 0u) == uint32_t(L.twin_object));
                                 if (cs != CODE_MISS && ts >= dist * (1.f - 1e-3f) && twin) {
                                     SECTK(9);
                                     V T;
@@ -1104,7 +1110,7 @@ void render_kernel(const RenderArgs a) {
                 const float tmin = ray_tmin(ro);
                 q_code = CODE_MISS;
                 q_inst = 0;
-                scan_or_tree<BVH, COUNT>(sc, ro, rd, tmin, q_t, q_code, q_inst, stk, stride, c_nodes, c_btris);
+                scan_or_tree<BVH, COUNT, MONO>(sc, ro, rd, tmin, q_t, q_code, q_inst, stk, stride, c_nodes, c_btris);
                 if (COUNT) c_rays++;
                 phase = mesh_roots_hit(sc, ro, rd, tmin, q_t) ? PH_WAITP : PH_HAVEP;
                 walk = walk_begin(sc);
@@ -1120,7 +1126,7 @@ void render_kernel(const RenderArgs a) {
                     need_path = true;
                     phase = PH_NEW;
                 } else {
-                    stage_event<COUNT>(a, tab, ro, rd, depth, v_medium, v_dmed, q_t, q_code, q_inst, v_x, v_n, v_mcol, v_mat, v_E);
+                    stage_event<COUNT, MONO>(a, tab, ro, rd, depth, v_medium, v_dmed, q_t, q_code, q_inst, v_x, v_n, v_mcol, v_mat, v_E);
                     v_li = 0;
                     phase = PH_LIGHT;
                 }
@@ -1143,7 +1149,7 @@ void render_kernel(const RenderArgs a) {
                             q_t = v_dist * (1.f + 1e-3f);
                             q_code = CODE_MISS;
                             q_inst = 0;
-                            scan_or_tree<BVH, COUNT>(sc, v_x, v_wi, tm, q_t, q_code, q_inst, stk, stride, c_nodes, c_btris);
+                            scan_or_tree<BVH, COUNT, MONO>(sc, v_x, v_wi, tm, q_t, q_code, q_inst, stk, stride, c_nodes, c_btris);
                             if (COUNT) c_rays++;
                             const AnyHit any{L.twin_lo <= L.twin_hi ? v_dist * (1.f - 1e-3f) : -kInf, L.twin_lo, L.twin_hi};
                             const bool blocked = q_code != CODE_MISS && any.blocks(q_t, q_code);
@@ -1156,7 +1162,7 @@ void render_kernel(const RenderArgs a) {
                 }
                 if (alive && phase == PH_HAVES && v_li == l) {
                     SECTK(9);
-                    stage_light_term(sc, L, albedo_med, rd, v_medium, q_t, q_code, q_inst, v_dist, v_I, v_wi, v_n, v_mcol, v_mat, v_E);
+                    stage_light_term<MONO>(sc, L, albedo_med, rd, v_medium, q_t, q_code, q_inst, v_dist, v_I, v_wi, v_n, v_mcol, v_mat, v_E);
                     v_li = l + 1u;
                     phase = PH_LIGHT;
                 }
@@ -1222,7 +1228,7 @@ void render_kernel(const RenderArgs a) {
         stage_distance<MEDIUM>(rng, inv_sigma_t, dmed, t);
         const float tmin = ray_tmin(ro);
         uint32_t code = CODE_MISS, inst = 0;
-        closest_hit<BVH, COUNT>(sc, ro, rd, tmin, t, code, inst, stk, stride, c_nodes, c_btris);
+        closest_hit<BVH, COUNT, false, MONO>(sc, ro, rd, tmin, t, code, inst, stk, stride, c_nodes, c_btris);
         if (COUNT) c_rays++;
         SECTK(3);
         const bool hit = code != CODE_MISS;
@@ -1243,7 +1249,7 @@ void render_kernel(const RenderArgs a) {
 
         V x, n = mk(0, 1, 0), mcol = mk(0, 0, 0), E;
         Mat mat = Mat{mk(0, 0, 0), 0.f, 0u, 0.f, 0.f};
-        stage_event<COUNT>(a, tab, ro, rd, depth, ev_medium, dmed, t, code, inst, x, n, mcol, mat, E);
+        stage_event<COUNT, MONO>(a, tab, ro, rd, depth, ev_medium, dmed, t, code, inst, x, n, mcol, mat, E);
 
         // ---- next-event estimation: sample_lights / sample_lights_for_media
         //      (src/renderer.rs:362-409 / 325-359); lights in scene order fix the draw order.
@@ -1262,11 +1268,11 @@ void render_kernel(const RenderArgs a) {
                     uint32_t cs = CODE_MISS, is = 0;
                     // tree-walking scenes: any hit in front of the light on something other than its twin settles the test
                     const bool range = L.twin_lo <= L.twin_hi;
-                    closest_hit<BVH, COUNT, BVH != 0>(sc, x, wi, ray_tmin(x), ts, cs, is, stk, stride, c_nodes, c_btris,
+                    closest_hit<BVH, COUNT, BVH != 0, MONO>(sc, x, wi, ray_tmin(x), ts, cs, is, stk, stride, c_nodes, c_btris,
                                                      AnyHit{range ? dist * (1.f - 1e-3f) : -kInf, L.twin_lo, L.twin_hi});
                     if (COUNT) c_rays++;
                     SECTK(9);
-                    stage_light_term(sc, L, albedo_med, rd, ev_medium, ts, cs, is, dist, I, wi, n, mcol, mat, E);
+                    stage_light_term<MONO>(sc, L, albedo_med, rd, ev_medium, ts, cs, is, dist, I, wi, n, mcol, mat, E);
                 }
             }
             // Point / Directional lights can never satisfy the reference's test (dist is the
@@ -1417,7 +1423,7 @@ __global__ __launch_bounds__(256) void frame_tiles_kernel(const double* __restri
 
 // (The SceneView MUST stay this kernel's first parameter: the device functions read the view from the kernel-argument segment at
 // offset 0 -- kernarg_scene() in device_core.h -- whatever reference they are handed.)
-template <int BVH>
+template <int BVH, bool MONO = false>
 __global__ __launch_bounds__(256) void intersect_kernel(const SceneView sc, uint64_t n, const float* __restrict__ o,
                                                         const float* __restrict__ d, float* __restrict__ t_out,
                                                         int32_t* __restrict__ obj_out, float* __restrict__ n_out) {
@@ -1428,10 +1434,10 @@ __global__ __launch_bounds__(256) void intersect_kernel(const SceneView sc, uint
     V ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
     float tmin = ray_tmin(ro), t = kInf;
     uint32_t code = CODE_MISS, inst = 0, c0 = 0, c1 = 0;
-    closest_hit<BVH, false>(sc, ro, rd, tmin, t, code, inst, stk, 256, c0, c1);
+    closest_hit<BVH, false, false, MONO>(sc, ro, rd, tmin, t, code, inst, stk, 256, c0, c1);
     V nn = mk(0, 0, 0);
     uint32_t obj = 0xFFFFFFFFu;
-    if (code != CODE_MISS) finalize_hit(sc, ro, rd, tmin, t, code, inst, nn, obj);
+    if (code != CODE_MISS) finalize_hit<MONO>(sc, ro, rd, tmin, t, code, inst, nn, obj);
     t_out[i] = t;
     obj_out[i] = int32_t(obj);
     if (n_out) {
@@ -1501,6 +1507,12 @@ static_assert(kTabBytes == kTabDwords * 4u, "one table layout");
 template <bool M, int B, bool C>
 static hipError_t launch_render_t(const RenderArgs& a, int n_blocks, hipStream_t stream) {
     const size_t lds = B == 1 ? kMeshTreeBytes : B ? kStackBytes + kStateBytesBvh : kStateBytes;
+    // monomial surfaces: instantiations of their own (no detached walks, no counters build: the counters stay zero for such scenes)
+    if (a.sc.n_mono) {
+        if (a.sc.n_lparts) hipLaunchKernelGGL((render_kernel<M, B, false, true, 0, true>), dim3(n_blocks), dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL((render_kernel<M, B, false, false, 0, true>), dim3(n_blocks), dim3(256), lds, stream, a);
+        return hipGetLastError();
+    }
     if constexpr (M && B == 1) {
 #ifdef RPT_EXPERIMENTS   // streamed walks: a measured-slower prototype (297 against 237 ms), not in the default build
         if (a.detach == 2 && !a.sc.n_lparts) {
@@ -1582,6 +1594,11 @@ hipError_t launch_frame_unpack(const double* d_packed, double* d_frame, const ui
 hipError_t launch_intersect(const SceneView& sc, uint64_t n, const float* d_o, const float* d_d, float* d_t,
                             int32_t* d_obj, float* d_n, bool bvh, hipStream_t stream) {
     uint32_t blocks = uint32_t((n + 255) / 256);
+    if (sc.n_mono) {
+        if (bvh) hipLaunchKernelGGL((intersect_kernel<2, true>), dim3(blocks), dim3(256), kStackBytes, stream, sc, n, d_o, d_d, d_t, d_obj, d_n);
+        else hipLaunchKernelGGL((intersect_kernel<0, true>), dim3(blocks), dim3(256), 0, stream, sc, n, d_o, d_d, d_t, d_obj, d_n);
+        return hipGetLastError();
+    }
     if (bvh) hipLaunchKernelGGL(intersect_kernel<2>, dim3(blocks), dim3(256), kStackBytes, stream, sc, n, d_o, d_d, d_t, d_obj, d_n);
     else hipLaunchKernelGGL(intersect_kernel<0>, dim3(blocks), dim3(256), 0, stream, sc, n, d_o, d_d, d_t, d_obj, d_n);
     return hipGetLastError();

@@ -19,8 +19,11 @@
 // (cull32 below).
 #include <hip/hip_runtime.h>
 
+#include <cstring>
+
 #include "device_core.h"   // Rng (the fp32 path's stream, bit for bit)
 #include "f64_layout.h"
+#include "host_internal.h"   // (rpt_intersect_batch_f64, at the end of the file)
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -128,7 +131,9 @@ struct PairHit {
 
 // Shape::intersect of object i (Transformed::intersect around it when has_xf, src/shape.rs:128-138; Ray::apply_transform
 // does not renormalise the direction, so t is shared) on an empty record.
-template <bool COUNT, class RP, class TP>
+// MONO: the scene holds monomial surfaces (SH_MONO records: an instantiation of its own, see render_f64_kernel).
+static constexpr uint32_t kMonoHit = 0x80000000u;   // PairHit::aux / Query::aux of a monomial surface's hit (see closest_hit_wave)
+template <bool COUNT, bool MONO = false, class RP, class TP>
 R64_DEV PairHit eval_pair(RP recs, TP trecs, uint32_t i, D o, D d) {
     SECT64(5);
     PairHit h{kInf, -kInf, 0u};
@@ -159,6 +164,64 @@ R64_DEV PairHit eval_pair(RP recs, TP trecs, uint32_t i, D o, D d) {
         const D p = xf_point(r.inv, ol), q = xf_dir(r.inv, dl);
         ol = p;
         dl = q;
+    }
+    if (MONO && kind == SH_MONO) {   // MonomialSurface::intersect, src/shape/monomial_surface.rs:22-107, literally
+        // BoundingBox::intersect (src/kdtree.rs:56-71) of (-1, 0, -1)..(1, height, 1); f64::min / max ignore a NaN like fmin / fmax
+        const double x1 = (r.b[0] - ol.x) / dl.x, x2 = (r.b[3] - ol.x) / dl.x;
+        const double y1 = (r.b[1] - ol.y) / dl.y, y2 = (r.b[4] - ol.y) / dl.y;
+        const double z1 = (r.b[2] - ol.z) / dl.z, z2 = (r.b[5] - ol.z) / dl.z;
+        const double b_min = fmax(fmax(fmin(x1, x2), fmin(y1, y2)), fmin(z1, z2));
+        const double b_max = fmin(fmin(fmax(x1, x2), fmax(y1, y2)), fmax(z1, z2));
+        // :23-26 on the empty record; the record's time enters through bm (as for a mesh: closest_hit_wave)
+        const double own = fmax(b_min, kEps);
+        h.bm = fmax(bm, own);
+        if (own > fmin(b_max, kInf)) return h;
+        const double height = r.b[4];
+        auto dist = [&](double t) {   // :27-32 (powi(2) is a multiply)
+            const double x = ol.x + t * dl.x, y = ol.y + t * dl.y, z = ol.z + t * dl.z;
+            const double s2 = x * x + z * z;
+            return y - height * (s2 * s2);
+        };
+        const double coef0 = ol.x * ol.x + ol.z * ol.z;         // :33-35
+        const double coef1 = 2. * (ol.x * dl.x + ol.z * dl.z);
+        const double coef2 = dl.x * dl.x + dl.z * dl.z;
+        auto deriv = [&](double t) {   // :36-42
+            const double dy = 2. * coef0 * coef1 + 2. * t * (coef1 * coef1 + 2. * coef0 * coef2) + 3. * (t * t) * 2. * coef1 * coef2 +
+                              4. * (t * t * t) * coef2 * coef2;
+            return dl.y - height * dy;
+        };
+        auto deriv2 = [&](double t) {   // :43-48
+            const double dy = 2. * (coef1 * coef1 + 2. * coef0 * coef2) + 3. * 2. * t * 2. * coef1 * coef2 + 4. * 3. * (t * t) * coef2 * coef2;
+            return -height * dy;
+        };
+        double t_max;
+        const bool maximize = dist(kEps) < 0.0;   // :50
+        if (maximize) {                            // :51-68 (the diagnostic print of :62-64 aside)
+            double cur_x = (b_min + b_max) / 2.;
+            for (int k = 0; k < 10; k++) {
+                const double f = dist(cur_x);
+                if (f > 0.) break;
+                const double der = deriv(cur_x), der2 = deriv2(cur_x);
+                cur_x -= der / der2;
+            }
+            t_max = cur_x;
+            if (t_max < kEps) return h;
+        } else {
+            t_max = 10000.;
+        }
+        if ((dist(kEps) < 0.0) == (dist(t_max) < 0.0)) return h;   // :72-74
+        double l = kEps, rr = t_max;
+        for (int k = 0; k < 60; k++) {                              // :75-84
+            const double m = (l + rr) / 2.0;
+            if ((dist(m) >= 0.0) == maximize) rr = m;
+            else l = m;
+        }
+        // :85-87 (`r > record.time`) is closest_hit_wave's; :88-92
+        const double px = ol.x + rr * dl.x, pz = ol.z + rr * dl.z;
+        if (px * px + pz * pz > 1.0) return h;
+        h.t = rr;   // (may be NaN: the reference's record then holds a NaN time)
+        h.aux = kMonoHit;
+        return h;
     }
     if (kind == SH_PLANE) {   // Plane::intersect, src/shape/plane.rs:17-32
         SECT64(6);
@@ -318,7 +381,13 @@ R64_DEV D lane_read(D v, uint32_t src_lane) { return mk(lane_read(v.x, src_lane)
 // !(max(b_min, t_min) > min(b_max, rec.time)); on the empty record that is `bm <= b_max` (else no triangle was tested), so
 // with the record's time R it is !(bm > R).  Inside a mesh the triangles run in order on one lane.  The record is
 // therefore the reference's after every object, bit for bit.
-template <bool COUNT, class RP, class TP>
+//
+// MONO (scenes with monomial surfaces): MonomialSurface::intersect replaces the record unless `r > record.time`
+// (src/shape/monomial_surface.rs:85): an equal time replaces it as well, and so does a NaN time -- which the reference can
+// produce --; after a NaN record only the objects whose own test lets it through replace it: another
+// monomial surface, or a mesh with a triangle hit (Triangle::intersect's `time >= record.time` is false against NaN, and the
+// first triangle hit turns the record finite again: the mesh's closest triangle is the result, as on the empty record).
+template <bool COUNT, bool MONO = false, class RP, class TP>
 R64_DEV void closest_hit_wave(RP recs, TP trecs, volatile uint32_t* slots, bool mine, D o, D d, double tlim, Query& q, uint32_t& c_evals,
                               uint32_t& c_rounds) {
     SECT64(3);
@@ -387,7 +456,7 @@ R64_DEV void closest_hit_wave(RP recs, TP trecs, volatile uint32_t* slots, bool 
             PairHit ph{kInf, -kInf, 0u};
             if (info != 0u) {
                 if (COUNT) c_evals++;
-                ph = eval_pair<COUNT>(recs, trecs, info >> 8, po, pd);
+                ph = eval_pair<COUNT, MONO>(recs, trecs, info >> 8, po, pd);
             }
             // ---- the owners collect, rank by rank = in scene order
             uint32_t cum = 0u;
@@ -397,7 +466,20 @@ R64_DEV void closest_hit_wave(RP recs, TP trecs, volatile uint32_t* slots, bool 
                 const bool has = mask != 0u;
                 const uint32_t src = has ? cum + mbcnt64(B) : lane;
                 const double t = lane_read(ph.t, src);
-                if (__ballot(has && t < q.t) != 0ull) {   // (the rest of the result only where some record may change)
+                if constexpr (MONO) {
+                    if (__ballot(has && t != kInf && !(t > q.t)) != 0ull) {   // (a superset of the changes: equal and NaN times)
+                        const double bm = lane_read(ph.bm, src);
+                        const uint32_t aux = lane_read(ph.aux, src);
+                        const uint32_t obj = base + uint32_t(__builtin_ctz(mask));
+                        bool take = t < q.t || (aux == kMonoHit && !(t > q.t));   // src/shape/monomial_surface.rs:85
+                        if (has && !take && q.t != q.t) take = recs[obj].kind == SH_MESH;   // (a NaN record: see above)
+                        if (has && t != kInf && !(bm > q.t) && take) {
+                            q.t = t;
+                            q.obj = int32_t(obj);
+                            q.aux = aux;
+                        }
+                    }
+                } else if (__ballot(has && t < q.t) != 0ull) {   // (the rest of the result only where some record may change)
                     const double bm = lane_read(ph.bm, src);
                     const uint32_t aux = lane_read(ph.aux, src);
                     if (has && !(bm > q.t) && t < q.t) {
@@ -416,7 +498,7 @@ R64_DEV void closest_hit_wave(RP recs, TP trecs, volatile uint32_t* slots, bool 
 // The winner's world-space normal: what its Shape::intersect stores in the record -- formed here from the ray, the time
 // and `aux` by the same operations on the same operands --, then Transformed::intersect's normalize(normal_transform * n)
 // (src/shape.rs:135-136).
-template <class RP, class TP>
+template <bool MONO = false, class RP, class TP>
 R64_DEV D hit_normal(RP recs, TP trecs, const Query& q, D o, D d) {
     const auto& r = recs[q.obj];
     D n;
@@ -440,7 +522,12 @@ R64_DEV D hit_normal(RP recs, TP trecs, const Query& q, D o, D d) {
             ol = p;
             dl = q2;
         }
-        if (r.kind == SH_SPHERE) {
+        if (MONO && r.kind == SH_MONO) {   // src/shape/monomial_surface.rs:88-104
+            const D pos = ol + q.t * dl;
+            const double height = r.b[4];
+            n = normalize(mk(height * 4.0 * pos.x * (pos.x * pos.x + pos.z * pos.z), -1.0, height * 4.0 * pos.z * (pos.x * pos.x + pos.z * pos.z)));
+            if (dot(n, dl) > 0.0) n = -n;   // two-sided: against the (local) ray
+        } else if (r.kind == SH_SPHERE) {
             n = normalize(ol + q.t * dl);   // src/shape/sphere.rs:40
         } else {   // src/shape/mesh.rs:64-80
             const auto& tr = trecs[q.aux];
@@ -712,7 +799,9 @@ static_assert(kLdsDoubles * 8u * 4u <= 160u * 1024u, "four blocks per CU");
 
 // GROUPL: some Light::Object is a KdTree group (per-lane child choice, sample_light_shape): an instantiation of its own, as in the fp32
 // megakernel -- inlined beside the wave-uniform sampler it cost C3 1.3 % through register allocation alone.
-template <bool MEDIUM, bool COUNT, bool LDSTAB, bool GROUPL = false>
+// MONO: some object is a MonomialSurface (eval_pair's ~700-flop quartic, closest_hit_wave's tie and NaN rules): an instantiation of
+// its own for the same reason -- C3eps already spills.
+template <bool MEDIUM, bool COUNT, bool LDSTAB, bool GROUPL = false, bool MONO = false>
 __global__ __launch_bounds__(256, R64_WAVES) void render_f64_kernel(const Args a_by_value) {
     (void)a_by_value;   // (read through KA)
     extern __shared__ double lds64[];
@@ -877,7 +966,7 @@ __global__ __launch_bounds__(256, R64_WAVES) void render_f64_kernel(const Args a
         auto surface_event = [&](const Query& h) {   // :207-216 in a medium, :289-299 without
             SECT64(16);
             hobj = h.obj;
-            n = hit_normal(recs, trecs, h, ro, rd);
+            n = hit_normal<MONO>(recs, trecs, h, ro, rd);
             ro = ro + h.t * rd;
             wo = -normalize(rd);
             const Mat& mat = KA.sc.shade[hobj].mat;
@@ -887,7 +976,7 @@ __global__ __launch_bounds__(256, R64_WAVES) void render_f64_kernel(const Args a
         const uint32_t n_lights = KA.sc.n_lights;
         for (uint32_t sub = 0;; sub++) {
             Query q;
-            closest_hit_wave<COUNT>(recs, trecs, slots, active, ro, rd, qlim, q, c_evals, c_rounds);
+            closest_hit_wave<COUNT, MONO>(recs, trecs, slots, active, ro, rd, qlim, q, c_evals, c_rounds);
             if (active) {
                 SECT64(14);
                 if (sub == 0) {
@@ -1364,13 +1453,71 @@ __global__ __launch_bounds__(256) void resolve_photon_f64_kernel(const Args a, c
     out[o + 2] = (accumulate ? out[o + 2] : 0.0) + b * scale_over_total;
 }
 
+// rpt_intersect_batch_f64: Renderer::get_closest_hit (src/renderer.rs:416-425) of this mode for n rays, one per lane -- the
+// query of the render kernel (closest_hit_wave, t_min = 1e-12) and its normal (hit_normal).
+#define KI (*rptg::kernarg_args<IsectArgs64>())
+template <bool LDSTAB, bool MONO>
+__global__ __launch_bounds__(256) void intersect_f64_kernel(const IsectArgs64 by_value) {
+    (void)by_value;
+    extern __shared__ double lds64[];
+    const ObjRec* recs;
+    const TriRec* trecs;
+    stage_tables<LDSTAB>(lds64, recs, trecs);
+    volatile uint32_t* const slots = reinterpret_cast<uint32_t*>(lds64 + kPhSlotBase) + (threadIdx.x >> 6) * 64u;
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    const bool mine = i < KI.n;   // (every lane of the wave takes part in closest_hit_wave)
+    D o = mk(0, 0, 0), d = mk(0, 0, 1);
+    if (mine) {
+        o = mk(KI.o[3 * i], KI.o[3 * i + 1], KI.o[3 * i + 2]);
+        d = mk(KI.d[3 * i], KI.d[3 * i + 1], KI.d[3 * i + 2]);
+    }
+    Query q;
+    uint32_t ce = 0, cr = 0;
+    closest_hit_wave<false, MONO>(recs, trecs, slots, mine, o, d, kInf, q, ce, cr);
+    if (!mine) return;
+    D n = mk(0, 0, 0);
+    if (q.obj >= 0) n = hit_normal<MONO>(recs, trecs, q, o, d);
+    KI.t[i] = q.t;
+    KI.obj[i] = q.obj;
+    if (KI.nrm) {
+        KI.nrm[3 * i] = n.x;
+        KI.nrm[3 * i + 1] = n.y;
+        KI.nrm[3 * i + 2] = n.z;
+    }
+}
+#undef KI
+
 }  // namespace rpt64
 
 namespace rptg {
+static hipError_t launch_intersect_f64(const rpt64::IsectArgs64& a, hipStream_t stream) {
+    if (!a.n) return hipSuccess;
+    const size_t lds = size_t(rpt64::kPhLdsDoubles) * 8u;
+    const bool tab = a.a.sc.n_objects <= rpt64::kLdsObjs && a.a.sc.n_obj_tris <= rpt64::kLdsTris;
+    const dim3 grid(uint32_t((a.n + 255u) / 256u));
+    if (a.a.mono) {
+        if (tab) hipLaunchKernelGGL((rpt64::intersect_f64_kernel<true, true>), grid, dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL((rpt64::intersect_f64_kernel<false, true>), grid, dim3(256), lds, stream, a);
+    } else {
+        if (tab) hipLaunchKernelGGL((rpt64::intersect_f64_kernel<true, false>), grid, dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL((rpt64::intersect_f64_kernel<false, false>), grid, dim3(256), lds, stream, a);
+    }
+    return hipGetLastError();
+}
 template <bool M, bool C>
 static hipError_t launch_f64_t(const rpt64::Args& a, int n_blocks, hipStream_t stream) {
     const size_t lds = size_t(rpt64::kLdsDoubles) * 8u;
     const bool tab = a.sc.n_objects <= rpt64::kLdsObjs && a.sc.n_obj_tris <= rpt64::kLdsTris;
+    if (a.mono) {   // (no counters build: the mode's counters stay zero for such scenes)
+        if (a.group_lights) {
+            if (tab) hipLaunchKernelGGL((rpt64::render_f64_kernel<M, false, true, true, true>), dim3(n_blocks), dim3(256), lds, stream, a);
+            else hipLaunchKernelGGL((rpt64::render_f64_kernel<M, false, false, true, true>), dim3(n_blocks), dim3(256), lds, stream, a);
+        } else {
+            if (tab) hipLaunchKernelGGL((rpt64::render_f64_kernel<M, false, true, false, true>), dim3(n_blocks), dim3(256), lds, stream, a);
+            else hipLaunchKernelGGL((rpt64::render_f64_kernel<M, false, false, false, true>), dim3(n_blocks), dim3(256), lds, stream, a);
+        }
+        return hipGetLastError();
+    }
     if (a.group_lights) {
         if (tab) hipLaunchKernelGGL((rpt64::render_f64_kernel<M, C, true, true>), dim3(n_blocks), dim3(256), lds, stream, a);
         else hipLaunchKernelGGL((rpt64::render_f64_kernel<M, C, false, true>), dim3(n_blocks), dim3(256), lds, stream, a);
@@ -1432,3 +1579,36 @@ hipError_t launch_resolve_photon_f64(const rpt64::Args& a, const void* slab32, u
     return hipGetLastError();
 }
 }  // namespace rptg
+
+// ---------------------------------------------------------------------------- C ABI: rpt_intersect_batch_f64 (include/rpt_hip.h)
+extern "C" int rpt_intersect_batch_f64(rpt_scene* s, uint64_t n, const double* origins, const double* dirs, double* t, int32_t* object,
+                                       double* normal) {
+    if (!s || !origins || !dirs || !t || !object) return rpti::fail(RPT_ERR_INVALID, "null argument");
+    const rpti::SceneDev sd = rpti::scene_dev(s);
+    if (!sd.committed) return rpti::fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (!sd.epsilon64) return rpti::fail(RPT_ERR_STATE, "rpt_intersect_batch_f64 needs a scene committed with epsilon_policy = 1");
+    if (n == 0) return RPT_OK;
+    RPTI_HIP_TRY(hipSetDevice(sd.device));
+    struct Bufs {   // (freed on every return)
+        void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Bufs() { for (void* q : p) if (q) (void)hipFree(q); }
+    } b;
+    const size_t bytes[5] = {n * 24, n * 24, n * 8, n * 4, n * 24};   // origins, directions, t, object, normal
+    for (int i = 0; i < 5; i++) RPTI_HIP_TRY(hipMalloc(&b.p[i], bytes[i]));
+    RPTI_HIP_TRY(hipMemcpy(b.p[0], origins, bytes[0], hipMemcpyHostToDevice));
+    RPTI_HIP_TRY(hipMemcpy(b.p[1], dirs, bytes[1], hipMemcpyHostToDevice));
+    rpt64::IsectArgs64 q;
+    std::memset(&q, 0, sizeof(q));
+    rpti::fill_args64(s, nullptr, nullptr, nullptr, q.a);
+    q.n = n;
+    q.o = static_cast<const double*>(b.p[0]);
+    q.d = static_cast<const double*>(b.p[1]);
+    q.t = static_cast<double*>(b.p[2]);
+    q.obj = static_cast<int32_t*>(b.p[3]);
+    q.nrm = static_cast<double*>(b.p[4]);
+    RPTI_HIP_TRY(rptg::launch_intersect_f64(q, nullptr));
+    RPTI_HIP_TRY(hipMemcpy(t, b.p[2], bytes[2], hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(object, b.p[3], bytes[3], hipMemcpyDeviceToHost));
+    if (normal) RPTI_HIP_TRY(hipMemcpy(normal, b.p[4], bytes[4], hipMemcpyDeviceToHost));
+    return RPT_OK;
+}

@@ -2348,6 +2348,8 @@ static int photon_args_ok(rpt_scene* s, uint64_t photon_count, int32_t kind) {
     if (photon_count == 0) return rpti::fail(RPT_ERR_INVALID, "photon_count must be > 0");
     if (kind != RPT_PHOTON_POINT_BEAM && kind != RPT_PHOTON_MAP && kind != RPT_PHOTON_BEAM_BEAM)
         return rpti::fail(RPT_ERR_INVALID, "unknown PhotonRenderKind");
+    if (sd.has_monomial)   // (every photon.hip flavour would need the monomial surfaces' kernel flag)
+        return rpti::fail(RPT_ERR_UNSUPPORTED, "photon mapping does not support scenes with a MonomialSurface");
     if (sd.first_object_light < 0)
         return rpti::fail(RPT_ERR_INVALID, "Only found non-object lights while photon mapping");  // the reference's panic
     RPTI_HIP_TRY(hipSetDevice(sd.device));

@@ -286,6 +286,7 @@ bool same_shape(const HShape& a, const HShape& b) {
     if (a.d.has_transform && std::memcmp(a.d.transform, b.d.transform, sizeof(a.d.transform)) != 0) return false;
     if (a.d.kind == RPT_SHAPE_PLANE)
         return std::memcmp(a.d.plane_normal, b.d.plane_normal, 24) == 0 && a.d.plane_value == b.d.plane_value;
+    if (a.d.kind == RPT_SHAPE_MONOMIAL) return std::memcmp(a.d.plane_normal, b.d.plane_normal, 16) == 0;   // height, exp
     if (a.d.kind == RPT_SHAPE_MESH)
         return a.mesh == b.mesh || (a.T().size() == b.T().size() &&
                                     (a.T().empty() || std::memcmp(a.T().data(), b.T().data(), a.T().size() * 8) == 0));
@@ -568,7 +569,8 @@ static std::shared_ptr<const std::vector<double>> intern_mesh(rpt_scene* s, cons
 static bool copy_shape(rpt_scene* s, MeshCallCache& seen, const rpt_shape_desc* d, HShape& out, std::string& why,
                        int depth = 0) {
     if (!d) { why = "null shape"; return false; }
-    if (d->kind < 0 || d->kind > RPT_SHAPE_GROUP) { why = "unknown shape kind"; return false; }
+    if (d->kind < 0 || d->kind > RPT_SHAPE_MONOMIAL) { why = "unknown shape kind"; return false; }
+    if (d->kind == RPT_SHAPE_MONOMIAL && !std::isfinite(d->plane_normal[0])) { why = "MonomialSurface height must be finite"; return false; }
     out.d = *d;
     out.mesh.reset();
     out.children.clear();
@@ -590,6 +592,12 @@ static bool copy_shape(rpt_scene* s, MeshCallCache& seen, const rpt_shape_desc* 
     Xf x;
     if (!make_xf(*d, x)) { why = "singular transform"; return false; }
     return true;
+}
+static bool holds_monomial(const HShape& h) {
+    if (h.d.kind == RPT_SHAPE_MONOMIAL) return true;
+    for (const HShape& c : h.children)
+        if (holds_monomial(c)) return true;
+    return false;
 }
 static bool check_material(const rpt_material* m, std::string& why) {
     if (!m) { why = "null material"; return false; }
@@ -710,6 +718,9 @@ int rpt_scene_add_light_object(rpt_scene* s, const rpt_shape_desc* d, const rpt_
     if (!copy_shape(s, seen, d, l.obj.shape, why) || !check_material(m, why)) return fail(RPT_ERR_INVALID, why);
     if (d->kind == RPT_SHAPE_PLANE)
         return fail(RPT_ERR_INVALID, "a plane cannot be a Light::Object (Plane::sample is unimplemented in rpt)");
+    if (holds_monomial(l.obj.shape))
+        return fail(RPT_ERR_UNSUPPORTED, "a MonomialSurface (alone or in a KdTree group) cannot be a Light::Object: MonomialSurface::sample "
+                                         "is not built (src/shape/monomial_surface.rs:109-123)");
     l.obj.mat = *m;
     s->lights.push_back(std::move(l));
     return RPT_OK;
@@ -874,6 +885,9 @@ struct Flattener {
 
     // world-space boxes of the bounded primitives (scene-level tree, scan boxes)
     std::vector<PBox> box_sph, box_cub, box_tri, box_mesh;
+    std::vector<MonoScan> mono;       // monomial surfaces (scanned after the triangles)
+    std::vector<XfShade> mono_sh;
+    std::vector<PBox> box_mono;
     std::vector<InstRec> insts;
     std::vector<PBox> box_inst;
     std::unordered_map<const std::vector<double>*, uint32_t> mesh_uses;
@@ -900,6 +914,21 @@ struct Flattener {
             h += 1e-5 * (h + std::fabs(x.M[i][3]));
             b.lo[i] = float(x.M[i][3] - h);
             b.hi[i] = float(x.M[i][3] + h);
+        }
+        return b;
+    }
+    static PBox mono_box(const Xf& x, double ylo, double yhi) {  // the local box [-1, ylo, -1]..[1, yhi, 1] under an affine map
+        PBox b;
+        for (int i = 0; i < 3; i++) {
+            double lo = HUGE_VAL, hi = -HUGE_VAL;
+            for (int c = 0; c < 8; c++) {
+                const D3 q = x.point(D3{(c & 1) ? 1.0 : -1.0, (c & 2) ? yhi : ylo, (c & 4) ? 1.0 : -1.0});
+                lo = std::min(lo, comp(q, i));
+                hi = std::max(hi, comp(q, i));
+            }
+            const double pad = 1e-5 * (hi - lo + std::fabs(lo) + std::fabs(hi)) + 1e-30;
+            b.lo[i] = std::nextafter(float(lo - pad), -std::numeric_limits<float>::infinity());
+            b.hi[i] = std::nextafter(float(hi + pad), std::numeric_limits<float>::infinity());
         }
         return b;
     }
@@ -1022,6 +1051,22 @@ struct Flattener {
                 sh.r2 = F4{float(x.N[2][0]), float(x.N[2][1]), float(x.N[2][2]), 0.f};
                 if (shape.d.kind == RPT_SHAPE_SPHERE) { sph.push_back(sc); sph_sh.push_back(sh); box_sph.push_back(xf_box(x, true)); }
                 else { cub.push_back(sc); cub_sh.push_back(sh); box_cub.push_back(xf_box(x, false)); }
+                break;
+            }
+            case RPT_SHAPE_MONOMIAL: {  // src/shape/monomial_surface.rs: local records, the box of :181-187 (min / max per axis)
+                const double h = shape.d.plane_normal[0], ylo = std::min(0.0, h), yhi = std::max(0.0, h);
+                MonoScan m;
+                m.r0 = F4{float(x.Minv[0][0]), float(x.Minv[0][1]), float(x.Minv[0][2]), float(x.Minv[0][3])};
+                m.r1 = F4{float(x.Minv[1][0]), float(x.Minv[1][1]), float(x.Minv[1][2]), float(x.Minv[1][3])};
+                m.r2 = F4{float(x.Minv[2][0]), float(x.Minv[2][1]), float(x.Minv[2][2]), float(x.Minv[2][3])};
+                m.h = F4{float(h), float(ylo), float(yhi), 0.f};
+                XfShade sh;
+                sh.r0 = F4{float(x.N[0][0]), float(x.N[0][1]), float(x.N[0][2]), bits_f(obj)};
+                sh.r1 = F4{float(x.N[1][0]), float(x.N[1][1]), float(x.N[1][2]), x.has ? 1.f : 0.f};
+                sh.r2 = F4{float(x.N[2][0]), float(x.N[2][1]), float(x.N[2][2]), 0.f};
+                mono.push_back(m);
+                mono_sh.push_back(sh);
+                box_mono.push_back(mono_box(x, ylo, yhi));
                 break;
             }
             case RPT_SHAPE_PLANE: {
@@ -1205,7 +1250,7 @@ struct Flattener {
     void fold_shell() {
         // ---- box shell: rectangles that are exactly the faces of the box around all rectangles (the walls of a
         // room) leave the scanned list and are answered by one slab test; linear-scan scenes only
-        const size_t n_items_total = sph.size() + cub.size() + aabb.size() + tri.size() + insts.size() + meshes.size() +
+        const size_t n_items_total = sph.size() + cub.size() + aabb.size() + tri.size() + mono.size() + insts.size() + meshes.size() +
                                      rect_axis[0].size() + rect_axis[1].size() + rect_axis[2].size();
         const bool will_bvh = n_items_total >= size_t(std::max<int64_t>(2, s->opt.scene_bvh_min)) || !insts.empty();
         {
@@ -1325,6 +1370,7 @@ struct Flattener {
                     }
             }
             for (size_t i = 0; i < tri.size(); i++) add_item(box_tri[i].lo, box_tri[i].hi, (K_TRI << 28) | uint32_t(i));
+            for (size_t i = 0; i < mono.size(); i++) add_item(box_mono[i].lo, box_mono[i].hi, (K_MONO << 28) | uint32_t(i));
             for (size_t i = 0; i < insts.size(); i++) add_item(box_inst[i].lo, box_inst[i].hi, (K_INST << 28) | uint32_t(i));
             std::vector<uint8_t> solo(items.size(), 0);
             // Meshes with trees of their own: leaves of the scene tree (option "scene_tree_meshes" = 1), or -- the default when
@@ -1417,6 +1463,7 @@ struct Flattener {
                     push_box(lo, hi);
                 }
             for (const PBox& b : box_tri) push_box(b.lo, b.hi);
+            for (const PBox& b : box_mono) push_box(b.lo, b.hi);   // (after the triangles; no masked scan reads them: device_core.h)
         }
     }
     // (7) one arena for every array, the SceneView over it, statistics, per-launch scratch
@@ -1448,6 +1495,7 @@ struct Flattener {
         size_t o_lxf = reserve(lxf.size() * sizeof(LightXf));
         size_t o_lparts = reserve(lparts.size() * sizeof(LightPart));
         size_t o_hdri = reserve(s->hdri.size() * sizeof(float));
+        size_t o_mono = reserve(mono.size() * sizeof(MonoScan)), o_monos = reserve(mono_sh.size() * sizeof(XfShade));
         std::vector<char> host(off, 0);
         auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) std::memcpy(host.data() + o, src, bytes); };
         put(o_sph, sph.data(), sph.size() * sizeof(XfScan));       put(o_sphs, sph_sh.data(), sph_sh.size() * sizeof(XfShade));
@@ -1469,6 +1517,7 @@ struct Flattener {
         put(o_lxf, lxf.data(), lxf.size() * sizeof(LightXf));
         put(o_lparts, lparts.data(), lparts.size() * sizeof(LightPart));
         put(o_hdri, s->hdri.data(), s->hdri.size() * sizeof(float));
+        put(o_mono, mono.data(), mono.size() * sizeof(MonoScan));  put(o_monos, mono_sh.data(), mono_sh.size() * sizeof(XfShade));
         HIP_TRY(hipMalloc(&s->arena, off));
         HIP_TRY(hipMemcpy(s->arena, host.data(), off, hipMemcpyHostToDevice));
         char* base = static_cast<char*>(s->arena);
@@ -1488,6 +1537,7 @@ struct Flattener {
         v.scene_bvh = scene_bvh ? 1u : 0u;          v.top_root = top_root;
         v.mesh_deferred = (scene_bvh && mesh_deferred) ? 1u : 0u;
         v.inst = (const InstRec*)(base + o_inst);   v.n_inst = uint32_t(insts.size());
+        v.mono = (const MonoScan*)(base + o_mono);  v.mono_sh = (const XfShade*)(base + o_monos);  v.n_mono = uint32_t(mono.size());
         v.mats = (const Material*)(base + o_mats);  v.n_obj = uint32_t(mats.size());
         v.lights = (const Light*)(base + o_lights); v.n_lights = uint32_t(lights.size());
         v.ltris = (const LightTri*)(base + o_ltris); v.lxf = (const LightXf*)(base + o_lxf);
@@ -1652,6 +1702,10 @@ static rpt64::CullBox cull_box64(const rpt64::Shape& sh) {
         const double h = sh.kind == rpt64::SH_SPHERE ? 1.0 : 0.5;
         lo[k] = sh.kind == rpt64::SH_MESH ? sh.bmin[k] : -h;
         hi[k] = sh.kind == rpt64::SH_MESH ? sh.bmax[k] : h;
+        if (sh.kind == rpt64::SH_MONO) {   // src/shape/monomial_surface.rs:181-187, min / max per axis (a height <= 0 flips y)
+            lo[k] = k == 1 ? std::min(0.0, sh.plane[0]) : -1.0;
+            hi[k] = k == 1 ? std::max(0.0, sh.plane[0]) : 1.0;
+        }
     }
     double wlo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, whi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
     for (int corner = 0; corner < 8; corner++) {
@@ -1685,6 +1739,9 @@ static Box64 bbox64(const HShape& hs) {
     if (hs.d.kind == RPT_SHAPE_SPHERE || hs.d.kind == RPT_SHAPE_CUBE) {
         const double h = hs.d.kind == RPT_SHAPE_SPHERE ? 1.0 : 0.5;
         for (int k = 0; k < 3; k++) { b.lo[k] = -h; b.hi[k] = h; }
+    } else if (hs.d.kind == RPT_SHAPE_MONOMIAL) {   // src/shape/monomial_surface.rs:181-187 (KdTree::new merges it with min / max)
+        const double h = hs.d.plane_normal[0];
+        for (int k = 0; k < 3; k++) { b.lo[k] = k == 1 ? std::min(0.0, h) : -1.0; b.hi[k] = k == 1 ? std::max(0.0, h) : 1.0; }
     } else if (hs.d.kind == RPT_SHAPE_MESH) {
         const std::vector<double>& T = hs.T();
         for (size_t t = 0; t < T.size() / 18; t++)
@@ -1764,6 +1821,7 @@ static int flatten64(const HShape& hs, const rpt_material& mat, std::vector<uint
         if (sh.kind == rpt64::SH_MESH) { r.b[k] = sh.bmin[k]; r.b[3 + k] = sh.bmax[k]; }
         else if (sh.kind == rpt64::SH_CUBE) { r.b[k] = -0.5; r.b[3 + k] = 0.5; }
         else if (sh.kind == rpt64::SH_PLANE) { r.b[k] = sh.plane[k]; }
+        else if (sh.kind == rpt64::SH_MONO) { r.b[k] = k == 1 ? 0.0 : -1.0; r.b[3 + k] = k == 1 ? sh.plane[0] : 1.0; }   // p_min, p_max as given
     }
     if (sh.kind == rpt64::SH_PLANE) r.b[3] = sh.plane[3];
     // the fp32 world box: the shape's own box under its matrix, then under the groups' matrices, innermost first
@@ -1968,6 +2026,9 @@ extern "C++" void rpti::fill_args64(rpt_scene* s, const rpt_camera* cam, const r
     q.group_lights = 0u;
     for (const auto& l : s->lights)
         if (l.kind == int(L_OBJECT) && l.obj.shape.d.kind == RPT_SHAPE_GROUP) q.group_lights = 1u;
+    q.mono = 0u;
+    for (const auto& o : s->objects)
+        if (holds_monomial(o.shape)) q.mono = 1u;
     if (cam) {
         const D3 dir = d3(cam->direction), up = d3(cam->up);
         const D3 right = normalize(cross(dir, up));   // src/camera.rs:67-68
@@ -2286,7 +2347,9 @@ extern "C++" rpti::SceneDev rpti::scene_dev(rpt_scene* s) {
     int first = -1;
     for (size_t i = 0; i < s->lights.size(); i++)
         if (s->lights[i].kind == L_OBJECT) { first = int(i); break; }
-    return SceneDev{s->committed, s->device, s->n_cus, s->view, first, s->arena64 != nullptr};
+    bool mono = false;
+    for (const auto& o : s->objects) mono = mono || holds_monomial(o.shape);
+    return SceneDev{s->committed, s->device, s->n_cus, s->view, first, s->arena64 != nullptr, mono};
 }
 extern "C++" void*& rpti::photon_slot(rpt_scene* s) { return s->photon; }
 extern "C++" int64_t rpti::option_photon_skip(rpt_scene* s) { return s->opt.photon_skip; }

@@ -11,8 +11,8 @@ import math
 
 import numpy as np
 
-from .api import (Camera, KdTree, Light, Material, Medium, Mesh, Object, Scene, Transformed, cube, hex_color, plane,
-                  polygon, sphere, vec3)
+from .api import (Camera, Environment, KdTree, Light, Material, Medium, Mesh, Object, Scene, Transformed, cube, hex_color,
+                  monomial_surface, plane, polygon, sphere, vec3)
 
 
 def spheres():
@@ -256,6 +256,23 @@ def fractal_meshes(levels=5, nu=48, nv=24):
     for l in scene.lights:
         out.add(l)
     return out, camera, cfg
+
+
+def monomial_glass(env=(0.6, 0.65, 0.7)):
+    """examples/monomial_glass.rs:30-86 (800x600x100, max_bounces(1) there): a metallic MonomialSurface "glass" with a cube, two
+    spheres and a floor.  The example downloads an HDRI (ballroom_2k.hdr); a constant environment `env` stands in for it.  Not in
+    CONFIGS (bench.py reads that)."""
+    scene = Scene()
+    scene.environment = Environment.Color(vec3(*env))
+    scene.add(Object(monomial_surface(2.0, 4.0).translate(vec3(0.0, -1.0, 0.0))).material(Material.metallic(hex_color(0xFFFFFF), 0.0001)))
+    scene.add(Object(cube().rotate_y(math.pi / 6.0).scale(vec3(0.5, 0.3, 0.4)).translate(vec3(0.4, -0.8, 4.0)))
+              .material(Material.specular(hex_color(0xFF00FF), 0.5)))
+    scene.add(Object(sphere().scale(vec3(0.5, 0.5, 0.5)).translate(vec3(1.5, -0.5, 1.0))).material(Material.specular(hex_color(0x0000FF), 0.1)))
+    scene.add(Object(sphere().scale(vec3(0.5, 0.5, 0.5)).translate(vec3(-1.5, -0.5, 1.0))).material(Material.specular(hex_color(0x00FF00), 0.1)))
+    scene.add(Object(plane(vec3(0.0, 1.0, 0.0), -1.0)).material(Material.specular(hex_color(0xAAAAAA), 0.5)))
+    scene.add(Light.Ambient(vec3(0.01, 0.01, 0.01)))
+    scene.add(Light.Point(vec3(100.0, 100.0, 100.0), vec3(0.0, 5.0, 5.0)))
+    return scene, Camera(), {"width": 800, "height": 600, "spp": 100, "max_bounces": 1}
 
 
 CONFIGS = {
