@@ -4,6 +4,7 @@
 
 #include <functional>
 #include <string>
+#include <utility>
 
 #include "../../include/rpt_hip.h"
 #include "kernels.h"
@@ -11,6 +12,82 @@
 namespace rpt64 { struct Args; }
 
 namespace rpti {
+// One hipMalloc block and its byte capacity, freed when the owner is reset, reassigned or destroyed.  hipFree runs on the
+// device that is current then: whoever destroys an owner of another device's memory sets that device first.
+class DevMem {
+  public:
+    DevMem() = default;
+    DevMem(DevMem&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+    DevMem& operator=(DevMem&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = std::exchange(o.p_, nullptr);
+            cap_ = std::exchange(o.cap_, 0);
+        }
+        return *this;
+    }
+    ~DevMem() { reset(); }
+    // Grow-only.  The old block is freed before the new one is allocated (peak memory stays one block), so a failure
+    // leaves an empty owner, never a capacity without memory behind it.
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= cap_) return hipSuccess;
+        hipError_t e = p_ ? hipFree(p_) : hipSuccess;
+        p_ = nullptr;
+        cap_ = 0;
+        if (e == hipSuccess) e = hipMalloc(&p_, bytes);
+        if (e != hipSuccess) { p_ = nullptr; return e; }
+        cap_ = bytes;
+        return hipSuccess;
+    }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    template <class T = void>
+    T* get() const { return static_cast<T*>(p_); }
+    size_t capacity() const { return cap_; }
+    explicit operator bool() const { return p_ != nullptr; }
+
+  private:
+    void* p_ = nullptr;
+    size_t cap_ = 0;
+};
+// One hipEvent_t, destroyed with its owner (on the device that is current then, as for DevMem).
+class Event {
+  public:
+    Event() = default;
+    Event(Event&& o) noexcept : e_(std::exchange(o.e_, nullptr)) {}
+    Event& operator=(Event&& o) noexcept {
+        if (this != &o) {
+            reset();
+            e_ = std::exchange(o.e_, nullptr);
+        }
+        return *this;
+    }
+    ~Event() { reset(); }
+    hipError_t create(unsigned flags = hipEventDefault) {
+        reset();
+        hipError_t e = hipEventCreateWithFlags(&e_, flags);
+        if (e != hipSuccess) e_ = nullptr;
+        return e;
+    }
+    void reset() {
+        if (e_) (void)hipEventDestroy(e_);
+        e_ = nullptr;
+    }
+    hipEvent_t get() const { return e_; }
+
+  private:
+    hipEvent_t e_ = nullptr;
+};
+// Milliseconds between two recorded events (0 if the runtime cannot tell).
+inline float elapsed_ms(const Event& a, const Event& b) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, a.get(), b.get());
+    return ms;
+}
+
 int fail(int code, const std::string& msg);
 uint64_t seed_mix(uint64_t seed);
 struct SceneDev {

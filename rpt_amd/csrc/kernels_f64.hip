@@ -1589,26 +1589,26 @@ extern "C" int rpt_intersect_batch_f64(rpt_scene* s, uint64_t n, const double* o
     if (!sd.epsilon64) return rpti::fail(RPT_ERR_STATE, "rpt_intersect_batch_f64 needs a scene committed with epsilon_policy = 1");
     if (n == 0) return RPT_OK;
     RPTI_HIP_TRY(hipSetDevice(sd.device));
-    struct Bufs {   // (freed on every return)
-        void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Bufs() { for (void* q : p) if (q) (void)hipFree(q); }
-    } b;
-    const size_t bytes[5] = {n * 24, n * 24, n * 8, n * 4, n * 24};   // origins, directions, t, object, normal
-    for (int i = 0; i < 5; i++) RPTI_HIP_TRY(hipMalloc(&b.p[i], bytes[i]));
-    RPTI_HIP_TRY(hipMemcpy(b.p[0], origins, bytes[0], hipMemcpyHostToDevice));
-    RPTI_HIP_TRY(hipMemcpy(b.p[1], dirs, bytes[1], hipMemcpyHostToDevice));
+    rpti::DevMem d_o, d_d, d_t, d_obj, d_nrm;
+    RPTI_HIP_TRY(d_o.reserve(n * 24));
+    RPTI_HIP_TRY(d_d.reserve(n * 24));
+    RPTI_HIP_TRY(d_t.reserve(n * 8));
+    RPTI_HIP_TRY(d_obj.reserve(n * 4));
+    RPTI_HIP_TRY(d_nrm.reserve(n * 24));
+    RPTI_HIP_TRY(hipMemcpy(d_o.get(), origins, n * 24, hipMemcpyHostToDevice));
+    RPTI_HIP_TRY(hipMemcpy(d_d.get(), dirs, n * 24, hipMemcpyHostToDevice));
     rpt64::IsectArgs64 q;
     std::memset(&q, 0, sizeof(q));
     rpti::fill_args64(s, nullptr, nullptr, nullptr, q.a);
     q.n = n;
-    q.o = static_cast<const double*>(b.p[0]);
-    q.d = static_cast<const double*>(b.p[1]);
-    q.t = static_cast<double*>(b.p[2]);
-    q.obj = static_cast<int32_t*>(b.p[3]);
-    q.nrm = static_cast<double*>(b.p[4]);
+    q.o = d_o.get<const double>();
+    q.d = d_d.get<const double>();
+    q.t = d_t.get<double>();
+    q.obj = d_obj.get<int32_t>();
+    q.nrm = d_nrm.get<double>();
     RPTI_HIP_TRY(rptg::launch_intersect_f64(q, nullptr));
-    RPTI_HIP_TRY(hipMemcpy(t, b.p[2], bytes[2], hipMemcpyDeviceToHost));
-    RPTI_HIP_TRY(hipMemcpy(object, b.p[3], bytes[3], hipMemcpyDeviceToHost));
-    if (normal) RPTI_HIP_TRY(hipMemcpy(normal, b.p[4], bytes[4], hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(t, d_t.get(), n * 8, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(object, d_obj.get(), n * 4, hipMemcpyDeviceToHost));
+    if (normal) RPTI_HIP_TRY(hipMemcpy(normal, d_nrm.get(), n * 24, hipMemcpyDeviceToHost));
     return RPT_OK;
 }

@@ -1967,77 +1967,78 @@ struct DevPool {
         }
     }
 };
+// n values of T in a block of a DevPool, back in the pool when the handle is reset, reassigned or destroyed: a handle must
+// not outlive its pool.  Scratch of one build step is a local handle (the step ends with a synchronise).
+template <class T>
+class PoolMem {
+  public:
+    PoolMem() = default;
+    PoolMem(PoolMem&& o) noexcept : pool_(o.pool_), p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+    PoolMem& operator=(PoolMem&& o) noexcept {
+        if (this != &o) {
+            reset();
+            pool_ = o.pool_;
+            p_ = std::exchange(o.p_, nullptr);
+            n_ = std::exchange(o.n_, 0);
+        }
+        return *this;
+    }
+    ~PoolMem() { reset(); }
+    hipError_t alloc(DevPool& pool, size_t n) {
+        reset();
+        pool_ = &pool;
+        void* p = nullptr;
+        hipError_t e = pool.alloc(&p, n * sizeof(T));
+        if (e != hipSuccess) return e;
+        p_ = static_cast<T*>(p);
+        n_ = n;
+        return hipSuccess;
+    }
+    // grow-only, for the buffers a map keeps from one camera pass to the next
+    hipError_t reserve(DevPool& pool, size_t n) { return n <= n_ ? hipSuccess : alloc(pool, n); }
+    void reset() {
+        if (p_) pool_->free(p_);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    T* get() const { return p_; }
+
+  private:
+    DevPool* pool_ = nullptr;
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
 struct DevLbvh {
-    BvhNode* nodes = nullptr;
-    PhotonRec* sorted = nullptr;
+    PoolMem<BvhNode> nodes;
+    PoolMem<PhotonRec> sorted;
     uint32_t n = 0;
 };
 struct PhotonMapDev {
+    // declared first, so that it is destroyed after the buffers that go back to it
+    std::shared_ptr<DevPool> pool = std::make_shared<DevPool>();   // handed on to the scene's next map (fresh_map)
     int device = 0;
     int kind = RPT_PHOTON_POINT_BEAM;
     uint64_t photon_count = 0;
     DevLbvh surf, vol;
     bool built = false;
     // records of the last shooting pass in shooting order (kept for rpt_photon_records / all-gather)
-    PhotonRec *raw_s = nullptr, *raw_v = nullptr;
+    PoolMem<PhotonRec> raw_s, raw_v;
     uint64_t n_raw_s = 0, n_raw_v = 0;
     double build_ms[4] = {0, 0, 0, 0};  // shoot, sort+build, radii, total
-    uint32_t* d_overflow = nullptr;
-    uint32_t* d_cand = nullptr;  // per-wave candidate lists of the camera pass
-    size_t cand_words = 0;
-    uint32_t* d_gather = nullptr;  // per-wave k-nearest lists of gathers too large for LDS
-    size_t gather_words = 0;
-    float* d_slab2 = nullptr;      // the surface term's partial sums of the split camera pass
-    size_t slab2_bytes = 0;
+    PoolMem<uint32_t> d_overflow;
+    PoolMem<uint32_t> d_cand;    // per-wave candidate lists of the camera pass
+    PoolMem<uint32_t> d_gather;  // per-wave k-nearest lists of gathers too large for LDS
+    PoolMem<float> d_slab2;      // the surface term's partial sums of the split camera pass
     // reference-epsilon mode (kernels_f64.hip): the surface photons' fp64 positions in shooting order, the camera pass's per-sample
     // selections of one slice of samples, and the fp64 partial sums of its surface estimate
-    double* pos64 = nullptr;
-    uint32_t* d_emit = nullptr;
-    size_t emit_words = 0;
-    double* d_slab64 = nullptr;
-    size_t slab64_bytes = 0;
+    PoolMem<double> pos64;
+    PoolMem<uint32_t> d_emit;
+    PoolMem<double> d_slab64;
     uint64_t emit_dims[3] = {0, 0, 0};   // of the last slice: owned pixel slots, gather_size + 2, samples
-    std::shared_ptr<DevPool> pool = std::make_shared<DevPool>();   // handed on to the scene's next map (fresh_map)
     void release_raw() {
-        pool->free(raw_s); pool->free(raw_v);
-        raw_s = raw_v = nullptr;
+        raw_s.reset();
+        raw_v.reset();
         n_raw_s = n_raw_v = 0;
-    }
-    void release() {
-        (void)hipSetDevice(device);
-        pool->free(surf.nodes); pool->free(surf.sorted);
-        pool->free(vol.nodes); pool->free(vol.sorted);
-        pool->free(d_overflow);
-        pool->free(d_cand);
-        pool->free(d_gather);
-        pool->free(d_slab2);
-        d_slab2 = nullptr;
-        slab2_bytes = 0;
-        pool->free(pos64); pool->free(d_emit); pool->free(d_slab64);
-        pos64 = nullptr; d_emit = nullptr; d_slab64 = nullptr;
-        emit_words = slab64_bytes = 0;
-        release_raw();
-        d_overflow = nullptr;
-        d_cand = nullptr;
-        d_gather = nullptr;
-        cand_words = gather_words = 0;
-        surf = DevLbvh{};
-        vol = DevLbvh{};
-        built = false;
-    }
-};
-struct Tmp {   // scratch buffers of one build step, back in the pool when it is over (the step ends with a synchronise)
-    DevPool& pool;
-    std::vector<void*> ptrs;
-    explicit Tmp(DevPool& p) : pool(p) {}
-    ~Tmp() {
-        for (void* p : ptrs) pool.free(p);
-    }
-    template <class T>
-    hipError_t alloc(T** p, size_t n) {
-        hipError_t e = pool.alloc((void**)p, n * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
     }
 };
 
@@ -2050,24 +2051,28 @@ int build_lbvh(DevPool& pool, PhotonRec* raw, uint32_t n, int mode, DevLbvh& out
     out = DevLbvh{};
     out.n = n;
     if (n == 0) return RPT_OK;
-    Tmp tmp(pool);
-    float* lohi;
-    uint64_t *keys, *keys2;
-    uint32_t *vals, *vals2, *left, *right, *par_i, *par_l, *flags, *rlo, *rhi;
-    float* box;
-    RPTI_HIP_TRY(tmp.alloc(&lohi, 6));
-    RPTI_HIP_TRY(tmp.alloc(&keys, n));
-    RPTI_HIP_TRY(tmp.alloc(&keys2, n));
-    RPTI_HIP_TRY(tmp.alloc(&vals, n));
-    RPTI_HIP_TRY(tmp.alloc(&vals2, n));
-    RPTI_HIP_TRY(tmp.alloc(&left, n));
-    RPTI_HIP_TRY(tmp.alloc(&right, n));
-    RPTI_HIP_TRY(tmp.alloc(&par_i, n));
-    RPTI_HIP_TRY(tmp.alloc(&par_l, n));
-    RPTI_HIP_TRY(tmp.alloc(&flags, n));
-    RPTI_HIP_TRY(tmp.alloc(&rlo, n));
-    RPTI_HIP_TRY(tmp.alloc(&rhi, n));
-    RPTI_HIP_TRY(tmp.alloc(&box, size_t(n) * 6));
+    PoolMem<float> m_lohi, m_box, m_radius;
+    PoolMem<uint64_t> m_keys, m_keys2;
+    PoolMem<uint32_t> m_vals, m_vals2, m_left, m_right, m_par_i, m_par_l, m_flags, m_rlo, m_rhi;
+    PoolMem<char> m_temp;
+    RPTI_HIP_TRY(m_lohi.alloc(pool, 6));
+    RPTI_HIP_TRY(m_keys.alloc(pool, n));
+    RPTI_HIP_TRY(m_keys2.alloc(pool, n));
+    RPTI_HIP_TRY(m_vals.alloc(pool, n));
+    RPTI_HIP_TRY(m_vals2.alloc(pool, n));
+    RPTI_HIP_TRY(m_left.alloc(pool, n));
+    RPTI_HIP_TRY(m_right.alloc(pool, n));
+    RPTI_HIP_TRY(m_par_i.alloc(pool, n));
+    RPTI_HIP_TRY(m_par_l.alloc(pool, n));
+    RPTI_HIP_TRY(m_flags.alloc(pool, n));
+    RPTI_HIP_TRY(m_rlo.alloc(pool, n));
+    RPTI_HIP_TRY(m_rhi.alloc(pool, n));
+    RPTI_HIP_TRY(m_box.alloc(pool, size_t(n) * 6));
+    float *const lohi = m_lohi.get(), *const box = m_box.get();
+    uint64_t *const keys = m_keys.get(), *const keys2 = m_keys2.get();
+    uint32_t *const vals = m_vals.get(), *const vals2 = m_vals2.get(), *const left = m_left.get(), *const right = m_right.get(),
+                   *const par_i = m_par_i.get(), *const par_l = m_par_l.get(), *const flags = m_flags.get(), *const rlo = m_rlo.get(),
+                   *const rhi = m_rhi.get();
     const float inf = std::numeric_limits<float>::infinity();
     float init[6] = {inf, inf, inf, -inf, -inf, -inf};
     RPTI_HIP_TRY(hipMemcpyAsync(lohi, init, sizeof(init), hipMemcpyHostToDevice, st));
@@ -2076,30 +2081,30 @@ int build_lbvh(DevPool& pool, PhotonRec* raw, uint32_t n, int mode, DevLbvh& out
     hipLaunchKernelGGL(morton_kernel, dim3(blocks), dim3(256), 0, st, raw, n, lohi, keys, vals, first_mode);
     // stable radix sort of (Morton key, photon index), eight 8-bit passes; the last one gathers the records (sort_scan.h).  Equal keys
     // keep their shooting order, so the sorted array -- and with it the tree -- is a function of the photons alone.
-    char* temp;
-    RPTI_HIP_TRY(tmp.alloc(&temp, ss::rsort_temp_bytes(n)));
-    RPTI_HIP_TRY(pool.alloc((void**)&out.sorted, size_t(n) * sizeof(PhotonRec)));
-    RPTI_HIP_TRY(ss::radix_sort_pairs(keys, vals, keys2, vals2, n, 8u, temp, GatherPhotons{raw, out.sorted, keys}, st));   // (pass 7 reads keys2 / vals2: keys is free for the sorted keys)
+    RPTI_HIP_TRY(m_temp.alloc(pool, ss::rsort_temp_bytes(n)));
+    RPTI_HIP_TRY(out.sorted.alloc(pool, n));
+    PhotonRec* const sorted = out.sorted.get();
+    RPTI_HIP_TRY(ss::radix_sort_pairs(keys, vals, keys2, vals2, n, 8u, m_temp.get(), GatherPhotons{raw, sorted, keys}, st));   // (pass 7 reads keys2 / vals2: keys is free for the sorted keys)
     if (n >= 2) {
-        RPTI_HIP_TRY(pool.alloc((void**)&out.nodes, size_t(n - 1) * sizeof(BvhNode)));
+        RPTI_HIP_TRY(out.nodes.alloc(pool, n - 1));
         hipLaunchKernelGGL(karras_kernel, dim3(blocks), dim3(256), 0, st, keys, int(n), left, right, par_i, par_l, rlo, rhi);
         RPTI_HIP_TRY(hipMemsetAsync(flags, 0, size_t(n) * 4, st));
-        hipLaunchKernelGGL(refit_small_kernel, dim3(blocks), dim3(256), 0, st, out.sorted, int(n), rlo, rhi, box, first_mode);
-        hipLaunchKernelGGL(refit_kernel, dim3(2u * blocks), dim3(256), 0, st, out.sorted, int(n), left, right, par_i, par_l, rlo, rhi, flags, box, first_mode);
+        hipLaunchKernelGGL(refit_small_kernel, dim3(blocks), dim3(256), 0, st, sorted, int(n), rlo, rhi, box, first_mode);
+        hipLaunchKernelGGL(refit_kernel, dim3(2u * blocks), dim3(256), 0, st, sorted, int(n), left, right, par_i, par_l, rlo, rhi, flags, box, first_mode);
         // point trees are walked by the k-NN search only (radii, gathers): collapsed leaves
-        hipLaunchKernelGGL(pack_kernel, dim3(blocks), dim3(256), 0, st, out.sorted, int(n), left, right, box, rlo, rhi, par_i, out.nodes,
+        hipLaunchKernelGGL(pack_kernel, dim3(blocks), dim3(256), 0, st, sorted, int(n), left, right, box, rlo, rhi, par_i, out.nodes.get(),
                            first_mode, first_mode == 0 ? kKnnLeaf : 1u);
     }
     if (with_radius) {
-        float* radius;
-        RPTI_HIP_TRY(tmp.alloc(&radius, n));
-        hipLaunchKernelGGL(knn_radius_kernel, dim3(blocks), dim3(256), 0, st, out.nodes, out.sorted, n, radius);
-        hipLaunchKernelGGL(set_radius_kernel, dim3(blocks), dim3(256), 0, st, out.sorted, n, radius);
+        RPTI_HIP_TRY(m_radius.alloc(pool, n));
+        float* const radius = m_radius.get();
+        hipLaunchKernelGGL(knn_radius_kernel, dim3(blocks), dim3(256), 0, st, out.nodes.get(), sorted, n, radius);
+        hipLaunchKernelGGL(set_radius_kernel, dim3(blocks), dim3(256), 0, st, sorted, n, radius);
         if (n >= 2) {
             RPTI_HIP_TRY(hipMemsetAsync(flags, 0, size_t(n) * 4, st));
-            hipLaunchKernelGGL(refit_small_kernel, dim3(blocks), dim3(256), 0, st, out.sorted, int(n), rlo, rhi, box, 1);
-            hipLaunchKernelGGL(refit_kernel, dim3(2u * blocks), dim3(256), 0, st, out.sorted, int(n), left, right, par_i, par_l, rlo, rhi, flags, box, 1);
-            hipLaunchKernelGGL(pack_kernel, dim3(blocks), dim3(256), 0, st, out.sorted, int(n), left, right, box, rlo, rhi, par_i, out.nodes, 1,
+            hipLaunchKernelGGL(refit_small_kernel, dim3(blocks), dim3(256), 0, st, sorted, int(n), rlo, rhi, box, 1);
+            hipLaunchKernelGGL(refit_kernel, dim3(2u * blocks), dim3(256), 0, st, sorted, int(n), left, right, par_i, par_l, rlo, rhi, flags, box, 1);
+            hipLaunchKernelGGL(pack_kernel, dim3(blocks), dim3(256), 0, st, sorted, int(n), left, right, box, rlo, rhi, par_i, out.nodes.get(), 1,
                                1u);  // sphere tree for the beam walkers: one photon per leaf
         }
     }
@@ -2125,7 +2130,7 @@ hipError_t launch_shoot(const ShootArgs& a, bool medium, bool bvh, int blocks, h
 void rpti::photon_release(void* p) {
     auto* m = static_cast<PhotonMapDev*>(p);
     if (m) {
-        m->release();
+        (void)hipSetDevice(m->device);
         delete m;
     }
 }
@@ -2193,80 +2198,17 @@ static void launch_query_emit(const QueryArgs& q, bool medium, bool bvh, bool gg
 
 extern "C" {
 
-// The shooting pass of the reference-epsilon mode: same two passes, same streams, same record arrays; the chains are traced by
-// kernels_f64.hip (t_min = 1e-12, fp64), which also keeps every surface photon's position in fp64 (pm->pos64).
-static int shoot_range64(rpt_scene* s, PhotonMapDev* pm, uint64_t photon_count, uint64_t first, uint64_t n, int32_t kind,
-                         double watts, uint64_t seed) {
-    rpti::SceneDev sd = rpti::scene_dev(s);
-    hipStream_t st = nullptr;
-    hipEvent_t e0, e1;
-    RPTI_HIP_TRY(hipEventCreate(&e0));
-    RPTI_HIP_TRY(hipEventCreate(&e1));
-    Tmp tmp(*pm->pool);
-    rpt64::ShootArgs64 a{};
-    rpti::fill_args64(s, nullptr, nullptr, nullptr, a.a);
-    a.a.seed_mixed = rpti::seed_mix(seed);
-    a.n_photons = n;
-    a.first_photon = first;
-    a.power = watts / double(photon_count);
-    a.light_index = uint32_t(sd.first_object_light);
-    a.kind = uint32_t(kind);
-    pm->release_raw();
-    pm->pool->free(pm->pos64);
-    pm->pos64 = nullptr;
-    if (n == 0) return RPT_OK;
-    RPTI_HIP_TRY(tmp.alloc(&a.cnt_s, n));
-    RPTI_HIP_TRY(tmp.alloc(&a.cnt_v, n));
-    RPTI_HIP_TRY(tmp.alloc(&a.a.queue, 1));
-    const int blocks = int(std::min<uint64_t>((n + 255) / 256, uint64_t(sd.n_cus) * 4));
-    RPTI_HIP_TRY(hipEventRecord(e0, st));
-    RPTI_HIP_TRY(hipMemsetAsync(a.a.queue, 0, 8, st));
-    RPTI_HIP_TRY(launch_photon_shoot_f64(a, blocks, st));
-    uint32_t *d_os, *d_ov;
-    RPTI_HIP_TRY(tmp.alloc(&d_os, n));
-    RPTI_HIP_TRY(tmp.alloc(&d_ov, n));
-    char* scan_tmp;
-    RPTI_HIP_TRY(tmp.alloc(&scan_tmp, std::max<size_t>(ss::scan2_temp_bytes(uint32_t(n)), 8)));
-    unsigned long long* d_tot;
-    RPTI_HIP_TRY(tmp.alloc(&d_tot, 2));
-    RPTI_HIP_TRY(ss::exclusive_scan2(a.cnt_s, a.cnt_v, uint32_t(n), d_os, d_ov, d_tot, scan_tmp, st));
-    unsigned long long tot[2] = {0, 0};
-    RPTI_HIP_TRY(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st));
-    RPTI_HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t ts = tot[0], tv = tot[1];
-    if (ts >= (1ull << 26) || tv >= (1ull << 26)) return rpti::fail(RPT_ERR_UNSUPPORTED, "too many photons (2^26 records per map)");
-    RPTI_HIP_TRY(pm->pool->alloc((void**)&pm->raw_s, ts * sizeof(PhotonRec)));
-    RPTI_HIP_TRY(pm->pool->alloc((void**)&pm->raw_v, tv * sizeof(PhotonRec)));
-    RPTI_HIP_TRY(pm->pool->alloc((void**)&pm->pos64, ts * 24u));
-    pm->n_raw_s = ts;
-    pm->n_raw_v = tv;
-    a.off_s = d_os;
-    a.off_v = d_ov;
-    a.surf = reinterpret_cast<rpt64::PhotonRec32*>(pm->raw_s);
-    a.vol = reinterpret_cast<rpt64::PhotonRec32*>(pm->raw_v);
-    a.pos64 = pm->pos64;
-    RPTI_HIP_TRY(hipMemsetAsync(a.a.queue, 0, 8, st));
-    RPTI_HIP_TRY(launch_photon_shoot_f64(a, blocks, st));
-    RPTI_HIP_TRY(hipEventRecord(e1, st));
-    RPTI_HIP_TRY(hipEventSynchronize(e1));
-    float m0 = 0;
-    (void)hipEventElapsedTime(&m0, e0, e1);
-    pm->build_ms[0] = m0;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return RPT_OK;
-}
-
 // Shooting pass for photons [first, first + n) of a map of `photon_count` photons: count, prefix, write.
-// Leaves the records in pm->raw_s / raw_v in shooting order.
+// Leaves the records in pm->raw_s / raw_v in shooting order.  The reference-epsilon mode runs the same two passes with the
+// chains traced by kernels_f64.hip (t_min = 1e-12, fp64), which also keeps every surface photon's position in fp64 (pm->pos64).
 static int shoot_range(rpt_scene* s, PhotonMapDev* pm, uint64_t photon_count, uint64_t first, uint64_t n, int32_t kind,
                        double watts, uint64_t seed) {
-    rpti::SceneDev sd = rpti::scene_dev(s);
-    if (sd.epsilon64) return shoot_range64(s, pm, photon_count, first, n, kind, watts, seed);
+    const rpti::SceneDev sd = rpti::scene_dev(s);
+    const bool f64 = sd.epsilon64;
     hipStream_t st = nullptr;
-    hipEvent_t e0, e1;
-    RPTI_HIP_TRY(hipEventCreate(&e0));
-    RPTI_HIP_TRY(hipEventCreate(&e1));
-    Tmp tmp(*pm->pool);
+    rpti::Event e0, e1;
+    RPTI_HIP_TRY(e0.create());
+    RPTI_HIP_TRY(e1.create());
     ShootArgs a{};
     a.sc = sd.view;
     a.n_photons = n;
@@ -2275,44 +2217,64 @@ static int shoot_range(rpt_scene* s, PhotonMapDev* pm, uint64_t photon_count, ui
     a.power = float(watts / double(photon_count));
     a.light_index = uint32_t(sd.first_object_light);
     a.kind = uint32_t(kind);
+    rpt64::ShootArgs64 a64{};
+    if (f64) {
+        rpti::fill_args64(s, nullptr, nullptr, nullptr, a64.a);
+        a64.a.seed_mixed = a.seed_mixed;
+        a64.power = watts / double(photon_count);
+    }
     pm->release_raw();
+    pm->pos64.reset();
     if (n == 0) return RPT_OK;
-    RPTI_HIP_TRY(tmp.alloc(&a.cnt_s, n));
-    RPTI_HIP_TRY(tmp.alloc(&a.cnt_v, n));
+    PoolMem<uint32_t> cnt_s, cnt_v, off_s, off_v;
+    PoolMem<unsigned long long> queue, d_tot;
+    PoolMem<char> scan_tmp;
+    RPTI_HIP_TRY(cnt_s.alloc(*pm->pool, n));
+    RPTI_HIP_TRY(cnt_v.alloc(*pm->pool, n));
+    a.cnt_s = cnt_s.get();
+    a.cnt_v = cnt_v.get();
+    if (f64) RPTI_HIP_TRY(queue.alloc(*pm->pool, 1));
     const bool medium = sd.view.has_medium != 0, bvh = sd.view.n_nodes != 0;
-    int blocks = int(std::min<uint64_t>((n + 255) / 256, uint64_t(sd.n_cus) * 8));
-    RPTI_HIP_TRY(hipEventRecord(e0, st));
-    RPTI_HIP_TRY(launch_shoot<false>(a, medium, bvh, blocks, st));
+    const int blocks = int(std::min<uint64_t>((n + 255) / 256, uint64_t(sd.n_cus) * (f64 ? 4 : 8)));
+    // the count pass (no record arrays yet), then the write pass
+    auto launch = [&](bool write) -> hipError_t {
+        if (!f64) return !write ? launch_shoot<false>(a, medium, bvh, blocks, st) : launch_shoot<true>(a, medium, bvh, blocks, st);
+        a64.n_photons = a.n_photons; a64.first_photon = a.first_photon; a64.light_index = a.light_index; a64.kind = a.kind;
+        a64.cnt_s = a.cnt_s; a64.cnt_v = a.cnt_v; a64.off_s = a.off_s; a64.off_v = a.off_v;
+        a64.surf = reinterpret_cast<rpt64::PhotonRec32*>(a.surf);
+        a64.vol = reinterpret_cast<rpt64::PhotonRec32*>(a.vol);
+        a64.pos64 = pm->pos64.get();
+        a64.a.queue = queue.get();
+        const hipError_t e = hipMemsetAsync(a64.a.queue, 0, 8, st);
+        return e != hipSuccess ? e : launch_photon_shoot_f64(a64, blocks, st);
+    };
+    RPTI_HIP_TRY(hipEventRecord(e0.get(), st));
+    RPTI_HIP_TRY(launch(false));
     // offsets = exclusive prefix sums of the per-photon record counts, on the device
-    uint32_t *d_os, *d_ov;
-    RPTI_HIP_TRY(tmp.alloc(&d_os, n));
-    RPTI_HIP_TRY(tmp.alloc(&d_ov, n));
+    RPTI_HIP_TRY(off_s.alloc(*pm->pool, n));
+    RPTI_HIP_TRY(off_v.alloc(*pm->pool, n));
     // (totals in 64 bits: the 32-bit offsets are only used once the totals are known to fit)
-    char* scan_tmp;
-    RPTI_HIP_TRY(tmp.alloc(&scan_tmp, std::max<size_t>(ss::scan2_temp_bytes(uint32_t(n)), 8)));
-    unsigned long long* d_tot;
-    RPTI_HIP_TRY(tmp.alloc(&d_tot, 2));
-    RPTI_HIP_TRY(ss::exclusive_scan2(a.cnt_s, a.cnt_v, uint32_t(n), d_os, d_ov, d_tot, scan_tmp, st));
+    RPTI_HIP_TRY(scan_tmp.alloc(*pm->pool, std::max<size_t>(ss::scan2_temp_bytes(uint32_t(n)), 8)));
+    RPTI_HIP_TRY(d_tot.alloc(*pm->pool, 2));
+    RPTI_HIP_TRY(ss::exclusive_scan2(a.cnt_s, a.cnt_v, uint32_t(n), off_s.get(), off_v.get(), d_tot.get(), scan_tmp.get(), st));
     unsigned long long tot[2] = {0, 0};
-    RPTI_HIP_TRY(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st));
+    RPTI_HIP_TRY(hipMemcpyAsync(tot, d_tot.get(), 16, hipMemcpyDeviceToHost, st));
     RPTI_HIP_TRY(hipStreamSynchronize(st));
     const uint64_t ts = tot[0], tv = tot[1];
     if (ts >= (1ull << 26) || tv >= (1ull << 26)) return rpti::fail(RPT_ERR_UNSUPPORTED, "too many photons (2^26 records per map)");
-    RPTI_HIP_TRY(pm->pool->alloc((void**)&pm->raw_s, ts * sizeof(PhotonRec)));
-    RPTI_HIP_TRY(pm->pool->alloc((void**)&pm->raw_v, tv * sizeof(PhotonRec)));
+    RPTI_HIP_TRY(pm->raw_s.alloc(*pm->pool, ts));
+    RPTI_HIP_TRY(pm->raw_v.alloc(*pm->pool, tv));
+    if (f64) RPTI_HIP_TRY(pm->pos64.alloc(*pm->pool, ts * 3u));
     pm->n_raw_s = ts;
     pm->n_raw_v = tv;
-    a.off_s = d_os;
-    a.off_v = d_ov;
-    a.surf = pm->raw_s;
-    a.vol = pm->raw_v;
-    RPTI_HIP_TRY(launch_shoot<true>(a, medium, bvh, blocks, st));
-    RPTI_HIP_TRY(hipEventRecord(e1, st));
-    RPTI_HIP_TRY(hipEventSynchronize(e1));
-    float m0 = 0;
-    (void)hipEventElapsedTime(&m0, e0, e1);
-    pm->build_ms[0] = m0;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    a.off_s = off_s.get();
+    a.off_v = off_v.get();
+    a.surf = pm->raw_s.get();
+    a.vol = pm->raw_v.get();
+    RPTI_HIP_TRY(launch(true));
+    RPTI_HIP_TRY(hipEventRecord(e1.get(), st));
+    RPTI_HIP_TRY(hipEventSynchronize(e1.get()));
+    pm->build_ms[0] = rpti::elapsed_ms(e0, e1);
     return RPT_OK;
 }
 
@@ -2320,23 +2282,20 @@ static int shoot_range(rpt_scene* s, PhotonMapDev* pm, uint64_t photon_count, ui
 static int build_maps(PhotonMapDev* pm, const PhotonRec* d_s, uint64_t n_s, const PhotonRec* d_v, uint64_t n_v) {
     if (n_s >= (1ull << 26) || n_v >= (1ull << 26)) return rpti::fail(RPT_ERR_UNSUPPORTED, "too many photons (2^26 records per map)");
     hipStream_t st = nullptr;
-    hipEvent_t e1, e2;
-    RPTI_HIP_TRY(hipEventCreate(&e1));
-    RPTI_HIP_TRY(hipEventCreate(&e2));
-    RPTI_HIP_TRY(hipEventRecord(e1, st));
+    rpti::Event e1, e2;
+    RPTI_HIP_TRY(e1.create());
+    RPTI_HIP_TRY(e2.create());
+    RPTI_HIP_TRY(hipEventRecord(e1.get(), st));
     const int kind = pm->kind;
     int rc = build_lbvh(*pm->pool, const_cast<PhotonRec*>(d_s), uint32_t(n_s), 0, pm->surf, st);
     if (rc == RPT_OK)
         rc = build_lbvh(*pm->pool, const_cast<PhotonRec*>(d_v), uint32_t(n_v),
                         kind == RPT_PHOTON_POINT_BEAM ? 1 : (kind == RPT_PHOTON_BEAM_BEAM ? 2 : 0), pm->vol, st);
     if (rc != RPT_OK) return rc;
-    RPTI_HIP_TRY(hipEventRecord(e2, st));
-    RPTI_HIP_TRY(hipEventSynchronize(e2));
-    float m1 = 0;
-    (void)hipEventElapsedTime(&m1, e1, e2);
-    pm->build_ms[1] = m1;
-    pm->build_ms[3] = pm->build_ms[0] + m1;
-    (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
+    RPTI_HIP_TRY(hipEventRecord(e2.get(), st));
+    RPTI_HIP_TRY(hipEventSynchronize(e2.get()));
+    pm->build_ms[1] = rpti::elapsed_ms(e1, e2);
+    pm->build_ms[3] = pm->build_ms[0] + pm->build_ms[1];
     pm->built = true;
     return RPT_OK;
 }
@@ -2387,7 +2346,7 @@ int rpt_photon_map_build(rpt_scene* s, uint64_t photon_count, int32_t kind, doub
     if (rc) return rc;
     PhotonMapDev* pm = fresh_map(s, photon_count, kind);
     rc = shoot_range(s, pm, photon_count, 0, photon_count, kind, watts, seed);
-    if (rc == RPT_OK) rc = build_maps(pm, pm->raw_s, pm->n_raw_s, pm->raw_v, pm->n_raw_v);
+    if (rc == RPT_OK) rc = build_maps(pm, pm->raw_s.get(), pm->n_raw_s, pm->raw_v.get(), pm->n_raw_v);
     if (rc != RPT_OK) { drop_map(s); return rc; }
     pm->release_raw();
     return RPT_OK;
@@ -2413,7 +2372,7 @@ int rpt_photon_records(rpt_scene* s, int32_t which, void** d_records, uint64_t* 
     if (!s || !d_records || !n) return rpti::fail(RPT_ERR_INVALID, "null argument");
     auto* pm = static_cast<PhotonMapDev*>(rpti::photon_slot(s));
     if (!pm || pm->built) return rpti::fail(RPT_ERR_STATE, "no shot photons: call rpt_photon_shoot first");
-    *d_records = which == 0 ? pm->raw_s : pm->raw_v;
+    *d_records = which == 0 ? pm->raw_s.get() : pm->raw_v.get();
     *n = which == 0 ? pm->n_raw_s : pm->n_raw_v;
     return RPT_OK;
 }
@@ -2425,13 +2384,16 @@ int rpt_photon_map_from_records(rpt_scene* s, uint64_t photon_count, int32_t kin
     if ((n_surface && !d_surface) || (n_volume && !d_volume)) return rpti::fail(RPT_ERR_INVALID, "null record array");
     if (rpti::scene_dev(s).epsilon64) return rpti::fail(RPT_ERR_UNSUPPORTED, "the reference-epsilon mode keeps the surface photons' positions in fp64 beside the 48-byte records: build the map with rpt_photon_map_build (on every rank)");
     auto* old = static_cast<PhotonMapDev*>(rpti::photon_slot(s));
-    // the arrays may be this scene's own shot records: keep them alive until the maps are built
-    PhotonMapDev keep;
-    if (old) { keep.raw_s = old->raw_s; keep.raw_v = old->raw_v; keep.build_ms[0] = old->build_ms[0]; old->raw_s = old->raw_v = nullptr; }
+    // the arrays may be this scene's own shot records: keep them alive until the maps are built (they go back to the pool
+    // the new map takes over from the old one, before a failed map takes that pool with it)
+    PoolMem<PhotonRec> keep_s, keep_v;
+    double shoot_ms = 0;
+    if (old) { keep_s = std::move(old->raw_s); keep_v = std::move(old->raw_v); shoot_ms = old->build_ms[0]; }
     PhotonMapDev* pm = fresh_map(s, photon_count, kind);
-    pm->build_ms[0] = keep.build_ms[0];
+    pm->build_ms[0] = shoot_ms;
     rc = build_maps(pm, static_cast<const PhotonRec*>(d_surface), n_surface, static_cast<const PhotonRec*>(d_volume), n_volume);
-    pm->pool->free(keep.raw_s); pm->pool->free(keep.raw_v);
+    keep_s.reset();
+    keep_v.reset();
     if (rc != RPT_OK) { drop_map(s); return rc; }
     return RPT_OK;
 }
@@ -2458,7 +2420,7 @@ int rpt_photon_map_download(rpt_scene* s, int32_t which, float* out, uint64_t ca
     const DevLbvh& l = which == 0 ? pm->surf : pm->vol;
     if (capacity < l.n) return rpti::fail(RPT_ERR_INVALID, "output buffer too small");
     std::vector<PhotonRec> h(l.n);
-    if (l.n) RPTI_HIP_TRY(hipMemcpy(h.data(), l.sorted, size_t(l.n) * sizeof(PhotonRec), hipMemcpyDeviceToHost));
+    if (l.n) RPTI_HIP_TRY(hipMemcpy(h.data(), l.sorted.get(), size_t(l.n) * sizeof(PhotonRec), hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < l.n; i++) {
         uint32_t orig;
         std::memcpy(&orig, &h[i].dir.w, 4);
@@ -2501,8 +2463,8 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
     const uint64_t n_items = uint64_t(q.r.n_owned / 64u) * q.parts * q.r.n_chunks;
     if (n_items >= (1ull << 32) - (1ull << 24)) return rpti::fail(RPT_ERR_INVALID, "too many work items");
     q.r.n_items = uint32_t(n_items);
-    q.s_nodes = pm->surf.nodes; q.s_ph = pm->surf.sorted; q.n_s = pm->surf.n;
-    q.v_nodes = pm->vol.nodes; q.v_ph = pm->vol.sorted; q.n_v = pm->vol.n;
+    q.s_nodes = pm->surf.nodes.get(); q.s_ph = pm->surf.sorted.get(); q.n_s = pm->surf.n;
+    q.v_nodes = pm->vol.nodes.get(); q.v_ph = pm->vol.sorted.get(); q.n_v = pm->vol.n;
     q.kind = uint32_t(pm->kind);
     q.skip = uint32_t(rpti::option_photon_skip(s));
     q.gather_size = uint32_t(gather_size);
@@ -2514,38 +2476,24 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
                                                  gg ? 0u : coop_base + 5u * 160u}));
     q.coop_cap = (gg || !rpti::option_photon_coop_gather(s)) ? 0u : uint32_t(std::min<size_t>(kCoopCap, ((q.region_dwords - coop_base) / 5u) & ~size_t(3)));
     const size_t lds = (bvh ? 32u * 256u * 4u : 0u) + 4u * size_t(q.region_dwords) * 4u;
-    if (!pm->d_overflow) RPTI_HIP_TRY(pm->pool->alloc((void**)&pm->d_overflow, 64));
-    RPTI_HIP_TRY(hipMemsetAsync(pm->d_overflow, 0, 4, st));
-    q.overflow = pm->d_overflow;
+    RPTI_HIP_TRY(pm->d_overflow.reserve(*pm->pool, 16));   // (64 bytes)
+    RPTI_HIP_TRY(hipMemsetAsync(pm->d_overflow.get(), 0, 4, st));
+    q.overflow = pm->d_overflow.get();
     rpt64::SurfArgs64 sa{};
     if (eps) {
-        if (!pm->pos64 && pm->surf.n) return rpti::fail(RPT_ERR_STATE, "this photon map was not shot in the reference-epsilon mode");
-        const size_t words = std::max<size_t>(size_t(q.r.n_owned) * (size_t(gather_size) + 2u) * num_samples, 16u);
-        if (words > pm->emit_words) {
-            pm->pool->free(pm->d_emit);
-            pm->d_emit = nullptr;
-            pm->emit_words = 0;
-            RPTI_HIP_TRY(pm->pool->alloc((void**)&pm->d_emit, words * 4u));
-            pm->emit_words = words;
-        }
-        q.emit = pm->d_emit;
+        if (!pm->pos64.get() && pm->surf.n) return rpti::fail(RPT_ERR_STATE, "this photon map was not shot in the reference-epsilon mode");
+        RPTI_HIP_TRY(pm->d_emit.reserve(*pm->pool, std::max<size_t>(size_t(q.r.n_owned) * (size_t(gather_size) + 2u) * num_samples, 16u)));
+        q.emit = pm->d_emit.get();
         pm->emit_dims[0] = q.r.n_owned; pm->emit_dims[1] = gather_size + 2u; pm->emit_dims[2] = num_samples;
         const uint32_t n_groups = (num_samples + 63u) / 64u;
-        const size_t bytes = std::max<size_t>(size_t(n_groups) * q.r.n_owned * 32u, 32u);
-        if (bytes > pm->slab64_bytes) {
-            pm->pool->free(pm->d_slab64);
-            pm->d_slab64 = nullptr;
-            pm->slab64_bytes = 0;
-            RPTI_HIP_TRY(pm->pool->alloc((void**)&pm->d_slab64, bytes));
-            pm->slab64_bytes = bytes;
-        }
+        RPTI_HIP_TRY(pm->d_slab64.reserve(*pm->pool, std::max<size_t>(size_t(n_groups) * q.r.n_owned * 4u, 4u)));   // 32 bytes per item
         rpti::fill_args64(s, cam, prm, &q.r, sa.a);
         sa.a.n_chunks = n_groups;                    // of 64 samples: one work item per (group, pixel)
         sa.a.n_items = n_groups * q.r.n_owned;       // (< 2^32: n_owned * n_chunks of kSuper was checked, and a chunk holds four groups)
-        sa.a.slab = pm->d_slab64;
-        sa.emit = pm->d_emit;
-        sa.s_ph = reinterpret_cast<const rpt64::PhotonRec32*>(pm->surf.sorted);
-        sa.pos64 = pm->pos64;
+        sa.a.slab = pm->d_slab64.get();
+        sa.emit = pm->d_emit.get();
+        sa.s_ph = reinterpret_cast<const rpt64::PhotonRec32*>(pm->surf.sorted.get());
+        sa.pos64 = pm->pos64.get();
         sa.K = uint32_t(gather_size);
         sa.kind = uint32_t(pm->kind);
         sa.skip = q.skip;
@@ -2570,26 +2518,12 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
         };
     int bpc = int(std::max<size_t>(1, std::min<size_t>(4, (160u * 1024u) / std::max<size_t>(lds, 1))));
     if (gg) {  // one [2][K][64]-dword region per wave of the largest grid run_persistent may launch
-        const size_t words = size_t(rpti::scene_dev(s).n_cus) * size_t(bpc) * 4u * size_t(gather_max) * 128u;
-        if (words > pm->gather_words) {
-            pm->pool->free(pm->d_gather);
-            pm->d_gather = nullptr;
-            pm->gather_words = 0;
-            RPTI_HIP_TRY(pm->pool->alloc((void**)&pm->d_gather, words * 4u));
-            pm->gather_words = words;
-        }
-        q.gather = pm->d_gather;
+        RPTI_HIP_TRY(pm->d_gather.reserve(*pm->pool, size_t(rpti::scene_dev(s).n_cus) * size_t(bpc) * 4u * size_t(gather_max) * 128u));
+        q.gather = pm->d_gather.get();
     }
     if (pm->kind == RPT_PHOTON_POINT_BEAM && medium && pm->vol.n && rpti::option_photon_block_lists(s)) {
-        const size_t words = size_t(rpti::scene_dev(s).n_cus) * size_t(bpc) * 4u * kCandCap;
-        if (words > pm->cand_words) {
-            pm->pool->free(pm->d_cand);
-            pm->d_cand = nullptr;
-            pm->cand_words = 0;
-            RPTI_HIP_TRY(pm->pool->alloc((void**)&pm->d_cand, words * 4u));
-            pm->cand_words = words;
-        }
-        q.cand = pm->d_cand;
+        RPTI_HIP_TRY(pm->d_cand.reserve(*pm->pool, size_t(rpti::scene_dev(s).n_cus) * size_t(bpc) * 4u * kCandCap));
+        q.cand = pm->d_cand.get();
         q.cand_cap = kCandCap;
     }
     // the split camera pass (option "photon_split"; off by default -- two launches cannot overlap the two estimates the way
@@ -2599,20 +2533,13 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
     if (rpti::option_photon_split(s)) return rpti::fail(RPT_ERR_UNSUPPORTED, "photon_split: a rejected prototype, built with -DRPT_EXPERIMENTS only");
 #endif
     if (medium && !gg && pm->kind != RPT_PHOTON_MAP && rpti::option_photon_split(s)) {
-        const size_t bytes = std::max<size_t>(size_t(q.r.n_chunks) * q.r.n_owned * 16u, 16u);
-        if (bytes > pm->slab2_bytes) {
-            pm->pool->free(pm->d_slab2);
-            pm->d_slab2 = nullptr;
-            pm->slab2_bytes = 0;
-            RPTI_HIP_TRY(pm->pool->alloc((void**)&pm->d_slab2, bytes));
-            pm->slab2_bytes = bytes;
-        }
-        q.r.slab2 = pm->d_slab2;
+        RPTI_HIP_TRY(pm->d_slab2.reserve(*pm->pool, std::max<size_t>(size_t(q.r.n_chunks) * q.r.n_owned * 4u, 4u)));   // 16 bytes per item
+        q.r.slab2 = pm->d_slab2.get();
     }
     rc = rpti::run_persistent(s, prm, q.r, d_out, st, bpc, launch, false, true, resolve);
     if (rc == RPT_OK && sync_counters) {
         uint32_t ov = 0;
-        RPTI_HIP_TRY(hipMemcpyAsync(&ov, pm->d_overflow, 4, hipMemcpyDeviceToHost, st));
+        RPTI_HIP_TRY(hipMemcpyAsync(&ov, pm->d_overflow.get(), 4, hipMemcpyDeviceToHost, st));
         RPTI_HIP_TRY(hipStreamSynchronize(st));
         if (ov) return rpti::fail(RPT_ERR_UNSUPPORTED, "photon beam walk: traversal stack overflow (photon tree too deep)");
         if (q.r.counters) rc = rpti::fetch_counters(s, q.r);
@@ -2673,23 +2600,23 @@ int rpt_debug_photon_positions64(rpt_scene* s, double* out, uint64_t capacity) {
     if (!s || !out) return rpti::fail(RPT_ERR_INVALID, "null argument");
     auto* pm = static_cast<PhotonMapDev*>(rpti::photon_slot(s));
     if (!pm || !pm->built) return rpti::fail(RPT_ERR_STATE, "no photon map: call rpt_photon_map_build first");
-    if (pm->surf.n && !pm->pos64) return rpti::fail(RPT_ERR_STATE, "this photon map was not shot in the reference-epsilon mode");
+    if (pm->surf.n && !pm->pos64.get()) return rpti::fail(RPT_ERR_STATE, "this photon map was not shot in the reference-epsilon mode");
     if (capacity < pm->surf.n) return rpti::fail(RPT_ERR_INVALID, "output buffer too small");
-    if (pm->surf.n) RPTI_HIP_TRY(hipMemcpy(out, pm->pos64, size_t(pm->surf.n) * 24u, hipMemcpyDeviceToHost));
+    if (pm->surf.n) RPTI_HIP_TRY(hipMemcpy(out, pm->pos64.get(), size_t(pm->surf.n) * 24u, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
 int rpt_debug_photon_selections(rpt_scene* s, uint32_t* out, uint64_t capacity_words, uint64_t dims[3]) {
     if (!s || !dims) return rpti::fail(RPT_ERR_INVALID, "null argument");
     auto* pm = static_cast<PhotonMapDev*>(rpti::photon_slot(s));
-    if (!pm || !pm->d_emit) return rpti::fail(RPT_ERR_STATE, "no camera pass in the reference-epsilon mode yet");
+    if (!pm || !pm->d_emit.get()) return rpti::fail(RPT_ERR_STATE, "no camera pass in the reference-epsilon mode yet");
     for (int i = 0; i < 3; i++) dims[i] = pm->emit_dims[i];
     const uint64_t words = dims[0] * dims[1] * dims[2];
     if (!out) return RPT_OK;
     if (capacity_words < words) return rpti::fail(RPT_ERR_INVALID, "output buffer too small");
     RPTI_HIP_TRY(hipSetDevice(pm->device));
     RPTI_HIP_TRY(hipDeviceSynchronize());
-    RPTI_HIP_TRY(hipMemcpy(out, pm->d_emit, words * 4u, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(out, pm->d_emit.get(), words * 4u, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
@@ -2699,24 +2626,22 @@ int rpt_debug_radix_sort(uint64_t n, const uint64_t* keys, uint64_t* keys_out, u
     if (n >= (1ull << 31)) return rpti::fail(RPT_ERR_INVALID, "too many pairs");
     if (n == 0) return RPT_OK;
     const uint32_t m = uint32_t(n);
-    uint64_t *k0 = nullptr, *k1 = nullptr;
-    uint32_t *v0 = nullptr, *v1 = nullptr;
-    char* temp = nullptr;
-    auto cleanup = [&]() { (void)hipFree(k0); (void)hipFree(k1); (void)hipFree(v0); (void)hipFree(v1); (void)hipFree(temp); };
+    rpti::DevMem k0, k1, v0, v1, temp;
     std::vector<uint32_t> iota(m);
     for (uint32_t i = 0; i < m; i++) iota[i] = i;
-    hipError_t e = hipMalloc((void**)&k0, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&k1, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&v0, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&v1, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&temp, ss::rsort_temp_bytes(m));
-    if (e == hipSuccess) e = hipMemcpy(k0, keys, n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(v0, iota.data(), n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = ss::radix_sort_pairs(k0, v0, k1, v1, m, 8u, temp, ss::StorePair{k0, v0}, nullptr);   // (pass 7 reads k1 / v1)
+    hipError_t e = k0.reserve(n * 8);
+    if (e == hipSuccess) e = k1.reserve(n * 8);
+    if (e == hipSuccess) e = v0.reserve(n * 4);
+    if (e == hipSuccess) e = v1.reserve(n * 4);
+    if (e == hipSuccess) e = temp.reserve(ss::rsort_temp_bytes(m));
+    if (e == hipSuccess) e = hipMemcpy(k0.get(), keys, n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(v0.get(), iota.data(), n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess)   // (pass 7 reads k1 / v1)
+        e = ss::radix_sort_pairs(k0.get<uint64_t>(), v0.get<uint32_t>(), k1.get<uint64_t>(), v1.get<uint32_t>(), m, 8u, temp.get<char>(),
+                                 ss::StorePair{k0.get<uint64_t>(), v0.get<uint32_t>()}, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(keys_out, k0, n * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(order_out, v0, n * 4, hipMemcpyDeviceToHost);
-    cleanup();
+    if (e == hipSuccess) e = hipMemcpy(keys_out, k0.get(), n * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(order_out, v0.get(), n * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return rpti::fail(RPT_ERR_DEVICE, std::string("rpt_debug_radix_sort: ") + hipGetErrorString(e));
     return RPT_OK;
 }
@@ -2724,26 +2649,24 @@ int rpt_debug_exclusive_scan2(uint64_t n, const uint32_t* a, const uint32_t* b, 
     if (!totals || (n && (!a || !b || !out_a || !out_b))) return rpti::fail(RPT_ERR_INVALID, "null argument");
     if (n >= (1ull << 31)) return rpti::fail(RPT_ERR_INVALID, "too many values");
     const uint32_t m = uint32_t(n);
-    uint32_t *da = nullptr, *db = nullptr, *oa = nullptr, *ob = nullptr;
-    unsigned long long* dt = nullptr;
-    char* temp = nullptr;
-    auto cleanup = [&]() { (void)hipFree(da); (void)hipFree(db); (void)hipFree(oa); (void)hipFree(ob); (void)hipFree(dt); (void)hipFree(temp); };
+    rpti::DevMem da, db, oa, ob, dt, temp;
     const size_t bytes = std::max<size_t>(n * 4, 4);
-    hipError_t e = hipMalloc((void**)&da, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&db, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&oa, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&ob, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&dt, 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&temp, std::max<size_t>(ss::scan2_temp_bytes(m), 8));
-    if (e == hipSuccess && n) e = hipMemcpy(da, a, n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n) e = hipMemcpy(db, b, n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = ss::exclusive_scan2(da, db, m, oa, ob, dt, temp, nullptr);
+    hipError_t e = da.reserve(bytes);
+    if (e == hipSuccess) e = db.reserve(bytes);
+    if (e == hipSuccess) e = oa.reserve(bytes);
+    if (e == hipSuccess) e = ob.reserve(bytes);
+    if (e == hipSuccess) e = dt.reserve(16);
+    if (e == hipSuccess) e = temp.reserve(std::max<size_t>(ss::scan2_temp_bytes(m), 8));
+    if (e == hipSuccess && n) e = hipMemcpy(da.get(), a, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(db.get(), b, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = ss::exclusive_scan2(da.get<uint32_t>(), db.get<uint32_t>(), m, oa.get<uint32_t>(), ob.get<uint32_t>(), dt.get<unsigned long long>(),
+                                temp.get<char>(), nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && n) e = hipMemcpy(out_a, oa, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && n) e = hipMemcpy(out_b, ob, n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && n) e = hipMemcpy(out_a, oa.get(), n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && n) e = hipMemcpy(out_b, ob.get(), n * 4, hipMemcpyDeviceToHost);
     unsigned long long t[2] = {0, 0};
-    if (e == hipSuccess) e = hipMemcpy(t, dt, 16, hipMemcpyDeviceToHost);
-    cleanup();
+    if (e == hipSuccess) e = hipMemcpy(t, dt.get(), 16, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return rpti::fail(RPT_ERR_DEVICE, std::string("rpt_debug_exclusive_scan2: ") + hipGetErrorString(e));
     totals[0] = t[0];
     totals[1] = t[1];

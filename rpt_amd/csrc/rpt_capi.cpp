@@ -495,37 +495,36 @@ struct rpt_scene {
     rpt_options opt;  // this scene's options (rpt_scene_set_option; starts as a copy of the process defaults)
     int device = 0;
     int n_cus = 256;
-    // device memory
-    void* arena = nullptr;
     SceneView view{};
-    // per-render cached buffers
-    uint32_t* d_tiles = nullptr;
-    size_t tiles_cap = 0;
     // What one launch owns until its resolve has run: the slab of partial sums and the work counter.  Two sets, so
     // that a caller who alternates between two streams (consecutive frames of an iterative render) gets launches
     // that overlap -- the next frame's blocks fill the CUs that the last paths of this frame no longer keep busy,
     // ~0.35 ms per launch -- while launches on one stream keep using one set.
     struct LaunchSet {
-        float* d_slab = nullptr;
-        size_t slab_cap = 0;  // bytes
-        unsigned long long* d_queue = nullptr;
-        uint32_t* d_stream = nullptr;   // streamed walks (detach = 2): rings and parked paths of the grid's waves
-        size_t stream_cap = 0;          // bytes
-        hipEvent_t done = nullptr;  // recorded after the resolve of the last launch that used the set
-        hipEvent_t launched = nullptr;  // recorded right before its render kernel
+        rpti::DevMem d_slab;
+        rpti::DevMem d_queue;
+        rpti::DevMem d_stream;   // streamed walks (detach = 2): rings and parked paths of the grid's waves
+        rpti::Event done;        // recorded after the resolve of the last launch that used the set
+        rpti::Event launched;    // recorded right before its render kernel
         hipStream_t stream = nullptr;
         bool used = false;
     };
-    LaunchSet sets[2];
+    // Everything a commit and the renders after it put on the device: release_device replaces it with an empty one.
+    struct Device {
+        rpti::DevMem arena;      // the flattened scene (view's arrays)
+        rpti::DevMem arena64;    // reference-epsilon mode: view64's arrays
+        // per-render cached buffers
+        rpti::DevMem d_tiles;
+        LaunchSet sets[2];
+        rpti::DevMem d_counters;
+        rpti::DevMem d_out;
+        // "timing": an event triple (before render, after render, after resolve) per launch, in a ring; nothing waits
+        // for them until rpt_get_timing / rpt_get_timing_mean is called
+        std::vector<rpti::Event> evs;
+    } dev;
     int cur_set = 0;
-    unsigned long long* d_counters = nullptr;
-    double* d_out = nullptr;
-    size_t out_cap = 0;  // bytes
     uint64_t last_counters[64] = {0};  // [0..7] counters, [8..63] diagnostic trip stamps
-    // "timing": an event triple (before render, after render, after resolve) per launch, in a ring; nothing waits
-    // for them until rpt_get_timing / rpt_get_timing_mean is called
     static constexpr size_t kTimedLaunches = 1024;
-    std::vector<hipEvent_t> evs;
     size_t ev_count = 0;  // timed launches since the last rpt_get_timing_mean
     int last_blocks = 0;
     uint64_t prims_per_ray = 0;
@@ -533,9 +532,7 @@ struct rpt_scene {
     bool twins_scanned = false;  // every Light::Object that can be visible has its twin among the scanned records, as one range of hit codes
     uint64_t stats[16] = {0};
     void* photon = nullptr;  // PhotonMapDev*, owned by photon.hip
-    // reference-epsilon mode (option "epsilon_policy" = 1 at commit): the fp64 scene of kernels_f64.hip
-    void* arena64 = nullptr;
-    size_t arena64_bytes = 0;
+    // reference-epsilon mode (option "epsilon_policy" = 1 at commit): the fp64 scene of kernels_f64.hip in dev.arena64
     rpt64::Scene view64{};
     double medium_color64[3] = {0, 0, 0}, medium_color_hi64[3] = {0, 0, 0};
     uint64_t last_counters64[64] = {0};   // [0..11] rpt_debug_epsilon_counters, [16 + 2k], [17 + 2k] section k of kernels_f64.hip (executions, lanes)
@@ -605,21 +602,6 @@ static bool check_material(const rpt_material* m, std::string& why) {
     return true;
 }
 
-namespace {
-struct TmpDev {
-    std::vector<void*> ptrs;
-    ~TmpDev() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <class T>
-    hipError_t alloc(T** p, size_t n) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(n * sizeof(T), 16));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-}  // namespace
-
 extern "C" {
 
 const char* rpt_last_error(void) { return g_err.c_str(); }
@@ -646,27 +628,12 @@ rpt_scene* rpt_scene_create(void) {
     return s;
 }
 
-// Everything a commit (and the renders after it) put on the device; the pointers are cleared, so this is safe to repeat and
-// a commit that fails half-way (the reference-epsilon scene after the fp32 upload) leaves nothing behind.
+// Everything a commit (and the renders after it) put on the device, freed on the scene's device; safe to repeat, and a
+// commit that fails half-way (the reference-epsilon scene after the fp32 upload) leaves nothing behind.
 static void release_device(rpt_scene* s) {
-    if (!s->committed && !s->arena && !s->arena64) return;
+    if (!s->committed && !s->dev.arena && !s->dev.arena64) return;
     (void)hipSetDevice(s->device);
-    (void)hipFree(s->arena); s->arena = nullptr;
-    (void)hipFree(s->arena64); s->arena64 = nullptr; s->arena64_bytes = 0;
-    (void)hipFree(s->d_tiles); s->d_tiles = nullptr; s->tiles_cap = 0;
-    for (auto& ls : s->sets) {
-        (void)hipFree(ls.d_slab); ls.d_slab = nullptr; ls.slab_cap = 0;
-        (void)hipFree(ls.d_queue); ls.d_queue = nullptr;
-        (void)hipFree(ls.d_stream); ls.d_stream = nullptr; ls.stream_cap = 0;
-        if (ls.done) (void)hipEventDestroy(ls.done);
-        if (ls.launched) (void)hipEventDestroy(ls.launched);
-        ls.done = nullptr; ls.launched = nullptr; ls.used = false;
-    }
-    (void)hipFree(s->d_counters); s->d_counters = nullptr;
-    (void)hipFree(s->d_out); s->d_out = nullptr; s->out_cap = 0;
-    for (auto& e : s->evs)
-        if (e) (void)hipEventDestroy(e);
-    s->evs.clear();
+    s->dev = rpt_scene::Device{};
     if (s->photon) rpti::photon_release(s->photon);
     s->photon = nullptr;
     s->committed = false;
@@ -1518,9 +1485,9 @@ struct Flattener {
         put(o_lparts, lparts.data(), lparts.size() * sizeof(LightPart));
         put(o_hdri, s->hdri.data(), s->hdri.size() * sizeof(float));
         put(o_mono, mono.data(), mono.size() * sizeof(MonoScan));  put(o_monos, mono_sh.data(), mono_sh.size() * sizeof(XfShade));
-        HIP_TRY(hipMalloc(&s->arena, off));
-        HIP_TRY(hipMemcpy(s->arena, host.data(), off, hipMemcpyHostToDevice));
-        char* base = static_cast<char*>(s->arena);
+        HIP_TRY(s->dev.arena.reserve(off));
+        HIP_TRY(hipMemcpy(s->dev.arena.get(), host.data(), off, hipMemcpyHostToDevice));
+        char* base = s->dev.arena.get<char>();
         SceneView& v = s->view;
         v.sph = (const XfScan*)(base + o_sph);      v.sph_sh = (const XfShade*)(base + o_sphs);    v.n_sph = uint32_t(sph.size());
         v.cub = (const XfScan*)(base + o_cub);      v.cub_sh = (const XfShade*)(base + o_cubs);    v.n_cub = uint32_t(cub.size());
@@ -1593,13 +1560,13 @@ struct Flattener {
         s->stats[12] = insts.size();
         s->stats[13] = shared.size();
 
-        for (auto& ls : s->sets) {
-            HIP_TRY(hipMalloc((void**)&ls.d_queue, 256));
-            HIP_TRY(hipEventCreateWithFlags(&ls.done, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&ls.launched, hipEventDisableTiming));
+        for (auto& ls : s->dev.sets) {
+            HIP_TRY(ls.d_queue.reserve(256));
+            HIP_TRY(ls.done.create(hipEventDisableTiming));
+            HIP_TRY(ls.launched.create(hipEventDisableTiming));
         }
-        HIP_TRY(hipMalloc((void**)&s->d_counters, 64 * sizeof(unsigned long long)));
-        s->view.stack_overflows = s->d_counters + 7;
+        HIP_TRY(s->dev.d_counters.reserve(64 * sizeof(unsigned long long)));
+        s->view.stack_overflows = s->dev.d_counters.get<unsigned long long>() + 7;
         s->device = device;
         s->committed = true;
         return RPT_OK;
@@ -1939,10 +1906,9 @@ static int build_scene64(rpt_scene* s) {
     size_t total = 0;
     for (auto& p : parts) { p.off = total; total = (total + p.bytes + 255) & ~size_t(255); }
     total = std::max<size_t>(total, 256);
-    HIP_TRY(hipMalloc(&s->arena64, total));
-    HIP_TRY(hipMemset(s->arena64, 0, total));   // (the gaps between the arrays too: the host tests checksum the arena)
-    s->arena64_bytes = total;
-    char* base = static_cast<char*>(s->arena64);
+    HIP_TRY(s->dev.arena64.reserve(total));
+    HIP_TRY(hipMemset(s->dev.arena64.get(), 0, total));   // (the gaps between the arrays too: the host tests checksum the arena)
+    char* base = s->dev.arena64.get<char>();
     for (auto& p : parts)
         if (p.bytes) HIP_TRY(hipMemcpy(base + p.off, p.src, p.bytes, hipMemcpyHostToDevice));
     rpt64::Scene& v = s->view64;
@@ -2211,21 +2177,17 @@ extern "C++" int rpti::prepare_render(rpt_scene* s, hipStream_t st, const rpt_ca
     uint32_t tiles_x = (prm->width + 31) / 32, tiles_y = (prm->height + 31) / 32;
     (void)tiles_y;
     if (s->tk_w != prm->width || s->tk_h != prm->height || s->tk_rank != prm->shard_rank || s->tk_count != shard_count ||
-        !s->d_tiles) {
+        !s->dev.d_tiles) {
         std::vector<uint32_t> tiles(size_t(tiles_x) * tiles_y);
         tiles.resize(size_t(rpt_shard_tiles(prm->width, prm->height, prm->shard_rank, shard_count, tiles.data(),
                                             tiles.size())));
-        if (tiles.size() > s->tiles_cap) {
-            if (s->d_tiles) HIP_TRY(hipFree(s->d_tiles));
-            HIP_TRY(hipMalloc((void**)&s->d_tiles, std::max<size_t>(tiles.size(), 1) * 4));
-            s->tiles_cap = tiles.size();
-        }
-        if (!tiles.empty()) HIP_TRY(hipMemcpy(s->d_tiles, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(s->dev.d_tiles.reserve(tiles.size() * 4));
+        if (!tiles.empty()) HIP_TRY(hipMemcpy(s->dev.d_tiles.get(), tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice));
         s->tk_w = prm->width; s->tk_h = prm->height; s->tk_rank = prm->shard_rank; s->tk_count = shard_count;
         s->n_tiles = uint32_t(tiles.size());
         s->tiles_x = tiles_x;
     }
-    a.tiles = s->d_tiles;
+    a.tiles = s->dev.d_tiles.get<uint32_t>();
     a.n_tiles = s->n_tiles;
     a.tiles_x = s->tiles_x;
     a.n_owned = a.n_tiles * 1024u;
@@ -2234,19 +2196,15 @@ extern "C++" int rpti::prepare_render(rpt_scene* s, hipStream_t st, const rpt_ca
     a.n_items = uint32_t(n_items);
     size_t slab_bytes = std::max<size_t>(size_t(n_items) * slab_item_bytes, 16);
     // the launch set: the one this stream used last, else the other one
-    if (s->sets[s->cur_set].used && s->sets[s->cur_set].stream != st) s->cur_set ^= 1;
-    rpt_scene::LaunchSet& ls = s->sets[s->cur_set];
-    if (ls.used && ls.stream != st) HIP_TRY(hipStreamWaitEvent(st, ls.done, 0));  // a third stream: wait for the set's last launch
-    if (slab_bytes > ls.slab_cap) {
-        if (ls.d_slab) HIP_TRY(hipFree(ls.d_slab));
-        HIP_TRY(hipMalloc((void**)&ls.d_slab, slab_bytes));
-        ls.slab_cap = slab_bytes;
-    }
+    if (s->dev.sets[s->cur_set].used && s->dev.sets[s->cur_set].stream != st) s->cur_set ^= 1;
+    rpt_scene::LaunchSet& ls = s->dev.sets[s->cur_set];
+    if (ls.used && ls.stream != st) HIP_TRY(hipStreamWaitEvent(st, ls.done.get(), 0));  // a third stream: wait for the set's last launch
+    HIP_TRY(ls.d_slab.reserve(slab_bytes));
     ls.stream = st;
     ls.used = true;
-    a.slab = ls.d_slab;
-    a.queue = ls.d_queue;
-    a.counters = s->opt.counters ? s->d_counters : nullptr;
+    a.slab = ls.d_slab.get<float>();
+    a.queue = ls.d_queue.get<unsigned long long>();
+    a.counters = s->opt.counters ? s->dev.d_counters.get<unsigned long long>() : nullptr;
     a.lds_stack = s->view.n_nodes ? 1u : 0u;
     a.defer_lanes = uint32_t(s->opt.defer_lanes);
     a.defer_stop = uint32_t(std::min(s->opt.defer_stop, s->opt.defer_lanes));
@@ -2272,21 +2230,22 @@ extern "C++" int rpti::prepare_render(rpt_scene* s, hipStream_t st, const rpt_ca
 // A launch that uses per-scene scratch beyond its launch set (the photon camera pass: candidate lists, overflow
 // flag) must not overlap a launch on another stream: wait for whatever the other stream still has in flight.
 extern "C++" int rpti::serialize_with_other_streams(rpt_scene* s, hipStream_t st) {
-    for (auto& ls : s->sets)
-        if (ls.used && ls.stream != st) HIP_TRY(hipStreamWaitEvent(st, ls.done, 0));
+    for (auto& ls : s->dev.sets)
+        if (ls.used && ls.stream != st) HIP_TRY(hipStreamWaitEvent(st, ls.done.get(), 0));
     return RPT_OK;
 }
 
 extern "C++" int rpti::run_persistent(rpt_scene* s, const rpt_render_params* prm, const RenderArgs& a, double* d_out, hipStream_t st,
                          int blocks_per_cu, const std::function<hipError_t(const RenderArgs&, int, hipStream_t)>& launch,
                          bool indexed_start, bool wave_items, const std::function<hipError_t(double, double*, hipStream_t)>& resolve) {
-    rpt_scene::LaunchSet& mine = s->sets[s->sets[0].d_queue == a.queue ? 0 : 1];
-    rpt_scene::LaunchSet& other = s->sets[s->sets[0].d_queue == a.queue ? 1 : 0];
+    const int k = s->dev.sets[0].d_queue.get() == a.queue ? 0 : 1;
+    rpt_scene::LaunchSet& mine = s->dev.sets[k];
+    rpt_scene::LaunchSet& other = s->dev.sets[k ^ 1];
     // Two launches that become ready at the same moment would share the CUs block by block, and the half of each
     // grid that finds no room would start after everything else has drained (measured: 31.3 instead of 30.0 ms per
     // step).  So a launch on the second stream is released only once the first stream has reached its kernel: the
     // grids then follow each other, the later one filling the CUs as the blocks of the earlier one retire.
-    if (other.used && other.stream != st) HIP_TRY(hipStreamWaitEvent(st, other.launched, 0));
+    if (other.used && other.stream != st) HIP_TRY(hipStreamWaitEvent(st, other.launched.get(), 0));
     HIP_TRY(hipMemsetAsync(a.queue, 0, 8, st));
     if (a.counters) HIP_TRY(hipMemsetAsync(a.counters, 0, 512, st));
     uint32_t shard_count = prm->shard_count == 0 ? 1 : prm->shard_count;
@@ -2298,28 +2257,28 @@ extern "C++" int rpti::run_persistent(rpt_scene* s, const rpt_render_params* prm
         // indexed_start: every wave of the grid takes the batch with its own index first (render_kernel's work
         // pull), so the counter starts behind those batches
         if (indexed_start) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)a.queue, int(uint32_t(n_blocks) * 4u * 64u), 1, st));
-        hipEvent_t* ev = nullptr;
+        const rpti::Event* ev = nullptr;
         if (s->opt.timing) {
             const size_t slot = s->ev_count % rpt_scene::kTimedLaunches;
-            while (s->evs.size() < 3 * (slot + 1)) {
-                hipEvent_t e = nullptr;
-                HIP_TRY(hipEventCreate(&e));
-                s->evs.push_back(e);
+            while (s->dev.evs.size() < 3 * (slot + 1)) {
+                rpti::Event e;
+                HIP_TRY(e.create());
+                s->dev.evs.push_back(std::move(e));
             }
-            ev = &s->evs[3 * slot];
-            HIP_TRY(hipEventRecord(ev[0], st));
+            ev = &s->dev.evs[3 * slot];
+            HIP_TRY(hipEventRecord(ev[0].get(), st));
         }
-        HIP_TRY(hipEventRecord(mine.launched, st));
+        HIP_TRY(hipEventRecord(mine.launched.get(), st));
         HIP_TRY(launch(a, n_blocks, st));
-        if (ev) HIP_TRY(hipEventRecord(ev[1], st));
+        if (ev) HIP_TRY(hipEventRecord(ev[1].get(), st));
         if (resolve) HIP_TRY(resolve(std::pow(2.0, prm->exposure_value), d_out, st));
         else HIP_TRY(launch_resolve(a, std::pow(2.0, prm->exposure_value), d_out, st));
         if (ev) {
-            HIP_TRY(hipEventRecord(ev[2], st));
+            HIP_TRY(hipEventRecord(ev[2].get(), st));
             s->ev_count++;
         }
     }
-    HIP_TRY(hipEventRecord(mine.done, st));
+    HIP_TRY(hipEventRecord(mine.done.get(), st));
     return RPT_OK;
 }
 static int run_render(rpt_scene* s, const rpt_render_params* prm, const RenderArgs& a_in, double* d_out, hipStream_t st) {
@@ -2330,15 +2289,9 @@ static int run_render(rpt_scene* s, const rpt_render_params* prm, const RenderAr
         if (bpc < 1) bpc = 1;
     }
     if (a.detach == 2) {   // the waves' rings and parked paths: per launch set, like the slab (two launches may be in flight)
-        rpt_scene::LaunchSet& ls = s->sets[s->sets[0].d_queue == a.queue ? 0 : 1];
-        const size_t need = size_t(s->n_cus) * size_t(bpc) * stream_scratch_bytes_per_block();
-        if (need > ls.stream_cap) {
-            if (ls.d_stream) HIP_TRY(hipFree(ls.d_stream));
-            ls.d_stream = nullptr; ls.stream_cap = 0;
-            HIP_TRY(hipMalloc((void**)&ls.d_stream, need));
-            ls.stream_cap = need;
-        }
-        a.stream_scratch = ls.d_stream;
+        rpt_scene::LaunchSet& ls = s->dev.sets[s->dev.sets[0].d_queue.get() == a.queue ? 0 : 1];
+        HIP_TRY(ls.d_stream.reserve(size_t(s->n_cus) * size_t(bpc) * stream_scratch_bytes_per_block()));
+        a.stream_scratch = ls.d_stream.get<uint32_t>();
     }
     return rpti::run_persistent(s, prm, a, d_out, st, bpc,
                                 [](const RenderArgs& ra, int nb, hipStream_t stream) { return launch_render(ra, nb, stream); }, true);
@@ -2349,7 +2302,7 @@ extern "C++" rpti::SceneDev rpti::scene_dev(rpt_scene* s) {
         if (s->lights[i].kind == L_OBJECT) { first = int(i); break; }
     bool mono = false;
     for (const auto& o : s->objects) mono = mono || holds_monomial(o.shape);
-    return SceneDev{s->committed, s->device, s->n_cus, s->view, first, s->arena64 != nullptr, mono};
+    return SceneDev{s->committed, s->device, s->n_cus, s->view, first, bool(s->dev.arena64), mono};
 }
 extern "C++" void*& rpti::photon_slot(rpt_scene* s) { return s->photon; }
 extern "C++" int64_t rpti::option_photon_skip(rpt_scene* s) { return s->opt.photon_skip; }
@@ -2359,14 +2312,7 @@ extern "C++" int64_t rpti::option_photon_parts(rpt_scene* s) { return s->opt.pho
 extern "C++" int64_t rpti::option_photon_split(rpt_scene* s) { return s->opt.photon_split; }
 extern "C++" int64_t rpti::option_photon_coop_gather(rpt_scene* s) { return s->opt.photon_coop_gather; }
 extern "C++" double* rpti::scratch_out(rpt_scene* s, size_t bytes) {
-    if (bytes > s->out_cap) {
-        if (s->d_out) (void)hipFree(s->d_out);
-        s->d_out = nullptr;
-        s->out_cap = 0;
-        if (hipMalloc((void**)&s->d_out, bytes) != hipSuccess) return nullptr;
-        s->out_cap = bytes;
-    }
-    return s->d_out;
+    return s->dev.d_out.reserve(bytes) == hipSuccess ? s->dev.d_out.get<double>() : nullptr;
 }
 extern "C++" int rpti::fetch_counters(rpt_scene* s, const RenderArgs& a) {
     std::memset(s->last_counters, 0, sizeof(s->last_counters));
@@ -2380,7 +2326,7 @@ extern "C++" int rpti::fetch_counters(rpt_scene* s, const RenderArgs& a) {
 int rpt_render_sample_device(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations,
                              uint64_t seed, uint32_t sample_offset, void* d_out_rgb, void* hip_stream) {
     if (!d_out_rgb) return fail(RPT_ERR_INVALID, "null output");
-    if (s && s->arena64) return run_render64(s, cam, prm, iterations, seed, sample_offset, static_cast<double*>(d_out_rgb), static_cast<hipStream_t>(hip_stream));
+    if (s && s->dev.arena64) return run_render64(s, cam, prm, iterations, seed, sample_offset, static_cast<double*>(d_out_rgb), static_cast<hipStream_t>(hip_stream));
     RenderArgs a{};
     int rc = rpti::prepare_render(s, static_cast<hipStream_t>(hip_stream), cam, prm, iterations, seed, sample_offset, a);
     if (rc) return rc;
@@ -2400,25 +2346,22 @@ int rpt_render_sample(rpt_scene* s, const rpt_camera* cam, const rpt_render_para
     int rc = rpti::prepare_render(s, nullptr, cam, prm, iterations, seed, sample_offset, a);
     if (rc) return rc;
     size_t bytes = size_t(prm->width) * prm->height * 24;
-    if (bytes > s->out_cap) {
-        if (s->d_out) HIP_TRY(hipFree(s->d_out));
-        HIP_TRY(hipMalloc((void**)&s->d_out, bytes));
-        s->out_cap = bytes;
-    }
-    if (s->arena64) {
-        rc = run_render64(s, cam, prm, iterations, seed, sample_offset, s->d_out, nullptr);
+    double* d_out = rpti::scratch_out(s, bytes);
+    if (!d_out) return fail(RPT_ERR_DEVICE, "out of device memory");
+    if (s->dev.arena64) {
+        rc = run_render64(s, cam, prm, iterations, seed, sample_offset, d_out, nullptr);
         if (rc) return rc;
-        HIP_TRY(hipMemcpy(out_rgb, s->d_out, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost));
         return RPT_OK;
     }
-    rc = run_render(s, prm, a, s->d_out, nullptr);
+    rc = run_render(s, prm, a, d_out, nullptr);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_rgb, s->d_out, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost));
     return rpti::fetch_counters(s, a);
 }
 int rpt_debug_epsilon_counters(rpt_scene* s, uint64_t out[12]) {
     if (!s || !out) return fail(RPT_ERR_INVALID, "null argument");
-    if (!s->arena64) return fail(RPT_ERR_STATE, "the scene was not committed with epsilon_policy = 1");
+    if (!s->dev.arena64) return fail(RPT_ERR_STATE, "the scene was not committed with epsilon_policy = 1");
     for (int i = 0; i < 12; i++) out[i] = s->last_counters64[i];
     return RPT_OK;
 }
@@ -2427,8 +2370,8 @@ int rpt_debug_epsilon_counters(rpt_scene* s, uint64_t out[12]) {
 struct rpt_buffer {
     int device = 0;
     uint32_t width = 0, height = 0, radius = 0, n_batches = 0;
-    double *d_sum = nullptr, *d_sumsq = nullptr, *d_stage = nullptr;  // stage: one batch / per-pixel variances
-    uint8_t* d_img = nullptr;
+    rpti::DevMem d_sum, d_sumsq, d_stage;  // stage: one batch / per-pixel variances
+    rpti::DevMem d_img;
 };
 rpt_buffer* rpt_buffer_create(int device, uint32_t width, uint32_t height, uint32_t filter_radius) {
     int ndev = 0;
@@ -2440,10 +2383,9 @@ rpt_buffer* rpt_buffer_create(int device, uint32_t width, uint32_t height, uint3
     b->height = height;
     b->radius = filter_radius;
     const size_t n = size_t(width) * height;
-    bool ok = hipSetDevice(device) == hipSuccess && hipMalloc((void**)&b->d_sum, n * 24) == hipSuccess &&
-              hipMalloc((void**)&b->d_sumsq, n * 8) == hipSuccess && hipMalloc((void**)&b->d_stage, n * 24) == hipSuccess &&
-              hipMalloc((void**)&b->d_img, n * 3) == hipSuccess && hipMemset(b->d_sum, 0, n * 24) == hipSuccess &&
-              hipMemset(b->d_sumsq, 0, n * 8) == hipSuccess;
+    bool ok = hipSetDevice(device) == hipSuccess && b->d_sum.reserve(n * 24) == hipSuccess && b->d_sumsq.reserve(n * 8) == hipSuccess &&
+              b->d_stage.reserve(n * 24) == hipSuccess && b->d_img.reserve(n * 3) == hipSuccess &&
+              hipMemset(b->d_sum.get(), 0, n * 24) == hipSuccess && hipMemset(b->d_sumsq.get(), 0, n * 8) == hipSuccess;
     if (!ok) {
         fail(RPT_ERR_DEVICE, "rpt_buffer_create: device allocation failed");
         rpt_buffer_destroy(b);
@@ -2454,13 +2396,12 @@ rpt_buffer* rpt_buffer_create(int device, uint32_t width, uint32_t height, uint3
 void rpt_buffer_destroy(rpt_buffer* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
-    (void)hipFree(b->d_sum); (void)hipFree(b->d_sumsq); (void)hipFree(b->d_stage); (void)hipFree(b->d_img);
     delete b;
 }
 int rpt_buffer_add_samples_device(rpt_buffer* b, const void* d_rgb, void* hip_stream) {
     if (!b || !d_rgb) return fail(RPT_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(launch_buffer_add(b->width * b->height, static_cast<const double*>(d_rgb), b->d_sum, b->d_sumsq,
+    HIP_TRY(launch_buffer_add(b->width * b->height, static_cast<const double*>(d_rgb), b->d_sum.get<double>(), b->d_sumsq.get<double>(),
                               static_cast<hipStream_t>(hip_stream)));
     b->n_batches++;
     return RPT_OK;
@@ -2468,16 +2409,16 @@ int rpt_buffer_add_samples_device(rpt_buffer* b, const void* d_rgb, void* hip_st
 int rpt_buffer_add_samples(rpt_buffer* b, const double* rgb) {
     if (!b || !rgb) return fail(RPT_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipMemcpy(b->d_stage, rgb, size_t(b->width) * b->height * 24, hipMemcpyHostToDevice));
-    return rpt_buffer_add_samples_device(b, b->d_stage, nullptr);
+    HIP_TRY(hipMemcpy(b->d_stage.get(), rgb, size_t(b->width) * b->height * 24, hipMemcpyHostToDevice));
+    return rpt_buffer_add_samples_device(b, b->d_stage.get(), nullptr);
 }
 int rpt_buffer_image(rpt_buffer* b, uint8_t* out_rgb8) {
     if (!b || !out_rgb8) return fail(RPT_ERR_INVALID, "null argument");
     if (b->n_batches == 0) return fail(RPT_ERR_STATE, "Pixel found with no samples");  // the reference's assert (buffer.rs:89)
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipDeviceSynchronize());  // batches may have been added on other streams
-    HIP_TRY(launch_buffer_image(b->width, b->height, b->radius, b->n_batches, b->d_sum, b->d_img, nullptr));
-    HIP_TRY(hipMemcpy(out_rgb8, b->d_img, size_t(b->width) * b->height * 3, hipMemcpyDeviceToHost));
+    HIP_TRY(launch_buffer_image(b->width, b->height, b->radius, b->n_batches, b->d_sum.get<double>(), b->d_img.get<uint8_t>(), nullptr));
+    HIP_TRY(hipMemcpy(out_rgb8, b->d_img.get(), size_t(b->width) * b->height * 3, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 int rpt_buffer_variance(rpt_buffer* b, double* out) {
@@ -2486,9 +2427,9 @@ int rpt_buffer_variance(rpt_buffer* b, double* out) {
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t n = size_t(b->width) * b->height;
-    HIP_TRY(launch_buffer_variance(uint32_t(n), b->n_batches, b->d_sum, b->d_sumsq, b->d_stage, nullptr));
+    HIP_TRY(launch_buffer_variance(uint32_t(n), b->n_batches, b->d_sum.get<double>(), b->d_sumsq.get<double>(), b->d_stage.get<double>(), nullptr));
     std::vector<double> v(n);
-    HIP_TRY(hipMemcpy(v.data(), b->d_stage, n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(v.data(), b->d_stage.get(), n * 8, hipMemcpyDeviceToHost));
     double acc = 0.0;
     for (double x : v) acc += x;  // pixel order, as buffer.rs:63-72
     *out = acc / double(n);
@@ -2506,17 +2447,17 @@ int rpt_render_into_buffer(rpt_scene* s, const rpt_camera* cam, const rpt_render
     if (!s || !prm) return fail(RPT_ERR_INVALID, "null argument");
     if (prm->width != b->width || prm->height != b->height) return fail(RPT_ERR_INVALID, "Invalid sample dimension");  // buffer.rs:33-36
     if (s->committed && s->device != b->device) return fail(RPT_ERR_INVALID, "buffer and scene live on different devices");
-    if (s->arena64) {
-        int rc64 = run_render64(s, cam, prm, iterations, seed, sample_offset, b->d_stage, nullptr);
-        return rc64 ? rc64 : rpt_buffer_add_samples_device(b, b->d_stage, nullptr);
+    if (s->dev.arena64) {
+        int rc64 = run_render64(s, cam, prm, iterations, seed, sample_offset, b->d_stage.get<double>(), nullptr);
+        return rc64 ? rc64 : rpt_buffer_add_samples_device(b, b->d_stage.get(), nullptr);
     }
     RenderArgs a{};
     int rc = rpti::prepare_render(s, nullptr, cam, prm, iterations, seed, sample_offset, a);
     if (rc) return rc;
-    if (prm->shard_count > 1) HIP_TRY(hipMemsetAsync(b->d_stage, 0, size_t(b->width) * b->height * 24, nullptr));
-    rc = run_render(s, prm, a, b->d_stage, nullptr);
+    if (prm->shard_count > 1) HIP_TRY(hipMemsetAsync(b->d_stage.get(), 0, size_t(b->width) * b->height * 24, nullptr));
+    rc = run_render(s, prm, a, b->d_stage.get<double>(), nullptr);
     if (rc) return rc;
-    rc = rpt_buffer_add_samples_device(b, b->d_stage, nullptr);
+    rc = rpt_buffer_add_samples_device(b, b->d_stage.get(), nullptr);
     if (rc) return rc;
     if (a.counters) {
         HIP_TRY(hipStreamSynchronize(nullptr));
@@ -2528,11 +2469,11 @@ int rpt_render_into_buffer(rpt_scene* s, const rpt_camera* cam, const rpt_render
 int rpt_get_timing(rpt_scene* s, double* render_ms, double* resolve_ms, int32_t* grid_blocks) {
     if (!s) return fail(RPT_ERR_INVALID, "null scene");
     if (!s->ev_count) return fail(RPT_ERR_STATE, "no timed render: rpt_set_option(\"timing\", 1) first");
-    const hipEvent_t* ev = &s->evs[3 * ((s->ev_count - 1) % rpt_scene::kTimedLaunches)];
-    HIP_TRY(hipEventSynchronize(ev[2]));
+    const rpti::Event* ev = &s->dev.evs[3 * ((s->ev_count - 1) % rpt_scene::kTimedLaunches)];
+    HIP_TRY(hipEventSynchronize(ev[2].get()));
     float a = 0.f, b = 0.f;
-    HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
-    HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
+    HIP_TRY(hipEventElapsedTime(&a, ev[0].get(), ev[1].get()));
+    HIP_TRY(hipEventElapsedTime(&b, ev[1].get(), ev[2].get()));
     if (render_ms) *render_ms = a;
     if (resolve_ms) *resolve_ms = b;
     if (grid_blocks) *grid_blocks = s->last_blocks;
@@ -2543,13 +2484,13 @@ int rpt_get_timing_mean(rpt_scene* s, double* render_ms, double* resolve_ms, int
     if (!s) return fail(RPT_ERR_INVALID, "null scene");
     if (!s->ev_count) return fail(RPT_ERR_STATE, "no timed render: rpt_set_option(\"timing\", 1) first");
     const size_t n = std::min(s->ev_count, rpt_scene::kTimedLaunches);  // the ring keeps the latest launches
-    HIP_TRY(hipEventSynchronize(s->evs[3 * ((s->ev_count - 1) % rpt_scene::kTimedLaunches) + 2]));
+    HIP_TRY(hipEventSynchronize(s->dev.evs[3 * ((s->ev_count - 1) % rpt_scene::kTimedLaunches) + 2].get()));
     double a = 0.0, b = 0.0;
     for (size_t i = 0; i < n; i++) {
-        const hipEvent_t* ev = &s->evs[3 * i];
+        const rpti::Event* ev = &s->dev.evs[3 * i];
         float x = 0.f, y = 0.f;
-        HIP_TRY(hipEventElapsedTime(&x, ev[0], ev[1]));
-        HIP_TRY(hipEventElapsedTime(&y, ev[1], ev[2]));
+        HIP_TRY(hipEventElapsedTime(&x, ev[0].get(), ev[1].get()));
+        HIP_TRY(hipEventElapsedTime(&y, ev[1].get(), ev[2].get()));
         a += x;
         b += y;
     }
@@ -2579,36 +2520,36 @@ int rpt_debug_section_counters(rpt_scene* s, uint64_t out[56]) {
 }
 
 // ---------------------------------------------------------------------------- test hooks
+// Device scratch of one hook call, at least 16 bytes (an empty batch still gets a valid pointer).
+static hipError_t hook_scratch(rpti::DevMem& m, size_t bytes) { return m.reserve(std::max<size_t>(bytes, 16)); }
 int rpt_intersect_batch(rpt_scene* s, uint64_t n, const float* origins, const float* dirs, float* t, int32_t* object,
                         float* normal) {
     if (!s || !origins || !dirs || !t || !object) return fail(RPT_ERR_INVALID, "null argument");
     if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
     if (n == 0) return RPT_OK;
     HIP_TRY(hipSetDevice(s->device));
-    TmpDev tmp;
-    float *d_o, *d_d, *d_t, *d_n;
-    int32_t* d_obj;
-    HIP_TRY(tmp.alloc(&d_o, n * 3));
-    HIP_TRY(tmp.alloc(&d_d, n * 3));
-    HIP_TRY(tmp.alloc(&d_t, n));
-    HIP_TRY(tmp.alloc(&d_n, n * 3));
-    HIP_TRY(tmp.alloc(&d_obj, n));
-    HIP_TRY(hipMemcpy(d_o, origins, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d, dirs, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(launch_intersect(s->view, n, d_o, d_d, d_t, d_obj, d_n, s->view.n_nodes != 0, nullptr));
-    HIP_TRY(hipMemcpy(t, d_t, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(object, d_obj, n * 4, hipMemcpyDeviceToHost));
-    if (normal) HIP_TRY(hipMemcpy(normal, d_n, n * 12, hipMemcpyDeviceToHost));
+    rpti::DevMem d_o, d_d, d_t, d_n, d_obj;
+    HIP_TRY(hook_scratch(d_o, n * 12));
+    HIP_TRY(hook_scratch(d_d, n * 12));
+    HIP_TRY(hook_scratch(d_t, n * 4));
+    HIP_TRY(hook_scratch(d_n, n * 12));
+    HIP_TRY(hook_scratch(d_obj, n * 4));
+    HIP_TRY(hipMemcpy(d_o.get(), origins, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d.get(), dirs, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(launch_intersect(s->view, n, d_o.get<float>(), d_d.get<float>(), d_t.get<float>(), d_obj.get<int32_t>(), d_n.get<float>(),
+                             s->view.n_nodes != 0, nullptr));
+    HIP_TRY(hipMemcpy(t, d_t.get(), n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(object, d_obj.get(), n * 4, hipMemcpyDeviceToHost));
+    if (normal) HIP_TRY(hipMemcpy(normal, d_n.get(), n * 12, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
 int rpt_debug_rng_u32(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t n, uint32_t* out) {
     if (!out) return fail(RPT_ERR_INVALID, "null argument");
-    TmpDev tmp;
-    uint32_t* d;
-    HIP_TRY(tmp.alloc(&d, n));
-    HIP_TRY(launch_debug_rng(seed_mix(seed), pixel, sample, n, d, nullptr));
-    HIP_TRY(hipMemcpy(out, d, size_t(n) * 4, hipMemcpyDeviceToHost));
+    rpti::DevMem d;
+    HIP_TRY(hook_scratch(d, size_t(n) * 4));
+    HIP_TRY(launch_debug_rng(seed_mix(seed), pixel, sample, n, d.get<uint32_t>(), nullptr));
+    HIP_TRY(hipMemcpy(out, d.get(), size_t(n) * 4, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 static Material to_gpu_material(const rpt_material* m) {
@@ -2621,37 +2562,35 @@ int rpt_debug_material_sample_f(const rpt_material* m, uint64_t n, const float* 
                                 float* wi, float* pdf, int32_t* some) {
     std::string why;
     if (!check_material(m, why) || !normals || !wos || !wi || !pdf || !some) return fail(RPT_ERR_INVALID, "bad argument");
-    TmpDev tmp;
-    float *d_n, *d_wo, *d_wi, *d_pdf;
-    int32_t* d_some;
-    HIP_TRY(tmp.alloc(&d_n, n * 3));
-    HIP_TRY(tmp.alloc(&d_wo, n * 3));
-    HIP_TRY(tmp.alloc(&d_wi, n * 3));
-    HIP_TRY(tmp.alloc(&d_pdf, n));
-    HIP_TRY(tmp.alloc(&d_some, n));
-    HIP_TRY(hipMemcpy(d_n, normals, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_wo, wos, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(launch_debug_sample_f(to_gpu_material(m), n, d_n, d_wo, seed_mix(seed), d_wi, d_pdf, d_some, nullptr));
-    HIP_TRY(hipMemcpy(wi, d_wi, n * 12, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(pdf, d_pdf, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(some, d_some, n * 4, hipMemcpyDeviceToHost));
+    rpti::DevMem d_n, d_wo, d_wi, d_pdf, d_some;
+    HIP_TRY(hook_scratch(d_n, n * 12));
+    HIP_TRY(hook_scratch(d_wo, n * 12));
+    HIP_TRY(hook_scratch(d_wi, n * 12));
+    HIP_TRY(hook_scratch(d_pdf, n * 4));
+    HIP_TRY(hook_scratch(d_some, n * 4));
+    HIP_TRY(hipMemcpy(d_n.get(), normals, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_wo.get(), wos, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(launch_debug_sample_f(to_gpu_material(m), n, d_n.get<float>(), d_wo.get<float>(), seed_mix(seed), d_wi.get<float>(), d_pdf.get<float>(),
+                                  d_some.get<int32_t>(), nullptr));
+    HIP_TRY(hipMemcpy(wi, d_wi.get(), n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pdf, d_pdf.get(), n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(some, d_some.get(), n * 4, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 int rpt_debug_material_bsdf(const rpt_material* m, uint64_t n, const float* normals, const float* wos, const float* wis,
                             float* out_rgb) {
     std::string why;
     if (!check_material(m, why) || !normals || !wos || !wis || !out_rgb) return fail(RPT_ERR_INVALID, "bad argument");
-    TmpDev tmp;
-    float *d_n, *d_wo, *d_wi, *d_out;
-    HIP_TRY(tmp.alloc(&d_n, n * 3));
-    HIP_TRY(tmp.alloc(&d_wo, n * 3));
-    HIP_TRY(tmp.alloc(&d_wi, n * 3));
-    HIP_TRY(tmp.alloc(&d_out, n * 3));
-    HIP_TRY(hipMemcpy(d_n, normals, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_wo, wos, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_wi, wis, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(launch_debug_bsdf(to_gpu_material(m), n, d_n, d_wo, d_wi, d_out, nullptr));
-    HIP_TRY(hipMemcpy(out_rgb, d_out, n * 12, hipMemcpyDeviceToHost));
+    rpti::DevMem d_n, d_wo, d_wi, d_out;
+    HIP_TRY(hook_scratch(d_n, n * 12));
+    HIP_TRY(hook_scratch(d_wo, n * 12));
+    HIP_TRY(hook_scratch(d_wi, n * 12));
+    HIP_TRY(hook_scratch(d_out, n * 12));
+    HIP_TRY(hipMemcpy(d_n.get(), normals, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_wo.get(), wos, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_wi.get(), wis, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(launch_debug_bsdf(to_gpu_material(m), n, d_n.get<float>(), d_wo.get<float>(), d_wi.get<float>(), d_out.get<float>(), nullptr));
+    HIP_TRY(hipMemcpy(out_rgb, d_out.get(), n * 12, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 int rpt_debug_camera_rays(const rpt_camera* cam, const rpt_render_params* prm, uint64_t seed, uint32_t sample,
@@ -2670,13 +2609,12 @@ int rpt_debug_camera_rays(const rpt_camera* cam, const rpt_render_params* prm, u
     c.aperture = float(cam->aperture);
     c.focal_distance = float(cam->focal_distance);
     size_t n = size_t(prm->width) * prm->height;
-    TmpDev tmp;
-    float *d_o, *d_d;
-    HIP_TRY(tmp.alloc(&d_o, n * 3));
-    HIP_TRY(tmp.alloc(&d_d, n * 3));
-    HIP_TRY(launch_debug_camera(c, prm->width, prm->height, seed_mix(seed), sample, d_o, d_d, nullptr));
-    HIP_TRY(hipMemcpy(origins, d_o, n * 12, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(dirs, d_d, n * 12, hipMemcpyDeviceToHost));
+    rpti::DevMem d_o, d_d;
+    HIP_TRY(hook_scratch(d_o, n * 12));
+    HIP_TRY(hook_scratch(d_d, n * 12));
+    HIP_TRY(launch_debug_camera(c, prm->width, prm->height, seed_mix(seed), sample, d_o.get<float>(), d_d.get<float>(), nullptr));
+    HIP_TRY(hipMemcpy(origins, d_o.get(), n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dirs, d_d.get(), n * 12, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 

@@ -105,13 +105,11 @@ struct rpt_comm {
     int rank = 0, n_ranks = 1, device = 0;
     // per frame size: the tile lists on the device and the packed staging buffer
     TileLayout layout;
-    uint32_t* d_tiles = nullptr;   // layout.all
-    double* d_stage = nullptr;     // rank 0: every rank's block (whole frame worth of tiles); others: their own block
-    size_t stage_cap = 0, tiles_cap = 0;
+    rpti::DevMem d_tiles;   // layout.all
+    rpti::DevMem d_stage;   // rank 0: every rank's block (whole frame worth of tiles); others: their own block
     // photon records: counts of every rank, and the padded blocks of the all-gather
-    unsigned long long* d_counts = nullptr;
-    void* d_rec_stage = nullptr;
-    size_t rec_stage_cap = 0;
+    rpti::DevMem d_counts;
+    rpti::DevMem d_rec_stage;
 };
 
 extern "C" {
@@ -144,10 +142,6 @@ int rpt_comm_create(const void* id, int rank, int n_ranks, int device, rpt_comm*
 void rpt_comm_destroy(rpt_comm* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->d_tiles) (void)hipFree(c->d_tiles);
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    if (c->d_counts) (void)hipFree(c->d_counts);
-    if (c->d_rec_stage) (void)hipFree(c->d_rec_stage);
     if (c->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c->comm);
     delete c;
 }
@@ -177,13 +171,12 @@ static int with_rank_tiles(uint32_t width, uint32_t height, uint32_t rank, uint3
     if (int rc = build_layout(width, height, n_ranks, L)) return rc;
     const uint32_t n = uint32_t(L.offsets[rank + 1] - L.offsets[rank]);
     if (n == 0) return RPT_OK;
-    uint32_t* d = nullptr;
-    RPTI_HIP_TRY(hipMalloc((void**)&d, size_t(n) * 4));
-    hipError_t e = hipMemcpyAsync(d, L.all.data() + L.offsets[rank], size_t(n) * 4, hipMemcpyHostToDevice, st);
+    rpti::DevMem d;
+    RPTI_HIP_TRY(d.reserve(size_t(n) * 4));
+    hipError_t e = hipMemcpyAsync(d.get(), L.all.data() + L.offsets[rank], size_t(n) * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);   // (the host vector goes away with this frame)
-    if (e == hipSuccess) e = fn(d, n, L.tiles_x);
+    if (e == hipSuccess) e = fn(d.get<uint32_t>(), n, L.tiles_x);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(RPT_ERR_DEVICE, std::string("frame tiles: ") + hipGetErrorString(e));
     return RPT_OK;
 }
@@ -222,64 +215,55 @@ int rpt_gather_frame_device(rpt_comm* c, uint32_t width, uint32_t height, const 
         c->layout.width = 0;
         TileLayout fresh;
         if (int rc = build_layout(width, height, uint32_t(c->n_ranks), fresh)) return rc;
-        if (fresh.all.size() > c->tiles_cap) {
-            if (c->d_tiles) RPTI_HIP_TRY(hipFree(c->d_tiles));
-            c->d_tiles = nullptr; c->tiles_cap = 0;
-            RPTI_HIP_TRY(hipMalloc((void**)&c->d_tiles, fresh.all.size() * 4));
-            c->tiles_cap = fresh.all.size();
-        }
-        RPTI_HIP_TRY(hipMemcpy(c->d_tiles, fresh.all.data(), fresh.all.size() * 4, hipMemcpyHostToDevice));
+        RPTI_HIP_TRY(c->d_tiles.reserve(fresh.all.size() * 4));
+        RPTI_HIP_TRY(hipMemcpy(c->d_tiles.get(), fresh.all.data(), fresh.all.size() * 4, hipMemcpyHostToDevice));
         // rank 0: every rank's block + room to receive its own once more (loopback); others: their own block
         const uint64_t tiles = c->rank == 0 ? fresh.offsets[fresh.n_ranks] + fresh.offsets[1] : fresh.offsets[c->rank + 1] - fresh.offsets[c->rank];
-        const size_t bytes = std::max<size_t>(size_t(tiles) * kTileDoubles * 8, 8);
-        if (bytes > c->stage_cap) {
-            if (c->d_stage) RPTI_HIP_TRY(hipFree(c->d_stage));
-            c->d_stage = nullptr; c->stage_cap = 0;
-            RPTI_HIP_TRY(hipMalloc((void**)&c->d_stage, bytes));
-            c->stage_cap = bytes;
-        }
+        RPTI_HIP_TRY(c->d_stage.reserve(std::max<size_t>(size_t(tiles) * kTileDoubles * 8, 8)));
         c->layout = std::move(fresh);
     }
     TileLayout& L = c->layout;
+    double* const d_stage = c->d_stage.get<double>();
+    const uint32_t* const d_tiles = c->d_tiles.get<uint32_t>();
     const bool loop = (flags & RPT_GATHER_LOOPBACK) != 0;
     const double* shard = static_cast<const double*>(d_shard);
     double* frame = static_cast<double*>(d_frame);
     auto n_of = [&](int r) { return uint32_t(L.offsets[r + 1] - L.offsets[r]); };
     if (c->rank != 0) {
         const uint32_t n = n_of(c->rank);
-        RPTI_HIP_TRY(rptg::launch_frame_pack(shard, c->d_stage, c->d_tiles + L.offsets[c->rank], n, L.tiles_x, width, height, st));
-        if (n) RCCL_TRY(g_rccl.Send(c->d_stage, size_t(n) * kTileDoubles, ncclDouble, 0, c->comm, st));
+        RPTI_HIP_TRY(rptg::launch_frame_pack(shard, d_stage, d_tiles + L.offsets[c->rank], n, L.tiles_x, width, height, st));
+        if (n) RCCL_TRY(g_rccl.Send(d_stage, size_t(n) * kTileDoubles, ncclDouble, 0, c->comm, st));
         return RPT_OK;
     }
     // rank 0: its own tiles are in place already (or are copied tile by tile, or -- loopback -- travel like the others)
-    if (loop) RPTI_HIP_TRY(rptg::launch_frame_pack(shard, c->d_stage, c->d_tiles, n_of(0), L.tiles_x, width, height, st));
+    if (loop) RPTI_HIP_TRY(rptg::launch_frame_pack(shard, d_stage, d_tiles, n_of(0), L.tiles_x, width, height, st));
     const bool any_transfer = c->n_ranks > 1 || (loop && n_of(0));
     if (any_transfer) {
         // loopback: rank 0's packed block (the start of the staging buffer) is sent to itself and received behind the last block
-        double* const self_recv = c->d_stage + L.offsets[L.n_ranks] * kTileDoubles;
+        double* const self_recv = d_stage + L.offsets[L.n_ranks] * kTileDoubles;
         RCCL_TRY(g_rccl.GroupStart());
         ncclResult_t bad = ncclSuccess;
         if (loop && n_of(0)) {
-            ncclResult_t r1 = g_rccl.Send(c->d_stage, size_t(n_of(0)) * kTileDoubles, ncclDouble, 0, c->comm, st);
+            ncclResult_t r1 = g_rccl.Send(d_stage, size_t(n_of(0)) * kTileDoubles, ncclDouble, 0, c->comm, st);
             ncclResult_t r2 = g_rccl.Recv(self_recv, size_t(n_of(0)) * kTileDoubles, ncclDouble, 0, c->comm, st);
             if (r1 != ncclSuccess) bad = r1; else if (r2 != ncclSuccess) bad = r2;
         }
         for (int r = 1; r < c->n_ranks; r++) {
             if (!n_of(r)) continue;
-            ncclResult_t rr = g_rccl.Recv(c->d_stage + L.offsets[r] * kTileDoubles, size_t(n_of(r)) * kTileDoubles, ncclDouble, r, c->comm, st);
+            ncclResult_t rr = g_rccl.Recv(d_stage + L.offsets[r] * kTileDoubles, size_t(n_of(r)) * kTileDoubles, ncclDouble, r, c->comm, st);
             if (rr != ncclSuccess && bad == ncclSuccess) bad = rr;
         }
         RCCL_TRY(g_rccl.GroupEnd());
         if (bad != ncclSuccess) return fail(RPT_ERR_DEVICE, std::string("ncclSend/ncclRecv: ") + g_rccl.GetErrorString(bad));
-        if (loop) RPTI_HIP_TRY(rptg::launch_frame_unpack(self_recv, frame, c->d_tiles, n_of(0), L.tiles_x, width, height, st));
+        if (loop) RPTI_HIP_TRY(rptg::launch_frame_unpack(self_recv, frame, d_tiles, n_of(0), L.tiles_x, width, height, st));
         // every other rank's block with one launch: their tiles are contiguous in the list and in the staging buffer
         const uint32_t n_others = uint32_t(L.offsets[L.n_ranks] - L.offsets[1]);
-        RPTI_HIP_TRY(rptg::launch_frame_unpack(c->d_stage + L.offsets[1] * kTileDoubles, frame, c->d_tiles + L.offsets[1], n_others, L.tiles_x,
+        RPTI_HIP_TRY(rptg::launch_frame_unpack(d_stage + L.offsets[1] * kTileDoubles, frame, d_tiles + L.offsets[1], n_others, L.tiles_x,
                                                 width, height, st));
     }
     if (!loop && frame != shard) {   // own tiles into a separate frame: pack + unpack on the device
-        RPTI_HIP_TRY(rptg::launch_frame_pack(shard, c->d_stage, c->d_tiles, n_of(0), L.tiles_x, width, height, st));
-        RPTI_HIP_TRY(rptg::launch_frame_unpack(c->d_stage, frame, c->d_tiles, n_of(0), L.tiles_x, width, height, st));
+        RPTI_HIP_TRY(rptg::launch_frame_pack(shard, d_stage, d_tiles, n_of(0), L.tiles_x, width, height, st));
+        RPTI_HIP_TRY(rptg::launch_frame_unpack(d_stage, frame, d_tiles, n_of(0), L.tiles_x, width, height, st));
     }
     return RPT_OK;
 }
@@ -295,13 +279,14 @@ int rpt_allgather_records_device(rpt_comm* c, const void* d_local, uint64_t n_lo
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     RPTI_HIP_TRY(hipSetDevice(c->device));
     const size_t n = size_t(c->n_ranks);
-    if (!c->d_counts) RPTI_HIP_TRY(hipMalloc((void**)&c->d_counts, (n + 1) * sizeof(unsigned long long)));
+    RPTI_HIP_TRY(c->d_counts.reserve((n + 1) * sizeof(unsigned long long)));
     // [n]: this rank's count (send buffer), [0, n): everybody's
+    unsigned long long* const d_counts = c->d_counts.get<unsigned long long>();
     unsigned long long mine = n_local;
-    RPTI_HIP_TRY(hipMemcpyAsync(c->d_counts + n, &mine, sizeof(mine), hipMemcpyHostToDevice, st));
-    RCCL_TRY(g_rccl.AllGather(c->d_counts + n, c->d_counts, 1, ncclUint64, c->comm, st));
+    RPTI_HIP_TRY(hipMemcpyAsync(d_counts + n, &mine, sizeof(mine), hipMemcpyHostToDevice, st));
+    RCCL_TRY(g_rccl.AllGather(d_counts + n, d_counts, 1, ncclUint64, c->comm, st));
     std::vector<unsigned long long> counts(n);
-    RPTI_HIP_TRY(hipMemcpyAsync(counts.data(), c->d_counts, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    RPTI_HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     RPTI_HIP_TRY(hipStreamSynchronize(st));
     uint64_t total = 0, largest = 0;
     for (size_t r = 0; r < n; r++) {
@@ -316,13 +301,8 @@ int rpt_allgather_records_device(rpt_comm* c, const void* d_local, uint64_t n_lo
     if (!d_out) return fail(RPT_ERR_INVALID, "null output");
     const size_t block = size_t(largest) * RPT_PHOTON_RECORD_BYTES;
     const size_t need = block * (n + 1);   // the padded copy of this rank's records + every rank's block
-    if (need > c->rec_stage_cap) {
-        if (c->d_rec_stage) RPTI_HIP_TRY(hipFree(c->d_rec_stage));
-        c->d_rec_stage = nullptr; c->rec_stage_cap = 0;
-        RPTI_HIP_TRY(hipMalloc(&c->d_rec_stage, need));
-        c->rec_stage_cap = need;
-    }
-    char* const send = static_cast<char*>(c->d_rec_stage), *const recv = send + block;
+    RPTI_HIP_TRY(c->d_rec_stage.reserve(need));
+    char* const send = c->d_rec_stage.get<char>(), *const recv = send + block;
     if (n_local) RPTI_HIP_TRY(hipMemcpyAsync(send, d_local, size_t(n_local) * RPT_PHOTON_RECORD_BYTES, hipMemcpyDeviceToDevice, st));
     RCCL_TRY(g_rccl.AllGather(send, recv, block, ncclUint8, c->comm, st));
     size_t at = 0;

@@ -2,16 +2,18 @@
 // rpt_capi.cpp and prints the flattened-layout statistics plus a checksum of every tree node and scan record.
 // tests/test_host_flatten.py compiles it with sanitizers and at several optimisation levels: the output must not
 // depend on the compiler (a loop whose result changed with -fno-unroll-loops exposed undefined behaviour once).
+// The launch stubs read the first byte of the buffers a kernel would write: a null or freed buffer fails under ASan.
 #include "hip_stubs.h"
 #include "../../rpt_amd/csrc/rpt_capi.cpp"
+static void touch(const void* p) { (void)*static_cast<const volatile char*>(p); }
 namespace rptg {
-hipError_t launch_render(const RenderArgs&, int, hipStream_t) { return hipSuccess; }
+hipError_t launch_render(const RenderArgs& a, int, hipStream_t) { touch(a.slab); touch(a.tiles); return hipSuccess; }
 hipError_t render_occupancy(bool, int, int* b, int) { *b = 4; return hipSuccess; }
 size_t stream_scratch_bytes_per_block() { return 0; }
 int bvh_mode(const SceneView& sc) { return sc.scene_bvh ? 2 : (sc.n_nodes ? 1 : 0); }
-hipError_t launch_resolve(const RenderArgs&, double, double*, hipStream_t) { return hipSuccess; }
-hipError_t launch_render_f64(const rpt64::Args&, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_resolve_f64(const rpt64::Args&, double, double*, hipStream_t) { return hipSuccess; }
+hipError_t launch_resolve(const RenderArgs& a, double, double* out, hipStream_t) { touch(a.slab); touch(a.tiles); touch(out); return hipSuccess; }
+hipError_t launch_render_f64(const rpt64::Args& q, int, hipStream_t) { touch(q.slab); touch(q.tiles); return hipSuccess; }
+hipError_t launch_resolve_f64(const rpt64::Args& q, double, double* out, hipStream_t) { touch(q.slab); touch(q.tiles); touch(out); return hipSuccess; }
 hipError_t render_f64_occupancy(bool, int* blocks_per_cu) { *blocks_per_cu = 4; return hipSuccess; }
 hipError_t launch_intersect(const SceneView&, uint64_t, const float*, const float*, float*, int32_t*, float*, bool, hipStream_t) { return hipSuccess; }
 hipError_t launch_debug_rng(uint64_t, uint32_t, uint32_t, uint32_t, uint32_t*, hipStream_t) { return hipSuccess; }
@@ -37,7 +39,7 @@ static void report(const char* name, rpt_scene* s) {
     uint64_t st[16] = {0};
     rpt_scene_stats(s, st);
     uint64_t h = 0;
-    if (rc == 0 && s->arena) h = fnv(s->arena, size_t(st[9]));   // every array of the flattened scene
+    if (rc == 0 && s->dev.arena) h = fnv(s->dev.arena.get(), size_t(st[9]));   // every array of the flattened scene
     std::printf("%s rc=%d", name, rc);
     for (int i = 0; i < 15; i++) std::printf(" %llu", (unsigned long long)st[i]);
     std::printf(" arena=%016llx\n", (unsigned long long)h);
@@ -125,7 +127,33 @@ int main() {
         add(s, quad, true);
         const int rc = rpt_scene_commit(s, 0);
         std::printf("epsilon rc=%d records=%u arena64=%016llx bytes=%zu\n", rc, s->view64.n_objects,
-                    (unsigned long long)(rc == 0 && s->arena64 ? fnv(s->arena64, s->arena64_bytes) : 0ull), s->arena64_bytes);
+                    (unsigned long long)(rc == 0 && s->dev.arena64 ? fnv(s->dev.arena64.get(), s->dev.arena64.capacity()) : 0ull), s->dev.arena64.capacity());
+        rpt_scene_destroy(s);
+    }
+    for (int eps = 0; eps < 2; eps++) {   // device buffers that fail to grow: the next smaller render must not launch on them
+        rpt_scene* s = rpt_scene_create();
+        rpt_scene_set_option(s, "epsilon_policy", eps);
+        rpt_scene_set_option(s, "timing", 1);   // (the timing events must be destroyed with the scene)
+        add(s, polygon({{0, 0, 0}, {0, 0, 5}, {5, 0, 5}, {5, 0, 0}}));
+        add(s, sphere().translate({2, 1, 2}));
+        add(s, polygon({{2, 4, 2}, {3, 4, 2}, {3, 4, 3}, {2, 4, 3}}), true);
+        const int rc = rpt_scene_commit(s, 0);
+        const rpt_camera cam{{2.5, 2, -6}, {0, 0, 1}, {0, 1, 0}, 0.8, 0, 1};
+        std::vector<double> rgb(512 * 512 * 3);
+        auto render = [&](uint32_t w) {
+            const rpt_render_params prm{w, w, 0.0, 4, 0, 1};
+            return rpt_render_sample(s, &cam, &prm, 4, 7, 0, rgb.data());
+        };
+        const int small = render(64);
+        g_stub_malloc_limit = 5u << 20;   // the 512x512 slab (8 MiB) cannot be had
+        const int big = render(512);
+        g_stub_malloc_limit = SIZE_MAX;
+        const int again = render(64);
+        rpt_buffer* b = rpt_buffer_create(0, 64, 64, 0);
+        const rpt_render_params prm{64, 64, 0.0, 4, 0, 1};
+        const int buf = b ? rpt_render_into_buffer(s, &cam, &prm, 4, 7, 0, b) : -100;
+        rpt_buffer_destroy(b);
+        std::printf("grow %s commit=%d render=%d,%d,%d buffer=%d\n", eps ? "epsilon" : "fp32", rc, small, big, again, buf);
         rpt_scene_destroy(s);
     }
     {   // error paths: nothing may be read out of bounds or leak

@@ -1,6 +1,7 @@
 """Host half of the library on a CPU: rpt_amd/csrc/rpt_capi.cpp compiled with malloc-backed HIP stubs
 (tests/host/) commits a room, a mesh scene, a scene of groups with a shared mesh, a scene in the reference-epsilon mode (groups as
-records under frames, per-triangle constants with the reference's own operation order) and a few invalid shapes.
+records under frames, per-triangle constants with the reference's own operation order) and a few invalid shapes, and renders
+into device buffers that fail to grow (in both modes).
 
   * under AddressSanitizer + UBSan (g++): no report, exit code 0;
   * at -O0, -O3 and -O3 -fno-unroll-loops: byte-identical flattened scenes (arena checksums).  The last
@@ -30,7 +31,7 @@ def _build_and_run(tmp_path, name, compiler, flags):
 
 
 @pytest.mark.timeout(600)
-def test_flatten_is_clean_under_sanitizers_and_independent_of_the_optimiser(tmp_path):
+def test_flatten_and_device_buffers_are_clean_under_sanitizers_and_independent_of_the_optimiser(tmp_path):
     if not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
         pytest.skip("HIP headers not installed")
     outs = {"g++ -O1 asan+ubsan": _build_and_run(tmp_path, "san", "g++", ["-O1", "-g", "-fsanitize=address,undefined",
@@ -52,3 +53,6 @@ def test_flatten_is_clean_under_sanitizers_and_independent_of_the_optimiser(tmp_
     eps = [l for l in first.splitlines() if l.startswith("epsilon ")]
     assert len(eps) == 1 and "rc=0" in eps[0] and "records=9 " in eps[0]     # 4 plain objects + the 5 shapes inside the (nested) groups
     assert "bad kind rc=-1" in first and "empty mesh rc=-1" in first and "singular rc=-1" in first and "second commit rc=-2" in first
+    # a render whose slab cannot grow fails with RPT_ERR_DEVICE, and the next smaller one runs on valid buffers (ASan would report a
+    # launch on the null slab); then a device buffer is filled and destroyed, and the timing events go with the scene (LeakSanitizer)
+    assert "grow fp32 commit=0 render=0,-3,0 buffer=0" in first and "grow epsilon commit=0 render=0,-3,0 buffer=0" in first
