@@ -191,6 +191,9 @@ int rpt_scene_render_chunking(rpt_scene*, uint32_t iterations, uint32_t* chunk_s
  * object scan, default 64), "instancing" 0/1 (read by rpt_scene_commit: store a mesh that several
  * shapes share once and instance it, default 1), "room_shell" 0/1 (read by rpt_scene_commit: answer the
  * rectangles that are the faces of one axis-aligned box with a single slab test, default 1),
+ * "scan_specialise" 0/1 (read by rpt_scene_commit: mark the sphere / cube records that are rotated about the vertical axis only
+ * and the adjacent box records with common slabs, so that the linear scans leave out the zero terms and the repeated slab
+ * arithmetic, default 1; the hits are bit-identical either way),
  * "photon_block_lists" 0/1 (camera pass of the beam x point kind: collect the photon spheres of each strip of an
  * 8x8 pixel block once per work item and test them with one photon per lane, default 1; 0 walks the tree per
  * sample), "photon_parts" (work items per 8x8 pixel block and sample chunk of the photon camera pass: the block's

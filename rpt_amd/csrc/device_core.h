@@ -258,6 +258,39 @@ RPT_DEV void to_local(const XfScan& x, V o, V d, V& ol, V& dl) {
     ol = mk(dot3w(x.r0, o), dot3w(x.r1, o), dot3w(x.r2, o));
     dl = mk(dot3(x.r0, d), dot3(x.r1, d), dot3(x.r2, d));
 }
+// to_local for a record whose rows hold exact zeros at r0.y, r1.x, r1.z and r2.y (a rotation about the vertical axis under any
+// scale and translation: SceneView::sph_yrot / cub_yrot, set at commit): the same fma chains with the terms fma(0, p, acc) and
+// 0 * p left out, 10 operations instead of 18.  Such a term returns acc exactly, so ol and dl keep their bits -- except that a
+// result which is zero may change its sign (-0 + 0 = +0).  In dl that swaps the +inf / -inf of a slab pair, whose min / max are
+// unchanged; tests/test_gpu_scan_specialise.py holds t and the hit code bit-equal to the generic form's.
+RPT_DEV void to_local_y(const XfScan& x, V o, V d, V& ol, V& dl) {
+    ol = mk(fmaf(x.r0.x, o.x, fmaf(x.r0.z, o.z, x.r0.w)), fmaf(x.r1.y, o.y, x.r1.w), fmaf(x.r2.x, o.x, fmaf(x.r2.z, o.z, x.r2.w)));
+    dl = mk(fmaf(x.r0.x, d.x, x.r0.z * d.z), x.r1.y * d.y, fmaf(x.r2.x, d.x, x.r2.z * d.z));
+}
+// Two world-space boxes that are adjacent in the scan, tested in record order: aabb_closer twice, operation for operation.  `shared`:
+// the axes (bit 0 = x, 1 = y, 2 = z) on which the second box's lo and hi are bit-equal to the first's (AabbScan::hi.w of the first,
+// wave-uniform): its slab interval there IS the first box's -- identical operands, identical results -- and is not computed again.
+// One uniform if per axis rather than a body per combination: every combination is served, and a three-way choice between whole
+// bodies compiles to a chain of flag tests that costs ~60 scalar instructions per trip on C3.  The first box's entry / exit are
+// pinned before the ifs: sunk below them they keep its intervals alive, and each shared one then costs two register copies.
+RPT_DEV void aabb_pair_closer(const AabbScan& b0, const AabbScan& b1, uint32_t shared, V o, V inv, float tmin, float& tbest,
+                              uint32_t& code, uint32_t i) {
+#pragma clang fp contract(off)
+    const float x1 = (b0.lo.x - o.x) * inv.x, x2 = (b0.hi.x - o.x) * inv.x;
+    const float y1 = (b0.lo.y - o.y) * inv.y, y2 = (b0.hi.y - o.y) * inv.y;
+    const float z1 = (b0.lo.z - o.z) * inv.z, z2 = (b0.hi.z - o.z) * inv.z;
+    float xl = fminf(x1, x2), xh = fmaxf(x1, x2), yl = fminf(y1, y2), yh = fmaxf(y1, y2), zl = fminf(z1, z2), zh = fmaxf(z1, z2);
+    float start = max3(xl, yl, zl), end = min3(xh, yh, zh);   // slabs_closer from here on
+    asm volatile("" : "+v"(start), "+v"(end));
+    float t = start < tmin ? end : start;
+    if (!(start > end) && !(end < tmin) && t < tbest) { tbest = t; code = (K_AABB << 28) | i; }
+    if (!(shared & 1u)) { const float u1 = (b1.lo.x - o.x) * inv.x, u2 = (b1.hi.x - o.x) * inv.x; xl = fminf(u1, u2); xh = fmaxf(u1, u2); }
+    if (!(shared & 2u)) { const float u1 = (b1.lo.y - o.y) * inv.y, u2 = (b1.hi.y - o.y) * inv.y; yl = fminf(u1, u2); yh = fmaxf(u1, u2); }
+    if (!(shared & 4u)) { const float u1 = (b1.lo.z - o.z) * inv.z, u2 = (b1.hi.z - o.z) * inv.z; zl = fminf(u1, u2); zh = fmaxf(u1, u2); }
+    start = max3(xl, yl, zl), end = min3(xh, yh, zh);
+    t = start < tmin ? end : start;
+    if (!(start > end) && !(end < tmin) && t < tbest) { tbest = t; code = (K_AABB << 28) | (i + 1u); }
+}
 // MonomialSurface::intersect, src/shape/monomial_surface.rs:22-107, in the surface's local space (t is shared), step for step:
 // the box test against [-1, 0, -1]..[1, h, 1] (min / max per axis, so h <= 0 works), maximize = dist(t_min) < 0, Newton from
 // the box's midpoint (at most 10 steps, leaving as soon as dist > 0) for the end of the bracket -- or 10000 --, the sign check,
@@ -467,11 +500,14 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
     (void)scene;
     uint32_t bit = 0;  // wave-uniform record number
     auto on = [&](uint32_t i) { return !MASKED || ((mask >> ((bit + i) & 63u)) & 1ull) != 0ull; };
+    // Unmasked scans: records the commit found to be rotations about the vertical axis take to_local_y (wave-uniform branches).
+    const uint64_t sph_yrot = MASKED ? 0ull : sc.sph_yrot, cub_yrot = MASKED ? 0ull : sc.cub_yrot;
     for (uint32_t i = 0; i < sc.n_sph; i++) {
         if (!on(i)) continue;
         const XfScan x = uload(&sc.sph[i]);
         V ol, dl;
-        to_local(x, o, d, ol, dl);
+        if (!MASKED && ((sph_yrot >> (i & 63u)) & 1ull)) to_local_y(x, o, d, ol, dl);
+        else to_local(x, o, d, ol, dl);
         float t;
         if (sphere_closer(ol, dl, tmin, tbest, t)) { tbest = t; code = (K_SPHERE << 28) | i; }
     }
@@ -482,9 +518,14 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
             for (; i + 1u < sc.n_cub; i += 2u) {
                 const XfScan x0 = uload(&sc.cub[i]), x1 = uload(&sc.cub[i + 1u]);
                 V ol0, dl0, ol1, dl1;
-                to_local(x0, o, d, ol0, dl0);
-                to_local(x1, o, d, ol1, dl1);
                 float t0, t1;
+                if (((cub_yrot >> (i & 63u)) & 3ull) == 3ull) {
+                    to_local_y(x0, o, d, ol0, dl0);
+                    to_local_y(x1, o, d, ol1, dl1);
+                } else {
+                    to_local(x0, o, d, ol0, dl0);
+                    to_local(x1, o, d, ol1, dl1);
+                }
                 if (cube_closer(ol0, dl0, tmin, tbest, t0)) { tbest = t0; code = (K_CUBE << 28) | i; }
                 if (cube_closer(ol1, dl1, tmin, tbest, t1)) { tbest = t1; code = (K_CUBE << 28) | (i + 1u); }
             }
@@ -492,7 +533,8 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
             if (!on(i)) continue;
             const XfScan x = uload(&sc.cub[i]);
             V ol, dl;
-            to_local(x, o, d, ol, dl);
+            if (!MASKED && ((cub_yrot >> (i & 63u)) & 1ull)) to_local_y(x, o, d, ol, dl);
+            else to_local(x, o, d, ol, dl);
             float t;
             if (cube_closer(ol, dl, tmin, tbest, t)) { tbest = t; code = (K_CUBE << 28) | i; }
         }
@@ -512,9 +554,7 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
             if (!MASKED)
                 for (; i + 1u < sc.n_aabb; i += 2u) {
                     const AabbScan b0 = uload(&sc.aabb[i]), b1 = uload(&sc.aabb[i + 1u]);
-                    float t0, t1;
-                    if (aabb_closer(b0.lo, b0.hi, o, inv, tmin, tbest, t0)) { tbest = t0; code = (K_AABB << 28) | i; }
-                    if (aabb_closer(b1.lo, b1.hi, o, inv, tmin, tbest, t1)) { tbest = t1; code = (K_AABB << 28) | (i + 1u); }
+                    aabb_pair_closer(b0, b1, __float_as_uint(b0.hi.w), o, inv, tmin, tbest, code, i);   // hi.w: the slabs they have in common
                 }
             for (; i < sc.n_aabb; i++) {
                 if (!on(i)) continue;
@@ -952,9 +992,13 @@ RPT_DEV V bsdf(const Mat& m, V n, V wo, V wi) {
     if (m.kind == M_PHONG) {
         V r = -normalize(fma3(-2.f * dot(n, wi), n, wi));
         float c = fminf(fmaxf(dot(r, wo), 0.f), 1.f);
+        // The shininess behind an opaque copy: its two terms below are invariant in the render kernels' light loop, and hoisted out
+        // of it each of them holds a register across the shadow scan (the kernels sit at their 80-register limit: two more spills).
+        float shin = m.shin;
+        asm volatile("" : "+v"(shin));
         // powf(0, s) = 0 for s > 0, 1 for s == 0
-        float pw = (c > 0.f) ? __powf(c, m.shin) : (m.shin == 0.f ? 1.f : 0.f);
-        return ((m.shin + 2.f) * (0.5f * kInvPi) * pw) * m.albedo;
+        float pw = (c > 0.f) ? __powf(c, shin) : (shin == 0.f ? 1.f : 0.f);
+        return ((shin + 2.f) * (0.5f * kInvPi) * pw) * m.albedo;
     }
     return mk(1.f, 1.f, 1.f);
 }

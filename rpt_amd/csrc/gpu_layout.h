@@ -60,6 +60,9 @@ struct alignas(16) TriShade {
 //  * AabbScan: a cube whose transform is a positive scale + translation, i.e. an axis-aligned box
 //    in world space; tested with the ray's shared 1/d (no per-box affine map, no per-box rcp).
 //    lo.w = object id (bits).  The face choice follows src/shape/cube.rs:37-55 unchanged.
+//    hi.w of an EVEN record 2k (bits; option "scan_specialise"): the axes (bit 0 = x, 1 = y, 2 = z) on which record
+//    2k+1 has bit-equal lo and hi -- the unmasked scan tests the pair together and computes a shared slab once
+//    (aabb_pair_closer).  0 in odd records, in a last record without a partner and for boxes that share nothing.
 //  * RectScan: two coplanar flat triangles of one mesh forming an axis-aligned rectangle
 //    (polygon() of 4 corners, e.g. every Cornell wall): plane coordinate c on `axis`, bounds on
 //    the other two axes in cyclic order (u = axis+1, v = axis+2).  Records are sorted by axis.
@@ -195,6 +198,12 @@ struct SceneView {
     // Monomial surfaces (K_MONO), scanned after the triangles (their pbox entries follow the triangles'); n_mono != 0 selects
     // the kernel instantiations that test them.  (Kept last: the fields above keep their offsets in the kernel arguments.)
     const MonoScan* mono;  const XfShade* mono_sh;  uint32_t n_mono;
+    // Flatten-time specialisation of the unmasked scans (option "scan_specialise"): bit i = sphere / cube record i is a
+    // rotation about the vertical axis (with any scale and translation), i.e. its XfScan rows hold exact zeros at r0.y, r1.x,
+    // r1.z and r2.y, and the scan maps the ray with to_local_y.  A linear scan holds fewer than 64 bounded records (from
+    // scene_bvh_min on the scene tree takes over); a kind with more than 64 records gets no bits at all.
+    uint32_t scan_pad_;
+    uint64_t sph_yrot, cub_yrot;
 };
 
 struct CameraG {

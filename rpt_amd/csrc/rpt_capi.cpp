@@ -58,6 +58,7 @@ struct rpt_options {
     int64_t blocks_per_cu = 0;      // 0 = occupancy query
     int64_t timing = 0;
     int64_t room_shell = 1;         // fold rectangles that are the faces of one box into a single slab test
+    int64_t scan_specialise = 1;    // mark y-rotated sphere / cube records and box pairs with common slabs for the unmasked scans (read by rpt_scene_commit)
     int64_t photon_skip = 0;
     int64_t photon_block_lists = 1;
     int64_t photon_coop_gather = 1; // surface gather of a pixel's samples by the wave together (0: one search per lane)
@@ -98,6 +99,7 @@ static int set_option_in(rpt_options& o, const char* name, int64_t value) {
     else if (s == "blocks_per_cu") o.blocks_per_cu = value;
     else if (s == "timing") o.timing = value;
     else if (s == "room_shell") o.room_shell = value;
+    else if (s == "scan_specialise") o.scan_specialise = value;
     else if (s == "photon_skip") o.photon_skip = value;
     else if (s == "photon_block_lists") o.photon_block_lists = value;
     else if (s == "photon_parts") o.photon_parts = value;
@@ -840,6 +842,7 @@ struct Flattener {
     std::vector<TriScan> tri, btri;
     std::vector<TriShade> tri_sh, btri_sh;
     std::vector<AabbScan> aabb;
+    uint64_t sph_yrot = 0, cub_yrot = 0;   // specialise_scans
     std::vector<RectScan> rect_axis[3];
     std::vector<RectShade> rect_sh_axis[3];
     std::vector<BvhNode> nodes;
@@ -1400,6 +1403,32 @@ struct Flattener {
         }
         return RPT_OK;
     }
+    // (5b) what the unmasked scans may leave out (SceneView::sph_yrot / cub_yrot, AabbScan::hi.w).  Nothing is reordered: record
+    // order is the tie-break of the scans and defines the hit codes.  Only exact equalities of the fp32 values as stored count.
+    static uint64_t yrot_mask(const std::vector<XfScan>& recs) {
+        uint64_t m = 0;
+        if (recs.size() > 64) return 0;   // (such a scene has a scene tree anyway)
+        for (size_t i = 0; i < recs.size(); i++) {
+            const XfScan& x = recs[i];
+            if (x.r0.y == 0.f && x.r1.x == 0.f && x.r1.z == 0.f && x.r2.y == 0.f) m |= 1ull << i;
+        }
+        return m;
+    }
+    void specialise_scans() {
+        sph_yrot = cub_yrot = 0;
+        for (AabbScan& b : aabb) b.hi.w = 0.f;
+        if (!s->opt.scan_specialise) return;
+        sph_yrot = yrot_mask(sph);
+        cub_yrot = yrot_mask(cub);
+        for (size_t i = 0; i + 1 < aabb.size(); i += 2) {
+            const AabbScan &a = aabb[i], &b = aabb[i + 1];
+            uint32_t shared = 0;
+            if (bits_u(a.lo.x) == bits_u(b.lo.x) && bits_u(a.hi.x) == bits_u(b.hi.x)) shared |= 1u;
+            if (bits_u(a.lo.y) == bits_u(b.lo.y) && bits_u(a.hi.y) == bits_u(b.hi.y)) shared |= 2u;
+            if (bits_u(a.lo.z) == bits_u(b.lo.z) && bits_u(a.hi.z) == bits_u(b.hi.z)) shared |= 4u;
+            aabb[i].hi.w = bits_f(shared);
+        }
+    }
     // (6) boxes of the scanned records, for ball-limited queries
     void collect_scan_boxes() {
         // world boxes of the scanned bounded records, in scan order (SceneView::pbox)
@@ -1505,6 +1534,7 @@ struct Flattener {
         v.mesh_deferred = (scene_bvh && mesh_deferred) ? 1u : 0u;
         v.inst = (const InstRec*)(base + o_inst);   v.n_inst = uint32_t(insts.size());
         v.mono = (const MonoScan*)(base + o_mono);  v.mono_sh = (const XfShade*)(base + o_monos);  v.n_mono = uint32_t(mono.size());
+        v.scan_pad_ = 0;  v.sph_yrot = sph_yrot;  v.cub_yrot = cub_yrot;
         v.mats = (const Material*)(base + o_mats);  v.n_obj = uint32_t(mats.size());
         v.lights = (const Light*)(base + o_lights); v.n_lights = uint32_t(lights.size());
         v.ltris = (const LightTri*)(base + o_ltris); v.lxf = (const LightXf*)(base + o_lxf);
@@ -2079,6 +2109,7 @@ int rpt_scene_commit(rpt_scene* s, int device) {
     f.mark_twin_ranges();
     rc = f.build_scene_tree();
     if (rc) return rc;
+    f.specialise_scans();
     f.collect_scan_boxes();
     rc = f.upload(device);
     if (rc) return rc;
