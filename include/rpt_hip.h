@@ -186,7 +186,9 @@ int rpt_scene_render_chunking(rpt_scene*, uint32_t iterations, uint32_t* chunk_s
  * a commit or render reads is process-global, so scenes with different options may be driven from different host
  * threads).  rpt_set_option changes the defaults, i.e. the scenes created afterwards (and what rpt_render_chunking
  * reports).  Names (all optional): "counters" 0/1, "chunk_spp" (samples per work item, 0 = auto),
- * "blocks_per_cu" (persistent grid size), "timing" 0/1, "scene_bvh_min" (read by rpt_scene_commit:
+ * "blocks_per_cu" (persistent grid size), "max_blocks" (cap on the blocks of every persistent launch -- renders, photon camera
+ * pass, the reference-epsilon shooting and surface passes --, 0 = none, the default: a small grid gives every lane or wave many work
+ * items, which is what the schedule tests need; no effect on the image), "timing" 0/1, "scene_bvh_min" (read by rpt_scene_commit:
  * number of bounded primitives + BVH meshes from which one scene-level BVH replaces the linear
  * object scan, default 64), "instancing" 0/1 (read by rpt_scene_commit: store a mesh that several
  * shapes share once and instance it, default 1), "room_shell" 0/1 (read by rpt_scene_commit: answer the
@@ -265,7 +267,8 @@ int rpt_photon_shoot(rpt_scene*, uint64_t photon_count, int32_t kind, double wat
 int rpt_photon_records(rpt_scene*, int32_t which /* 0 surface, 1 volume */, void** d_records, uint64_t* n);
 int rpt_photon_map_from_records(rpt_scene*, uint64_t photon_count, int32_t kind, const void* d_surface,
                                 uint64_t n_surface, const void* d_volume, uint64_t n_volume);
-/* [0] surface photons, [1] volume photons, [2] photons shot, [3] shooting us, [4] map build us. */
+/* [0] surface photons, [1] volume photons, [2] photons shot, [3] shooting us, [4] map build us, [5] blocks of the shooting
+ * pass's grid, [6] blocks of the last reference-epsilon surface pass over this map (0: none yet). */
 int rpt_photon_map_stats(rpt_scene*, uint64_t out[8]);
 /* Test hook: which = 0 surface / 1 volume; out = n * 10 floats in shooting order:
  * position, direction (toward the previous vertex), power, gather radius (volume photons). */

@@ -846,13 +846,13 @@ class Renderer:
         out = (C.c_uint64 * 8)()
         _lib.check(lib.rpt_photon_map_stats(h, out))
         return {"surface": int(out[0]), "volume": int(out[1]), "shot": int(out[2]), "shoot_us": int(out[3]),
-                "build_us": int(out[4])}
+                "build_us": int(out[4]), "shoot_blocks": int(out[5]), "surface64_blocks": int(out[6])}
 
     def _photon_stats(self):
         out = (C.c_uint64 * 8)()
         _lib.check(_lib.load().rpt_photon_map_stats(self.scene._handle, out))
         return {"surface": int(out[0]), "volume": int(out[1]), "shot": int(out[2]), "shoot_us": int(out[3]),
-                "build_us": int(out[4])}
+                "build_us": int(out[4]), "shoot_blocks": int(out[5]), "surface64_blocks": int(out[6])}
 
     def photon_shoot(self, photon_count, kind, shard_rank=0, shard_count=1):
         """rpt_photon_shoot: this rank's contiguous block of the shooting loop (photon.rs:656-690);

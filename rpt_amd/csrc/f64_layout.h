@@ -174,6 +174,7 @@ struct ShootArgs64 {
     PhotonRec32* surf;
     PhotonRec32* vol;
     double* pos64;              // [3 per surface record, shooting order]: the position as the reference holds it
+    uint32_t* mismatch;         // write pass: set when a chain's records are not the ones the count pass counted (the store is skipped)
 };
 // The surface estimate of the camera pass (src/photon.rs:327-375): the gathered photons' visibility rays and terms, per sample.
 struct SurfArgs64 {

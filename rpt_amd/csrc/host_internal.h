@@ -115,13 +115,15 @@ int prepare_render(rpt_scene* s, hipStream_t st, const rpt_camera* cam, const rp
 int run_persistent(rpt_scene* s, const rpt_render_params* prm, const rptg::RenderArgs& a, double* d_out, hipStream_t st,
                    int blocks_per_cu, const std::function<hipError_t(const rptg::RenderArgs&, int, hipStream_t)>& launch,
                    bool indexed_start = false, bool wave_items = false,   // wave_items: n_items counts one item per wave, not per lane
-                   const std::function<hipError_t(double, double*, hipStream_t)>& resolve = nullptr);   // (scale, d_out, stream): instead of resolve_kernel
+                   const std::function<hipError_t(double, double*, hipStream_t)>& resolve = nullptr,   // (scale, d_out, stream): instead of resolve_kernel
+                   bool clear_sharded = true);   // false: a sharded frame keeps what is in d_out (a resolve that adds to the earlier slices of the same frame)
 int serialize_with_other_streams(rpt_scene* s, hipStream_t st);  // for launches with per-scene scratch outside the launch set
 int fetch_counters(rpt_scene* s, const rptg::RenderArgs& a);  // after the stream has been synchronised
 // Arguments the fp64 kernels share (rpt_capi.cpp): scene; camera, frame and `a`'s tiles / chunking / work counter / slab when given.
 void fill_args64(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, const rptg::RenderArgs* a, rpt64::Args& q);
 double* scratch_out(rpt_scene* s, size_t bytes);  // cached device frame for the host-buffer entry points
 int64_t option_photon_skip(rpt_scene* s);  // option "photon_skip" of the scene: diagnostic bit mask for the camera pass
+int64_t option_max_blocks(rpt_scene* s);          // option "max_blocks": cap on the blocks of a persistent launch (0: none)
 int64_t option_f64_photon_slice(rpt_scene* s);    // option "f64_photon_slice": samples per slice of the reference-epsilon photon camera pass (0: automatic)
 int64_t option_photon_parts(rpt_scene* s);        // option "photon_parts": strips per 8x8 pixel block of the camera pass (1, 2, 4, 8)
 int64_t option_photon_coop_gather(rpt_scene* s);  // option "photon_coop_gather": wave-level surface gather on (default) / off

@@ -1174,6 +1174,7 @@ R64_DEV void stage_tables(double* t0, const ObjRec*& recs, const TriRec*& trecs)
 // One photon per lane; a lane whose photon is absorbed takes the next one of the wave's batch (64 per atomic).  WRITE = false
 // counts the records of every photon; the write pass retraces the same chains (same streams, and closest_hit_wave's record does
 // not depend on which rays share the wave) and stores them at the prefix sums of the counts: the arrays are in shooting order.
+// The write pass checks that: a record the count pass did not count is not stored, and the launch reports it (ShootArgs64::mismatch).
 template <bool MEDIUM, bool WRITE, bool LDSTAB>
 __global__ __launch_bounds__(256, R64_WAVES) void photon_shoot_f64_kernel(const ShootArgs64 by_value) {
     (void)by_value;
@@ -1263,7 +1264,8 @@ __global__ __launch_bounds__(256, R64_WAVES) void photon_shoot_f64_kernel(const 
                     const D dv = beams ? ro : wo;   // beams: where the beam starts
                     r.dir[0] = float(dv.x); r.dir[1] = float(dv.y); r.dir[2] = float(dv.z); r.dir[3] = 0.f;
                     r.pow[0] = float(boost * power.x); r.pow[1] = float(boost * power.y); r.pow[2] = float(boost * power.z); r.pow[3] = 0.f;
-                    KS.vol[ov + nv] = r;
+                    if (nv < KS.cnt_v[idx]) KS.vol[ov + nv] = r;   // (the arrays are sized from the count pass)
+                    else atomicOr(KS.mismatch, 1u);
                 }
                 nv++;
             }
@@ -1297,9 +1299,13 @@ __global__ __launch_bounds__(256, R64_WAVES) void photon_shoot_f64_kernel(const 
                         r.pos_r[0] = float(x.x); r.pos_r[1] = float(x.y); r.pos_r[2] = float(x.z); r.pos_r[3] = 0.f;
                         r.dir[0] = float(wo.x); r.dir[1] = float(wo.y); r.dir[2] = float(wo.z); r.dir[3] = 0.f;
                         r.pow[0] = float(power.x); r.pow[1] = float(power.y); r.pow[2] = float(power.z); r.pow[3] = 0.f;
-                        KS.surf[os + ns] = r;
-                        double* const p64 = KS.pos64 + size_t(os + ns) * 3u;
-                        p64[0] = x.x; p64[1] = x.y; p64[2] = x.z;
+                        if (ns < KS.cnt_s[idx]) {   // (the arrays are sized from the count pass)
+                            KS.surf[os + ns] = r;
+                            double* const p64 = KS.pos64 + size_t(os + ns) * 3u;
+                            p64[0] = x.x; p64[1] = x.y; p64[2] = x.z;
+                        } else {
+                            atomicOr(KS.mismatch, 1u);
+                        }
                     }
                     ns++;
                 }
@@ -1312,6 +1318,8 @@ __global__ __launch_bounds__(256, R64_WAVES) void photon_shoot_f64_kernel(const 
             if (!WRITE) {
                 KS.cnt_s[idx] = ns;
                 KS.cnt_v[idx] = nv;
+            } else if (ns != KS.cnt_s[idx] || nv != KS.cnt_v[idx]) {   // fewer records than counted: the rest of the range stays unwritten
+                atomicOr(KS.mismatch, 2u);
             }
             have = false;
         }
@@ -1320,7 +1328,11 @@ __global__ __launch_bounds__(256, R64_WAVES) void photon_shoot_f64_kernel(const 
 
 // One wave per (pixel, 64 samples of it), dealt out statically.  (With a work counter drawn from by lane 0, as in the other persistent
 // kernels, this one was not a function of its inputs: ~20 pixels of 4,096 changed from run to run, always items a wave took after its
-// first, written by lane 0 alone -- the cause was not isolated; tools/eps_photon_determinism.py is the check.)  Every lane retraces its sample's camera ray with the reference's arithmetic, then the wave
+// first, written by lane 0 alone.  The cause was in that hand-out, not in what a wave keeps from one item to the next: dealt out
+// statically, a wave that takes 13, 27, 512 or 1,024 items in a row -- grids capped with "max_blocks" -- writes the bits of the launch
+// that gives every wave one item, selections and frame, and so do render_f64_kernel and the shooting kernel, which share
+// closest_hit_wave and its LDS slots and do draw from a counter: tests/test_gpu_schedule.py.  tools/eps_photon_determinism.py is the
+// run-to-run check.)  Every lane retraces its sample's camera ray with the reference's arithmetic, then the wave
 // goes through the lanes' gathered photons rank by rank -- one visibility query per lane and rank (closest_hit_wave; the search may
 // end at the query point: only a hit closer than `len` blocks).  The pixel's partial sum: per lane in rank order, then the lanes
 // in a fixed butterfly order.

@@ -2035,6 +2035,7 @@ struct PhotonMapDev {
     PoolMem<uint32_t> d_emit;
     PoolMem<double> d_slab64;
     uint64_t emit_dims[3] = {0, 0, 0};   // of the last slice: owned pixel slots, gather_size + 2, samples
+    int shoot_blocks = 0, surf64_blocks = 0;   // grids of the last shooting pass and of the last fp64 surface pass (rpt_photon_map_stats)
     void release_raw() {
         raw_s.reset();
         raw_v.reset();
@@ -2235,7 +2236,15 @@ static int shoot_range(rpt_scene* s, PhotonMapDev* pm, uint64_t photon_count, ui
     a.cnt_v = cnt_v.get();
     if (f64) RPTI_HIP_TRY(queue.alloc(*pm->pool, 1));
     const bool medium = sd.view.has_medium != 0, bvh = sd.view.n_nodes != 0;
-    const int blocks = int(std::min<uint64_t>((n + 255) / 256, uint64_t(sd.n_cus) * (f64 ? 4 : 8)));
+    int blocks = int(std::min<uint64_t>((n + 255) / 256, uint64_t(sd.n_cus) * (f64 ? 4 : 8)));
+    if (const int64_t cap = rpti::option_max_blocks(s)) blocks = int(std::min<int64_t>(blocks, cap));
+    pm->shoot_blocks = blocks;
+    PoolMem<uint32_t> d_mismatch;   // fp64 write pass: raised by a chain that does not store exactly the records the count pass counted
+    if (f64) {
+        RPTI_HIP_TRY(d_mismatch.alloc(*pm->pool, 4));
+        RPTI_HIP_TRY(hipMemsetAsync(d_mismatch.get(), 0, 4, st));
+        a64.mismatch = d_mismatch.get();
+    }
     // the count pass (no record arrays yet), then the write pass
     auto launch = [&](bool write) -> hipError_t {
         if (!f64) return !write ? launch_shoot<false>(a, medium, bvh, blocks, st) : launch_shoot<true>(a, medium, bvh, blocks, st);
@@ -2275,6 +2284,11 @@ static int shoot_range(rpt_scene* s, PhotonMapDev* pm, uint64_t photon_count, ui
     RPTI_HIP_TRY(hipEventRecord(e1.get(), st));
     RPTI_HIP_TRY(hipEventSynchronize(e1.get()));
     pm->build_ms[0] = rpti::elapsed_ms(e0, e1);
+    if (f64) {
+        uint32_t mismatch = 0;
+        RPTI_HIP_TRY(hipMemcpy(&mismatch, d_mismatch.get(), 4, hipMemcpyDeviceToHost));
+        if (mismatch) return rpti::fail(RPT_ERR_DEVICE, "photon shooting: write pass did not retrace the count pass");
+    }
     return RPT_OK;
 }
 
@@ -2407,7 +2421,9 @@ int rpt_photon_map_stats(rpt_scene* s, uint64_t out[8]) {
     out[2] = pm->photon_count;
     out[3] = uint64_t(pm->build_ms[0] * 1000.0);  // microseconds: shooting (both passes)
     out[4] = uint64_t(pm->build_ms[1] * 1000.0);  // microseconds: sort + LBVH + radii
-    out[5] = out[6] = out[7] = 0;
+    out[5] = uint64_t(pm->shoot_blocks);    // blocks of the shooting pass's grid (both passes)
+    out[6] = uint64_t(pm->surf64_blocks);   // blocks of the last reference-epsilon surface pass (0: none yet)
+    out[7] = 0;
     return RPT_OK;
 }
 
@@ -2499,6 +2515,9 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
         sa.skip = q.skip;
         if (uint64_t(n_groups) * q.r.n_owned >= (1ull << 32)) return rpti::fail(RPT_ERR_INVALID, "too many work items");
     }
+    int surf64_blocks = rpti::scene_dev(s).n_cus * 4;
+    if (const int64_t cap = rpti::option_max_blocks(s)) surf64_blocks = int(std::min<int64_t>(surf64_blocks, cap));
+    if (eps) pm->surf64_blocks = surf64_blocks;
     auto launch = [&](const RenderArgs& ra, int nb, hipStream_t stream) -> hipError_t {
         QueryArgs qq = q;
         qq.r = ra;
@@ -2509,7 +2528,7 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
         launch_query_emit(qq, medium, bvh, gg, pm->kind, nb, lds, stream);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        return launch_photon_surface_f64(sa, rpti::scene_dev(s).n_cus * 4, stream);
+        return launch_photon_surface_f64(sa, surf64_blocks, stream);
     };
     std::function<hipError_t(double, double*, hipStream_t)> resolve;
     if (eps)
@@ -2536,7 +2555,7 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
         RPTI_HIP_TRY(pm->d_slab2.reserve(*pm->pool, std::max<size_t>(size_t(q.r.n_chunks) * q.r.n_owned * 4u, 4u)));   // 16 bytes per item
         q.r.slab2 = pm->d_slab2.get();
     }
-    rc = rpti::run_persistent(s, prm, q.r, d_out, st, bpc, launch, false, true, resolve);
+    rc = rpti::run_persistent(s, prm, q.r, d_out, st, bpc, launch, false, true, resolve, !eps || eps->first);
     if (rc == RPT_OK && sync_counters) {
         uint32_t ov = 0;
         RPTI_HIP_TRY(hipMemcpyAsync(&ov, pm->d_overflow.get(), 4, hipMemcpyDeviceToHost, st));
@@ -2555,16 +2574,17 @@ static int photon_render_any(rpt_scene* s, const rpt_camera* cam, const rpt_rend
     if (!s || !rpti::scene_dev(s).epsilon64)
         return photon_render_impl(s, cam, prm, gather_size, gather_size_volume, num_samples, seed, sample_offset, d_out, st, true);
     if (!prm || num_samples == 0) return rpti::fail(RPT_ERR_INVALID, "empty render");
-    if (prm->shard_count > 1) {   // (run_persistent clears a sharded frame per launch: the slices would not add up)
-        const size_t per_sample = size_t(prm->width) * prm->height * (size_t(gather_size) + 2u) * 4u;
-        if (per_sample * num_samples > kEmitBudget)
-            return rpti::fail(RPT_ERR_UNSUPPORTED, "reference-epsilon photon camera pass on a sharded frame: too many samples for one slice; render in several calls");
-    }
-    // slices: whole chunks of kSuper samples while the selections fit the budget, else fewer samples
-    const size_t per_sample = std::max<size_t>(size_t((prm->width + 31u) / 32u) * ((prm->height + 31u) / 32u) * 1024u * (size_t(gather_size) + 2u) * 4u, 1);
+    // slices: whole chunks of kSuper samples while the selections fit the budget, else fewer samples.  The selections are kept for the
+    // pixel slots of the tiles this rank owns (32x32 each, clipped ones included).
+    const int64_t n_tiles = rpt_shard_tiles(prm->width, prm->height, prm->shard_rank, prm->shard_count, nullptr, 0);
+    if (n_tiles < 0) return int(n_tiles);
+    const size_t per_sample = std::max<size_t>(size_t(n_tiles) * 1024u * (size_t(gather_size) + 2u) * 4u, 1);
     uint32_t slice = uint32_t(std::min<uint64_t>(num_samples, std::max<uint64_t>(kEmitBudget / per_sample, 1)));
     if (slice >= kSuper) slice -= slice % kSuper;
     if (const int64_t forced = rpti::option_f64_photon_slice(s)) slice = uint32_t(std::min<int64_t>(forced, slice));
+    if (per_sample * slice > kEmitBudget)   // (a slice is at least one sample)
+        return rpti::fail(RPT_ERR_UNSUPPORTED, "reference-epsilon photon camera pass: the selections of one sample exceed the budget of a slice; render a smaller frame or more shards");
+    // (a sharded frame is cleared before its first slice only, photon_render_impl: the resolve adds each slice to what the earlier ones left)
     for (uint32_t done = 0; done < num_samples; done += slice) {
         const uint32_t n = std::min(slice, num_samples - done);
         const EpsSlice e{num_samples, done == 0};

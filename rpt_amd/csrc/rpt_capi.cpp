@@ -56,6 +56,8 @@ struct rpt_options {
     int64_t counters = 0;
     int64_t chunk_spp = 0;          // 0 = auto: ceil(iterations / 16) clamped to [2, 32]
     int64_t blocks_per_cu = 0;      // 0 = occupancy query
+    int64_t max_blocks = 0;         // cap on the blocks of every persistent launch (renders, photon camera pass, fp64 shooting and surface passes); 0 = no cap.
+                                    // A small grid gives every lane / wave many work items: what the schedule tests run (the frame bits do not depend on it)
     int64_t timing = 0;
     int64_t room_shell = 1;         // fold rectangles that are the faces of one box into a single slab test
     int64_t scan_specialise = 1;    // mark y-rotated sphere / cube records and box pairs with common slabs for the unmasked scans (read by rpt_scene_commit)
@@ -97,6 +99,7 @@ static int set_option_in(rpt_options& o, const char* name, int64_t value) {
     if (s == "counters") o.counters = value;
     else if (s == "chunk_spp") { if (value < 0) return fail(RPT_ERR_INVALID, "chunk_spp must be >= 0 (0 = auto)"); o.chunk_spp = value; }
     else if (s == "blocks_per_cu") o.blocks_per_cu = value;
+    else if (s == "max_blocks") { if (value < 0 || value > (1 << 20)) return fail(RPT_ERR_INVALID, "max_blocks must be 0..2^20 (0 = no cap)"); o.max_blocks = value; }
     else if (s == "timing") o.timing = value;
     else if (s == "room_shell") o.room_shell = value;
     else if (s == "scan_specialise") o.scan_specialise = value;
@@ -2268,7 +2271,8 @@ extern "C++" int rpti::serialize_with_other_streams(rpt_scene* s, hipStream_t st
 
 extern "C++" int rpti::run_persistent(rpt_scene* s, const rpt_render_params* prm, const RenderArgs& a, double* d_out, hipStream_t st,
                          int blocks_per_cu, const std::function<hipError_t(const RenderArgs&, int, hipStream_t)>& launch,
-                         bool indexed_start, bool wave_items, const std::function<hipError_t(double, double*, hipStream_t)>& resolve) {
+                         bool indexed_start, bool wave_items, const std::function<hipError_t(double, double*, hipStream_t)>& resolve,
+                         bool clear_sharded) {
     const int k = s->dev.sets[0].d_queue.get() == a.queue ? 0 : 1;
     rpt_scene::LaunchSet& mine = s->dev.sets[k];
     rpt_scene::LaunchSet& other = s->dev.sets[k ^ 1];
@@ -2280,10 +2284,11 @@ extern "C++" int rpti::run_persistent(rpt_scene* s, const rpt_render_params* prm
     HIP_TRY(hipMemsetAsync(a.queue, 0, 8, st));
     if (a.counters) HIP_TRY(hipMemsetAsync(a.counters, 0, 512, st));
     uint32_t shard_count = prm->shard_count == 0 ? 1 : prm->shard_count;
-    if (shard_count > 1) HIP_TRY(hipMemsetAsync(d_out, 0, size_t(prm->width) * prm->height * 24, st));
+    if (shard_count > 1 && clear_sharded) HIP_TRY(hipMemsetAsync(d_out, 0, size_t(prm->width) * prm->height * 24, st));
     if (a.n_items) {
         uint64_t want = wave_items ? (uint64_t(a.n_items) + 3) / 4 : (uint64_t(a.n_items) + 255) / 256;
         int n_blocks = int(std::min<uint64_t>(uint64_t(s->n_cus) * std::max(blocks_per_cu, 1), want));
+        if (s->opt.max_blocks > 0) n_blocks = int(std::min<int64_t>(n_blocks, s->opt.max_blocks));   // (scratch per wave is sized for the uncapped grid)
         s->last_blocks = n_blocks;
         // indexed_start: every wave of the grid takes the batch with its own index first (render_kernel's work
         // pull), so the counter starts behind those batches
@@ -2337,6 +2342,7 @@ extern "C++" rpti::SceneDev rpti::scene_dev(rpt_scene* s) {
 }
 extern "C++" void*& rpti::photon_slot(rpt_scene* s) { return s->photon; }
 extern "C++" int64_t rpti::option_photon_skip(rpt_scene* s) { return s->opt.photon_skip; }
+extern "C++" int64_t rpti::option_max_blocks(rpt_scene* s) { return s->opt.max_blocks; }
 extern "C++" int64_t rpti::option_f64_photon_slice(rpt_scene* s) { return s->opt.f64_photon_slice; }
 extern "C++" int64_t rpti::option_photon_block_lists(rpt_scene* s) { return s->opt.photon_block_lists; }
 extern "C++" int64_t rpti::option_photon_parts(rpt_scene* s) { return s->opt.photon_parts; }

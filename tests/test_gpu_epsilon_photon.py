@@ -167,6 +167,19 @@ def test_the_frame_does_not_depend_on_the_slices():
     b = r_eps.photon_sample_array(8)
     rel = np.abs((16 * a + 8 * b) / 24 - whole) / np.abs(whole)
     assert (rel > 2e-6).sum() <= 4 and rel.max() < 1e-3
+    # ... and a sharded frame whose camera pass runs in several slices: the slices of a rank add up in its frame (it is cleared before
+    # the first one only), the ranks' tiles are disjoint, and their sum is the unsharded frame of the same slices, bit for bit
+    r64, _ = _renderers("C4", 64, n)
+    r64.seed(3).photon_map_build(n, Renderer.PHOTON_POINT_BEAM)
+    r64.scene.set_option("f64_photon_slice", 5)
+    sliced = r64.seed(0).photon_sample_array(24)
+    parts = []
+    for rank in range(2):
+        r64._sample_offset = 0
+        parts.append(r64.shard(rank, 2).photon_sample_array(24))
+    assert np.all(np.isfinite(sliced)) and (parts[0] != 0).any() and (parts[1] != 0).any()
+    assert np.all(parts[0][parts[1] != 0] == 0) and np.all(parts[1][parts[0] != 0] == 0)      # disjoint tiles
+    assert np.array_equal(parts[0] + parts[1], sliced)
 
 
 def test_the_camera_pass_is_a_function_of_its_inputs():
@@ -177,6 +190,15 @@ def test_the_camera_pass_is_a_function_of_its_inputs():
     for _ in range(4):
         r_eps._sample_offset = 0
         assert np.array_equal(first, r_eps.photon_sample_array(spp))
+    # Those launches deal every wave one (pixel, 64 samples) item at most: 4,096 items on CUs x 4 blocks x 4 waves.  On 37 blocks a wave
+    # takes 27 items one after the other, and whatever it carried from one into the next would show: the same frame, bit for bit.
+    n_items = 4096
+    assert n_items <= r_eps._photon_stats()["surface64_blocks"] * 4
+    r_eps.scene.set_option("max_blocks", 37)
+    r_eps._sample_offset = 0
+    capped = r_eps.photon_sample_array(spp)
+    assert r_eps._photon_stats()["surface64_blocks"] == 37 and n_items >= 8 * 37 * 4
+    assert np.array_equal(first, capped)
 
 
 @pytest.mark.parametrize("kind", [Renderer.PHOTON_MAP, Renderer.PHOTON_BEAM_BEAM])

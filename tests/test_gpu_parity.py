@@ -179,9 +179,14 @@ def test_shards_grid_sizes_and_reruns_are_bit_identical():
     import rpt_amd
     scene, cam, cfg = scenes.lampshade()
     w, h, spp = 100, 70, 9                                   # ragged: tiles clipped, spp not a chunk multiple
+    grids = []
     def render(rank=0, count=1):
         s2, c2, _ = scenes.lampshade()
-        return Renderer(s2, c2).width(w).height(h).max_bounces(10).seed(2).shard(rank, count).sample_array(spp)
+        s2.set_option("timing", 1)
+        r = Renderer(s2, c2).width(w).height(h).max_bounces(10).seed(2).shard(rank, count)
+        img = r.sample_array(spp)
+        grids.append(r.timing()[2])
+        return img
     full = render()
     assert np.array_equal(full, render())                    # deterministic
     parts = [render(r, 3) for r in range(3)]
@@ -193,6 +198,20 @@ def test_shards_grid_sizes_and_reruns_are_bit_identical():
         assert np.array_equal(full, render())                # independent of the persistent grid size
     finally:
         rpt_amd.set_option("blocks_per_cu", 0)
+    # 12 tiles x 1024 pixel slots x 5 chunks = 61,440 items are 240 blocks' worth: blocks_per_cu = 1 launches the same grid on a card
+    # with 240 CUs or more.  "max_blocks" does change it: 1 block (240 items per lane) and 7 blocks (34 per lane)
+    default_grid, n_items = grids[0], 12 * 1024 * Renderer(scene, cam).chunking(spp)[1]
+    assert n_items <= default_grid * 256                     # every lane of the frames above had one item at most
+    try:
+        for cap in (1, 7):
+            rpt_amd.set_option("max_blocks", cap)
+            assert np.array_equal(full, render())
+            assert grids[-1] == cap != default_grid and n_items >= 8 * cap * 256
+            print(f"max_blocks {cap}: {grids[-1]} blocks instead of {default_grid}, {n_items / (cap * 256):.1f} items per lane")
+        rpt_amd.set_option("max_blocks", 3)                  # ... and the shards on a small grid
+        assert np.array_equal(sum(render(r, 3) for r in range(3)), full)
+    finally:
+        rpt_amd.set_option("max_blocks", 0)
     exp = _oracle(scene).render(cam, w, h, spp, 10, seed=2, robust=1)
     assert rel_rms(full, exp) < 5e-3
 
@@ -332,6 +351,8 @@ def test_deferred_tree_walks_do_not_depend_on_the_schedule(fog):
         sc.add(Medium.homogeneous_isotropic(0.02, 0.1))
     cam = Camera.look_at(vec3(0.0, 1.5, 6.0), vec3(0.0, 0.0, 0.0), vec3(0, 1, 0), 0.8)
     w, h, spp = 96, 72, 24
+    sc.set_option("timing", 1)
+    capped = []                                                   # per render: on the grid of 37 blocks
 
     def render(lanes, stop, leaf_quarters=6):
         rpt_amd.set_option("defer_lanes", lanes)
@@ -341,6 +362,7 @@ def test_deferred_tree_walks_do_not_depend_on_the_schedule(fog):
         img = r.sample_array(spp)
         st = r.scene_stats()
         assert st["bvh_nodes"] > 0 and st["scene_bvh"] == 0      # the per-mesh-tree kernel
+        capped.append(r.timing()[2] == 37)
         return img
     def render_detached(lanes, trigger, stop, leaf_quarters=6):
         rpt_amd.set_option("detach_lanes", lanes)
@@ -351,19 +373,24 @@ def test_deferred_tree_walks_do_not_depend_on_the_schedule(fog):
         rpt_amd.set_option("detach_shadows", 0)
         frames = [render(*v) for v in ((32, 16), (1, 1), (64, 64), (64, 1), (8, 5), (32, 16, 0), (32, 16, 1), (40, 8, 64))]
         # how many lanes wait for a new work item before the wave hands items out ("pull_batch"): lanes between items idle
+        # (on a grid of 37 blocks, 11 items per lane: on the default grid every lane has one item and never waits for a second)
+        rpt_amd.set_option("max_blocks", 37)
         for pb in (1, 7, 64):
             rpt_amd.set_option("pull_batch", pb)
             frames.append(render(32, 16))
         rpt_amd.set_option("pull_batch", 2)
+        rpt_amd.set_option("max_blocks", 0)
         rpt_amd.set_option("detach_shadows", 1)
         # detached shadow queries (kernels.hip, DETACH): when a walk session starts (waiting + queued queries, queued alone), when
         # it is left, a queue that overflows at every vertex (trigger 32 with sessions that start late) -- not one bit
         detached = [render_detached(*v) for v in ((48, 20, 16), (1, 1, 1), (96, 32, 32), (64, 32, 1), (8, 3, 5), (48, 20, 16, 0), (96, 32, 8, 64))] if fog else []
         if fog:   # stalled lanes (answers outstanding), lanes waiting for the hand-out and the session trigger must not wait for each other
+            rpt_amd.set_option("max_blocks", 37)
             for pb in (1, 9, 64):
                 rpt_amd.set_option("pull_batch", pb)
                 detached.append(render_detached(48, 20, 16))
             rpt_amd.set_option("pull_batch", 2)
+            rpt_amd.set_option("max_blocks", 0)
         # streamed walks (DETACH = 2): primary queries leave as well, their paths wait in memory; session threshold and exit rule
         streamed = []
         have_streamed = fog
@@ -380,6 +407,7 @@ def test_deferred_tree_walks_do_not_depend_on_the_schedule(fog):
             rpt_amd.set_option("pull_batch", 16)
             streamed.append(render(32, 16))
     finally:
+        rpt_amd.set_option("max_blocks", 0)
         rpt_amd.set_option("pull_batch", 2)
         rpt_amd.set_option("detach_shadows", 1)
         rpt_amd.set_option("stream_backlog", 48)
@@ -389,6 +417,8 @@ def test_deferred_tree_walks_do_not_depend_on_the_schedule(fog):
         rpt_amd.set_option("walk_leaf_quarters", 6)
         rpt_amd.set_option("detach_lanes", 44)
         rpt_amd.set_option("detach_trigger", 28)
+    n_items = 9 * 1024 * Renderer(sc, cam).chunking(spp)[1]
+    assert sum(capped) == (6 if fog else 3) and not capped[0] and n_items >= 8 * 37 * 256   # the pull_batch legs: 8+ items per lane
     for f in frames[1:]:
         assert np.array_equal(frames[0], f)
     for f in detached[1:]:
@@ -557,14 +587,22 @@ def test_item_hand_out_batches_do_not_change_the_frame(name):
     lanes between items take no part in a trip.  Which lane renders an item, and when, must not change one bit."""
     import rpt_amd
     scene, cam, cfg = scenes.CONFIGS[name]()
-    frames = []
+    scene.set_option("timing", 1)
+    r = Renderer(scene, cam).width(80).height(72).max_bounces(cfg["max_bounces"]).seed(3)
+    n_items = 9 * 1024 * r.chunking(40)[1]
+    frames = [r.sample_array(40)]                                # the default grid: one item per lane, the hand-out never runs again
+    assert n_items <= r.timing()[2] * 256
     try:
+        # 37 blocks, 13 items per lane: lanes do wait for a next item, and "pull_batch" decides when they get it
+        rpt_amd.set_option("max_blocks", 37)
         for pb in (1, 2, 5, 33, 64):
             rpt_amd.set_option("pull_batch", pb)
             r = Renderer(scene, cam).width(80).height(72).max_bounces(cfg["max_bounces"]).seed(3)
             frames.append(r.sample_array(40))
+            assert r.timing()[2] == 37 and n_items >= 8 * 37 * 256
     finally:
         rpt_amd.set_option("pull_batch", 2)
+        rpt_amd.set_option("max_blocks", 0)
     assert np.all(np.isfinite(frames[0])) and frames[0].mean() > 0
     for f in frames[1:]:
         assert np.array_equal(frames[0], f)
