@@ -141,6 +141,12 @@ int rpt_render_sample_device(rpt_scene*, const rpt_camera*, const rpt_render_par
  * t = +inf, object = -1 on a miss.  normal may be NULL. */
 int rpt_intersect_batch(rpt_scene*, uint64_t n, const float* origins, const float* dirs, float* t,
                         int32_t* object, float* normal);
+/* The primary query of the scan kernels over n segments: the closest accepted hit with t in [t_min(origin), t_max[i]), through
+ * the culled scan when the scene was committed with "scan_cull" = 1 (and is eligible for it) and through the plain scan
+ * otherwise.  Consecutive groups of 64 segments form a wave, as 64 paths do in a render.  t = t_max[i] and code = 0xFFFFFFFF on a
+ * miss; code = kind << 28 | record otherwise.  For scenes whose records are all scanned (no tree), else RPT_ERR_UNSUPPORTED. */
+int rpt_intersect_segments(rpt_scene*, uint64_t n, const float* origins, const float* dirs, const float* t_max, float* t,
+                           uint32_t* code);
 /* The same query in the reference-epsilon mode (a scene committed with epsilon_policy = 1, else RPT_ERR_STATE): the fp64
  * closest hit of that mode's kernels, t_min = 1e-12, over n rays given in fp64.  t = +inf, object = -1 on a miss; a hit may
  * carry t = NaN where the reference's own test produces one (MonomialSurface).  normal may be NULL. */
@@ -166,6 +172,18 @@ int rpt_get_counters(rpt_scene*, uint64_t out[8]);
  * out[2k] = wave-level executions and out[2k+1] = lanes active in them during the last path-traced
  * render: the lane utilisation of each divergent piece of code. */
 int rpt_debug_section_counters(rpt_scene*, uint64_t out[56]);
+/* Diagnostic (counters on; a render of a scene with a medium whose records are all scanned): the primary scans of the last render
+ * by wave trip.  out[0..4]: trips in which 0, 1-2, 3-4, 5-8, more than 8 lanes have a search interval that reaches the box around
+ * all scanned records; out[5..8]: trips with such a lane in which none of them reaches the box of candidate record group 0..3
+ * (rpt_scan_cull_groups); out[9]: trips whose scan left out its tail (option "scan_cull"); out[10..11]: 0.  out[12]: the scene has
+ * a bound and groups (no planes, at most 64 scanned records), out[13]: the number of groups, out[14]: the records in no group
+ * because their box is most of the bound (mask), out[15]: the scene's primary scans are culled. */
+int rpt_scan_cull_counters(rpt_scene*, uint64_t out[16]);
+/* The boxes of a committed scene's primary scans: out_boxes[0..5] = lo, hi of the box around all scanned records, [6..29] lo, hi of
+ * the candidate groups (6 floats each, 4 groups), [30..35] lo, hi of the box around the scan's tail -- boxes, rectangles,
+ * triangles --, which "scan_cull" tests; out_masks[0..3] the groups' records (the scan's numbering: spheres, cubes, boxes,
+ * rectangles, triangles), out_masks[4] the records in no group; *n_groups their number; *enabled = the scans are culled. */
+int rpt_scan_cull_groups(rpt_scene*, float out_boxes[36], uint64_t out_masks[5], uint32_t* n_groups, uint32_t* enabled);
 /* HIP-event timing of the last render on this scene (needs rpt_set_option("timing", 1)):
  * milliseconds of the megakernel and of the resolve kernel on the stream they ran on, and the
  * persistent grid size.  Synchronises on the last recorded event. */
@@ -196,6 +214,9 @@ int rpt_scene_render_chunking(rpt_scene*, uint32_t iterations, uint32_t* chunk_s
  * "scan_specialise" 0/1 (read by rpt_scene_commit: mark the sphere / cube records that are rotated about the vertical axis only
  * and the adjacent box records with common slabs, so that the linear scans leave out the zero terms and the repeated slab
  * arithmetic, default 1; the hits are bit-identical either way),
+ * "scan_cull" 0/1 (read by rpt_scene_commit, default 1: in a medium a primary scan tests the box around the records behind the
+ * shell in scan order -- boxes, rectangles, triangles -- once per lane and leaves those records out when no lane of the wave has a
+ * search interval that reaches it; the frames are bit-identical either way),
  * "photon_block_lists" 0/1 (camera pass of the beam x point kind: collect the photon spheres of each strip of an
  * 8x8 pixel block once per work item and test them with one photon per lane, default 1; 0 walks the tree per
  * sample), "photon_parts" (work items per 8x8 pixel block and sample chunk of the photon camera pass: the block's

@@ -89,6 +89,9 @@ SYMBOLS = [
      [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P, _P]),
     ("rpt_intersect_batch", C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("rpt_intersect_batch_f64", C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P]),
+    ("rpt_intersect_segments", C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P]),
+    ("rpt_scan_cull_counters", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("rpt_scan_cull_groups", C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("rpt_scene_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("rpt_get_counters", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("rpt_debug_section_counters", C.c_int, [_P, C.POINTER(C.c_uint64)]),

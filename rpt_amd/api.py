@@ -47,7 +47,7 @@ def set_option(name, value):
     """Process-wide convenience over the C ABI's per-scene options: sets the default for scenes created from now on
     (rpt_set_option) and the option of every scene this process has on a device (rpt_scene_set_option), so that
     `set_option("counters", 1)` acts on the renderer at hand as it always did.  Options read by rpt_scene_commit
-    ("scene_bvh_min", "instancing", "room_shell", "scan_specialise", "bvh_leaf_max", "bvh_max_depth") only matter before a scene's
+    ("scene_bvh_min", "instancing", "room_shell", "scan_specialise", "scan_cull", "bvh_leaf_max", "bvh_max_depth") only matter before a scene's
     first render; use Scene.set_option to give one scene its own value."""
     lib = _lib.load()
     _lib.check(lib.rpt_set_option(name.encode(), int(value)))

@@ -485,13 +485,42 @@ RPT_DEV void bvh_traverse(const SceneView& scene_, uint32_t root, V o, V d, floa
     }
 }
 
+// Does the lane's interval [tmin, tbest) overlap the slab interval of the box?  The slab pairs are ordered as the scan orders them, so
+// that a NaN ((plane - o) * inv with o in the plane and the direction parallel to it) is treated as there: with fminf / fmaxf, which
+// drop it, like slabs_closer (box records); SHELL: with a compare and two selects like hit_shell, where a NaN leaves the pair's other
+// value as the only bound.  The final comparison lets a NaN pass.
+template <bool SHELL>
+RPT_DEV bool interval_meets_box(const SceneView::ScanBox& b, V o, V inv, float tmin, float tbest) {
+#pragma clang fp contract(off)
+    const float x1 = (b.lo[0] - o.x) * inv.x, x2 = (b.hi[0] - o.x) * inv.x;
+    const float y1 = (b.lo[1] - o.y) * inv.y, y2 = (b.hi[1] - o.y) * inv.y;
+    const float z1 = (b.lo[2] - o.z) * inv.z, z2 = (b.hi[2] - o.z) * inv.z;
+    float start, end;
+    if (SHELL) {
+        const bool sx = x1 > x2, sy = y1 > y2, sz = z1 > z2;
+        start = max3(sx ? x2 : x1, sy ? y2 : y1, sz ? z2 : z1);
+        end = min3(sx ? x1 : x2, sy ? y1 : y2, sz ? z1 : z2);
+    } else {
+        start = max3(fminf(x1, x2), fminf(y1, y2), fminf(z1, z2));
+        end = min3(fmaxf(x1, x2), fmaxf(y1, y2), fmaxf(z1, z2));
+    }
+    return !(fmaxf(start, tmin) > fminf(end, tbest));
+}
 // The linear scan over the wave-uniform primitive records (everything that is not in a tree).
 // MASKED: bit i of `mask` (wave-uniform) says whether bounded record i -- numbered in scan order: spheres, cubes,
 // boxes, rectangles, triangles, as in SceneView::pbox -- can be hit at all; planes and the shell are always tested.
 // MONO: ... and then the monomial surfaces; an instantiation of its own.  Not with MASKED: scan_mask_for_ball numbers only the
 // records up to the triangles (only photon mapping masks its scans, and it refuses scenes with monomial surfaces).
-template <bool MASKED = false, bool MONO = false>
-RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbest, uint32_t& code, uint64_t mask = ~0ull) {
+// TAIL (the primary scans in a medium; option "scan_cull"): the records behind the shell in scan order -- boxes, rectangles, triangles --
+// are left out when no lane's interval [tmin, tbest) reaches the box around them (SceneView::scan_tail; tbest as the records before
+// them have left it).  A primary interval mostly ends at the sampled medium distance: on C3 the tail is the lampshade under the
+// ceiling, which four trips in five do not reach.  One slab test and one ballot; the records that are tested are tested as ever, and a record
+// that is left out could not have been accepted by any lane (rpt_capi.cpp, group_scans, has the rounding argument).  tail_skipped
+// (counters builds): set when the tail was left out.
+template <bool MASKED = false, bool MONO = false, bool TAIL = false>
+RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbest, uint32_t& code, uint64_t mask = ~0ull,
+                        bool* tail_skipped = nullptr) {
+    static_assert(!(TAIL && MASKED), "one cull at a time");
     // The scene view is a kernel argument (every caller passes its kernarg struct): its fields are read HERE, through the
     // constant address space, behind an opaque copy of the pointer.  Read as plain kernel arguments they are all hoisted to
     // the kernel's entry and held in scalar registers for its whole life -- the render kernels have ~110 such values, the
@@ -549,6 +578,15 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
     if (sc.n_aabb + n_rect + sc.has_shell != 0) {  // wave-uniform: these kinds share one reciprocal direction per ray
         const V inv = mk(rcp(d.x), rcp(d.y), rcp(d.z));
         if (sc.has_shell) hit_shell(uload(sc.shell), o, inv, tmin, tbest, code);
+        if constexpr (TAIL) {
+            if (sc.scan_cull) {   // (wave-uniform)
+                const SceneView::ScanBox tb = kernarg_load(&sc.scan_tail);
+                if (__ballot(interval_meets_box<false>(tb, o, inv, tmin, tbest)) == 0ull) {
+                    if (tail_skipped) *tail_skipped = true;
+                    return;   // (no monomial surfaces behind the tail: TAIL is not instantiated with MONO)
+                }
+            }
+        }
         {
             uint32_t i = 0;
             if (!MASKED)
@@ -594,7 +632,7 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
         if (t >= 0.f) { tbest = t; code = (K_TRI << 28) | i; }
     }
     if constexpr (MONO) {
-        static_assert(!MASKED, "scan_mask_for_ball does not cover the monomial surfaces");
+        static_assert(!MASKED && !TAIL, "scan_mask_for_ball and the tail cull do not cover the monomial surfaces");
         for (uint32_t i = 0; i < sc.n_mono; i++) {
             const MonoScan m = uload(&sc.mono[i]);
             V ol, dl;
@@ -638,6 +676,36 @@ RPT_DEV uint64_t scan_mask_for_ball(const SceneView& scene_, bool live, V c, flo
     if (touched) *touched = mine;
     return mask;
 }
+// The primary query of a scan flavour in a medium: the scan with its tail cull.  The counters build also classifies the trip (`cnt`,
+// rpt_scan_cull_counters): cnt[0..4] trips by the number of lanes whose interval reaches the box around all scanned records (0, 1-2,
+// 3-4, 5-8, more), cnt[5..8] trips with such a lane in which none of them reaches the box of record group g (SceneView::scan_groups:
+// the candidates of a finer cull, measured and not built: DESIGN.md section 4, round 6), cnt[9] trips that left out the tail.
+template <bool COUNT>
+RPT_DEV void scan_primary(const SceneView& scene, V o, V d, float tmin, float& tbest, uint32_t& code, unsigned long long* cnt) {
+    if constexpr (COUNT) {
+        const auto& sc = *kernarg_scene();
+        const SceneView::ScanBox bound = kernarg_load(&sc.scan_bound);
+        const bool first = cnt && uint32_t(__builtin_ctzll(__ballot(true))) == (threadIdx.x & 63u);
+        if (!(bound.lo[0] > bound.hi[0])) {
+            const V inv = mk(rcp(d.x), rcp(d.y), rcp(d.z));
+            const bool need = interval_meets_box<true>(bound, o, inv, tmin, tbest);
+            const uint32_t n_need = uint32_t(__popcll(__ballot(need)));
+            if (first) atomicAdd(&cnt[n_need == 0u ? 0 : n_need <= 2u ? 1 : n_need <= 4u ? 2 : n_need <= 8u ? 3 : 4], 1ull);
+            if (n_need != 0u)
+                for (uint32_t g = 0; g < sc.n_scan_groups; g++) {
+                    const SceneView::ScanGroup grp = kernarg_load(&sc.scan_groups[g]);
+                    const bool reach = need && interval_meets_box<false>(grp.box, o, inv, tmin, tbest);
+                    if (__ballot(reach) == 0ull && first) atomicAdd(&cnt[5u + g], 1ull);
+                }
+        }
+        bool skipped = false;
+        scan_prims<false, false, true>(scene, o, d, tmin, tbest, code, ~0ull, &skipped);
+        if (skipped && first) atomicAdd(&cnt[9], 1ull);
+    } else {
+        scan_prims<false, false, true>(scene, o, d, tmin, tbest, code);
+    }
+}
+
 // Would a walk of the per-mesh trees visit anything?  The two child boxes of every mesh root against the
 // interval the scan left (scalar loads: the roots are wave-uniform).
 RPT_DEV bool mesh_roots_hit(const SceneView& scene_, V o, V d, float tmin, float tbest) {

@@ -204,7 +204,28 @@ struct SceneView {
     // scene_bvh_min on the scene tree takes over); a kind with more than 64 records gets no bits at all.
     uint32_t scan_pad_;
     uint64_t sph_yrot, cub_yrot;
+    // Culled primary scans in a medium (option "scan_cull"; scan_prims<.., TAIL> in device_core.h).  A primary search interval ends
+    // at the sampled medium distance.  scan_tail: the box around the records behind the shell in scan order -- boxes, rectangles,
+    // triangles --, which a wave leaves out when no lane's interval reaches it (scan_cull = 1; 0: the plain scans).  For the counters
+    // build (rpt_scan_cull_counters; candidates of a finer cull): scan_bound, the box around every scanned record, the shell
+    // included, and scan_groups, up to four boxes, each around the records whose numbers -- in the scan's numbering: spheres, cubes,
+    // boxes, rectangles, triangles, as in pbox -- are set in its mask; every record is in exactly one group or in scan_always
+    // (records whose box is most of the bound).  Scenes with planes, monomial surfaces or more than 64 scanned records have no
+    // bound and no groups.  The extents of box records enter exactly (the scan tests them with the same (plane - o) * inv
+    // arithmetic, which is monotone in the plane), those of every other kind with a margin (rpt_capi.cpp, group_scans).
+    uint64_t scan_always;
+    struct ScanBox {
+        float lo[3], hi[3];
+    };
+    struct ScanGroup {
+        ScanBox box;
+        uint64_t mask;
+    } scan_groups[4];
+    ScanBox scan_bound;   // lo[0] > hi[0]: the scene has none (see scan_cull)
+    ScanBox scan_tail;    // around the records behind the shell in scan order: boxes, rectangles, triangles
+    uint32_t n_scan_groups, scan_cull, scan_pad2_[2];
 };
+static const uint32_t kMaxScanGroups = 4;
 
 struct CameraG {
     float eye[3], ddir[3], right[3], up[3];  // ddir = cot(fov/2) * direction

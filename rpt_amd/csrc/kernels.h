@@ -65,6 +65,10 @@ hipError_t launch_frame_pack(const double* d_frame, double* d_packed, const uint
                              uint32_t width, uint32_t height, hipStream_t st);
 hipError_t launch_frame_unpack(const double* d_packed, double* d_frame, const uint32_t* d_tiles, uint32_t n_tiles, uint32_t tiles_x,
                                uint32_t width, uint32_t height, hipStream_t st);
+// (Weak: the host-only test harnesses link rpt_capi.cpp against stubs of the launchers they know; this one is reached from
+// rpt_intersect_segments alone, which reports RPT_ERR_UNSUPPORTED where no kernel library is linked.)
+__attribute__((weak)) hipError_t launch_intersect_segments(const SceneView& sc, uint64_t n, const float* d_o, const float* d_d, const float* d_tmax,
+                                                           float* d_t, uint32_t* d_code, hipStream_t stream);
 hipError_t launch_intersect(const SceneView& sc, uint64_t n, const float* d_o, const float* d_d, float* d_t,
                             int32_t* d_obj, float* d_n, bool bvh, hipStream_t stream);
 hipError_t launch_debug_rng(uint64_t seed_mixed, uint32_t pixel, uint32_t sample, uint32_t n, uint32_t* d_out,

@@ -112,6 +112,7 @@ RPT_DEV unsigned long long to_fixed(float v) {
 }
 RPT_DEV float from_fixed(unsigned long long x) { return float(double(x) * 0x1p-32); }
 
+static constexpr uint32_t kCullCounters = 64u;   // counters[64..75]: scan_primary's (rpt_scan_cull_counters)
 // Diagnostic sections of the megakernel (COUNT build): per section, counters[8 + 2k] counts wave-level
 // executions and counters[9 + 2k] the lanes active in them (lane utilisation of divergent code).
 // -DRPT_MARKERS additionally drops "; SECT k" comments into the ISA for static instruction counts.
@@ -1228,7 +1229,10 @@ void render_kernel(const RenderArgs a) {
         stage_distance<MEDIUM>(rng, inv_sigma_t, dmed, t);
         const float tmin = ray_tmin(ro);
         uint32_t code = CODE_MISS, inst = 0;
-        closest_hit<BVH, COUNT, false, MONO>(sc, ro, rd, tmin, t, code, inst, stk, stride, c_nodes, c_btris);
+        if constexpr (MEDIUM && BVH == 0 && !MONO)   // (the interval mostly ends at the medium distance: the scan's tail is seldom in reach)
+            scan_primary<COUNT>(sc, ro, rd, tmin, t, code, COUNT ? a.counters + kCullCounters : nullptr);
+        else
+            closest_hit<BVH, COUNT, false, MONO>(sc, ro, rd, tmin, t, code, inst, stk, stride, c_nodes, c_btris);
         if (COUNT) c_rays++;
         SECTK(3);
         const bool hit = code != CODE_MISS;
@@ -1447,6 +1451,20 @@ __global__ __launch_bounds__(256) void intersect_kernel(const SceneView sc, uint
     }
 }
 
+// rpt_intersect_segments: the primary query of the scan flavours (culled when the view says so) over given segments, 64 to a wave.
+__global__ __launch_bounds__(256) void intersect_segments_kernel(const SceneView sc, uint64_t n, const float* __restrict__ o,
+                                                                 const float* __restrict__ d, const float* __restrict__ tmax,
+                                                                 float* __restrict__ t_out, uint32_t* __restrict__ code_out) {
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= n) return;
+    const V ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+    float t = tmax[i];
+    uint32_t code = CODE_MISS;
+    scan_primary<false>(sc, ro, rd, ray_tmin(ro), t, code, nullptr);
+    t_out[i] = t;
+    code_out[i] = code;
+}
+
 __global__ void debug_rng_kernel(uint64_t seed_mixed, uint32_t pixel, uint32_t sample, uint32_t n, uint32_t* out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     Rng r;
@@ -1601,6 +1619,11 @@ hipError_t launch_intersect(const SceneView& sc, uint64_t n, const float* d_o, c
     }
     if (bvh) hipLaunchKernelGGL(intersect_kernel<2>, dim3(blocks), dim3(256), kStackBytes, stream, sc, n, d_o, d_d, d_t, d_obj, d_n);
     else hipLaunchKernelGGL(intersect_kernel<0>, dim3(blocks), dim3(256), 0, stream, sc, n, d_o, d_d, d_t, d_obj, d_n);
+    return hipGetLastError();
+}
+hipError_t launch_intersect_segments(const SceneView& sc, uint64_t n, const float* d_o, const float* d_d, const float* d_tmax, float* d_t,
+                                     uint32_t* d_code, hipStream_t stream) {
+    hipLaunchKernelGGL(intersect_segments_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, stream, sc, n, d_o, d_d, d_tmax, d_t, d_code);
     return hipGetLastError();
 }
 hipError_t launch_debug_rng(uint64_t seed_mixed, uint32_t pixel, uint32_t sample, uint32_t n, uint32_t* d_out,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -61,6 +62,8 @@ struct rpt_options {
     int64_t timing = 0;
     int64_t room_shell = 1;         // fold rectangles that are the faces of one box into a single slab test
     int64_t scan_specialise = 1;    // mark y-rotated sphere / cube records and box pairs with common slabs for the unmasked scans (read by rpt_scene_commit)
+    int64_t scan_cull = 1;          // primary scans in a medium leave out their tail -- boxes, rectangles, triangles -- when no lane's search interval reaches
+                                    // the box around it (read by rpt_scene_commit; 0: the plain scans)
     int64_t photon_skip = 0;
     int64_t photon_block_lists = 1;
     int64_t photon_coop_gather = 1; // surface gather of a pixel's samples by the wave together (0: one search per lane)
@@ -103,6 +106,7 @@ static int set_option_in(rpt_options& o, const char* name, int64_t value) {
     else if (s == "timing") o.timing = value;
     else if (s == "room_shell") o.room_shell = value;
     else if (s == "scan_specialise") o.scan_specialise = value;
+    else if (s == "scan_cull") o.scan_cull = value;
     else if (s == "photon_skip") o.photon_skip = value;
     else if (s == "photon_block_lists") o.photon_block_lists = value;
     else if (s == "photon_parts") o.photon_parts = value;
@@ -529,6 +533,7 @@ struct rpt_scene {
     } dev;
     int cur_set = 0;
     uint64_t last_counters[64] = {0};  // [0..7] counters, [8..63] diagnostic trip stamps
+    uint64_t last_cull[12] = {0};      // rpt_scan_cull_counters (device counters [64..75])
     static constexpr size_t kTimedLaunches = 1024;
     size_t ev_count = 0;  // timed launches since the last rpt_get_timing_mean
     int last_blocks = 0;
@@ -1465,6 +1470,112 @@ struct Flattener {
             for (const PBox& b : box_mono) push_box(b.lo, b.hi);   // (after the triangles; no masked scan reads them: device_core.h)
         }
     }
+    // (6b) the box a culled primary scan tests before its tail (SceneView::scan_tail; option "scan_cull"), and, for the counters
+    // build, the box around all scanned records and up to four candidate groups of records (scan_bound, scan_groups, scan_always:
+    // what a finer cull would test -- measured, not built).  Nothing is reordered: a group is a box and a mask of record numbers in
+    // the scan's numbering (= pbox order).
+    //
+    // Why a record that is left out could not have been hit.  A record is left out when the search interval [tmin, tbest) of every
+    // lane misses a box B around the record's own box b.  Boxes (and the shell) are tested by the scan with t = (plane - o) * inv per
+    // plane and fminf / fmaxf, the arithmetic of the box test itself: for planes P <= p, P - o <= p - o after rounding and the
+    // product with the same inv keeps the order (fp32 rounding is monotone), a NaN (o in the plane, direction parallel to it) is
+    // dropped by both alike, so the slab interval of b lies inside the one of B exactly and B needs no margin.  Every other kind
+    // reaches its t through other operations: spheres and transformed cubes in local space, triangles through functionals solved
+    // on the host, rectangles with a slab parameter on their own axis but a closed comparison of the hit point on the other two --
+    // a ray that runs exactly in the plane of a rectangle's edge hits it, while the slab pair of a box that ends in that plane is
+    // (NaN, +-inf) and misses.  Their relative errors are a few ulp of the coordinates involved, ~1e-6 of the scene's extent at
+    // worst; their boxes are padded by 1e-4 of the extent, two orders of magnitude more, which also takes every such edge plane
+    // off the faces of B.
+    struct ScanGroupH { float lo[3], hi[3]; uint64_t mask; };
+    std::vector<ScanGroupH> scan_groups;
+    uint64_t scan_always = 0;
+    float scan_lo[3] = {1, 0, 0}, scan_hi[3] = {0, 0, 0};   // lo > hi: no bound (the scene is not eligible)
+    float tail_lo[3] = {0, 0, 0}, tail_hi[3] = {0, 0, 0};
+    bool scan_cull = false;
+    static double half_area(const float lo[3], const float hi[3]) {
+        const double x = double(hi[0]) - lo[0], y = double(hi[1]) - lo[1], z = double(hi[2]) - lo[2];
+        return x * y + y * z + z * x;
+    }
+    void group_scans() {
+        scan_groups.clear();
+        scan_always = 0;
+        scan_cull = false;
+        scan_lo[0] = 1.f; scan_hi[0] = 0.f;
+        const size_t n_rect = rect.size();
+        const size_t n = sph.size() + cub.size() + aabb.size() + n_rect + tri.size();
+        if (scene_bvh || (n == 0 && !has_shell)) return;   // (a scene tree has taken the records)
+        // the records' own boxes, in scan order; `local`: tested in local space or through solved functionals -> padded below
+        std::vector<PBox> box;
+        std::vector<bool> local;
+        for (const PBox& b : box_sph) { box.push_back(b); local.push_back(true); }
+        for (const PBox& b : box_cub) { box.push_back(b); local.push_back(true); }
+        for (const AabbScan& b : aabb) { box.push_back(PBox{{b.lo.x, b.lo.y, b.lo.z}, {b.hi.x, b.hi.y, b.hi.z}}); local.push_back(false); }
+        {
+            size_t i = 0;
+            for (int axis = 0; axis < 3; axis++)
+                for (size_t k = 0; k < rect_axis[axis].size(); k++, i++) {
+                    const RectScan& r = rect[i];
+                    PBox b;
+                    b.lo[axis] = b.hi[axis] = r.a.x;
+                    b.lo[(axis + 1) % 3] = r.a.y; b.hi[(axis + 1) % 3] = r.a.z;
+                    b.lo[(axis + 2) % 3] = r.a.w; b.hi[(axis + 2) % 3] = r.b.x;
+                    box.push_back(b);
+                    local.push_back(true);   // (its in-plane test is a comparison of the hit point, not a slab: see above)
+                }
+        }
+        for (const PBox& b : box_tri) { box.push_back(b); local.push_back(true); }
+        float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+        auto grow = [](float lo_[3], float hi_[3], const float blo[3], const float bhi[3]) {
+            for (int a = 0; a < 3; a++) { lo_[a] = std::min(lo_[a], blo[a]); hi_[a] = std::max(hi_[a], bhi[a]); }
+        };
+        for (const PBox& b : box) grow(lo, hi, b.lo, b.hi);
+        if (has_shell) { const float sl[3] = {shell.lo.x, shell.lo.y, shell.lo.z}, sh[3] = {shell.hi.x, shell.hi.y, shell.hi.z}; grow(lo, hi, sl, sh); }
+        for (int a = 0; a < 3; a++)
+            if (!(std::fabs(lo[a]) < FLT_MAX) || !(std::fabs(hi[a]) < FLT_MAX) || lo[a] > hi[a]) return;   // (a record without finite extent: no culling)
+        const float pad = 1e-4f * std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+        for (size_t i = 0; i < box.size(); i++)
+            if (local[i])
+                for (int a = 0; a < 3; a++) { box[i].lo[a] -= pad; box[i].hi[a] += pad; }
+        for (const PBox& b : box) grow(lo, hi, b.lo, b.hi);   // (the padded boxes as well)
+        // the tail: what the scan tests after the shell
+        const size_t n_tail = aabb.size() + n_rect + tri.size();
+        if (n_tail != 0) {
+            float tl[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, th[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+            for (size_t i = sph.size() + cub.size(); i < box.size(); i++) grow(tl, th, box[i].lo, box[i].hi);
+            for (int a = 0; a < 3; a++) { tail_lo[a] = tl[a]; tail_hi[a] = th[a]; }
+            scan_cull = s->opt.scan_cull != 0;
+        }
+        // the bound and the candidate groups of a finer cull, for the counters build (which classifies its trips by them whether
+        // the option is on or off).  Planes are unbounded, monomial surfaces have no number, a mask has 64 bits.
+        if (!pln.empty() || !mono.empty() || n > 64) return;
+        for (int a = 0; a < 3; a++) { scan_lo[a] = lo[a]; scan_hi[a] = hi[a]; }
+        // one group per record; a record whose box is most of the bound is always tested instead
+        const double bound_area = half_area(lo, hi);
+        for (size_t i = 0; i < box.size(); i++) {
+            if (half_area(box[i].lo, box[i].hi) > 0.5 * bound_area) { scan_always |= 1ull << i; continue; }
+            ScanGroupH g;
+            for (int a = 0; a < 3; a++) { g.lo[a] = box[i].lo[a]; g.hi[a] = box[i].hi[a]; }
+            g.mask = 1ull << i;
+            scan_groups.push_back(g);
+        }
+        // merge the pair whose union has the smallest surface area (ties: the first pair in record order) until four are left
+        while (scan_groups.size() > kMaxScanGroups) {
+            size_t bi = 0, bj = 1;
+            double best = -1.0;
+            for (size_t i = 0; i < scan_groups.size(); i++)
+                for (size_t j = i + 1; j < scan_groups.size(); j++) {
+                    float ulo[3], uhi[3];
+                    for (int a = 0; a < 3; a++) { ulo[a] = std::min(scan_groups[i].lo[a], scan_groups[j].lo[a]); uhi[a] = std::max(scan_groups[i].hi[a], scan_groups[j].hi[a]); }
+                    const double ar = half_area(ulo, uhi);
+                    if (best < 0.0 || ar < best) { best = ar; bi = i; bj = j; }
+                }
+            ScanGroupH& g = scan_groups[bi];
+            const ScanGroupH& h = scan_groups[bj];
+            for (int a = 0; a < 3; a++) { g.lo[a] = std::min(g.lo[a], h.lo[a]); g.hi[a] = std::max(g.hi[a], h.hi[a]); }
+            g.mask |= h.mask;
+            scan_groups.erase(scan_groups.begin() + long(bj));
+        }
+    }
     // (7) one arena for every array, the SceneView over it, statistics, per-launch scratch
     int upload(int device) {
         // ---- one arena for every array
@@ -1538,6 +1649,16 @@ struct Flattener {
         v.inst = (const InstRec*)(base + o_inst);   v.n_inst = uint32_t(insts.size());
         v.mono = (const MonoScan*)(base + o_mono);  v.mono_sh = (const XfShade*)(base + o_monos);  v.n_mono = uint32_t(mono.size());
         v.scan_pad_ = 0;  v.sph_yrot = sph_yrot;  v.cub_yrot = cub_yrot;
+        v.scan_always = scan_always;
+        std::memset(v.scan_groups, 0, sizeof(v.scan_groups));
+        for (size_t g = 0; g < scan_groups.size(); g++) {
+            for (int a = 0; a < 3; a++) { v.scan_groups[g].box.lo[a] = scan_groups[g].lo[a]; v.scan_groups[g].box.hi[a] = scan_groups[g].hi[a]; }
+            v.scan_groups[g].mask = scan_groups[g].mask;
+        }
+        for (int a = 0; a < 3; a++) { v.scan_bound.lo[a] = scan_lo[a]; v.scan_bound.hi[a] = scan_hi[a]; v.scan_tail.lo[a] = tail_lo[a]; v.scan_tail.hi[a] = tail_hi[a]; }
+        v.n_scan_groups = uint32_t(scan_groups.size());
+        v.scan_cull = scan_cull ? 1u : 0u;
+        v.scan_pad2_[0] = v.scan_pad2_[1] = 0;
         v.mats = (const Material*)(base + o_mats);  v.n_obj = uint32_t(mats.size());
         v.lights = (const Light*)(base + o_lights); v.n_lights = uint32_t(lights.size());
         v.ltris = (const LightTri*)(base + o_ltris); v.lxf = (const LightXf*)(base + o_lxf);
@@ -1598,7 +1719,7 @@ struct Flattener {
             HIP_TRY(ls.done.create(hipEventDisableTiming));
             HIP_TRY(ls.launched.create(hipEventDisableTiming));
         }
-        HIP_TRY(s->dev.d_counters.reserve(64 * sizeof(unsigned long long)));
+        HIP_TRY(s->dev.d_counters.reserve(80 * sizeof(unsigned long long)));
         s->view.stack_overflows = s->dev.d_counters.get<unsigned long long>() + 7;
         s->device = device;
         s->committed = true;
@@ -2114,6 +2235,7 @@ int rpt_scene_commit(rpt_scene* s, int device) {
     if (rc) return rc;
     f.specialise_scans();
     f.collect_scan_boxes();
+    f.group_scans();
     rc = f.upload(device);
     if (rc) return rc;
     if (s->opt.epsilon_policy == 1) {
@@ -2282,7 +2404,7 @@ extern "C++" int rpti::run_persistent(rpt_scene* s, const rpt_render_params* prm
     // grids then follow each other, the later one filling the CUs as the blocks of the earlier one retire.
     if (other.used && other.stream != st) HIP_TRY(hipStreamWaitEvent(st, other.launched.get(), 0));
     HIP_TRY(hipMemsetAsync(a.queue, 0, 8, st));
-    if (a.counters) HIP_TRY(hipMemsetAsync(a.counters, 0, 512, st));
+    if (a.counters) HIP_TRY(hipMemsetAsync(a.counters, 0, 640, st));
     uint32_t shard_count = prm->shard_count == 0 ? 1 : prm->shard_count;
     if (shard_count > 1 && clear_sharded) HIP_TRY(hipMemsetAsync(d_out, 0, size_t(prm->width) * prm->height * 24, st));
     if (a.n_items) {
@@ -2353,8 +2475,10 @@ extern "C++" double* rpti::scratch_out(rpt_scene* s, size_t bytes) {
 }
 extern "C++" int rpti::fetch_counters(rpt_scene* s, const RenderArgs& a) {
     std::memset(s->last_counters, 0, sizeof(s->last_counters));
+    std::memset(s->last_cull, 0, sizeof(s->last_cull));
     if (a.counters) {
         HIP_TRY(hipMemcpy(s->last_counters, a.counters, 512, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(s->last_cull, a.counters + 64, sizeof(s->last_cull), hipMemcpyDeviceToHost));
         s->last_counters[4] = s->last_counters[1] * s->prims_per_ray;
     }
     return RPT_OK;
@@ -2556,6 +2680,34 @@ int rpt_debug_section_counters(rpt_scene* s, uint64_t out[56]) {
     return RPT_OK;
 }
 
+int rpt_scan_cull_counters(rpt_scene* s, uint64_t out[16]) {
+    if (!s || !out) return fail(RPT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    for (int i = 0; i < 12; i++) out[i] = s->last_cull[i];
+    const SceneView& v = s->view;
+    const bool eligible = !(v.scan_bound.lo[0] > v.scan_bound.hi[0]);
+    out[12] = eligible ? 1 : 0;
+    out[13] = v.n_scan_groups;
+    out[14] = v.scan_always;
+    out[15] = v.scan_cull;
+    return RPT_OK;
+}
+int rpt_scan_cull_groups(rpt_scene* s, float out_boxes[36], uint64_t out_masks[5], uint32_t* n_groups, uint32_t* enabled) {
+    if (!s || !out_boxes || !out_masks || !n_groups || !enabled) return fail(RPT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    const SceneView& v = s->view;
+    for (int a = 0; a < 3; a++) { out_boxes[a] = v.scan_bound.lo[a]; out_boxes[3 + a] = v.scan_bound.hi[a]; }
+    for (int a = 0; a < 3; a++) { out_boxes[30 + a] = v.scan_tail.lo[a]; out_boxes[33 + a] = v.scan_tail.hi[a]; }
+    for (uint32_t g = 0; g < kMaxScanGroups; g++) {
+        for (int a = 0; a < 3; a++) { out_boxes[6 + 6 * g + a] = v.scan_groups[g].box.lo[a]; out_boxes[9 + 6 * g + a] = v.scan_groups[g].box.hi[a]; }
+        out_masks[g] = v.scan_groups[g].mask;
+    }
+    out_masks[4] = v.scan_always;
+    *n_groups = v.n_scan_groups;
+    *enabled = v.scan_cull;
+    return RPT_OK;
+}
+
 // ---------------------------------------------------------------------------- test hooks
 // Device scratch of one hook call, at least 16 bytes (an empty batch still gets a valid pointer).
 static hipError_t hook_scratch(rpti::DevMem& m, size_t bytes) { return m.reserve(std::max<size_t>(bytes, 16)); }
@@ -2578,6 +2730,29 @@ int rpt_intersect_batch(rpt_scene* s, uint64_t n, const float* origins, const fl
     HIP_TRY(hipMemcpy(t, d_t.get(), n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(object, d_obj.get(), n * 4, hipMemcpyDeviceToHost));
     if (normal) HIP_TRY(hipMemcpy(normal, d_n.get(), n * 12, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+int rpt_intersect_segments(rpt_scene* s, uint64_t n, const float* origins, const float* dirs, const float* t_max, float* t, uint32_t* code) {
+    if (!s || !origins || !dirs || !t_max || !t || !code) return fail(RPT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (s->view.n_nodes != 0 || s->view.scene_bvh || s->view.n_mono || s->view.n_inst)
+        return fail(RPT_ERR_UNSUPPORTED, "rpt_intersect_segments: the scene has a tree or monomial surfaces (the query is the linear scan's)");
+    if (!launch_intersect_segments) return fail(RPT_ERR_UNSUPPORTED, "rpt_intersect_segments: built without the kernels");
+    if (n == 0) return RPT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    rpti::DevMem d_o, d_d, d_m, d_t, d_c;
+    HIP_TRY(hook_scratch(d_o, n * 12));
+    HIP_TRY(hook_scratch(d_d, n * 12));
+    HIP_TRY(hook_scratch(d_m, n * 4));
+    HIP_TRY(hook_scratch(d_t, n * 4));
+    HIP_TRY(hook_scratch(d_c, n * 4));
+    HIP_TRY(hipMemcpy(d_o.get(), origins, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d.get(), dirs, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_m.get(), t_max, n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(launch_intersect_segments(s->view, n, d_o.get<float>(), d_d.get<float>(), d_m.get<float>(), d_t.get<float>(), d_c.get<uint32_t>(), nullptr));
+    HIP_TRY(hipMemcpy(t, d_t.get(), n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(code, d_c.get(), n * 4, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
