@@ -397,6 +397,22 @@ int rpt_debug_photon_positions64(rpt_scene*, double* out, uint64_t capacity);
 int rpt_debug_photon_selections(rpt_scene*, uint32_t* out, uint64_t capacity_words, uint64_t dims[3]);
 int rpt_debug_camera_rays(const rpt_camera*, const rpt_render_params*, uint64_t seed, uint32_t sample,
                           float* origins, float* dirs); /* one ray per pixel, width*height*3 each */
+/* What a path vertex calls besides the above, one call per lane on the committed scene (host arrays in and out).
+ * Shape::sample and Light::illuminate of Light::Object `light` (index into the scene's lights, RPT_ERR_INVALID for another kind)
+ * at n positions: lane i seeds its stream with (seed, i, 0), runs the render kernels' sample_light_shape on one copy (v, nrm, pdf)
+ * and their illuminate_object on another (intensity, wi, dist) -- the kernel instantiation (group lights or not) and the staging of the
+ * light-triangle table in LDS are the render kernels' --, and next_word[i] is the stream's next word after illuminate_object.
+ * The _f64 twin runs the reference-epsilon mode's functions; each refuses a scene of the other mode with RPT_ERR_STATE. */
+int rpt_debug_light_sample(rpt_scene*, uint32_t light, uint64_t n, const float* positions, uint64_t seed, float* v, float* nrm,
+                           float* pdf, float* intensity, float* wi, float* dist, uint32_t* next_word);
+int rpt_debug_light_sample_f64(rpt_scene*, uint32_t light, uint64_t n, const double* positions, uint64_t seed, double* v, double* nrm,
+                               double* pdf, double* intensity, double* wi, double* dist, uint32_t* next_word);
+/* Environment::get_color of n directions (any length), each mode's env_color. */
+int rpt_debug_env_color(rpt_scene*, uint64_t n, const float* dirs, float* rgb);
+int rpt_debug_env_color_f64(rpt_scene*, uint64_t n, const double* dirs, double* rgb);
+/* The distance sample of a vertex in the scene's medium (fp32 mode; RPT_ERR_INVALID without a medium): lane i on stream
+ * (seed, i, 0) -> the sampled distance and the search limit the closest-hit query gets (+inf: the whole ray). */
+int rpt_debug_medium_distance(rpt_scene*, uint64_t n, uint64_t seed, float* dmed, float* t_limit);
 
 #ifdef __cplusplus
 }

@@ -88,6 +88,8 @@ def lib():
                                           C.c_uint32, D, D]
         L.orc_pixel_ndc.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, D, D]
         L.orc_light_illuminate.argtypes = [P, C.c_int, D, C.c_uint64, C.c_uint32, C.c_uint32, D, D, D]
+        L.orc_light_sample.argtypes = [P, C.c_int, C.c_uint64, P, C.c_uint64, P, P, P, P, P, P, P]
+        L.orc_env_color.argtypes = [P, C.c_uint64, P, P]
         L.orc_photon_map_build.restype = P
         L.orc_photon_map_build.argtypes = [P, C.c_uint64, C.c_int, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int]
         L.orc_photon_map_from_photons.restype = P
@@ -188,6 +190,27 @@ class OracleScene:
         lib().orc_intersect(self.h, n, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), robust,
                             t.ctypes.data_as(C.c_void_p), obj.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p))
         return t, obj, nrm
+
+    def light_sample(self, light_index, positions, seed=0):
+        """Shape::sample and Light::illuminate of one Light::Object at n positions, case i on Rng(seed, i, 0):
+        -> dict of v, nrm (n, 3), p (n), intensity, wi (n, 3), dist (n), next_word (n, uint32: the stream's next word
+        after illuminate)."""
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        n = pos.shape[0]
+        out = {"v": np.empty((n, 3)), "nrm": np.empty((n, 3)), "p": np.empty(n), "intensity": np.empty((n, 3)),
+               "wi": np.empty((n, 3)), "dist": np.empty(n), "next_word": np.empty(n, dtype=np.uint32)}
+        rc = lib().orc_light_sample(self.h, light_index, n, pos.ctypes.data_as(C.c_void_p), C.c_uint64(seed),
+                                    *[out[k].ctypes.data_as(C.c_void_p) for k in ("v", "nrm", "p", "intensity", "wi", "dist", "next_word")])
+        if rc != 0:
+            raise ValueError(f"light {light_index} is not a Light::Object that can be sampled")
+        return out
+
+    def env_color(self, dirs):
+        """Environment::get_color of n directions (any length) -> (n, 3)."""
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        out = np.empty_like(d)
+        lib().orc_env_color(self.h, d.shape[0], d.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+        return out
 
     def photon_map_from_photons(self, photon_count, kind, watts, gather_size, gather_size_volume, surface, volume, robust=0):
         """The maps of PhotonMap::new over photon lists handed in ((n, 10) arrays laid out as OraclePhotonMap.photons returns them):

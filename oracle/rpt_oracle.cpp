@@ -1799,6 +1799,38 @@ void orc_light_illuminate(orc_scene* s, int light_index, const double* pos, uint
     intensity[0] = I.x; intensity[1] = I.y; intensity[2] = I.z;
     wi[0] = w.x; wi[1] = w.y; wi[2] = w.z;
 }
+// The same over n positions, for the per-call device tests: case i runs on Rng(seed, i, 0).  Shape::sample of the light's shape
+// (v, nrm, p) on one copy of the stream, Light::illuminate on another -- the same call orc_light_illuminate makes, so the two
+// agree bit for bit --, and next_word[i] = the stream's next word after illuminate: equal words on both sides of a comparison
+// mean equal numbers of draws.  Returns -1 unless the light is a Light::Object.
+int orc_light_sample(orc_scene* s, int light_index, uint64_t n, const double* pos, uint64_t seed, double* v, double* nrm,
+                     double* p, double* intensity, double* wi, double* dist, uint32_t* next_word) {
+    if (light_index < 0 || size_t(light_index) >= s->scene.lights.size()) return -1;
+    const Light& L = s->scene.lights[light_index];
+    if (L.kind != L_OBJECT || !L.object.shape || !L.object.shape->can_sample()) return -1;
+    for (uint64_t i = 0; i < n; i++) {
+        const V3 x = v3(pos + 3 * i);
+        Rng r1(seed, uint32_t(i), 0);
+        SurfSample ss = L.object.shape->sample(x, r1);
+        v[3 * i] = ss.v.x; v[3 * i + 1] = ss.v.y; v[3 * i + 2] = ss.v.z;
+        nrm[3 * i] = ss.n.x; nrm[3 * i + 1] = ss.n.y; nrm[3 * i + 2] = ss.n.z;
+        p[i] = ss.p;
+        Rng r2(seed, uint32_t(i), 0);
+        V3 I, w;
+        L.illuminate(x, r2, I, w, dist[i]);
+        intensity[3 * i] = I.x; intensity[3 * i + 1] = I.y; intensity[3 * i + 2] = I.z;
+        wi[3 * i] = w.x; wi[3 * i + 1] = w.y; wi[3 * i + 2] = w.z;
+        next_word[i] = r2.next();
+    }
+    return 0;
+}
+// Environment::get_color over n directions (not normalised by the caller).
+void orc_env_color(orc_scene* s, uint64_t n, const double* dirs, double* rgb) {
+    for (uint64_t i = 0; i < n; i++) {
+        V3 c = s->scene.env_color(v3(dirs + 3 * i));
+        rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+    }
+}
 
 // ---------------------------------------------------------------------------- photon mapping (next tier)
 struct orc_photon_map {

@@ -141,6 +141,11 @@ SYMBOLS = [
     ("rpt_debug_photon_selections", C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("rpt_debug_camera_rays", C.c_int,
      [C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint64, C.c_uint32, _P, _P]),
+    ("rpt_debug_light_sample", C.c_int, [_P, C.c_uint32, C.c_uint64, _P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P]),
+    ("rpt_debug_light_sample_f64", C.c_int, [_P, C.c_uint32, C.c_uint64, _P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P]),
+    ("rpt_debug_env_color", C.c_int, [_P, C.c_uint64, _P, _P]),
+    ("rpt_debug_env_color_f64", C.c_int, [_P, C.c_uint64, _P, _P]),
+    ("rpt_debug_medium_distance", C.c_int, [_P, C.c_uint64, C.c_uint64, _P, _P]),
 ]
 
 _lib = None

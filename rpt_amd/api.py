@@ -977,3 +977,38 @@ class Renderer:
                                                t.ctypes.data_as(C.c_void_p), obj.ctypes.data_as(C.c_void_p),
                                                nrm.ctypes.data_as(C.c_void_p)))
         return t, obj, nrm
+
+    # ---- per-call hooks on the committed scene (rpt_debug_*): one device-function call per case
+    def debug_light_sample(self, light_index, positions, seed=0, f64=False):
+        """Shape::sample and Light::illuminate of Light::Object `light_index` at n positions, case i on stream (seed, i, 0), by the
+        scene's own mode (f64: the reference-epsilon mode's functions) -> dict of v, nrm (n, 3), p (n), intensity, wi (n, 3),
+        dist (n), next_word (n, uint32)."""
+        lib = _lib.load()
+        h = self.scene._commit(self.device_)
+        ft = np.float64 if f64 else np.float32
+        pos = np.ascontiguousarray(positions, dtype=ft).reshape(-1, 3)
+        n = pos.shape[0]
+        out = {"v": np.empty((n, 3), ft), "nrm": np.empty((n, 3), ft), "p": np.empty(n, ft), "intensity": np.empty((n, 3), ft),
+               "wi": np.empty((n, 3), ft), "dist": np.empty(n, ft), "next_word": np.empty(n, np.uint32)}
+        fn = lib.rpt_debug_light_sample_f64 if f64 else lib.rpt_debug_light_sample
+        _lib.check(fn(h, light_index, n, pos.ctypes.data_as(C.c_void_p), seed,
+                      *[out[k].ctypes.data_as(C.c_void_p) for k in ("v", "nrm", "p", "intensity", "wi", "dist", "next_word")]))
+        return out
+
+    def debug_env_color(self, dirs, f64=False):
+        """Environment::get_color of n directions (any length) by the scene's own mode -> (n, 3)."""
+        lib = _lib.load()
+        h = self.scene._commit(self.device_)
+        d = np.ascontiguousarray(dirs, dtype=np.float64 if f64 else np.float32).reshape(-1, 3)
+        out = np.empty_like(d)
+        fn = lib.rpt_debug_env_color_f64 if f64 else lib.rpt_debug_env_color
+        _lib.check(fn(h, d.shape[0], d.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def debug_medium_distance(self, n, seed=0):
+        """The distance sample of a vertex in the scene's medium, case i on stream (seed, i, 0) -> (dmed, t_limit), fp32."""
+        lib = _lib.load()
+        h = self.scene._commit(self.device_)
+        dmed, lim = np.empty(n, np.float32), np.empty(n, np.float32)
+        _lib.check(lib.rpt_debug_medium_distance(h, n, seed, dmed.ctypes.data_as(C.c_void_p), lim.ctypes.data_as(C.c_void_p)))
+        return dmed, lim

@@ -153,6 +153,16 @@ struct IsectArgs64 {
     int32_t* obj;               // [n] object index, -1: none
     double* nrm;                // [3 n] normal, or null
 };
+// rpt_debug_light_sample_f64 / rpt_debug_env_color_f64 (kernels_f64.hip): one call of the mode's device function per lane.
+struct DebugArgs64 {
+    Args a;                     // scene, a.seed_mixed, a.group_lights
+    uint64_t n;
+    uint32_t light, pad_;       // index into Scene::lights (an LT_OBJECT)
+    const double* in;           // [3 n] positions / directions
+    double *v, *nrm, *pdf;      // Shape::sample: [3 n], [3 n], [n]
+    double *intensity, *wi, *dist;   // Light::illuminate: [3 n], [3 n], [n]; env_color: intensity = [3 n] colours
+    uint32_t* next_word;        // [n]: the stream's next word after illuminate
+};
 
 // ---- photon mapping in the reference-epsilon mode (kernels_f64.hip; the maps, the k-nearest selection and the volume estimates are
 // photon.hip's, on the records in fp32)

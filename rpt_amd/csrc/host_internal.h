@@ -99,6 +99,7 @@ struct SceneDev {
     bool has_monomial;       // some object is (or holds) a MonomialSurface: photon mapping refuses such scenes
 };
 SceneDev scene_dev(rpt_scene* s);
+int light_kind(rpt_scene* s, uint32_t light);   // kind of scene.lights[light] (0 point, 1 ambient, 2 directional, 3 object), -1: no such light
 void*& photon_slot(rpt_scene* s);  // owned by photon.hip (PhotonMapDev*), released through photon_release
 void photon_release(void* p);      // defined in photon.hip
 // Fills camera, tiles, slab, queue, chunking exactly as for the path tracer; `st` is the stream the launch will run

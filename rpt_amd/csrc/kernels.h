@@ -79,6 +79,22 @@ hipError_t launch_debug_bsdf(const Material& m, uint64_t n, const float* d_n, co
                              float* d_out, hipStream_t s);
 hipError_t launch_debug_camera(const CameraG& cam, uint32_t w, uint32_t h, uint64_t seed_mixed, uint32_t sample,
                                float* d_o, float* d_d, hipStream_t s);
+// rpt_debug_light_sample / rpt_debug_env_color / rpt_debug_medium_distance: one call of the device function per lane on the committed
+// scene (device arrays).  (Weak, like launch_intersect_segments: the host-only harnesses do not know them.)
+struct LightSampleArgs {
+    uint32_t light;           // index into SceneView::lights (an L_OBJECT)
+    uint32_t pad_;
+    uint64_t n;
+    uint64_t seed_mixed;
+    const float* pos;         // [3 n]
+    float *v, *nrm, *pdf;     // sample_light_shape: [3 n], [3 n], [n]
+    float *intensity, *wi, *dist;   // illuminate_object: [3 n], [3 n], [n]
+    uint32_t* next_word;      // [n]: the stream's next word after illuminate_object
+};
+__attribute__((weak)) hipError_t launch_debug_light_sample(const SceneView& sc, const LightSampleArgs& q, hipStream_t s);
+__attribute__((weak)) hipError_t launch_debug_env_color(const SceneView& sc, uint64_t n, const float* d_dirs, float* d_rgb, hipStream_t s);
+__attribute__((weak)) hipError_t launch_debug_medium_distance(const SceneView& sc, uint64_t n, uint64_t seed_mixed, float* d_dmed,
+                                                              float* d_limit, hipStream_t s);
 
 }  // namespace rptg
 namespace rpt64 { struct Args; struct ShootArgs64; struct SurfArgs64; }

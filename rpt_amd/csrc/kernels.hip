@@ -1512,6 +1512,59 @@ __global__ void debug_camera_kernel(const CameraG cam, uint32_t w, uint32_t h, u
     o[3 * i] = ro.x; o[3 * i + 1] = ro.y; o[3 * i + 2] = ro.z;
     d[3 * i] = rd.x; d[3 * i + 1] = rd.y; d[3 * i + 2] = rd.z;
 }
+// rpt_debug_light_sample: Shape::sample and Light::illuminate of one Light::Object, one position per lane, through the functions and
+// the kernel flavour the render kernels use: GROUPS as launch_render_t chooses it, and the light-triangle table staged in LDS under
+// render_kernel's own condition.  (The SceneView MUST stay the first parameter: see intersect_kernel.)
+template <bool GROUPS>
+__global__ __launch_bounds__(256) void debug_light_sample_kernel(const SceneView sc, const LightSampleArgs q) {
+    __shared__ F4 lds_ltris[6u * kLdsLtris];
+    LdsTables tab;
+    {
+        const uint32_t nl = sc.n_ltris <= kLdsLtris ? sc.n_ltris : 0u;
+        for (uint32_t i = threadIdx.x; i < 6u * nl; i += 256u) lds_ltris[i] = reinterpret_cast<const F4*>(sc.ltris)[i];
+        __syncthreads();
+        tab.ltris = lds_ltris; tab.n_ltris = nl;
+    }
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= q.n) return;
+    const Light L = uload(&sc.lights[q.light]);
+    const V pos = mk(q.pos[3 * i], q.pos[3 * i + 1], q.pos[3 * i + 2]);
+    Rng r;
+    r.seed(q.seed_mixed, uint32_t(i), 0);
+    Rng r2 = r;
+    V v, n, I, wi;
+    float p, dist;
+    sample_light_shape<GROUPS>(sc, L, pos, r, v, n, p, tab);
+    illuminate_object<GROUPS>(sc, L, pos, r2, I, wi, dist, tab);
+    q.v[3 * i] = v.x; q.v[3 * i + 1] = v.y; q.v[3 * i + 2] = v.z;
+    q.nrm[3 * i] = n.x; q.nrm[3 * i + 1] = n.y; q.nrm[3 * i + 2] = n.z;
+    q.pdf[i] = p;
+    q.intensity[3 * i] = I.x; q.intensity[3 * i + 1] = I.y; q.intensity[3 * i + 2] = I.z;
+    q.wi[3 * i] = wi.x; q.wi[3 * i + 1] = wi.y; q.wi[3 * i + 2] = wi.z;
+    q.dist[i] = dist;
+    q.next_word[i] = r2.next();
+}
+__global__ __launch_bounds__(256) void debug_env_color_kernel(const SceneView sc, uint64_t n, const float* __restrict__ dirs,
+                                                              float* __restrict__ rgb) {
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= n) return;
+    const V c = env_color(sc, mk(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
+    rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+}
+// rpt_debug_medium_distance: stage_distance<true> with inv_sigma_t formed as render_kernel forms it.
+__global__ __launch_bounds__(256) void debug_medium_distance_kernel(const SceneView sc, uint64_t n, uint64_t seed_mixed,
+                                                                    float* __restrict__ dmed, float* __restrict__ limit) {
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float sigma_t = sc.sigma_a + sc.sigma_s;
+    const float inv_sigma_t = 1.f / sigma_t;
+    Rng r;
+    r.seed(seed_mixed, uint32_t(i), 0);
+    float d, t;
+    stage_distance<true>(r, inv_sigma_t, d, t);
+    dmed[i] = d;
+    limit[i] = t;
+}
 
 // ------------------------------------------------------------------ launchers
 static constexpr size_t kStackBytes = 32u * 256u * sizeof(uint32_t);
@@ -1645,6 +1698,21 @@ hipError_t launch_debug_bsdf(const Material& m, uint64_t n, const float* d_n, co
 hipError_t launch_debug_camera(const CameraG& cam, uint32_t w, uint32_t h, uint64_t seed_mixed, uint32_t sample,
                                float* d_o, float* d_d, hipStream_t s) {
     hipLaunchKernelGGL(debug_camera_kernel, dim3((w * h + 255) / 256), dim3(256), 0, s, cam, w, h, seed_mixed, sample, d_o, d_d);
+    return hipGetLastError();
+}
+hipError_t launch_debug_light_sample(const SceneView& sc, const LightSampleArgs& q, hipStream_t s) {
+    const dim3 grid(uint32_t((q.n + 255) / 256));
+    if (sc.n_lparts) hipLaunchKernelGGL(debug_light_sample_kernel<true>, grid, dim3(256), 0, s, sc, q);   // (as launch_render_t chooses)
+    else hipLaunchKernelGGL(debug_light_sample_kernel<false>, grid, dim3(256), 0, s, sc, q);
+    return hipGetLastError();
+}
+hipError_t launch_debug_env_color(const SceneView& sc, uint64_t n, const float* d_dirs, float* d_rgb, hipStream_t s) {
+    hipLaunchKernelGGL(debug_env_color_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, s, sc, n, d_dirs, d_rgb);
+    return hipGetLastError();
+}
+hipError_t launch_debug_medium_distance(const SceneView& sc, uint64_t n, uint64_t seed_mixed, float* d_dmed, float* d_limit,
+                                        hipStream_t s) {
+    hipLaunchKernelGGL(debug_medium_distance_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, s, sc, n, seed_mixed, d_dmed, d_limit);
     return hipGetLastError();
 }
 

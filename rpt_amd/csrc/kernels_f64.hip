@@ -1499,6 +1499,43 @@ __global__ __launch_bounds__(256) void intersect_f64_kernel(const IsectArgs64 by
 }
 #undef KI
 
+// rpt_debug_light_sample_f64: Shape::sample of a Light::Object's shape and Light::illuminate, one position per lane, through this
+// mode's own functions -- the dispatch on GROUPL is illuminate_object's -- on two copies of stream (seed, lane, 0).  The argument
+// struct begins with the Args, as every kernel's whose code reads KA.
+#define KD (*rptg::kernarg_args<DebugArgs64>())
+static_assert(offsetof(DebugArgs64, a) == 0 && offsetof(IsectArgs64, a) == 0, "KA reads the Args at kernarg + 0");
+template <bool GROUPL>
+__global__ __launch_bounds__(256) void debug_light_sample_f64_kernel(const DebugArgs64 by_value) {
+    (void)by_value;
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= KD.n) return;
+    const auto& L = uniform_ref(&KA.sc.lights[KD.light]);
+    const D pos = mk(KD.in[3 * i], KD.in[3 * i + 1], KD.in[3 * i + 2]);
+    Rng64 r1, r2;
+    r1.r.seed(KA.seed_mixed, uint32_t(i), 0);
+    r2 = r1;
+    D v, n, I, wi;
+    double p, dist;
+    if constexpr (GROUPL) sample_light_shape(L.shape, pos, r1, v, n, p);
+    else sample_shape(L.shape, pos, r1, v, n, p);
+    illuminate_object<GROUPL>(L, pos, r2, I, wi, dist);
+    KD.v[3 * i] = v.x; KD.v[3 * i + 1] = v.y; KD.v[3 * i + 2] = v.z;
+    KD.nrm[3 * i] = n.x; KD.nrm[3 * i + 1] = n.y; KD.nrm[3 * i + 2] = n.z;
+    KD.pdf[i] = p;
+    KD.intensity[3 * i] = I.x; KD.intensity[3 * i + 1] = I.y; KD.intensity[3 * i + 2] = I.z;
+    KD.wi[3 * i] = wi.x; KD.wi[3 * i + 1] = wi.y; KD.wi[3 * i + 2] = wi.z;
+    KD.dist[i] = dist;
+    KD.next_word[i] = r2.r.next();
+}
+__global__ __launch_bounds__(256) void debug_env_color_f64_kernel(const DebugArgs64 by_value) {
+    (void)by_value;
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= KD.n) return;
+    const D c = env_color(mk(KD.in[3 * i], KD.in[3 * i + 1], KD.in[3 * i + 2]));
+    KD.intensity[3 * i] = c.x; KD.intensity[3 * i + 1] = c.y; KD.intensity[3 * i + 2] = c.z;
+}
+#undef KD
+
 }  // namespace rpt64
 
 namespace rptg {
@@ -1622,5 +1659,67 @@ extern "C" int rpt_intersect_batch_f64(rpt_scene* s, uint64_t n, const double* o
     RPTI_HIP_TRY(hipMemcpy(t, d_t.get(), n * 8, hipMemcpyDeviceToHost));
     RPTI_HIP_TRY(hipMemcpy(object, d_obj.get(), n * 4, hipMemcpyDeviceToHost));
     if (normal) RPTI_HIP_TRY(hipMemcpy(normal, d_nrm.get(), n * 24, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+// ---------------------------------------------------------------------------- C ABI: the per-call hooks of this mode (include/rpt_hip.h)
+extern "C" int rpt_debug_light_sample_f64(rpt_scene* s, uint32_t light, uint64_t n, const double* positions, uint64_t seed, double* v,
+                                          double* nrm, double* pdf, double* intensity, double* wi, double* dist, uint32_t* next_word) {
+    if (!s || !positions || !v || !nrm || !pdf || !intensity || !wi || !dist || !next_word) return rpti::fail(RPT_ERR_INVALID, "null argument");
+    if (rpti::light_kind(s, light) != int(rpt64::LT_OBJECT)) return rpti::fail(RPT_ERR_INVALID, "rpt_debug_light_sample_f64: not a Light::Object");
+    const rpti::SceneDev sd = rpti::scene_dev(s);
+    if (!sd.committed) return rpti::fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (!sd.epsilon64) return rpti::fail(RPT_ERR_STATE, "rpt_debug_light_sample_f64 needs a scene committed with epsilon_policy = 1");
+    if (n == 0) return RPT_OK;
+    if (n > 0xFFFFFFFFull) return rpti::fail(RPT_ERR_INVALID, "rpt_debug_light_sample_f64: the case number keys a 32-bit stream field");
+    RPTI_HIP_TRY(hipSetDevice(sd.device));
+    rpti::DevMem d_pos, d_out;   // d_out: v, nrm, intensity, wi (3 n each), pdf, dist (n each), next_word (n dwords)
+    RPTI_HIP_TRY(d_pos.reserve(n * 24));
+    RPTI_HIP_TRY(d_out.reserve(n * (14 * 8 + 4)));
+    RPTI_HIP_TRY(hipMemcpy(d_pos.get(), positions, n * 24, hipMemcpyHostToDevice));
+    double* const o = d_out.get<double>();
+    rpt64::DebugArgs64 q;
+    std::memset(&q, 0, sizeof(q));
+    rpti::fill_args64(s, nullptr, nullptr, nullptr, q.a);
+    q.a.seed_mixed = rpti::seed_mix(seed);
+    q.n = n;
+    q.light = light;
+    q.in = d_pos.get<const double>();
+    q.v = o; q.nrm = o + 3 * n; q.intensity = o + 6 * n; q.wi = o + 9 * n;
+    q.pdf = o + 12 * n; q.dist = o + 13 * n;
+    q.next_word = reinterpret_cast<uint32_t*>(o + 14 * n);
+    const dim3 grid(uint32_t((n + 255u) / 256u));
+    if (q.a.group_lights) hipLaunchKernelGGL(rpt64::debug_light_sample_f64_kernel<true>, grid, dim3(256), 0, nullptr, q);   // (as launch_f64_t chooses)
+    else hipLaunchKernelGGL(rpt64::debug_light_sample_f64_kernel<false>, grid, dim3(256), 0, nullptr, q);
+    RPTI_HIP_TRY(hipGetLastError());
+    RPTI_HIP_TRY(hipMemcpy(v, q.v, n * 24, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(nrm, q.nrm, n * 24, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(intensity, q.intensity, n * 24, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(wi, q.wi, n * 24, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(pdf, q.pdf, n * 8, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(dist, q.dist, n * 8, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(next_word, q.next_word, n * 4, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+extern "C" int rpt_debug_env_color_f64(rpt_scene* s, uint64_t n, const double* dirs, double* rgb) {
+    if (!s || !dirs || !rgb) return rpti::fail(RPT_ERR_INVALID, "null argument");
+    const rpti::SceneDev sd = rpti::scene_dev(s);
+    if (!sd.committed) return rpti::fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (!sd.epsilon64) return rpti::fail(RPT_ERR_STATE, "rpt_debug_env_color_f64 needs a scene committed with epsilon_policy = 1");
+    if (n == 0) return RPT_OK;
+    RPTI_HIP_TRY(hipSetDevice(sd.device));
+    rpti::DevMem d_d, d_c;
+    RPTI_HIP_TRY(d_d.reserve(n * 24));
+    RPTI_HIP_TRY(d_c.reserve(n * 24));
+    RPTI_HIP_TRY(hipMemcpy(d_d.get(), dirs, n * 24, hipMemcpyHostToDevice));
+    rpt64::DebugArgs64 q;
+    std::memset(&q, 0, sizeof(q));
+    rpti::fill_args64(s, nullptr, nullptr, nullptr, q.a);
+    q.n = n;
+    q.in = d_d.get<const double>();
+    q.intensity = d_c.get<double>();
+    hipLaunchKernelGGL(rpt64::debug_env_color_f64_kernel, dim3(uint32_t((n + 255u) / 256u)), dim3(256), 0, nullptr, q);
+    RPTI_HIP_TRY(hipGetLastError());
+    RPTI_HIP_TRY(hipMemcpy(rgb, d_c.get(), n * 24, hipMemcpyDeviceToHost));
     return RPT_OK;
 }

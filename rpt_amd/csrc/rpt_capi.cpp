@@ -2829,5 +2829,73 @@ int rpt_debug_camera_rays(const rpt_camera* cam, const rpt_render_params* prm, u
     HIP_TRY(hipMemcpy(dirs, d_d.get(), n * 12, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
+// The per-call hooks on a committed scene.  What the caller got wrong (null arrays, the light's kind, a scene without a medium) is
+// reported before the scene's state, so those answers need no device.
+extern "C++" int rpti::light_kind(rpt_scene* s, uint32_t light) { return light < s->lights.size() ? int(s->lights[light].kind) : -1; }
+int rpt_debug_light_sample(rpt_scene* s, uint32_t light, uint64_t n, const float* positions, uint64_t seed, float* v, float* nrm,
+                           float* pdf, float* intensity, float* wi, float* dist, uint32_t* next_word) {
+    if (!s || !positions || !v || !nrm || !pdf || !intensity || !wi || !dist || !next_word) return fail(RPT_ERR_INVALID, "null argument");
+    if (rpti::light_kind(s, light) != int(L_OBJECT)) return fail(RPT_ERR_INVALID, "rpt_debug_light_sample: not a Light::Object");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (s->dev.arena64) return fail(RPT_ERR_STATE, "rpt_debug_light_sample: the scene was committed with epsilon_policy = 1 (rpt_debug_light_sample_f64)");
+    if (!launch_debug_light_sample) return fail(RPT_ERR_UNSUPPORTED, "rpt_debug_light_sample: built without the kernels");
+    if (n == 0) return RPT_OK;
+    if (n > 0xFFFFFFFFull) return fail(RPT_ERR_INVALID, "rpt_debug_light_sample: the case number keys a 32-bit stream field");
+    HIP_TRY(hipSetDevice(s->device));
+    rpti::DevMem d_pos, d_out;   // d_out: v, nrm, intensity, wi (3 n each), pdf, dist, next_word (n each)
+    HIP_TRY(hook_scratch(d_pos, n * 12));
+    HIP_TRY(hook_scratch(d_out, n * 60));
+    HIP_TRY(hipMemcpy(d_pos.get(), positions, n * 12, hipMemcpyHostToDevice));
+    float* const o = d_out.get<float>();
+    LightSampleArgs q{};
+    q.light = light;
+    q.n = n;
+    q.seed_mixed = seed_mix(seed);
+    q.pos = d_pos.get<float>();
+    q.v = o; q.nrm = o + 3 * n; q.intensity = o + 6 * n; q.wi = o + 9 * n;
+    q.pdf = o + 12 * n; q.dist = o + 13 * n;
+    q.next_word = reinterpret_cast<uint32_t*>(o + 14 * n);
+    HIP_TRY(launch_debug_light_sample(s->view, q, nullptr));
+    HIP_TRY(hipMemcpy(v, q.v, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(nrm, q.nrm, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(intensity, q.intensity, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(wi, q.wi, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pdf, q.pdf, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dist, q.dist, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(next_word, q.next_word, n * 4, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+int rpt_debug_env_color(rpt_scene* s, uint64_t n, const float* dirs, float* rgb) {
+    if (!s || !dirs || !rgb) return fail(RPT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (s->dev.arena64) return fail(RPT_ERR_STATE, "rpt_debug_env_color: the scene was committed with epsilon_policy = 1 (rpt_debug_env_color_f64)");
+    if (!launch_debug_env_color) return fail(RPT_ERR_UNSUPPORTED, "rpt_debug_env_color: built without the kernels");
+    if (n == 0) return RPT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    rpti::DevMem d_d, d_c;
+    HIP_TRY(hook_scratch(d_d, n * 12));
+    HIP_TRY(hook_scratch(d_c, n * 12));
+    HIP_TRY(hipMemcpy(d_d.get(), dirs, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(launch_debug_env_color(s->view, n, d_d.get<float>(), d_c.get<float>(), nullptr));
+    HIP_TRY(hipMemcpy(rgb, d_c.get(), n * 12, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+int rpt_debug_medium_distance(rpt_scene* s, uint64_t n, uint64_t seed, float* dmed, float* t_limit) {
+    if (!s || !dmed || !t_limit) return fail(RPT_ERR_INVALID, "null argument");
+    if (s->media.empty()) return fail(RPT_ERR_INVALID, "rpt_debug_medium_distance: the scene has no medium");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (s->dev.arena64) return fail(RPT_ERR_STATE, "rpt_debug_medium_distance: the scene was committed with epsilon_policy = 1");
+    if (!launch_debug_medium_distance) return fail(RPT_ERR_UNSUPPORTED, "rpt_debug_medium_distance: built without the kernels");
+    if (n == 0) return RPT_OK;
+    if (n > 0xFFFFFFFFull) return fail(RPT_ERR_INVALID, "rpt_debug_medium_distance: the case number keys a 32-bit stream field");
+    HIP_TRY(hipSetDevice(s->device));
+    rpti::DevMem d_m, d_t;
+    HIP_TRY(hook_scratch(d_m, n * 4));
+    HIP_TRY(hook_scratch(d_t, n * 4));
+    HIP_TRY(launch_debug_medium_distance(s->view, n, seed_mix(seed), d_m.get<float>(), d_t.get<float>(), nullptr));
+    HIP_TRY(hipMemcpy(dmed, d_m.get(), n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(t_limit, d_t.get(), n * 4, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
 
 }  // extern "C"

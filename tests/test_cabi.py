@@ -121,3 +121,41 @@ def test_no_gpu_means_a_loud_error_not_a_fallback():
     scene, cam, cfg = scenes.cornell()
     with pytest.raises(RptError):
         Renderer(scene, cam).width(8).height(8).sample_array(1)
+
+
+def test_per_call_hooks_validate_their_arguments_without_a_gpu():
+    """rpt_debug_light_sample(_f64), rpt_debug_env_color(_f64), rpt_debug_medium_distance: what the caller got wrong -- a null
+    array, a light that is not a Light::Object, a scene without a medium -- is RPT_ERR_INVALID (-1) and is said before the scene's
+    state; a well-formed call on a scene that was never committed is RPT_ERR_STATE (-2).  (The answer to a scene committed in the
+    other mode needs a device: tests/test_gpu_device_samplers.py.)"""
+    from rpt_amd import Light, Medium
+    lib = _lib.load()
+    h = lib.rpt_scene_create()
+    try:
+        col = np.array([1.0, 1.0, 1.0])
+        D3 = C.POINTER(C.c_double)
+        assert lib.rpt_scene_add_light_ambient(h, col.ctypes.data_as(D3)) == 0
+        sd, keep = shape_desc(sphere().translate(vec3(0, 3, 0)), _lib.ShapeDesc)
+        md = material_desc(Material.light(vec3(1, 1, 1), 5.0), _lib.MaterialDesc)
+        assert lib.rpt_scene_add_light_object(h, C.byref(sd), C.byref(md)) >= 0
+        buf = np.zeros(16)
+        p = buf.ctypes.data
+        for fn in (lib.rpt_debug_light_sample, lib.rpt_debug_light_sample_f64):
+            assert fn(None, 1, 1, p, 0, p, p, p, p, p, p, p) == -1
+            for k in range(8):                                                   # each array in turn
+                args = [p] * 8
+                args[k] = None
+                assert fn(h, 1, 1, args[0], 0, *args[1:]) == -1 and b"null" in lib.rpt_last_error()
+            assert fn(h, 0, 1, p, 0, p, p, p, p, p, p, p) == -1 and b"Light::Object" in lib.rpt_last_error()   # the ambient light
+            assert fn(h, 2, 1, p, 0, p, p, p, p, p, p, p) == -1                                                # no such light
+            assert fn(h, 1, 1, p, 0, p, p, p, p, p, p, p) == -2 and b"commit" in lib.rpt_last_error()
+        for fn in (lib.rpt_debug_env_color, lib.rpt_debug_env_color_f64):
+            assert fn(None, 1, p, p) == -1 and fn(h, 1, None, p) == -1 and fn(h, 1, p, None) == -1
+            assert fn(h, 1, p, p) == -2 and b"commit" in lib.rpt_last_error()
+        assert lib.rpt_debug_medium_distance(None, 1, 0, p, p) == -1
+        assert lib.rpt_debug_medium_distance(h, 1, 0, None, p) == -1 and lib.rpt_debug_medium_distance(h, 1, 0, p, None) == -1
+        assert lib.rpt_debug_medium_distance(h, 1, 0, p, p) == -1 and b"medium" in lib.rpt_last_error()        # no medium
+        assert lib.rpt_scene_add_medium(h, 0, 0.02, 0.1) == 0
+        assert lib.rpt_debug_medium_distance(h, 1, 0, p, p) == -2 and b"commit" in lib.rpt_last_error()
+    finally:
+        lib.rpt_scene_destroy(h)

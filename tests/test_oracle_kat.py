@@ -11,7 +11,7 @@ import pytest
 
 from oracle import pyoracle
 from oracle.pyoracle import CameraDesc, MaterialDesc, OracleScene, ShapeDesc
-from rpt_amd import (Camera, KdTree, Light, Material, Medium, Mesh, Object, Scene, cube, hex_color, plane, polygon,
+from rpt_amd import (Camera, Environment, KdTree, Light, Material, Medium, Mesh, Object, Scene, cube, hex_color, plane, polygon,
                      scenes, sphere, vec3)
 from rpt_amd.api import camera_desc, material_desc, shape_desc
 
@@ -416,3 +416,55 @@ def test_hdri_lookup_is_equirectangular_bilinear():
         x = az / (2 * math.pi) * (w - 1)
         y = math.acos(dv[1]) / math.pi * (h - 1)
         assert np.allclose(got, [x, y, 0.0], atol=1e-4)        # a linear ramp is reproduced exactly by bilinear lookup
+
+
+# ---- the array entry points the per-call device tests compare against (tests/test_gpu_device_samplers.py)
+@pytest.mark.parametrize("case", ["A", "B", "C", "D", "E", "F", "G"])
+def test_light_sample_is_shape_sample_and_illuminate_bit_for_bit(case):
+    """orc_light_sample over an array of positions = orc_shape_sample and orc_light_illuminate case by case, every bit; the word it
+    reports after illuminate is the stream's word at the position the shape's own draw count gives."""
+    from tests import sampler_cases as sc
+    L = pyoracle.lib()
+    shape = sc.light_shapes()[case]
+    osc = OracleScene(sc.light_scene(shape))
+    pos = sc.positions(96, seed=3).astype(np.float64)
+    got = osc.light_sample(0, pos, seed=5)
+    sd, _keep = shape_desc(shape, ShapeDesc)
+    for i in range(pos.shape[0]):
+        I, wi, dist = D(0, 0, 0), D(0, 0, 0), C.c_double()
+        L.orc_light_illuminate(osc.h, 0, D(*pos[i]), C.c_uint64(5), i, 0, I, wi, C.byref(dist))
+        assert list(I) == list(got["intensity"][i]) and list(wi) == list(got["wi"][i]) and dist.value == got["dist"][i]
+        v, n, p = D(0, 0, 0), D(0, 0, 0), C.c_double()
+        draws = L.orc_shape_sample(C.byref(sd), D(*pos[i]), C.c_uint64(5), i, 0, v, n, C.byref(p))
+        assert list(v) == list(got["v"][i]) and list(n) == list(got["nrm"][i]) and p.value == got["p"][i]
+        words = np.zeros(draws + 1, dtype=np.uint32)
+        L.orc_rng_u32(C.c_uint64(5), i, 0, draws + 1, words.ctypes.data_as(C.c_void_p))
+        assert words[draws] == got["next_word"][i]
+    assert np.all(np.isfinite(got["intensity"])) and np.all(got["p"] != 0)
+    if case in "DG":      # a mirrored transform: the reference divides by a signed area factor
+        assert np.all(got["intensity"] <= 0) and np.any(got["intensity"] < 0) and np.all(got["p"] < 0)
+    with pytest.raises(ValueError):
+        osc.light_sample(1, pos)
+    amb = Scene()
+    amb.add(Light.Ambient(vec3(1, 1, 1)))
+    with pytest.raises(ValueError):
+        OracleScene(amb).light_sample(0, pos)
+
+
+def test_env_color_reproduces_a_linear_ramp():
+    """orc_env_color = Environment::get_color: bilinear lookup of a linear ramp is the ramp, x = azimuth / 2 pi (w - 1),
+    y = polar / pi (h - 1) (the closed form of test_hdri_lookup_is_equirectangular_bilinear, without the camera)."""
+    from tests import sampler_cases as sc
+    ramp = sc.sky_images()["ramp8x4"]
+    h, w = ramp.shape[:2]
+    osc = OracleScene(sc.sky_scene(ramp))
+    d = sc.sky_directions().astype(np.float64)
+    got = osc.env_color(d)
+    u = d / np.linalg.norm(d, axis=1, keepdims=True)
+    x = (np.arctan2(u[:, 2], u[:, 0]) + math.pi) / (2 * math.pi) * (w - 1)
+    y = np.arccos(u[:, 1]) / math.pi * (h - 1)
+    assert np.allclose(got, np.stack([x, y, np.full_like(x, 0.5)], 1), rtol=0, atol=1e-12)
+    assert got[:, 0].min() == 0.0 and got[:, 0].max() > 6.99       # both sides of the seam are among the directions
+    const = Scene()
+    const.environment = Environment.Color(vec3(0.25, 0.5, 0.75))
+    assert np.array_equal(OracleScene(const).env_color(d[:5]), np.broadcast_to([0.25, 0.5, 0.75], (5, 3)))
