@@ -397,6 +397,14 @@ int rpt_debug_photon_positions64(rpt_scene*, double* out, uint64_t capacity);
 int rpt_debug_photon_selections(rpt_scene*, uint32_t* out, uint64_t capacity_words, uint64_t dims[3]);
 int rpt_debug_camera_rays(const rpt_camera*, const rpt_render_params*, uint64_t seed, uint32_t sample,
                           float* origins, float* dirs); /* one ray per pixel, width*height*3 each */
+/* The camera sample of a render for every pixel of a width x height frame and one sample index: the render kernels' pixel -> NDC
+ * mapping, their two jitter draws and cast_ray on stream (seed, pixel, sample) -> one ray per pixel (width*height*3 each) and
+ * next_word[pixel], the stream's next word after cast_ray (fp32: may be null).  rpt_debug_camera_rays is the same without the word.
+ * The _f64 twin runs the reference-epsilon mode's functions.  Neither reads a scene. */
+int rpt_debug_camera_sample(const rpt_camera*, const rpt_render_params*, uint64_t seed, uint32_t sample,
+                            float* origins, float* dirs, uint32_t* next_word);
+int rpt_debug_camera_sample_f64(const rpt_camera*, const rpt_render_params*, uint64_t seed, uint32_t sample,
+                                double* origins, double* dirs, uint32_t* next_word);
 /* What a path vertex calls besides the above, one call per lane on the committed scene (host arrays in and out).
  * Shape::sample and Light::illuminate of Light::Object `light` (index into the scene's lights, RPT_ERR_INVALID for another kind)
  * at n positions: lane i seeds its stream with (seed, i, 0), runs the render kernels' sample_light_shape on one copy (v, nrm, pdf)
@@ -414,6 +422,22 @@ int rpt_debug_env_color_f64(rpt_scene*, uint64_t n, const double* dirs, double* 
  * (seed, i, 0) -> the sampled distance and the search limit the closest-hit query gets (+inf: the whole ray). */
 int rpt_debug_medium_distance(rpt_scene*, uint64_t n, uint64_t seed, float* dmed, float* t_limit);
 
+/* The bounce of a path vertex, one case per lane on stream (seed, i, 0) (fp32 mode; needs no scene): the render kernels' own stage
+ * (roulette or max_bounces, phase or BSDF sample, path weight) at a surface of material `m` with normal normals[i], reached along
+ * rds[i] (not normalised by the hook), or -- medium_event != 0, which needs in_medium != 0 -- at a point of a medium with
+ * scattering / extinction = albedo_med and colour medium_color[3].  in_medium chooses the kernels' instantiation for scenes with a
+ * medium (roulette at surfaces too).  flag[i]: the path goes on with a non-zero weight; wi, k: its next direction and weight (zero
+ * where the stage wrote none); next_word[i]: the stream's next word after the stage. */
+int rpt_debug_bounce(const rpt_material* m, uint32_t max_bounces, uint32_t depth, int32_t in_medium, int32_t medium_event,
+                     float albedo_med, const float* medium_color, uint64_t n, const float* normals, const float* rds, uint64_t seed,
+                     int32_t* flag, float* wi, float* k, uint32_t* next_word);
+/* The reference-epsilon mode's Material::sample_f on stream (seed, i, 0), then its Material::bsdf at the sampled direction (wi, pdf and f zero for
+ * None); next_word[i]: the stream's next word after sample_f.  rpt_debug_material_bsdf_f64: its bsdf at given directions.  Neither
+ * reads a scene. */
+int rpt_debug_material_f64(const rpt_material* m, uint64_t n, const double* normals, const double* wos, uint64_t seed, int32_t* some,
+                           double* wi, double* pdf, double* f, uint32_t* next_word);
+int rpt_debug_material_bsdf_f64(const rpt_material* m, uint64_t n, const double* normals, const double* wos, const double* wis,
+                                double* f);
 #ifdef __cplusplus
 }
 #endif

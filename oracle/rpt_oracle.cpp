@@ -901,6 +901,50 @@ struct Scene {  // src/scene.rs:12-24
     }
 };
 
+// ------------------------------------------------------------------ the camera sample of get_color
+// Pixel -> NDC (src/renderer.rs:174-176) and the jittered ray of one sample (:179-181), as get_color forms them: shared with
+// orc_pixel_ndc and orc_camera_rays.
+static void pixel_ndc(uint32_t x, uint32_t y, uint32_t w, uint32_t h, double& xn, double& yn) {
+    double dim = double(std::max(w, h));
+    xn = (double(2 * x + 1) - double(w)) / dim;
+    yn = (double(2 * (h - y) - 1) - double(h)) / dim;
+}
+static Ray jittered_ray(const Camera& camera, double xn, double yn, double dim, Rng& rng) {
+    double dx = rng.range(-1.0 / dim, 1.0 / dim);
+    double dy = rng.range(-1.0 / dim, 1.0 / dim);
+    return camera.cast_ray(xn + dx, yn + dy, rng);
+}
+
+// ------------------------------------------------------------------ the bounce of a path vertex
+// The continuation of trace_ray (src/renderer.rs:222-232, 262-281, 301-313) in the two halves the recursion separates: the decision
+// with its sample, and the weighting of the radiance that comes back.  trace_ray calls them around its recursive call and orc_bounce
+// calls them with unit radiance, so the per-call device tests see the very arithmetic of the frames.
+// Surface vertex: rr_p > 0 is the roulette of a scene with a medium (:222, 262), rr_p == 0 the max_bounces rule (:301).
+static bool bounce_surface_sample(const Material& material, const V3& normal, const V3& wo, double rr_p, uint32_t num_bounces,
+                                  uint32_t max_bounces, Rng& rng, V3& wi, double& pdf, V3& f) {
+    if (rr_p > 0.0 ? !(rng.uniform() < rr_p) : !(num_bounces < max_bounces)) return false;
+    if (!sample_f(material, normal, wo, rng, wi, pdf)) return false;
+    f = bsdf(material, normal, wo, wi);
+    return true;
+}
+static V3 bounce_surface_weigh(const V3& f, double pdf, double rr_p, const V3& wi, const V3& normal, const V3& radiance) {
+    return (1.0 / (rr_p > 0.0 ? pdf * rr_p : pdf)) * cmul(f, radiance) * std::fabs(dot(wi, normal));
+}
+// Medium vertex (:222-232).
+static bool bounce_medium_sample(const Medium& medium, const V3& wo, double rr_p, Rng& rng, V3& wi, double& ph_p) {
+    if (!(rng.uniform() < rr_p)) return false;
+    medium.sample_ph(wo, rng, wi, ph_p);
+    return true;
+}
+static V3 bounce_medium_weigh(const Medium& medium, const V3& collision, const V3& wo, const V3& wi, double ph_p, double rr_p,
+                              const V3& radiance) {
+    const double scat = medium.scattering(collision), extinction = medium.absorption(collision) + scat;
+    V3 indirect = (scat / extinction) * radiance;
+    indirect = indirect / ph_p;
+    indirect = cmul(indirect, medium.color(collision)) * medium.phase(wo, wi);
+    return indirect / rr_p;
+}
+
 // ------------------------------------------------------------------ renderer.rs
 static const double EPSILON = 1e-12;       // src/renderer.rs:17
 static const double FIREFLY_CLAMP = 100.0;  // src/renderer.rs:18
@@ -1020,16 +1064,11 @@ struct Renderer {
                     const Material& material = scene.objects[oi].material;
                     V3 color = (num_bounces == 0) ? material.color() * material.emittance() : V3(0, 0, 0);
                     color = color + sample_lights(material, world_pos, h.normal, wo, rng);
-                    if (rng.uniform() < rr_p) {
-                        V3 wi;
-                        double pdf;
-                        if (sample_f(material, h.normal, wo, rng, wi, pdf)) {
-                            V3 f = bsdf(material, h.normal, wo, wi);
-                            Ray nr{world_pos, wi};
-                            V3 indirect = (1.0 / (pdf * rr_p)) * cmul(f, trace_ray(nr, num_bounces + 1, rng)) *
-                                          std::fabs(dot(wi, h.normal));
-                            color = color + indirect;
-                        }
+                    V3 wi, f;
+                    double pdf;
+                    if (bounce_surface_sample(material, h.normal, wo, rr_p, num_bounces, p.max_bounces, rng, wi, pdf, f)) {
+                        Ray nr{world_pos, wi};
+                        color = color + bounce_surface_weigh(f, pdf, rr_p, wi, h.normal, trace_ray(nr, num_bounces + 1, rng));
                     }
                     surface_color = color;
                 }
@@ -1037,23 +1076,15 @@ struct Renderer {
             }
             if (d < max_dist) {
                 V3 collision = ray.at(d);
-                double abs_ = medium.absorption(collision);
                 double emm = medium.emission(collision);
                 V3 medium_color = medium.color(collision);
-                double scat = medium.scattering(collision);
-                double extinction = abs_ + scat;
                 V3 color = (num_bounces == 0) ? emm * medium_color : V3(0, 0, 0);
                 color = color + sample_lights_for_media(medium, collision, wo, rng);
-                if (rng.uniform() < rr_p) {
-                    V3 wi;
-                    double ph_p;
-                    medium.sample_ph(wo, rng, wi, ph_p);
+                V3 wi;
+                double ph_p;
+                if (bounce_medium_sample(medium, wo, rr_p, rng, wi, ph_p)) {
                     Ray nr{collision, wi};
-                    V3 indirect = (scat / extinction) * trace_ray(nr, num_bounces + 1, rng);
-                    indirect = indirect / ph_p;
-                    indirect = cmul(indirect, medium_color) * medium.phase(wo, wi);
-                    indirect = indirect / rr_p;
-                    color = color + indirect;
+                    color = color + bounce_medium_weigh(medium, collision, wo, wi, ph_p, rr_p, trace_ray(nr, num_bounces + 1, rng));
                 }
                 return color;
             }
@@ -1067,33 +1098,29 @@ struct Renderer {
         V3 wo = -normalize(ray.dir);
         V3 color = (num_bounces == 0) ? material.color() * material.emittance() : V3(0, 0, 0);
         color = color + sample_lights(material, world_pos, h.normal, wo, rng);
-        if (num_bounces < p.max_bounces) {
-            V3 wi;
-            double pdf;
-            if (sample_f(material, h.normal, wo, rng, wi, pdf)) {
-                V3 f = bsdf(material, h.normal, wo, wi);
-                Ray nr{world_pos, wi};
-                V3 indirect = (1.0 / pdf) * cmul(f, trace_ray(nr, num_bounces + 1, rng)) * std::fabs(dot(wi, h.normal));
-                // f64::min returns the non-NaN operand (src/renderer.rs:311-313)
-                color.x += std::fmin(indirect.x, FIREFLY_CLAMP);
-                color.y += std::fmin(indirect.y, FIREFLY_CLAMP);
-                color.z += std::fmin(indirect.z, FIREFLY_CLAMP);
-            }
+        V3 wi, f;
+        double pdf;
+        if (bounce_surface_sample(material, h.normal, wo, 0.0, num_bounces, p.max_bounces, rng, wi, pdf, f)) {
+            Ray nr{world_pos, wi};
+            V3 indirect = bounce_surface_weigh(f, pdf, 0.0, wi, h.normal, trace_ray(nr, num_bounces + 1, rng));
+            // f64::min returns the non-NaN operand (src/renderer.rs:311-313)
+            color.x += std::fmin(indirect.x, FIREFLY_CLAMP);
+            color.y += std::fmin(indirect.y, FIREFLY_CLAMP);
+            color.z += std::fmin(indirect.z, FIREFLY_CLAMP);
         }
         return color;
     }
     // src/renderer.rs:173-184; the RNG stream is per (pixel, sample) instead of per row.
     V3 get_color(uint32_t x, uint32_t y, uint32_t iterations, uint64_t seed, uint32_t sample_offset) const {
         double dim = double(std::max(p.width, p.height));
-        double xn = (double(2 * x + 1) - double(p.width)) / dim;
-        double yn = (double(2 * (p.height - y) - 1) - double(p.height)) / dim;
+        double xn, yn;
+        pixel_ndc(x, y, p.width, p.height, xn, yn);
         V3 color(0, 0, 0);
         for (uint32_t s = 0; s < iterations; s++) {
             Rng rng(seed, y * p.width + x, sample_offset + s);
-            double dx = rng.range(-1.0 / dim, 1.0 / dim);
-            double dy = rng.range(-1.0 / dim, 1.0 / dim);
             CNT(samples);
-            color = color + trace_ray(camera.cast_ray(xn + dx, yn + dy, rng), 0, rng);
+            Ray ray = jittered_ray(camera, xn, yn, dim, rng);
+            color = color + trace_ray(ray, 0, rng);
         }
         return color / double(iterations) * std::pow(2.0, p.exposure_value);
     }
@@ -1764,6 +1791,67 @@ void orc_material_bsdf(const orc_material* m, const double* normal, const double
     V3 f = bsdf(make_material(m), v3(normal), v3(wo), v3(wi));
     out[0] = f.x; out[1] = f.y; out[2] = f.z;
 }
+// Material::sample_f over n cases for the per-call device tests, case i on Rng(seed, i, 0), then Material::bsdf at the sampled
+// direction (zero for None); next_word[i] = the stream's next word after sample_f.
+void orc_material_sample(const orc_material* m, uint64_t n, const double* normals, const double* wos, uint64_t seed, int32_t* some,
+                         double* wi, double* pdf, double* f, uint32_t* next_word) {
+    const Material mat = make_material(m);
+    for (uint64_t i = 0; i < n; i++) {
+        Rng rng(seed, uint32_t(i), 0);
+        V3 w(0, 0, 0), ff(0, 0, 0);
+        double p = 0;
+        const V3 nrm = v3(normals + 3 * i), wo = v3(wos + 3 * i);
+        const bool ok = sample_f(mat, nrm, wo, rng, w, p);
+        if (ok) ff = bsdf(mat, nrm, wo, w);
+        some[i] = ok ? 1 : 0;
+        wi[3 * i] = w.x; wi[3 * i + 1] = w.y; wi[3 * i + 2] = w.z;
+        pdf[i] = p;
+        f[3 * i] = ff.x; f[3 * i + 1] = ff.y; f[3 * i + 2] = ff.z;
+        next_word[i] = rng.next();
+    }
+}
+// Material::bsdf over n cases.
+void orc_material_bsdf_n(const orc_material* m, uint64_t n, const double* normals, const double* wos, const double* wis, double* f) {
+    const Material mat = make_material(m);
+    for (uint64_t i = 0; i < n; i++) {
+        const V3 ff = bsdf(mat, v3(normals + 3 * i), v3(wos + 3 * i), v3(wis + 3 * i));
+        f[3 * i] = ff.x; f[3 * i + 1] = ff.y; f[3 * i + 2] = ff.z;
+    }
+}
+// The bounce of a path vertex as trace_ray performs it (bounce_*_sample, bounce_*_weigh), over n cases on Rng(seed, i, 0):
+// medium_kind < 0: a scene without a medium (max_bounces rule), else one with Medium{medium_kind, absorption, scattering};
+// medium_event: the vertex is a medium point at `position`, else a surface of material m with normal normals[i]; wo = -normalize(rds[i])
+// as trace_ray forms it.  cont[i]: the path goes on; wi; k = the factor on the radiance that comes back (the weighing of unit
+// radiance; zero where the path ends); next_word[i] = the stream's next word.  Returns -1 for a medium event without a medium.
+int orc_bounce(const orc_material* m, int medium_kind, double absorption, double scattering, int medium_event, const double* position,
+               uint32_t max_bounces, uint32_t depth, uint64_t n, const double* normals, const double* rds, uint64_t seed,
+               int32_t* cont, double* wi, double* k, uint32_t* next_word) {
+    if (medium_event && medium_kind < 0) return -1;
+    const Material mat = make_material(m);
+    const Medium medium{medium_kind < 0 ? 0 : medium_kind, absorption, scattering};
+    const double rr_p = medium_kind < 0 ? 0.0 : 0.8;
+    const V3 one(1, 1, 1), pos = v3(position);
+    for (uint64_t i = 0; i < n; i++) {
+        Rng rng(seed, uint32_t(i), 0);
+        const V3 wo = -normalize(v3(rds + 3 * i)), nrm = v3(normals + 3 * i);
+        V3 w(0, 0, 0), kk(0, 0, 0), f;
+        double p;
+        bool go;
+        if (medium_event) {
+            go = bounce_medium_sample(medium, wo, rr_p, rng, w, p);
+            if (go) kk = bounce_medium_weigh(medium, pos, wo, w, p, rr_p, one);
+        } else {
+            go = bounce_surface_sample(mat, nrm, wo, rr_p, depth, max_bounces, rng, w, p, f);
+            if (go) kk = bounce_surface_weigh(f, p, rr_p, w, nrm, one);
+            else w = V3(0, 0, 0);
+        }
+        cont[i] = go ? 1 : 0;
+        wi[3 * i] = w.x; wi[3 * i + 1] = w.y; wi[3 * i + 2] = w.z;
+        k[3 * i] = kk.x; k[3 * i + 1] = kk.y; k[3 * i + 2] = kk.z;
+        next_word[i] = rng.next();
+    }
+    return 0;
+}
 void orc_medium_sample_d(int kind, double absorption, double scattering, uint64_t seed, uint32_t pixel, uint32_t sample,
                          double* dist, double* pdf, double* cdf) {
     Medium m{kind, absorption, scattering};
@@ -1786,10 +1874,24 @@ void orc_camera_cast_ray(const orc_camera* c, double x, double y, uint64_t seed,
     d[0] = r.dir.x; d[1] = r.dir.y; d[2] = r.dir.z;
 }
 // Pixel -> NDC mapping of get_color (src/renderer.rs:174-176), KAT 13.
-void orc_pixel_ndc(uint32_t x, uint32_t y, uint32_t w, uint32_t h, double* xn, double* yn) {
-    double dim = double(std::max(w, h));
-    *xn = (double(2 * x + 1) - double(w)) / dim;
-    *yn = (double(2 * (h - y) - 1) - double(h)) / dim;
+void orc_pixel_ndc(uint32_t x, uint32_t y, uint32_t w, uint32_t h, double* xn, double* yn) { pixel_ndc(x, y, w, h, *xn, *yn); }
+// The camera sample of get_color for every pixel of a w x h frame and one sample index, pixel y * w + x on Rng(seed, pixel, sample):
+// pixel_ndc, the two jitter draws and Camera::cast_ray on that one stream; next_word = the stream's next word after cast_ray.
+void orc_camera_rays(const orc_camera* c, uint32_t w, uint32_t h, uint64_t seed, uint32_t sample, double* o, double* d,
+                     uint32_t* next_word) {
+    const Camera cam = make_camera(c);
+    const double dim = double(std::max(w, h));
+    for (uint32_t y = 0; y < h; y++)
+        for (uint32_t x = 0; x < w; x++) {
+            const size_t i = size_t(y) * w + x;
+            Rng rng(seed, uint32_t(i), sample);
+            double xn, yn;
+            pixel_ndc(x, y, w, h, xn, yn);
+            const Ray r = jittered_ray(cam, xn, yn, dim, rng);
+            o[3 * i] = r.origin.x; o[3 * i + 1] = r.origin.y; o[3 * i + 2] = r.origin.z;
+            d[3 * i] = r.dir.x; d[3 * i + 1] = r.dir.y; d[3 * i + 2] = r.dir.z;
+            next_word[i] = rng.next();
+        }
 }
 void orc_light_illuminate(orc_scene* s, int light_index, const double* pos, uint64_t seed, uint32_t pixel, uint32_t sample,
                           double* intensity, double* wi, double* dist) {

@@ -146,9 +146,22 @@ SYMBOLS = [
     ("rpt_debug_env_color", C.c_int, [_P, C.c_uint64, _P, _P]),
     ("rpt_debug_env_color_f64", C.c_int, [_P, C.c_uint64, _P, _P]),
     ("rpt_debug_medium_distance", C.c_int, [_P, C.c_uint64, C.c_uint64, _P, _P]),
+    ("rpt_debug_camera_sample", C.c_int,
+     [C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint64, C.c_uint32, _P, _P, _P]),
+    ("rpt_debug_camera_sample_f64", C.c_int,
+     [C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint64, C.c_uint32, _P, _P, _P]),
+    ("rpt_debug_bounce", C.c_int, [C.POINTER(MaterialDesc), C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_float, _P,
+                                   C.c_uint64, _P, _P, C.c_uint64, _P, _P, _P, _P]),
+    ("rpt_debug_material_f64", C.c_int, [C.POINTER(MaterialDesc), C.c_uint64, _P, _P, C.c_uint64, _P, _P, _P, _P, _P]),
+    ("rpt_debug_material_bsdf_f64", C.c_int, [C.POINTER(MaterialDesc), C.c_uint64, _P, _P, _P, _P]),
 ]
 
 _lib = None
+
+
+def vp(a):
+    """A numpy array's buffer as the void pointer the array arguments of both C ABIs (this library's and the oracle's) take."""
+    return a.ctypes.data_as(C.c_void_p)
 
 
 def load():

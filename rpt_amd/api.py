@@ -20,7 +20,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import RptError
+from ._lib import RptError, vp as _vp
 
 def shard_pixels(width, height, rank, count):
     """Pixel indices (y*width + x) owned by `rank` of `count` under the renderer's 32x32-tile
@@ -1012,3 +1012,67 @@ class Renderer:
         dmed, lim = np.empty(n, np.float32), np.empty(n, np.float32)
         _lib.check(lib.rpt_debug_medium_distance(h, n, seed, dmed.ctypes.data_as(C.c_void_p), lim.ctypes.data_as(C.c_void_p)))
         return dmed, lim
+
+
+# ---- per-call hooks that need no scene (rpt_debug_bounce, rpt_debug_material_f64, rpt_debug_material_bsdf_f64)
+def debug_bounce(material, normals, rds, max_bounces=3, depth=0, seed=0, in_medium=False, medium_event=False, albedo_med=0.0,
+                 medium_color=(0.0, 0.0, 0.0)):
+    """The render kernels' bounce stage (fp32 mode), case i on stream (seed, i, 0), at a surface of `material` with normal
+    normals[i] reached along rds[i], or at a medium point (medium_event) -> dict of flag (n, int32), wi, k (n, 3),
+    next_word (n, uint32)."""
+    nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    rd = np.ascontiguousarray(rds, dtype=np.float32).reshape(-1, 3)
+    n = nrm.shape[0]
+    if rd.shape[0] != n:
+        raise ValueError("normals and rds differ in length")
+    mcol = np.ascontiguousarray(medium_color, dtype=np.float32).reshape(3)
+    out = {"flag": np.empty(n, np.int32), "wi": np.empty((n, 3), np.float32), "k": np.empty((n, 3), np.float32),
+           "next_word": np.empty(n, np.uint32)}
+    md = material_desc(material, _lib.MaterialDesc)
+    _lib.check(_lib.load().rpt_debug_bounce(C.byref(md), max_bounces, depth, int(bool(in_medium)), int(bool(medium_event)),
+                                            float(albedo_med), _vp(mcol), n, _vp(nrm), _vp(rd), seed,
+                                            *[_vp(out[k]) for k in ("flag", "wi", "k", "next_word")]))
+    return out
+
+
+def debug_material_f64(material, normals, wos, seed=0):
+    """The reference-epsilon mode's sample_f, case i on stream (seed, i, 0), and its bsdf at the sampled direction -> dict of
+    some (n, int32), wi (n, 3), pdf (n), f (n, 3), next_word (n, uint32)."""
+    nrm = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+    wo = np.ascontiguousarray(wos, dtype=np.float64).reshape(-1, 3)
+    n = nrm.shape[0]
+    if wo.shape[0] != n:
+        raise ValueError("normals and wos differ in length")
+    out = {"some": np.empty(n, np.int32), "wi": np.empty((n, 3)), "pdf": np.empty(n), "f": np.empty((n, 3)),
+           "next_word": np.empty(n, np.uint32)}
+    md = material_desc(material, _lib.MaterialDesc)
+    _lib.check(_lib.load().rpt_debug_material_f64(C.byref(md), n, _vp(nrm), _vp(wo), seed,
+                                                  *[_vp(out[k]) for k in ("some", "wi", "pdf", "f", "next_word")]))
+    return out
+
+
+def debug_material_bsdf_f64(material, normals, wos, wis):
+    """The reference-epsilon mode's bsdf at given directions -> (n, 3)."""
+    arrs = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3) for a in (normals, wos, wis)]
+    n = arrs[0].shape[0]
+    if any(a.shape[0] != n for a in arrs):
+        raise ValueError("normals, wos and wis differ in length")
+    f = np.empty((n, 3))
+    md = material_desc(material, _lib.MaterialDesc)
+    _lib.check(_lib.load().rpt_debug_material_bsdf_f64(C.byref(md), n, *[_vp(a) for a in arrs], _vp(f)))
+    return f
+
+
+def debug_camera_sample(camera, width, height, sample=0, seed=0, f64=False):
+    """The camera sample of a render for every pixel of a width x height frame: pixel -> NDC, the two jitter draws and cast_ray
+    on stream (seed, pixel, sample), by the fp32 mode's functions or (f64) the reference-epsilon mode's -> dict of o, d (n, 3),
+    next_word (n, uint32), pixel y * width + x."""
+    ft = np.float64 if f64 else np.float32
+    n = width * height
+    out = {"o": np.empty((n, 3), ft), "d": np.empty((n, 3), ft), "next_word": np.empty(n, np.uint32)}
+    prm = _lib.RenderParams(width, height, 0.0, 0, 0, 1)
+    lib = _lib.load()
+    fn = lib.rpt_debug_camera_sample_f64 if f64 else lib.rpt_debug_camera_sample
+    _lib.check(fn(C.byref(camera_desc(camera, _lib.CameraDesc)), C.byref(prm), seed, sample,
+                  *[_vp(out[k]) for k in ("o", "d", "next_word")]))
+    return out

@@ -987,9 +987,11 @@ RPT_DEV float mat_emit(const Mat& m) { return (m.kind <= 1u) ? m.emit : 0.f; }  
 // Rotation taking +Y onto `b` applied to v (nalgebra rotation_between(+Y, b)): axis k =
 // normalize(Y x b), angle acos(b.y).  `pi_fallback_x`: Lambertian's (0,1,1e-8) retry
 // (src/material.rs:186-194) is a half-turn about +X; Phong's quat_rotation falls back to identity.
+// nalgebra rotates only when |Y x b| > f64::EPSILON = 2^-52 and falls back below that (sin(pi) = 1.2e-16 is below: a face
+// turned with rotate_z(pi)); the square of the threshold, 2^-104, is a normal fp32 number, so no denormal reaches rsq either.
 RPT_DEV V rotate_from_y(V b, V v, bool pi_fallback_x) {
     float s2 = fmaf(b.x, b.x, b.z * b.z);
-    if (s2 > 0.f) {
+    if (s2 > 0x1p-104f) {
         float is = rsq(s2);
         float s = s2 * is;           // sin(angle)
         float kx = b.z * is, kz = -b.x * is;  // k = (b.z, 0, -b.x)/s
@@ -1221,6 +1223,9 @@ RPT_DEV V env_color(const SceneView& scene_, V dir) {
 }
 
 // ------------------------------------------------------------------ camera
+// Pixel -> NDC of get_color, src/renderer.rs:174-176 (2 x + 1 and 2 (h - y) - 1 in u32, like the reference; inv_dim = 1 / max(w, h)).
+RPT_DEV float pixel_xn(uint32_t x, uint32_t w, float inv_dim) { return (float(2u * x + 1u) - float(w)) * inv_dim; }
+RPT_DEV float pixel_yn(uint32_t y, uint32_t h, float inv_dim) { return (float(2u * (h - y) - 1u) - float(h)) * inv_dim; }
 // Camera::cast_ray, src/camera.rs:65-82 (cot(fov/2)*direction and `right` hoisted to the host).
 RPT_DEV void cast_ray(const CameraG& c, float x, float y, Rng& rng, V& o, V& d) {
     V right = mk(c.right[0], c.right[1], c.right[2]), up = mk(c.up[0], c.up[1], c.up[2]);

@@ -163,6 +163,25 @@ struct DebugArgs64 {
     double *intensity, *wi, *dist;   // Light::illuminate: [3 n], [3 n], [n]; env_color: intensity = [3 n] colours
     uint32_t* next_word;        // [n]: the stream's next word after illuminate
 };
+// rpt_debug_material_f64 / rpt_debug_material_bsdf_f64 (kernels_f64.hip): sample_f and bsdf of one material, one case per lane.
+struct MaterialArgs64 {
+    Mat m;
+    uint64_t n, seed_mixed;
+    const double *nrm, *wo;     // [3 n] each
+    const double* wi_in;        // [3 n]: the bsdf hook's directions
+    int32_t* some;              // [n] sample_f's Some / None
+    double *wi, *pdf, *f;       // [3 n], [n], [3 n]: f = bsdf at the sampled wi (or at wi_in)
+    uint32_t* next_word;        // [n] the stream's next word after sample_f
+};
+// rpt_debug_camera_sample_f64 (kernels_f64.hip): one camera sample per pixel.
+struct CameraArgs64 {
+    Camera cam;
+    uint32_t width, height, sample, pad_;
+    double dim;                 // max(width, height)
+    uint64_t seed_mixed;
+    double *o, *d;              // [3 n] each, n = width * height
+    uint32_t* next_word;        // [n] the stream's next word after cast_ray
+};
 
 // ---- photon mapping in the reference-epsilon mode (kernels_f64.hip; the maps, the k-nearest selection and the volume estimates are
 // photon.hip's, on the records in fp32)

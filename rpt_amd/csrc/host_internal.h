@@ -9,7 +9,7 @@
 #include "../../include/rpt_hip.h"
 #include "kernels.h"
 
-namespace rpt64 { struct Args; }
+namespace rpt64 { struct Args; struct Camera; }
 
 namespace rpti {
 // One hipMalloc block and its byte capacity, freed when the owner is reset, reassigned or destroyed.  hipFree runs on the
@@ -99,6 +99,7 @@ struct SceneDev {
     bool has_monomial;       // some object is (or holds) a MonomialSurface: photon mapping refuses such scenes
 };
 SceneDev scene_dev(rpt_scene* s);
+void fill_camera64(const rpt_camera* cam, rpt64::Camera& q);   // the reference-epsilon mode's camera record (renders and rpt_debug_camera_sample_f64)
 int light_kind(rpt_scene* s, uint32_t light);   // kind of scene.lights[light] (0 point, 1 ambient, 2 directional, 3 object), -1: no such light
 void*& photon_slot(rpt_scene* s);  // owned by photon.hip (PhotonMapDev*), released through photon_release
 void photon_release(void* p);      // defined in photon.hip

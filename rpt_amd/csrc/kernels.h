@@ -77,8 +77,11 @@ hipError_t launch_debug_sample_f(const Material& m, uint64_t n, const float* d_n
                                  uint64_t seed_mixed, float* d_wi, float* d_pdf, int32_t* d_some, hipStream_t s);
 hipError_t launch_debug_bsdf(const Material& m, uint64_t n, const float* d_n, const float* d_wo, const float* d_wi,
                              float* d_out, hipStream_t s);
-hipError_t launch_debug_camera(const CameraG& cam, uint32_t w, uint32_t h, uint64_t seed_mixed, uint32_t sample,
-                               float* d_o, float* d_d, hipStream_t s);
+// rpt_debug_camera_rays / rpt_debug_camera_sample: the camera sample of a render, inv_dim as the host forms it, and the stream's next
+// word.  (Weak, like the hooks below.)
+__attribute__((weak)) hipError_t launch_debug_camera_sample(const CameraG& cam, uint32_t w, uint32_t h, float inv_dim, uint64_t seed_mixed,
+                                                            uint32_t sample, float* d_o, float* d_d, uint32_t* d_next_word /* or null */,
+                                                            hipStream_t s);
 // rpt_debug_light_sample / rpt_debug_env_color / rpt_debug_medium_distance: one call of the device function per lane on the committed
 // scene (device arrays).  (Weak, like launch_intersect_segments: the host-only harnesses do not know them.)
 struct LightSampleArgs {
@@ -95,6 +98,22 @@ __attribute__((weak)) hipError_t launch_debug_light_sample(const SceneView& sc, 
 __attribute__((weak)) hipError_t launch_debug_env_color(const SceneView& sc, uint64_t n, const float* d_dirs, float* d_rgb, hipStream_t s);
 __attribute__((weak)) hipError_t launch_debug_medium_distance(const SceneView& sc, uint64_t n, uint64_t seed_mixed, float* d_dmed,
                                                               float* d_limit, hipStream_t s);
+// rpt_debug_bounce: stage_bounce<MEDIUM, false> of the render kernels, one case per lane on stream (seed, lane, 0).
+struct BounceArgs {
+    Material m;
+    uint32_t max_bounces, depth;
+    uint32_t in_medium;       // the scene has a medium: the MEDIUM instantiation (roulette at surfaces, pdf * 0.8)
+    uint32_t medium_event;    // the vertex is a medium point (in_medium only)
+    float albedo_med;         // scattering / extinction
+    float mcol[3];            // Medium::color at the vertex
+    uint64_t n;
+    uint64_t seed_mixed;
+    const float *nrm, *rd;    // [3 n] surface normal, direction of the arriving ray (not normalised by the hook)
+    int32_t* flag;            // [n] stage_bounce's return value
+    float *wi, *k;            // [3 n] next direction and path weight (zero where the stage wrote none)
+    uint32_t* next_word;      // [n] the stream's next word after the stage
+};
+__attribute__((weak)) hipError_t launch_debug_bounce(const BounceArgs& q, hipStream_t s);
 
 }  // namespace rptg
 namespace rpt64 { struct Args; struct ShootArgs64; struct SurfArgs64; }

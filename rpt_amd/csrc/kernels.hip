@@ -487,8 +487,8 @@ void render_kernel(const RenderArgs a) {
                         stu(S_END, s_end_r, min(s0 + ka.chunk_spp, ka.iterations));
                         stu(S_PIX, pix_r, y * ka.width + x);
                         // src/renderer.rs:174-176
-                        stf(S_XN, xn_r, (float(2u * x + 1u) - float(ka.width)) * ka.inv_dim);
-                        stf(S_YN, yn_r, (float(2u * (ka.height - y) - 1u) - float(ka.height)) * ka.inv_dim);
+                        stf(S_XN, xn_r, pixel_xn(x, ka.width, ka.inv_dim));
+                        stf(S_YN, yn_r, pixel_yn(y, ka.height, ka.inv_dim));
                     }
                 }
             }
@@ -1496,21 +1496,24 @@ __global__ void debug_bsdf_kernel(const Material m, uint64_t n, const float* nrm
                mk(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]));
     out[3 * i] = f.x; out[3 * i + 1] = f.y; out[3 * i + 2] = f.z;
 }
-__global__ void debug_camera_kernel(const CameraG cam, uint32_t w, uint32_t h, uint64_t seed_mixed, uint32_t sample,
-                                    float* o, float* d) {
+// rpt_debug_camera_rays / rpt_debug_camera_sample: the camera sample of render_kernel for pixel i of a w x h frame -- its pixel_xn /
+// pixel_yn, its two jitter draws and cast_ray on stream (seed, i, sample), with inv_dim as the host forms it for a render.
+__global__ void debug_camera_kernel(const CameraG cam, uint32_t w, uint32_t h, float inv_dim, uint64_t seed_mixed, uint32_t sample,
+                                    float* o, float* d, uint32_t* next_word) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= w * h) return;
     uint32_t x = i % w, y = i / w;
-    float inv_dim = 1.f / float(max(w, h));
-    float xn = (float(2u * x + 1u) - float(w)) * inv_dim;
-    float yn = (float(2u * (h - y) - 1u) - float(h)) * inv_dim;
+    float xn = pixel_xn(x, w, inv_dim);
+    float yn = pixel_yn(y, h, inv_dim);
     Rng r;
     r.seed(seed_mixed, i, sample);
-    float dx = r.range(-inv_dim, inv_dim), dy = r.range(-inv_dim, inv_dim);
+    float dx = r.range(-inv_dim, inv_dim);
+    float dy = r.range(-inv_dim, inv_dim);
     V ro, rd;
     cast_ray(cam, xn + dx, yn + dy, r, ro, rd);
     o[3 * i] = ro.x; o[3 * i + 1] = ro.y; o[3 * i + 2] = ro.z;
     d[3 * i] = rd.x; d[3 * i + 1] = rd.y; d[3 * i + 2] = rd.z;
+    if (next_word) next_word[i] = r.next();
 }
 // rpt_debug_light_sample: Shape::sample and Light::illuminate of one Light::Object, one position per lane, through the functions and
 // the kernel flavour the render kernels use: GROUPS as launch_render_t chooses it, and the light-triangle table staged in LDS under
@@ -1564,6 +1567,23 @@ __global__ __launch_bounds__(256) void debug_medium_distance_kernel(const SceneV
     stage_distance<true>(r, inv_sigma_t, d, t);
     dmed[i] = d;
     limit[i] = t;
+}
+// rpt_debug_bounce: the render kernels' own stage_bounce at a surface or a medium event.  Of the RenderArgs the stage reads
+// max_bounces alone (COUNT = false: no counters); they stay the first parameter as in render_kernel.
+template <bool MEDIUM>
+__global__ __launch_bounds__(256) void debug_bounce_kernel(const RenderArgs a, const BounceArgs q) {
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= q.n) return;
+    Rng r;
+    r.seed(q.seed_mixed, uint32_t(i), 0);
+    V wi = mk(0.f, 0.f, 0.f), k = mk(0.f, 0.f, 0.f);
+    const bool go = stage_bounce<MEDIUM, false>(a, q.albedo_med, mk(q.rd[3 * i], q.rd[3 * i + 1], q.rd[3 * i + 2]), q.depth,
+                                                MEDIUM && q.medium_event != 0u, mk(q.nrm[3 * i], q.nrm[3 * i + 1], q.nrm[3 * i + 2]),
+                                                mk(q.mcol[0], q.mcol[1], q.mcol[2]), mat_from(q.m), r, wi, k);
+    q.flag[i] = go ? 1 : 0;
+    q.wi[3 * i] = wi.x; q.wi[3 * i + 1] = wi.y; q.wi[3 * i + 2] = wi.z;
+    q.k[3 * i] = k.x; q.k[3 * i + 1] = k.y; q.k[3 * i + 2] = k.z;
+    q.next_word[i] = r.next();
 }
 
 // ------------------------------------------------------------------ launchers
@@ -1695,9 +1715,10 @@ hipError_t launch_debug_bsdf(const Material& m, uint64_t n, const float* d_n, co
     hipLaunchKernelGGL(debug_bsdf_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, s, m, n, d_n, d_wo, d_wi, d_out);
     return hipGetLastError();
 }
-hipError_t launch_debug_camera(const CameraG& cam, uint32_t w, uint32_t h, uint64_t seed_mixed, uint32_t sample,
-                               float* d_o, float* d_d, hipStream_t s) {
-    hipLaunchKernelGGL(debug_camera_kernel, dim3((w * h + 255) / 256), dim3(256), 0, s, cam, w, h, seed_mixed, sample, d_o, d_d);
+hipError_t launch_debug_camera_sample(const CameraG& cam, uint32_t w, uint32_t h, float inv_dim, uint64_t seed_mixed, uint32_t sample,
+                                      float* d_o, float* d_d, uint32_t* d_next_word, hipStream_t s) {
+    hipLaunchKernelGGL(debug_camera_kernel, dim3((w * h + 255) / 256), dim3(256), 0, s, cam, w, h, inv_dim, seed_mixed, sample, d_o, d_d,
+                       d_next_word);
     return hipGetLastError();
 }
 hipError_t launch_debug_light_sample(const SceneView& sc, const LightSampleArgs& q, hipStream_t s) {
@@ -1713,6 +1734,14 @@ hipError_t launch_debug_env_color(const SceneView& sc, uint64_t n, const float* 
 hipError_t launch_debug_medium_distance(const SceneView& sc, uint64_t n, uint64_t seed_mixed, float* d_dmed, float* d_limit,
                                         hipStream_t s) {
     hipLaunchKernelGGL(debug_medium_distance_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, s, sc, n, seed_mixed, d_dmed, d_limit);
+    return hipGetLastError();
+}
+hipError_t launch_debug_bounce(const BounceArgs& q, hipStream_t s) {
+    RenderArgs a{};   // (stage_bounce reads max_bounces only)
+    a.max_bounces = q.max_bounces;
+    const dim3 grid(uint32_t((q.n + 255) / 256));
+    if (q.in_medium) hipLaunchKernelGGL(debug_bounce_kernel<true>, grid, dim3(256), 0, s, a, q);
+    else hipLaunchKernelGGL(debug_bounce_kernel<false>, grid, dim3(256), 0, s, a, q);
     return hipGetLastError();
 }
 

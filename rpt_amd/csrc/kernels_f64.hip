@@ -673,22 +673,39 @@ R64_DEV void illuminate_object(const LT& L, D pos, Rng64& rng, D& intensity, D& 
 R64_DEV D mat_color(const Mat& m) { return m.kind <= 1 ? ld(m.albedo) : mk(0, 0, 0); }
 R64_DEV double mat_emit(const Mat& m) { return m.kind <= 1 ? m.emittance : 0.0; }
 // nalgebra Rotation3::rotation_between(+Y, b) applied to v: axis normalize(Y x b), angle acos(Y.b); when the axis
-// vanishes: identity if Y.b >= 0, else `None` -- Lambertian then retries from (0, 1, 1e-8), a half-turn about +X
-// (src/material.rs:186-194); glm::quat_rotation (Phong, :213) falls back to the identity.
+// vanishes (|Y x b| <= f64::EPSILON): identity if Y.b >= 0, else `None` -- Lambertian then retries from (0, 1, 1e-8), all but a half-turn
+// about +X (src/material.rs:186-194); glm::quat_rotation (Phong, :213) falls back to the identity.
 R64_DEV D rotate_from_y(D b, D v, bool pi_fallback_x) {
     const double s2 = b.x * b.x + b.z * b.z;
-    if (s2 > 0.0) {
-        const double s = sqrt(s2);
+    const double s = sqrt(s2);
+    if (s > 2.220446049250313e-16) {
         const double kx = b.z / s, kz = -b.x / s;   // k = Y x b / |Y x b| = (b.z, 0, -b.x) / s
         const double kv = kx * v.x + kz * v.z;
         const D kxv = mk(-kz * v.y, kz * v.x - kx * v.z, kx * v.y);
-        const double c = b.y, omc = 1.0 - c;
-        return mk(c * v.x + s * kxv.x + omc * kv * kx, c * v.y + s * kxv.y, c * v.z + s * kxv.z + omc * kv * kz);
+        // from_axis_angle(k, acos(Y.b)), as nalgebra forms it: for b next to +-Y the angle that acos returns is off by up to 1e-9
+        // of the true one (cos is flat there), and the reference's directions are the ones of that angle
+        const double ang = acos(b.y);
+        const double sn = sin(ang), c = cos(ang), omc = 1.0 - c;
+        return mk(c * v.x + sn * kxv.x + omc * kv * kx, c * v.y + sn * kxv.y, c * v.z + sn * kxv.z + omc * kv * kz);
     }
-    if (b.y < 0.0 && pi_fallback_x) return mk(v.x, -v.y, -v.z);
+    if (b.y < 0.0 && pi_fallback_x) {
+        // Lambertian's retry, rotation_between((0, 1, 1e-8), b), as nalgebra performs it: the axis is X to 1e-8 and the angle
+        // pi - 1e-8, so a plain half-turn about +X would be 2e-8 off
+        const D a = mk(0.0, 1.0, 0.00000001);
+        const D na = a / length(a);   // (b is normalised by the caller, once, as the reference normalises it)
+        const D c = cross(na, b);
+        const double lc = length(c);
+        if (lc > 2.220446049250313e-16) {
+            const D k = c / lc;
+            const double ang = acos(dot(na, b));
+            const double sn = sin(ang), co = cos(ang);
+            return co * v + sn * cross(k, v) + ((1.0 - co) * dot(k, v)) * k;
+        }
+    }
     return v;
 }
-R64_DEV D reflect_neg(D w, D n) { return (2.0 * dot(n, w)) * n - w; }   // -glm::reflect_vec(w, n)
+// -glm::reflect_vec(w, n), negated as the reference negates it: (2 n.w) n - w would give +0 where this gives -0, and bsdf asks for the sign
+R64_DEV D reflect_neg(D w, D n) { return -(w - (2.0 * dot(n, w)) * n); }
 // Material::sample_f, src/material.rs:166-263
 R64_DEV bool sample_f(const Mat& m, D n, D wo, Rng64& rng, D& wi, double& pdf) {
     if (m.kind == 0) {
@@ -771,6 +788,9 @@ R64_DEV D env_color(D dir_in) {
 R64_DEV D medium_color(D pos) {
     return (KA.sc.medium_kind == 1 && pos.y > 250.0) ? ld(KA.medium_color_hi) : ld(KA.medium_color);
 }
+// Pixel -> NDC of get_color, src/renderer.rs:174-176 (2 * x + 1 and 2 * (h - y) - 1 in u32, like the reference)
+R64_DEV double pixel_xn(uint32_t x, uint32_t w, double dim) { return (double(2u * x + 1u) - double(w)) / dim; }
+R64_DEV double pixel_yn(uint32_t y, uint32_t h, double dim) { return (double(2u * (h - y) - 1u) - double(h)) / dim; }
 // Camera::cast_ray, src/camera.rs:65-82
 template <class CP>
 R64_DEV void cast_ray(const CP& c, double x, double y, Rng64& rng, D& o, D& d) {
@@ -909,10 +929,9 @@ __global__ __launch_bounds__(256, R64_WAVES) void render_f64_kernel(const Args a
             const auto& ka = KA;
             const uint32_t s = cu[U_S * 256], xy = cu[U_XY * 256], x = xy & 0xFFFFu, y = xy >> 16;
             rng.r.seed(ka.seed_mixed, y * ka.width + x, ka.sample_offset + s);
-            // (2 * x + 1 and 2 * (h - y) - 1 in u32, like the reference)
             const double dim = ka.dim;
-            const double xn = (double(2u * x + 1u) - double(ka.width)) / dim;
-            const double yn = (double(2u * (ka.height - y) - 1u) - double(ka.height)) / dim;
+            const double xn = pixel_xn(x, ka.width, dim);
+            const double yn = pixel_yn(y, ka.height, dim);
             const double dx = rng.range(-1.0 / dim, 1.0 / dim);
             const double dy = rng.range(-1.0 / dim, 1.0 / dim);
             cast_ray(ka.cam, xn + dx, yn + dy, rng, ro, rd);
@@ -1361,8 +1380,8 @@ __global__ __launch_bounds__(256, R64_WAVES) void photon_surface_f64_kernel(cons
         Rng64 rng;
         rng.r.seed(KA.seed_mixed, y * KA.width + x, KA.sample_offset + s);
         const double dim = KA.dim;
-        const double xn = (double(2u * x + 1u) - double(KA.width)) / dim;            // src/renderer.rs:174-176
-        const double yn = (double(2u * (KA.height - y) - 1u) - double(KA.height)) / dim;
+        const double xn = pixel_xn(x, KA.width, dim);            // src/renderer.rs:174-176
+        const double yn = pixel_yn(y, KA.height, dim);
         const double dx = rng.range(-1.0 / dim, 1.0 / dim);
         const double dy = rng.range(-1.0 / dim, 1.0 / dim);
         D ro, rd;
@@ -1535,6 +1554,48 @@ __global__ __launch_bounds__(256) void debug_env_color_f64_kernel(const DebugArg
     KD.intensity[3 * i] = c.x; KD.intensity[3 * i + 1] = c.y; KD.intensity[3 * i + 2] = c.z;
 }
 #undef KD
+// rpt_debug_material_f64: this mode's sample_f on stream (seed, lane, 0), then its bsdf at the sampled direction;
+// rpt_debug_material_bsdf_f64: bsdf at a given one.  Neither reads the scene.
+__global__ __launch_bounds__(256) void debug_material_f64_kernel(const MaterialArgs64 q) {
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= q.n) return;
+    const D n = mk(q.nrm[3 * i], q.nrm[3 * i + 1], q.nrm[3 * i + 2]), wo = mk(q.wo[3 * i], q.wo[3 * i + 1], q.wo[3 * i + 2]);
+    D wi = mk(0, 0, 0), f = mk(0, 0, 0);
+    if (q.wi_in) {
+        f = bsdf(q.m, n, wo, mk(q.wi_in[3 * i], q.wi_in[3 * i + 1], q.wi_in[3 * i + 2]));
+    } else {
+        Rng64 rng;
+        rng.r.seed(q.seed_mixed, uint32_t(i), 0);
+        double pdf = 0.0;
+        const bool some = sample_f(q.m, n, wo, rng, wi, pdf);
+        if (some) f = bsdf(q.m, n, wo, wi);
+        else pdf = 0.0;
+        q.some[i] = some ? 1 : 0;
+        q.wi[3 * i] = wi.x; q.wi[3 * i + 1] = wi.y; q.wi[3 * i + 2] = wi.z;
+        q.pdf[i] = pdf;
+        q.next_word[i] = rng.r.next();
+    }
+    q.f[3 * i] = f.x; q.f[3 * i + 1] = f.y; q.f[3 * i + 2] = f.z;
+}
+// rpt_debug_camera_sample_f64: the camera sample of render_f64_kernel for pixel i of a w x h frame -- pixel_xn / pixel_yn, the two
+// jitter draws and cast_ray on stream (seed, i, sample).
+__global__ __launch_bounds__(256) void debug_camera_f64_kernel(const CameraArgs64 q) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= q.width * q.height) return;
+    const uint32_t x = i % q.width, y = i / q.width;
+    Rng64 rng;
+    rng.r.seed(q.seed_mixed, y * q.width + x, q.sample);
+    const double dim = q.dim;
+    const double xn = pixel_xn(x, q.width, dim);
+    const double yn = pixel_yn(y, q.height, dim);
+    const double dx = rng.range(-1.0 / dim, 1.0 / dim);
+    const double dy = rng.range(-1.0 / dim, 1.0 / dim);
+    D ro, rd;
+    cast_ray(q.cam, xn + dx, yn + dy, rng, ro, rd);
+    q.o[3 * i] = ro.x; q.o[3 * i + 1] = ro.y; q.o[3 * i + 2] = ro.z;
+    q.d[3 * i] = rd.x; q.d[3 * i + 1] = rd.y; q.d[3 * i + 2] = rd.z;
+    q.next_word[i] = rng.r.next();
+}
 
 }  // namespace rpt64
 
@@ -1721,5 +1782,92 @@ extern "C" int rpt_debug_env_color_f64(rpt_scene* s, uint64_t n, const double* d
     hipLaunchKernelGGL(rpt64::debug_env_color_f64_kernel, dim3(uint32_t((n + 255u) / 256u)), dim3(256), 0, nullptr, q);
     RPTI_HIP_TRY(hipGetLastError());
     RPTI_HIP_TRY(hipMemcpy(rgb, d_c.get(), n * 24, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+static int material64(const rpt_material* m, rpt64::Mat& o) {
+    if (!m || m->kind < 0 || m->kind > RPT_MAT_TRANSMISSIVE) return rpti::fail(RPT_ERR_INVALID, "null material or unknown material kind");
+    std::memset(&o, 0, sizeof(o));
+    o.kind = m->kind;
+    for (int i = 0; i < 3; i++) o.albedo[i] = m->albedo[i];
+    o.emittance = m->emittance;
+    o.shininess = m->shininess;
+    o.ior = m->ior;
+    return RPT_OK;
+}
+extern "C" int rpt_debug_material_f64(const rpt_material* m, uint64_t n, const double* normals, const double* wos, uint64_t seed,
+                                      int32_t* some, double* wi, double* pdf, double* f, uint32_t* next_word) {
+    rpt64::MaterialArgs64 q;
+    std::memset(&q, 0, sizeof(q));
+    if (const int rc = material64(m, q.m)) return rc;
+    if (!normals || !wos || !some || !wi || !pdf || !f || !next_word) return rpti::fail(RPT_ERR_INVALID, "null argument");
+    if (n > 0xFFFFFFFFull) return rpti::fail(RPT_ERR_INVALID, "rpt_debug_material_f64: the case number keys a 32-bit stream field");
+    if (n == 0) return RPT_OK;
+    rpti::DevMem d_in, d_out;   // d_in: normals, wos (3 n each); d_out: wi, f (3 n each), pdf (n), some, next_word (n dwords each)
+    RPTI_HIP_TRY(d_in.reserve(n * 48));
+    RPTI_HIP_TRY(d_out.reserve(n * (7 * 8 + 8)));
+    double* const in = d_in.get<double>();
+    double* const o = d_out.get<double>();
+    RPTI_HIP_TRY(hipMemcpy(in, normals, n * 24, hipMemcpyHostToDevice));
+    RPTI_HIP_TRY(hipMemcpy(in + 3 * n, wos, n * 24, hipMemcpyHostToDevice));
+    q.n = n;
+    q.seed_mixed = rpti::seed_mix(seed);
+    q.nrm = in; q.wo = in + 3 * n;
+    q.wi = o; q.f = o + 3 * n; q.pdf = o + 6 * n;
+    q.some = reinterpret_cast<int32_t*>(o + 7 * n);
+    q.next_word = reinterpret_cast<uint32_t*>(o + 7 * n) + n;
+    hipLaunchKernelGGL(rpt64::debug_material_f64_kernel, dim3(uint32_t((n + 255u) / 256u)), dim3(256), 0, nullptr, q);
+    RPTI_HIP_TRY(hipGetLastError());
+    RPTI_HIP_TRY(hipMemcpy(wi, q.wi, n * 24, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(f, q.f, n * 24, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(pdf, q.pdf, n * 8, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(some, q.some, n * 4, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(next_word, q.next_word, n * 4, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+extern "C" int rpt_debug_material_bsdf_f64(const rpt_material* m, uint64_t n, const double* normals, const double* wos,
+                                           const double* wis, double* f) {
+    rpt64::MaterialArgs64 q;
+    std::memset(&q, 0, sizeof(q));
+    if (const int rc = material64(m, q.m)) return rc;
+    if (!normals || !wos || !wis || !f) return rpti::fail(RPT_ERR_INVALID, "null argument");
+    if (n == 0) return RPT_OK;
+    rpti::DevMem d_in, d_out;   // d_in: normals, wos, wis
+    RPTI_HIP_TRY(d_in.reserve(n * 72));
+    RPTI_HIP_TRY(d_out.reserve(n * 24));
+    double* const in = d_in.get<double>();
+    RPTI_HIP_TRY(hipMemcpy(in, normals, n * 24, hipMemcpyHostToDevice));
+    RPTI_HIP_TRY(hipMemcpy(in + 3 * n, wos, n * 24, hipMemcpyHostToDevice));
+    RPTI_HIP_TRY(hipMemcpy(in + 6 * n, wis, n * 24, hipMemcpyHostToDevice));
+    q.n = n;
+    q.nrm = in; q.wo = in + 3 * n; q.wi_in = in + 6 * n;
+    q.f = d_out.get<double>();
+    hipLaunchKernelGGL(rpt64::debug_material_f64_kernel, dim3(uint32_t((n + 255u) / 256u)), dim3(256), 0, nullptr, q);
+    RPTI_HIP_TRY(hipGetLastError());
+    RPTI_HIP_TRY(hipMemcpy(f, q.f, n * 24, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+extern "C" int rpt_debug_camera_sample_f64(const rpt_camera* cam, const rpt_render_params* prm, uint64_t seed, uint32_t sample,
+                                           double* origins, double* dirs, uint32_t* next_word) {
+    if (!cam || !prm || !origins || !dirs || !next_word) return rpti::fail(RPT_ERR_INVALID, "null argument");
+    if (prm->width == 0 || prm->height == 0) return rpti::fail(RPT_ERR_INVALID, "empty frame");
+    if (uint64_t(prm->width) * prm->height > (1ull << 31)) return rpti::fail(RPT_ERR_INVALID, "image too large");
+    const size_t n = size_t(prm->width) * prm->height;
+    rpti::DevMem d_out;   // origins, dirs (3 n each), next_word (n dwords)
+    RPTI_HIP_TRY(d_out.reserve(n * 52));
+    rpt64::CameraArgs64 q;
+    std::memset(&q, 0, sizeof(q));
+    rpti::fill_camera64(cam, q.cam);
+    q.width = prm->width; q.height = prm->height;
+    q.sample = sample;
+    q.dim = double(std::max(prm->width, prm->height));   // (as fill_args64)
+    q.seed_mixed = rpti::seed_mix(seed);
+    q.o = d_out.get<double>(); q.d = q.o + 3 * n;
+    q.next_word = reinterpret_cast<uint32_t*>(q.o + 6 * n);
+    hipLaunchKernelGGL(rpt64::debug_camera_f64_kernel, dim3(uint32_t((n + 255u) / 256u)), dim3(256), 0, nullptr, q);
+    RPTI_HIP_TRY(hipGetLastError());
+    RPTI_HIP_TRY(hipMemcpy(origins, q.o, n * 24, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(dirs, q.d, n * 24, hipMemcpyDeviceToHost));
+    RPTI_HIP_TRY(hipMemcpy(next_word, q.next_word, n * 4, hipMemcpyDeviceToHost));
     return RPT_OK;
 }

@@ -1734,8 +1734,8 @@ __global__ __launch_bounds__(256, RPT_MIN_WAVES_QUERY) void photon_query_kernel(
         pi++;
         if (px >= a.width || py >= a.height) continue;  // slots of clipped tiles lie outside the image (wave-uniform)
         const uint32_t pix = py * a.width + px;
-        const float xn = (float(2u * px + 1u) - float(a.width)) * a.inv_dim;           // src/renderer.rs:174-176
-        const float yn = (float(2u * (a.height - py) - 1u) - float(a.height)) * a.inv_dim;
+        const float xn = pixel_xn(px, a.width, a.inv_dim);           // src/renderer.rs:174-176
+        const float yn = pixel_yn(py, a.height, a.inv_dim);
         const uint32_t n_sub = (n_s + 63u) >> 6;   // trips of 64 samples
         // camera ray of sample (chunk, sub, lane) and its closest hit
         auto gen_ray = [&](uint32_t sub, Rng& rng, V& ro, V& rd, float& tmin, float& t, uint32_t& code, uint32_t& inst) {

@@ -2149,19 +2149,7 @@ extern "C++" void rpti::fill_args64(rpt_scene* s, const rpt_camera* cam, const r
     q.mono = 0u;
     for (const auto& o : s->objects)
         if (holds_monomial(o.shape)) q.mono = 1u;
-    if (cam) {
-        const D3 dir = d3(cam->direction), up = d3(cam->up);
-        const D3 right = normalize(cross(dir, up));   // src/camera.rs:67-68
-        for (int i = 0; i < 3; i++) {
-            q.cam.eye[i] = cam->eye[i];
-            q.cam.direction[i] = cam->direction[i];
-            q.cam.up[i] = cam->up[i];
-            q.cam.right[i] = comp(right, i);
-        }
-        q.cam.d = 1.0 / std::tan(cam->fov / 2.0);
-        q.cam.aperture = cam->aperture;
-        q.cam.focal_distance = cam->focal_distance;
-    }
+    if (cam) fill_camera64(cam, q.cam);
     if (prm) {
         q.width = prm->width; q.height = prm->height;
         q.max_bounces = prm->max_bounces;
@@ -2296,6 +2284,38 @@ int rpt_scene_render_chunking(rpt_scene* s, uint32_t iterations, uint32_t* chunk
     return RPT_OK;
 }
 
+// Camera::cast_ray constants (src/camera.rs:66-69), fp64 then rounded once; 1 / max(width, height) of the pixel -> NDC mapping.
+// (Renders and the camera hooks form them here.)
+static CameraG camera_g(const rpt_camera* cam) {
+    CameraG c;
+    D3 dir = d3(cam->direction), up = d3(cam->up);
+    double dd = 1.0 / std::tan(cam->fov / 2.0);
+    D3 right = normalize(cross(dir, up));
+    for (int i = 0; i < 3; i++) {
+        c.eye[i] = float(cam->eye[i]);
+        c.ddir[i] = float(dd * cam->direction[i]);
+        c.right[i] = float(comp(right, i));
+        c.up[i] = float(cam->up[i]);
+    }
+    c.aperture = float(cam->aperture);
+    c.focal_distance = float(cam->focal_distance);
+    return c;
+}
+static float inv_dim_of(const rpt_render_params* prm) { return float(1.0 / double(std::max(prm->width, prm->height))); }
+extern "C++" void rpti::fill_camera64(const rpt_camera* cam, rpt64::Camera& q) {
+    const D3 dir = d3(cam->direction), up = d3(cam->up);
+    const D3 right = normalize(cross(dir, up));   // src/camera.rs:67-68
+    for (int i = 0; i < 3; i++) {
+        q.eye[i] = cam->eye[i];
+        q.direction[i] = cam->direction[i];
+        q.up[i] = cam->up[i];
+        q.right[i] = comp(right, i);
+    }
+    q.d = 1.0 / std::tan(cam->fov / 2.0);
+    q.aperture = cam->aperture;
+    q.focal_distance = cam->focal_distance;
+}
+
 extern "C++" int rpti::prepare_render(rpt_scene* s, hipStream_t st, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations,
                          uint64_t seed, uint32_t sample_offset, RenderArgs& a, uint32_t min_chunk, uint32_t fixed_chunk, uint32_t slab_item_bytes) {
     if (!s || !cam || !prm) return fail(RPT_ERR_INVALID, "null argument");
@@ -2307,21 +2327,10 @@ extern "C++" int rpti::prepare_render(rpt_scene* s, hipStream_t st, const rpt_ca
     HIP_TRY(hipSetDevice(s->device));
 
     a.sc = s->view;
-    // Camera::cast_ray constants (src/camera.rs:66-69), fp64 then rounded once
-    D3 dir = d3(cam->direction), up = d3(cam->up);
-    double dd = 1.0 / std::tan(cam->fov / 2.0);
-    D3 right = normalize(cross(dir, up));
-    for (int i = 0; i < 3; i++) {
-        a.cam.eye[i] = float(cam->eye[i]);
-        a.cam.ddir[i] = float(dd * cam->direction[i]);
-        a.cam.right[i] = float(comp(right, i));
-        a.cam.up[i] = float(cam->up[i]);
-    }
-    a.cam.aperture = float(cam->aperture);
-    a.cam.focal_distance = float(cam->focal_distance);
+    a.cam = camera_g(cam);
     a.width = prm->width;
     a.height = prm->height;
-    a.inv_dim = float(1.0 / double(std::max(prm->width, prm->height)));
+    a.inv_dim = inv_dim_of(prm);
     a.max_bounces = prm->max_bounces;
     a.iterations = iterations;
     a.sample_offset = sample_offset;
@@ -2805,29 +2814,27 @@ int rpt_debug_material_bsdf(const rpt_material* m, uint64_t n, const float* norm
     HIP_TRY(hipMemcpy(out_rgb, d_out.get(), n * 12, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
-int rpt_debug_camera_rays(const rpt_camera* cam, const rpt_render_params* prm, uint64_t seed, uint32_t sample,
-                          float* origins, float* dirs) {
+int rpt_debug_camera_sample(const rpt_camera* cam, const rpt_render_params* prm, uint64_t seed, uint32_t sample,
+                            float* origins, float* dirs, uint32_t* next_word) {
     if (!cam || !prm || !origins || !dirs) return fail(RPT_ERR_INVALID, "null argument");
-    CameraG c;
-    D3 dir = d3(cam->direction), up = d3(cam->up);
-    double dd = 1.0 / std::tan(cam->fov / 2.0);
-    D3 right = normalize(cross(dir, up));
-    for (int i = 0; i < 3; i++) {
-        c.eye[i] = float(cam->eye[i]);
-        c.ddir[i] = float(dd * cam->direction[i]);
-        c.right[i] = float(comp(right, i));
-        c.up[i] = float(cam->up[i]);
-    }
-    c.aperture = float(cam->aperture);
-    c.focal_distance = float(cam->focal_distance);
-    size_t n = size_t(prm->width) * prm->height;
-    rpti::DevMem d_o, d_d;
+    if (prm->width == 0 || prm->height == 0) return fail(RPT_ERR_INVALID, "empty frame");
+    if (uint64_t(prm->width) * prm->height > (1ull << 31)) return fail(RPT_ERR_INVALID, "image too large");
+    if (!launch_debug_camera_sample) return fail(RPT_ERR_UNSUPPORTED, "rpt_debug_camera_sample: built without the kernels");
+    const size_t n = size_t(prm->width) * prm->height;
+    rpti::DevMem d_o, d_d, d_w;
     HIP_TRY(hook_scratch(d_o, n * 12));
     HIP_TRY(hook_scratch(d_d, n * 12));
-    HIP_TRY(launch_debug_camera(c, prm->width, prm->height, seed_mix(seed), sample, d_o.get<float>(), d_d.get<float>(), nullptr));
+    if (next_word) HIP_TRY(hook_scratch(d_w, n * 4));
+    HIP_TRY(launch_debug_camera_sample(camera_g(cam), prm->width, prm->height, inv_dim_of(prm), seed_mix(seed), sample, d_o.get<float>(),
+                                       d_d.get<float>(), next_word ? d_w.get<uint32_t>() : nullptr, nullptr));
     HIP_TRY(hipMemcpy(origins, d_o.get(), n * 12, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(dirs, d_d.get(), n * 12, hipMemcpyDeviceToHost));
+    if (next_word) HIP_TRY(hipMemcpy(next_word, d_w.get(), n * 4, hipMemcpyDeviceToHost));
     return RPT_OK;
+}
+int rpt_debug_camera_rays(const rpt_camera* cam, const rpt_render_params* prm, uint64_t seed, uint32_t sample,
+                          float* origins, float* dirs) {
+    return rpt_debug_camera_sample(cam, prm, seed, sample, origins, dirs, nullptr);   // (same kernel, same argument checks)
 }
 // The per-call hooks on a committed scene.  What the caller got wrong (null arrays, the light's kind, a scene without a medium) is
 // reported before the scene's state, so those answers need no device.
@@ -2895,6 +2902,46 @@ int rpt_debug_medium_distance(rpt_scene* s, uint64_t n, uint64_t seed, float* dm
     HIP_TRY(launch_debug_medium_distance(s->view, n, seed_mix(seed), d_m.get<float>(), d_t.get<float>(), nullptr));
     HIP_TRY(hipMemcpy(dmed, d_m.get(), n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(t_limit, d_t.get(), n * 4, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+// stage_bounce on a material descriptor: needs no scene.  (The medium enters through its albedo and colour alone.)
+int rpt_debug_bounce(const rpt_material* m, uint32_t max_bounces, uint32_t depth, int32_t in_medium, int32_t medium_event,
+                     float albedo_med, const float* medium_color, uint64_t n, const float* normals, const float* rds, uint64_t seed,
+                     int32_t* flag, float* wi, float* k, uint32_t* next_word) {
+    std::string why;
+    if (!check_material(m, why)) return fail(RPT_ERR_INVALID, why);
+    if (!medium_color || !normals || !rds || !flag || !wi || !k || !next_word) return fail(RPT_ERR_INVALID, "null argument");
+    if (medium_event && !in_medium) return fail(RPT_ERR_INVALID, "rpt_debug_bounce: a medium event needs in_medium");
+    if (n > 0xFFFFFFFFull) return fail(RPT_ERR_INVALID, "rpt_debug_bounce: the case number keys a 32-bit stream field");
+    if (!launch_debug_bounce) return fail(RPT_ERR_UNSUPPORTED, "rpt_debug_bounce: built without the kernels");
+    if (n == 0) return RPT_OK;
+    rpti::DevMem d_in, d_out;   // d_in: normals, rds (3 n each); d_out: wi, k (3 n each), flag, next_word (n each)
+    HIP_TRY(hook_scratch(d_in, n * 24));
+    HIP_TRY(hook_scratch(d_out, n * 32));
+    float* const in = d_in.get<float>();
+    float* const o = d_out.get<float>();
+    HIP_TRY(hipMemcpy(in, normals, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(in + 3 * n, rds, n * 12, hipMemcpyHostToDevice));
+    BounceArgs q{};
+    q.m = to_gpu_material(m);
+    q.max_bounces = max_bounces;
+    q.depth = depth;
+    q.in_medium = in_medium ? 1u : 0u;
+    q.medium_event = medium_event ? 1u : 0u;
+    q.albedo_med = albedo_med;
+    for (int i = 0; i < 3; i++) q.mcol[i] = medium_color[i];
+    q.n = n;
+    q.seed_mixed = seed_mix(seed);
+    q.nrm = in; q.rd = in + 3 * n;
+    q.wi = o; q.k = o + 3 * n;
+    q.flag = reinterpret_cast<int32_t*>(o + 6 * n);
+    q.next_word = reinterpret_cast<uint32_t*>(o + 7 * n);
+    HIP_TRY(launch_debug_bounce(q, nullptr));
+    HIP_TRY(hipMemcpy(wi, q.wi, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(k, q.k, n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flag, q.flag, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(next_word, q.next_word, n * 4, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 

@@ -159,3 +159,52 @@ def test_per_call_hooks_validate_their_arguments_without_a_gpu():
         assert lib.rpt_debug_medium_distance(h, 1, 0, p, p) == -2 and b"commit" in lib.rpt_last_error()
     finally:
         lib.rpt_scene_destroy(h)
+
+
+def test_material_bounce_and_camera_hooks_validate_their_arguments_without_a_gpu():
+    """rpt_debug_bounce, rpt_debug_material_f64, rpt_debug_material_bsdf_f64, rpt_debug_camera_sample(_f64): a null array, a null
+    material or one of an unknown kind, a medium event without a medium, an empty frame are RPT_ERR_INVALID (-1), said before
+    anything is launched; n = 0 is RPT_OK and launches nothing either.  (None of them reads a scene, so there is no mode to refuse.)"""
+    from rpt_amd.api import camera_desc
+    from rpt_amd import Camera
+    lib = _lib.load()
+    md = material_desc(Material.diffuse(vec3(0.5, 0.5, 0.5)), _lib.MaterialDesc)
+    bad = material_desc(Material.diffuse(vec3(0.5, 0.5, 0.5)), _lib.MaterialDesc)
+    bad.kind = 4
+    buf = np.zeros(16)
+    p = buf.ctypes.data
+    m = C.byref(md)
+    # rpt_debug_bounce(m, max_bounces, depth, in_medium, medium_event, albedo_med, medium_color, n, normals, rds, seed, flag, wi, k, next_word)
+    assert lib.rpt_debug_bounce(None, 3, 0, 0, 0, 0.0, p, 1, p, p, 0, p, p, p, p) == -1
+    assert lib.rpt_debug_bounce(C.byref(bad), 3, 0, 0, 0, 0.0, p, 1, p, p, 0, p, p, p, p) == -1 and b"kind" in lib.rpt_last_error()
+    for k in range(7):
+        args = [p] * 7
+        args[k] = None
+        assert lib.rpt_debug_bounce(m, 3, 0, 0, 0, 0.0, args[0], 1, args[1], args[2], 0, *args[3:]) == -1 and b"null" in lib.rpt_last_error()
+    assert lib.rpt_debug_bounce(m, 3, 0, 0, 1, 0.5, p, 1, p, p, 0, p, p, p, p) == -1 and b"in_medium" in lib.rpt_last_error()
+    assert lib.rpt_debug_bounce(m, 3, 0, 1, 1, 0.5, p, 1 << 32, p, p, 0, p, p, p, p) == -1 and b"32-bit" in lib.rpt_last_error()
+    assert lib.rpt_debug_bounce(m, 3, 0, 1, 1, 0.5, p, 0, p, p, 0, p, p, p, p) == 0
+    # rpt_debug_material_f64(m, n, normals, wos, seed, some, wi, pdf, f, next_word)
+    assert lib.rpt_debug_material_f64(None, 1, p, p, 0, p, p, p, p, p) == -1
+    assert lib.rpt_debug_material_f64(C.byref(bad), 1, p, p, 0, p, p, p, p, p) == -1 and b"kind" in lib.rpt_last_error()
+    for k in range(7):
+        args = [p] * 7
+        args[k] = None
+        assert lib.rpt_debug_material_f64(m, 1, args[0], args[1], 0, *args[2:]) == -1 and b"null" in lib.rpt_last_error()
+    assert lib.rpt_debug_material_f64(m, 1 << 32, p, p, 0, p, p, p, p, p) == -1
+    assert lib.rpt_debug_material_f64(m, 0, p, p, 0, p, p, p, p, p) == 0
+    # rpt_debug_material_bsdf_f64(m, n, normals, wos, wis, f)
+    assert lib.rpt_debug_material_bsdf_f64(None, 1, p, p, p, p) == -1 and lib.rpt_debug_material_bsdf_f64(C.byref(bad), 1, p, p, p, p) == -1
+    for k in range(4):
+        args = [p] * 4
+        args[k] = None
+        assert lib.rpt_debug_material_bsdf_f64(m, 1, *args) == -1 and b"null" in lib.rpt_last_error()
+    assert lib.rpt_debug_material_bsdf_f64(m, 0, p, p, p, p) == 0
+    # rpt_debug_camera_sample(_f64)(cam, params, seed, sample, origins, dirs, next_word)
+    cd = camera_desc(Camera(), _lib.CameraDesc)
+    prm, empty = _lib.RenderParams(4, 2, 0.0, 0, 0, 1), _lib.RenderParams(4, 0, 0.0, 0, 0, 1)
+    for fn in (lib.rpt_debug_camera_sample, lib.rpt_debug_camera_sample_f64):
+        assert fn(None, C.byref(prm), 0, 0, p, p, p) == -1 and fn(C.byref(cd), None, 0, 0, p, p, p) == -1
+        assert fn(C.byref(cd), C.byref(prm), 0, 0, None, p, p) == -1 and fn(C.byref(cd), C.byref(prm), 0, 0, p, None, p) == -1
+        assert fn(C.byref(cd), C.byref(empty), 0, 0, p, p, p) == -1 and b"empty" in lib.rpt_last_error()
+    assert lib.rpt_debug_camera_sample_f64(C.byref(cd), C.byref(prm), 0, 0, p, p, None) == -1      # (fp32: the word is optional)
