@@ -217,6 +217,10 @@ int rpt_scene_render_chunking(rpt_scene*, uint32_t iterations, uint32_t* chunk_s
  * "scan_cull" 0/1 (read by rpt_scene_commit, default 1: in a medium a primary scan tests the box around the records behind the
  * shell in scan order -- boxes, rectangles, triangles -- once per lane and leaves those records out when no lane of the wave has a
  * search interval that reaches it; the frames are bit-identical either way),
+ * "shadow_scan" 0/1 (read by rpt_scene_commit, default 1: the shadow query of a linear scan keeps one bit, "the closest hit is a
+ * record of the light's twin object", in place of the hit code, for every object light whose twin is one range of records of one
+ * scanned kind; group lights, twins that are faces of the room shell or monomial surfaces, and 0 keep the closest-hit scan; the
+ * frames are bit-identical either way),
  * "photon_block_lists" 0/1 (camera pass of the beam x point kind: collect the photon spheres of each strip of an
  * 8x8 pixel block once per work item and test them with one photon per lane, default 1; 0 walks the tree per
  * sample), "photon_parts" (work items per 8x8 pixel block and sample chunk of the photon camera pass: the block's
@@ -421,6 +425,23 @@ int rpt_debug_env_color_f64(rpt_scene*, uint64_t n, const double* dirs, double* 
 /* The distance sample of a vertex in the scene's medium (fp32 mode; RPT_ERR_INVALID without a medium): lane i on stream
  * (seed, i, 0) -> the sampled distance and the search limit the closest-hit query gets (+inf: the whole ray). */
 int rpt_debug_medium_distance(rpt_scene*, uint64_t n, uint64_t seed, float* dmed, float* t_limit);
+/* The shadow query and the light decision of the scan kernels (fp32 mode, scenes without a tree: RPT_ERR_UNSUPPORTED otherwise) for
+ * Light::Object `light`, one segment per lane, 64 consecutive ones to a wave: from origins[i] along dirs[i] (used as given; the
+ * render kernels pass the unit vector towards the light's sample) with the sample at dist[i].  out_flag[i]: the kernels would add
+ * the light's term -- the closest hit in [t_min(origin), dist (1 + 1e-3)) is a record of the light's twin object at
+ * t >= dist (1 - 1e-3); out_t[i]: that hit's parameter (dist (1 + 1e-3) where there is none).  The query takes the form the commit
+ * chose for the light (option "shadow_scan"; rpt_shadow_scan_info), as in a render. */
+int rpt_debug_shadow_test(rpt_scene*, uint32_t light, uint64_t n, const float* origins, const float* dirs, const float* dist,
+                          int32_t* out_flag, float* out_t);
+/* How the committed scene tests Light::Object `light`: out[0], out[1] = first and last hit code of its twin object's records
+ * (out[0] > out[1]: they are no single range), out[2] = 1 if the scan kernels use the scan's shadow form for it (option
+ * "shadow_scan" = 1, the scene is scanned, and the range is of one scanned kind -- not faces of the room shell), out[3] = the twin
+ * object's index (0xFFFFFFFF: the light has none and is never visible). */
+int rpt_shadow_scan_info(rpt_scene*, uint32_t light, uint32_t out[4]);
+/* The medium distance -ln(xi) / sigma_t of the draws xi = (2 k + 1) 2^-24, k = k0 .. k0 + n - 1 (k0 + n <= 2^23; needs no scene):
+ * out_new as the render kernels compute it (the bare v_log_f32 and the two-word product with ln 2), out_guarded through __logf with
+ * its denormal and infinity guards, which no such draw needs.  The two are the same bits for every k. */
+int rpt_debug_distance_pair(float sigma_t, uint32_t k0, uint32_t n, float* out_new, float* out_guarded);
 
 /* The bounce of a path vertex, one case per lane on stream (seed, i, 0) (fp32 mode; needs no scene): the render kernels' own stage
  * (roulette or max_bounces, phase or BSDF sample, path weight) at a surface of material `m` with normal normals[i], reached along

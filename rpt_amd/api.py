@@ -47,7 +47,7 @@ def set_option(name, value):
     """Process-wide convenience over the C ABI's per-scene options: sets the default for scenes created from now on
     (rpt_set_option) and the option of every scene this process has on a device (rpt_scene_set_option), so that
     `set_option("counters", 1)` acts on the renderer at hand as it always did.  Options read by rpt_scene_commit
-    ("scene_bvh_min", "instancing", "room_shell", "scan_specialise", "scan_cull", "bvh_leaf_max", "bvh_max_depth") only matter before a scene's
+    ("scene_bvh_min", "instancing", "room_shell", "scan_specialise", "scan_cull", "shadow_scan", "bvh_leaf_max", "bvh_max_depth") only matter before a scene's
     first render; use Scene.set_option to give one scene its own value."""
     lib = _lib.load()
     _lib.check(lib.rpt_set_option(name.encode(), int(value)))
@@ -1013,8 +1013,40 @@ class Renderer:
         _lib.check(lib.rpt_debug_medium_distance(h, n, seed, dmed.ctypes.data_as(C.c_void_p), lim.ctypes.data_as(C.c_void_p)))
         return dmed, lim
 
+    def debug_shadow_test(self, light_index, origins, dirs, dist):
+        """The scan kernels' shadow query and light decision for Light::Object `light_index`, one segment per case: from origins[i]
+        along dirs[i] with the light's sample at dist[i] -> (flag (n, int32): the light is visible, t (n, fp32): the closest hit's
+        parameter, dist (1 + 1e-3) on a miss).  Scenes without a tree (the linear scan's query)."""
+        lib = _lib.load()
+        h = self.scene._commit(self.device_)
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        ds = np.ascontiguousarray(dist, dtype=np.float32).reshape(-1)
+        n = o.shape[0]
+        if d.shape[0] != n or ds.shape[0] != n:
+            raise ValueError("origins, dirs and dist differ in length")
+        flag, t = np.empty(n, np.int32), np.empty(n, np.float32)
+        _lib.check(lib.rpt_debug_shadow_test(h, light_index, n, _vp(o), _vp(d), _vp(ds), _vp(flag), _vp(t)))
+        return flag, t
 
-# ---- per-call hooks that need no scene (rpt_debug_bounce, rpt_debug_material_f64, rpt_debug_material_bsdf_f64)
+    def shadow_scan_info(self, light_index):
+        """How the scan kernels test the visibility of Light::Object `light_index` -> dict of twin_lo, twin_hi (hit codes of its twin
+        object's records; lo > hi: no single range), shadow_form (1: the scan's shadow form, option "shadow_scan"; 0: the closest-hit
+        scan) and twin_object (-1: none)."""
+        out = (C.c_uint32 * 4)()
+        _lib.check(_lib.load().rpt_shadow_scan_info(self.scene._commit(self.device_), light_index, out))
+        return {"twin_lo": int(out[0]), "twin_hi": int(out[1]), "shadow_form": int(out[2]), "twin_object": int(np.int32(np.uint32(out[3])))}
+
+
+# ---- per-call hooks that need no scene (rpt_debug_bounce, rpt_debug_distance_pair, rpt_debug_material_f64, rpt_debug_material_bsdf_f64)
+def debug_distance_pair(sigma_t, k0, n):
+    """The medium distance -ln(xi) / sigma_t of the draws xi = (2 k + 1) 2^-24, k = k0 .. k0 + n - 1 -> (as the render kernels form
+    it, by the guarded __logf), fp32 each."""
+    new, guarded = np.empty(n, np.float32), np.empty(n, np.float32)
+    _lib.check(_lib.load().rpt_debug_distance_pair(float(sigma_t), int(k0), int(n), _vp(new), _vp(guarded)))
+    return new, guarded
+
+
 def debug_bounce(material, normals, rds, max_bounces=3, depth=0, seed=0, in_medium=False, medium_event=False, albedo_med=0.0,
                  medium_color=(0.0, 0.0, 0.0)):
     """The render kernels' bounce stage (fp32 mode), case i on stream (seed, i, 0), at a surface of `material` with normal

@@ -2,6 +2,7 @@
 // Reference line citations are relative to the rpt source tree (src/...).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "gpu_layout.h"
 
 namespace rptg {
@@ -203,16 +204,27 @@ RPT_DEV float hit_plane(const F4& nv, V o, V d, float tmin) {
     float t = (nv.w - dot3(nv, o)) * rcp(c);
     return (t >= tmin) ? t : -1.f;
 }
+// The scans' form, as sphere_closer: "is there an accepted t closer than tbest" (hit_plane's value with the compare the scan
+// puts behind it: the scan then selects tbest once instead of selecting -1 first and comparing that with 0).  The same accepts
+// because tmin > 0 in every caller (ray_tmin): t >= tmin implies the t >= 0 that followed hit_plane.  tri_closer, rect_closer alike.
+RPT_DEV bool plane_closer(const F4& nv, V o, V d, float tmin, float tbest, float& t) {
+    float c = dot3(nv, d);
+    t = (nv.w - dot3(nv, o)) * rcp(c);
+    return !(fabsf(c) < 1e-8f) && t >= tmin && t < tbest;
+}
 // Triangle, src/shape/mesh.rs:50-83, with the plane normal and the barycentric functionals
 // pre-solved on the host.  Accepts t in [tmin, tmax).
-RPT_DEV float hit_tri(const F4& pn, const F4& A, const F4& B, V o, V d, float tmin, float tmax) {
+RPT_DEV bool tri_closer(const F4& pn, const F4& A, const F4& B, V o, V d, float tmin, float tmax, float& t) {
     float c = dot3(pn, d);
-    float t = (pn.w - dot3(pn, o)) * rcp(c);
+    t = (pn.w - dot3(pn, o)) * rcp(c);
     V p = fma3(t, d, o);
     float v = dot3w(A, p), w = dot3w(B, p);
     float u = 1.f - v - w;
-    bool ok = fabsf(c) >= 1e-8f && t >= tmin && t < tmax && u >= 0.f && v >= 0.f && w >= 0.f;
-    return ok ? t : -1.f;
+    return fabsf(c) >= 1e-8f && t >= tmin && t < tmax && u >= 0.f && v >= 0.f && w >= 0.f;
+}
+RPT_DEV float hit_tri(const F4& pn, const F4& A, const F4& B, V o, V d, float tmin, float tmax) {
+    float t;
+    return tri_closer(pn, A, B, o, d, tmin, tmax, t) ? t : -1.f;
 }
 // Axis-aligned box in world space (a cube under positive scale + translation): the reference's
 // local slab test (src/shape/cube.rs:22-74) evaluated in world coordinates, where it yields the
@@ -224,16 +236,23 @@ RPT_DEV float hit_aabb(const F4& lo, const F4& hi, V o, V inv, float tmin) {
 // Axis-aligned rectangle = two coplanar triangles of src/shape/mesh.rs:50-83 (u,v,w >= 0 on one
 // of them <=> the point lies in the closed rectangle).  oa/da/ia: origin, direction and 1/direction
 // on the rectangle's axis; (ou,du), (ov,dv) on the two in-plane axes.
+RPT_DEV bool rect_closer(const F4& a, float vmax, float oa, float ia, float ou, float du, float ov, float dv,
+                         float tmin, float tmax, float& t) {
+    t = (a.x - oa) * ia;
+    float pu = fmaf(t, du, ou), pv = fmaf(t, dv, ov);
+    return t >= tmin && t < tmax && pu >= a.y && pu <= a.z && pv >= a.w && pv <= vmax;
+}
 RPT_DEV float hit_rect(const F4& a, float vmax, float oa, float ia, float ou, float du, float ov, float dv,
                        float tmin, float tmax) {
-    float t = (a.x - oa) * ia;
-    float pu = fmaf(t, du, ou), pv = fmaf(t, dv, ov);
-    bool ok = t >= tmin && t < tmax && pu >= a.y && pu <= a.z && pv >= a.w && pv <= vmax;
-    return ok ? t : -1.f;
+    float t;
+    return rect_closer(a, vmax, oa, ia, ou, du, ov, dv, tmin, tmax, t) ? t : -1.f;
 }
 // Box shell (ShellScan): the closest rectangle among the faces of one axis-aligned box = the slab entry if
 // that face exists and lies at or beyond tmin, else the slab exit.  Same t = (plane - o) * inv as hit_rect.
-RPT_DEV void hit_shell(const ShellScan& s, V o, V inv, float tmin, float& tbest, uint32_t& code) {
+// `acc(ok, t, code_of)`: what the caller keeps of an accepted face (code_of() selects its hit code: the shadow form never calls it;
+// which faces exist is decided from the codes either way, because an open face must not hit).
+template <class Acc>
+RPT_DEV void shell_closer(const ShellScan& s, V o, V inv, float tmin, float tbest, Acc&& acc) {
     float x1 = (s.lo.x - o.x) * inv.x, x2 = (s.hi.x - o.x) * inv.x;
     float y1 = (s.lo.y - o.y) * inv.y, y2 = (s.hi.y - o.y) * inv.y;
     float z1 = (s.lo.z - o.z) * inv.z, z2 = (s.hi.z - o.z) * inv.z;
@@ -252,7 +271,7 @@ RPT_DEV void hit_shell(const ShellScan& s, V o, V inv, float tmin, float& tbest,
     bool use_in = box && start >= tmin && c_in != CODE_MISS;
     bool use_out = box && end >= tmin && c_out != CODE_MISS;
     float t = use_in ? start : end;
-    if ((use_in || use_out) && t < tbest) { tbest = t; code = use_in ? c_in : c_out; }
+    acc((use_in || use_out) && t < tbest, t, [&] { return use_in ? c_in : c_out; });
 }
 RPT_DEV void to_local(const XfScan& x, V o, V d, V& ol, V& dl) {
     ol = mk(dot3w(x.r0, o), dot3w(x.r1, o), dot3w(x.r2, o));
@@ -273,8 +292,9 @@ RPT_DEV void to_local_y(const XfScan& x, V o, V d, V& ol, V& dl) {
 // One uniform if per axis rather than a body per combination: every combination is served, and a three-way choice between whole
 // bodies compiles to a chain of flag tests that costs ~60 scalar instructions per trip on C3.  The first box's entry / exit are
 // pinned before the ifs: sunk below them they keep its intervals alive, and each shared one then costs two register copies.
-RPT_DEV void aabb_pair_closer(const AabbScan& b0, const AabbScan& b1, uint32_t shared, V o, V inv, float tmin, float& tbest,
-                              uint32_t& code, uint32_t i) {
+template <class Acc>
+RPT_DEV void aabb_pair_closer(const AabbScan& b0, const AabbScan& b1, uint32_t shared, V o, V inv, float tmin, float& tbest, uint32_t i,
+                              Acc&& acc) {   // acc(ok, t, record): `ok` was formed against tbest, which acc lowers (scan_prims)
 #pragma clang fp contract(off)
     const float x1 = (b0.lo.x - o.x) * inv.x, x2 = (b0.hi.x - o.x) * inv.x;
     const float y1 = (b0.lo.y - o.y) * inv.y, y2 = (b0.hi.y - o.y) * inv.y;
@@ -283,13 +303,13 @@ RPT_DEV void aabb_pair_closer(const AabbScan& b0, const AabbScan& b1, uint32_t s
     float start = max3(xl, yl, zl), end = min3(xh, yh, zh);   // slabs_closer from here on
     asm volatile("" : "+v"(start), "+v"(end));
     float t = start < tmin ? end : start;
-    if (!(start > end) && !(end < tmin) && t < tbest) { tbest = t; code = (K_AABB << 28) | i; }
+    acc(!(start > end) && !(end < tmin) && t < tbest, t, i);
     if (!(shared & 1u)) { const float u1 = (b1.lo.x - o.x) * inv.x, u2 = (b1.hi.x - o.x) * inv.x; xl = fminf(u1, u2); xh = fmaxf(u1, u2); }
     if (!(shared & 2u)) { const float u1 = (b1.lo.y - o.y) * inv.y, u2 = (b1.hi.y - o.y) * inv.y; yl = fminf(u1, u2); yh = fmaxf(u1, u2); }
     if (!(shared & 4u)) { const float u1 = (b1.lo.z - o.z) * inv.z, u2 = (b1.hi.z - o.z) * inv.z; zl = fminf(u1, u2); zh = fmaxf(u1, u2); }
     start = max3(xl, yl, zl), end = min3(xh, yh, zh);
     t = start < tmin ? end : start;
-    if (!(start > end) && !(end < tmin) && t < tbest) { tbest = t; code = (K_AABB << 28) | (i + 1u); }
+    acc(!(start > end) && !(end < tmin) && t < tbest, t, i + 1u);
 }
 // MonomialSurface::intersect, src/shape/monomial_surface.rs:22-107, in the surface's local space (t is shared), step for step:
 // the box test against [-1, 0, -1]..[1, h, 1] (min / max per axis, so h <= 0 works), maximize = dist(t_min) < 0, Newton from
@@ -517,31 +537,75 @@ RPT_DEV bool interval_meets_box(const SceneView::ScanBox& b, V o, V inv, float t
 // ceiling, which four trips in five do not reach.  One slab test and one ballot; the records that are tested are tested as ever, and a record
 // that is left out could not have been accepted by any lane (rpt_capi.cpp, group_scans, has the rounding argument).  tail_skipped
 // (counters builds): set when the tail was left out.
-template <bool MASKED = false, bool MONO = false, bool TAIL = false>
+// SHADOW (the shadow query of an object light whose twin -- the scene object that IS the light -- is one index range of one scanned
+// kind; option "shadow_scan"): the light test reads one bit of the closest hit, "it is a twin record", so this form keeps no hit code.
+// The tbest chain is the closest-hit form's, compare for compare; beside it runs one lane predicate, "the best so far is a twin
+// record": an accepted twin record sets it, every other accepted record clears it (clearing before the twin range changes nothing:
+// it is still false there).  Which of the two a record does is wave-uniform -- the kind's loop is chosen once per kind, and only the
+// twin kind's loop looks at the index -- and the predicate lives in a scalar register pair.  `twin`: see ShadowTwin.
+// Why the bit is the closest-hit form's `code in [twin_lo, twin_hi]`: DESIGN.md section 4, round 7.
+struct ShadowTwin {
+    uint32_t kind, lo, span;   // twin records: kind `kind`, indices lo .. lo + span
+    RPT_DEV bool has(uint32_t i) const { return i - lo <= span; }
+};
+template <bool MASKED = false, bool MONO = false, bool TAIL = false, bool SHADOW = false>
 RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbest, uint32_t& code, uint64_t mask = ~0ull,
-                        bool* tail_skipped = nullptr) {
+                        bool* tail_skipped = nullptr, ShadowTwin twin = ShadowTwin{0u, 1u, 0u}, bool* best_is_twin = nullptr) {
     static_assert(!(TAIL && MASKED), "one cull at a time");
+    static_assert(!(SHADOW && (MASKED || TAIL)), "the shadow form is a plain scan");
     // The scene view is a kernel argument (every caller passes its kernarg struct): its fields are read HERE, through the
     // constant address space, behind an opaque copy of the pointer.  Read as plain kernel arguments they are all hoisted to
     // the kernel's entry and held in scalar registers for its whole life -- the render kernels have ~110 such values, the
     // compiler parks the overflow in VGPR lanes, and 14 % of their VALU instructions were v_readlane / v_writelane.
     const auto& sc = *kernarg_scene();
     (void)scene;
+    bool flag = false;   // (SHADOW) the best so far is a twin record
+    // ... and inside the twin kind's loop: tbest as the last accepted TWIN record left it (NaN: none yet).  At the loop's end the best
+    // so far is a twin record iff tbest still has that value: every later accepted record lowered it (t < tbest is strict).  A float
+    // select under (lane mask & uniform bit) -- a select between a uniform and a divergent bool is compiled to four vector instructions.
+    float t_twin = __builtin_nanf("");
+    // An accepted record (`ok` holds t < tbest): the new tbest, and its code or -- SHADOW -- whether it is a twin record (`is_twin`: a
+    // std::false_type outside the twin kind's loop, a wave-uniform bool inside).
+    auto acc = [&](bool ok, float t, uint32_t c, auto is_twin) {
+        if (ok) tbest = t;
+        asm volatile("" : "+v"(tbest));   // one tbest: without the pin the loops carry a second copy of it (a third select per record)
+        if constexpr (!SHADOW) { if (ok) code = c; }
+        else if constexpr (std::is_same_v<decltype(is_twin), std::false_type>) flag = flag && !ok;
+        else if (ok && is_twin) t_twin = t;
+    };
+    // twin_at(tw, i): acc's last argument for record i of a kind whose loop was entered as the twin kind's (tw: true_type) or not.
+    auto twin_at = [&](auto tw, uint32_t i) {
+        if constexpr (decltype(tw)::value) return twin.has(i);
+        else return std::false_type{};
+    };
+    // A kind's loop: SHADOW compiles it twice, for the twin's kind (its records ask twin.has(i)) and for every other kind.
+    auto kind_loop = [&](uint32_t kind, auto&& loop) {
+        if constexpr (SHADOW) {
+            if (twin.kind == kind) {   // (wave-uniform)
+                loop(std::true_type{});
+                flag = t_twin == tbest;
+                return;
+            }
+        }
+        loop(std::false_type{});
+    };
     uint32_t bit = 0;  // wave-uniform record number
     auto on = [&](uint32_t i) { return !MASKED || ((mask >> ((bit + i) & 63u)) & 1ull) != 0ull; };
     // Unmasked scans: records the commit found to be rotations about the vertical axis take to_local_y (wave-uniform branches).
     const uint64_t sph_yrot = MASKED ? 0ull : sc.sph_yrot, cub_yrot = MASKED ? 0ull : sc.cub_yrot;
-    for (uint32_t i = 0; i < sc.n_sph; i++) {
-        if (!on(i)) continue;
-        const XfScan x = uload(&sc.sph[i]);
-        V ol, dl;
-        if (!MASKED && ((sph_yrot >> (i & 63u)) & 1ull)) to_local_y(x, o, d, ol, dl);
-        else to_local(x, o, d, ol, dl);
-        float t;
-        if (sphere_closer(ol, dl, tmin, tbest, t)) { tbest = t; code = (K_SPHERE << 28) | i; }
-    }
+    kind_loop(K_SPHERE, [&](auto tw) {
+        for (uint32_t i = 0; i < sc.n_sph; i++) {
+            if (!on(i)) continue;
+            const XfScan x = uload(&sc.sph[i]);
+            V ol, dl;
+            if (!MASKED && ((sph_yrot >> (i & 63u)) & 1ull)) to_local_y(x, o, d, ol, dl);
+            else to_local(x, o, d, ol, dl);
+            float t;
+            acc(sphere_closer(ol, dl, tmin, tbest, t), t, (K_SPHERE << 28) | i, twin_at(tw, i));
+        }
+    });
     bit += sc.n_sph;
-    {   // two records per iteration: independent instruction streams for the scheduler (unmasked scans)
+    kind_loop(K_CUBE, [&](auto tw) {   // two records per iteration: independent instruction streams for the scheduler (unmasked scans)
         uint32_t i = 0;
         if (!MASKED)
             for (; i + 1u < sc.n_cub; i += 2u) {
@@ -555,8 +619,8 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
                     to_local(x0, o, d, ol0, dl0);
                     to_local(x1, o, d, ol1, dl1);
                 }
-                if (cube_closer(ol0, dl0, tmin, tbest, t0)) { tbest = t0; code = (K_CUBE << 28) | i; }
-                if (cube_closer(ol1, dl1, tmin, tbest, t1)) { tbest = t1; code = (K_CUBE << 28) | (i + 1u); }
+                acc(cube_closer(ol0, dl0, tmin, tbest, t0), t0, (K_CUBE << 28) | i, twin_at(tw, i));
+                acc(cube_closer(ol1, dl1, tmin, tbest, t1), t1, (K_CUBE << 28) | (i + 1u), twin_at(tw, i + 1u));
             }
         for (; i < sc.n_cub; i++) {
             if (!on(i)) continue;
@@ -565,19 +629,23 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
             if (!MASKED && ((cub_yrot >> (i & 63u)) & 1ull)) to_local_y(x, o, d, ol, dl);
             else to_local(x, o, d, ol, dl);
             float t;
-            if (cube_closer(ol, dl, tmin, tbest, t)) { tbest = t; code = (K_CUBE << 28) | i; }
+            acc(cube_closer(ol, dl, tmin, tbest, t), t, (K_CUBE << 28) | i, twin_at(tw, i));
         }
-    }
+    });
     bit += sc.n_cub;
-    for (uint32_t i = 0; i < sc.n_pln; i++) {
+    for (uint32_t i = 0; i < sc.n_pln; i++) {   // (a plane is never a twin: no light shape is one)
         const F4 nv = uload(&sc.pln[i]).nv;
-        float t = hit_plane(nv, o, d, tmin);
-        if (t >= 0.f && t < tbest) { tbest = t; code = (K_PLANE << 28) | i; }
+        float t;
+        acc(plane_closer(nv, o, d, tmin, tbest, t), t, (K_PLANE << 28) | i, std::false_type{});
     }
     const uint32_t n_rect = sc.n_rect_x + sc.n_rect_y + sc.n_rect_z;
     if (sc.n_aabb + n_rect + sc.has_shell != 0) {  // wave-uniform: these kinds share one reciprocal direction per ray
         const V inv = mk(rcp(d.x), rcp(d.y), rcp(d.z));
-        if (sc.has_shell) hit_shell(uload(sc.shell), o, inv, tmin, tbest, code);
+        if (sc.has_shell)   // (SHADOW: a light whose twin is a shell face takes the closest-hit form)
+            shell_closer(uload(sc.shell), o, inv, tmin, tbest, [&](bool ok, float t, auto code_of) {
+                if constexpr (SHADOW) acc(ok, t, 0u, std::false_type{});
+                else { if (ok) { tbest = t; code = code_of(); } }
+            });
         if constexpr (TAIL) {
             if (sc.scan_cull) {   // (wave-uniform)
                 const SceneView::ScanBox tb = kernarg_load(&sc.scan_tail);
@@ -587,60 +655,66 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
                 }
             }
         }
-        {
+        kind_loop(K_AABB, [&](auto tw) {
             uint32_t i = 0;
             if (!MASKED)
                 for (; i + 1u < sc.n_aabb; i += 2u) {
                     const AabbScan b0 = uload(&sc.aabb[i]), b1 = uload(&sc.aabb[i + 1u]);
-                    aabb_pair_closer(b0, b1, __float_as_uint(b0.hi.w), o, inv, tmin, tbest, code, i);   // hi.w: the slabs they have in common
+                    aabb_pair_closer(b0, b1, __float_as_uint(b0.hi.w), o, inv, tmin, tbest, i,   // hi.w: the slabs they have in common
+                                     [&](bool ok, float t, uint32_t k) { acc(ok, t, (K_AABB << 28) | k, twin_at(tw, k)); });
                 }
             for (; i < sc.n_aabb; i++) {
                 if (!on(i)) continue;
                 const AabbScan b = uload(&sc.aabb[i]);
                 float t;
-                if (aabb_closer(b.lo, b.hi, o, inv, tmin, tbest, t)) { tbest = t; code = (K_AABB << 28) | i; }
+                acc(aabb_closer(b.lo, b.hi, o, inv, tmin, tbest, t), t, (K_AABB << 28) | i, twin_at(tw, i));
             }
-        }
+        });
         bit += sc.n_aabb;
-        uint32_t i = 0;
-        for (uint32_t e = sc.n_rect_x; i < e; i++) {
-            if (!on(i)) continue;
-            const RectScan r = uload(&sc.rect[i]);
-            float t = hit_rect(r.a, r.b.x, o.x, inv.x, o.y, d.y, o.z, d.z, tmin, tbest);
-            if (t >= 0.f) { tbest = t; code = (K_RECT << 28) | i; }
-        }
-        for (uint32_t e = sc.n_rect_x + sc.n_rect_y; i < e; i++) {
-            if (!on(i)) continue;
-            const RectScan r = uload(&sc.rect[i]);
-            float t = hit_rect(r.a, r.b.x, o.y, inv.y, o.z, d.z, o.x, d.x, tmin, tbest);
-            if (t >= 0.f) { tbest = t; code = (K_RECT << 28) | i; }
-        }
-        for (uint32_t e = n_rect; i < e; i++) {
-            if (!on(i)) continue;
-            const RectScan r = uload(&sc.rect[i]);
-            float t = hit_rect(r.a, r.b.x, o.z, inv.z, o.x, d.x, o.y, d.y, tmin, tbest);
-            if (t >= 0.f) { tbest = t; code = (K_RECT << 28) | i; }
-        }
+        kind_loop(K_RECT, [&](auto tw) {
+            uint32_t i = 0;
+            for (uint32_t e = sc.n_rect_x; i < e; i++) {
+                if (!on(i)) continue;
+                const RectScan r = uload(&sc.rect[i]);
+                float t;
+                acc(rect_closer(r.a, r.b.x, o.x, inv.x, o.y, d.y, o.z, d.z, tmin, tbest, t), t, (K_RECT << 28) | i, twin_at(tw, i));
+            }
+            for (uint32_t e = sc.n_rect_x + sc.n_rect_y; i < e; i++) {
+                if (!on(i)) continue;
+                const RectScan r = uload(&sc.rect[i]);
+                float t;
+                acc(rect_closer(r.a, r.b.x, o.y, inv.y, o.z, d.z, o.x, d.x, tmin, tbest, t), t, (K_RECT << 28) | i, twin_at(tw, i));
+            }
+            for (uint32_t e = n_rect; i < e; i++) {
+                if (!on(i)) continue;
+                const RectScan r = uload(&sc.rect[i]);
+                float t;
+                acc(rect_closer(r.a, r.b.x, o.z, inv.z, o.x, d.x, o.y, d.y, tmin, tbest, t), t, (K_RECT << 28) | i, twin_at(tw, i));
+            }
+        });
         bit += n_rect;
     } else {
         bit += sc.n_aabb + n_rect;
     }
-    for (uint32_t i = 0; i < sc.n_tri; i++) {
-        if (!on(i)) continue;
-        const TriScan tr = uload(&sc.tri[i]);
-        float t = hit_tri(tr.pn, tr.A, tr.B, o, d, tmin, tbest);
-        if (t >= 0.f) { tbest = t; code = (K_TRI << 28) | i; }
-    }
+    kind_loop(K_TRI, [&](auto tw) {
+        for (uint32_t i = 0; i < sc.n_tri; i++) {
+            if (!on(i)) continue;
+            const TriScan tr = uload(&sc.tri[i]);
+            float t;
+            acc(tri_closer(tr.pn, tr.A, tr.B, o, d, tmin, tbest, t), t, (K_TRI << 28) | i, twin_at(tw, i));
+        }
+    });
     if constexpr (MONO) {
         static_assert(!MASKED && !TAIL, "scan_mask_for_ball and the tail cull do not cover the monomial surfaces");
-        for (uint32_t i = 0; i < sc.n_mono; i++) {
+        for (uint32_t i = 0; i < sc.n_mono; i++) {   // (SHADOW: a light with a monomial-surface twin takes the closest-hit form)
             const MonoScan m = uload(&sc.mono[i]);
             V ol, dl;
             to_local(XfScan{m.r0, m.r1, m.r2}, o, d, ol, dl);
             float t;
-            if (mono_closer(ol, dl, m.h, tmin, tbest, t)) { tbest = t; code = (K_MONO << 28) | i; }
+            acc(mono_closer(ol, dl, m.h, tmin, tbest, t), t, (K_MONO << 28) | i, std::false_type{});
         }
     }
+    if constexpr (SHADOW) *best_is_twin = flag;
 }
 // Which scanned records can a query touch that stays inside the ball (c, r) of each live lane?  Wave-uniform mask
 // for scan_prims<true> (the union over the lanes: one lane's ball reaching a box keeps that record for all of them).
@@ -1082,13 +1156,20 @@ RPT_DEV V bsdf(const Mat& m, V n, V wo, V wi) {
 // A leaf picked out of a group differs per lane: its rows are loaded where they are used, so that the 48
 // floats never live in VGPRs at once.
 template <bool UNIFORM> struct LightXfRows;
+// (UNIFORM: rows and the has-transform word are scalar loads AT THEIR USE, inside the wave-uniform branches that need them.  Loaded by
+// value up front the record is three s_load_dwordx16 and 48 live scalar registers -- for a world-space mesh light, which reads the
+// one word nrm[1].w -- and the kernels park the overflow in VGPR lanes.)
 template <> struct LightXfRows<true> {
-    LightXf x;
-    RPT_DEV explicit LightXfRows(const LightXf* p) : x(uload(p)) {}
-    RPT_DEV F4 fwd(int r) const { return x.fwd[r]; }
-    RPT_DEV F4 inv(int r) const { return x.inv[r]; }
-    RPT_DEV F4 nrm(int r) const { return x.nrm[r]; }
-    RPT_DEV F4 lin(int r) const { return x.lin[r]; }
+    const LightXf* p;
+    RPT_DEV explicit LightXfRows(const LightXf* q) : p(q) {}
+    RPT_DEV F4 fwd(int r) const { return uload(&p->fwd[r]); }
+    RPT_DEV F4 inv(int r) const { return uload(&p->inv[r]); }
+    RPT_DEV F4 nrm(int r) const { return uload(&p->nrm[r]); }
+    RPT_DEV F4 lin(int r) const { return uload(&p->lin[r]); }
+    RPT_DEV bool has_transform() const {
+        typedef const __attribute__((address_space(4))) float* CF;
+        return *(CF)(uintptr_t)&p->nrm[1].w != 0.f;
+    }
 };
 template <> struct LightXfRows<false> {
     const LightXf* p;
@@ -1097,6 +1178,7 @@ template <> struct LightXfRows<false> {
     RPT_DEV F4 inv(int r) const { return p->inv[r]; }
     RPT_DEV F4 nrm(int r) const { return p->nrm[r]; }
     RPT_DEV F4 lin(int r) const { return p->lin[r]; }
+    RPT_DEV bool has_transform() const { return p->nrm[1].w != 0.f; }
 };
 // One leaf shape of a Light::Object (Sphere/Cube/Mesh::sample under Transformed::sample, src/shape.rs:140-151).
 template <bool UNIFORM>
@@ -1105,7 +1187,7 @@ RPT_DEV void sample_light_leaf(const SceneView& scene_, uint32_t shape, uint32_t
     const auto& sc = *kernarg_scene();   // (see kernarg_scene)
     V vl, nl;
     const LightXfRows<UNIFORM> x(xp);
-    const bool xf = x.nrm(1).w != 0.f;
+    const bool xf = x.has_transform();
     const bool mesh = shape == LS_MESH;
     if (mesh) {
         uint32_t idx = rng.index(count);
@@ -1118,19 +1200,25 @@ RPT_DEV void sample_light_leaf(const SceneView& scene_, uint32_t shape, uint32_t
         }
         // `while u + v > 1 { redraw }` (src/shape/mesh.rs:89-93) on the draws' integers: with u = (2k+1) 2^-24 the sum is exact
         // in fp32 and u + v > 1 <=> ku + kv >= 2^23, so the rejected pairs are never converted (the wave runs the loop for its
-        // unluckiest lane: ~7 rounds for 2 on average)
-        uint32_t ku = rng.next() >> 9, kv = rng.next() >> 9;
-        while (ku + kv >= (1u << 23)) {
-            ku = rng.next() >> 9;
-            kv = rng.next() >> 9;
+        // unluckiest lane: ~7 rounds for 2 on average).  On the words themselves: (a & ~511) + (b & ~511) = 512 (ku + kv) carries
+        // out of 32 bits exactly when ku + kv >= 2^23 -- and, and, add with carry, instead of shift, shift, add, compare.
+        uint32_t wu = rng.next() & ~511u, wv = rng.next() & ~511u, sum;
+        while (__builtin_add_overflow(wu, wv, &sum)) {
+            wu = rng.next() & ~511u;
+            wv = rng.next() & ~511u;
         }
+        const uint32_t ku = wu >> 9, kv = wv >> 9;
         const float u = float((ku << 1) | 1u) * 0x1p-24f, vv = float((kv << 1) | 1u) * 0x1p-24f;
         float w = 1.f - u - vv;
         vl = u * xyz(tr.v1) + vv * xyz(tr.v2) + w * xyz(tr.v3);  // already world space
         nl = normalize(u * xyz(tr.n1) + vv * xyz(tr.n2) + w * xyz(tr.n3));
         p = tr.v1.w * rcp(float(count));
     } else if (shape == LS_SPHERE) {
-        V tl = xf ? mk(dot3w(x.inv(0), pos), dot3w(x.inv(1), pos), dot3w(x.inv(2), pos)) : pos;
+        V tl = pos;
+        if (xf) {
+            const F4 i0 = x.inv(0), i1 = x.inv(1), i2 = x.inv(2);
+            tl = mk(dot3w(i0, pos), dot3w(i1, pos), dot3w(i2, pos));
+        }
         float dx, dy;
         rng.unit_disc(dx, dy);
         float z = sqrt1(fmaxf(1.f - dx * dx - dy * dy, 0.f));
@@ -1155,11 +1243,18 @@ RPT_DEV void sample_light_leaf(const SceneView& scene_, uint32_t shape, uint32_t
         p = 1.f / 6.f;
     }
     if (xf) {
-        n = normalize(mk(dot3(x.nrm(0), nl), dot3(x.nrm(1), nl), dot3(x.nrm(2), nl)));
-        V ln = mk(dot3(x.lin(0), nl), dot3(x.lin(1), nl), dot3(x.lin(2), nl));
+        const F4 n0 = x.nrm(0), n1 = x.nrm(1), n2 = x.nrm(2);
+        n = normalize(mk(dot3(n0, nl), dot3(n1, nl), dot3(n2, nl)));
+        const F4 l0 = x.lin(0), l1 = x.lin(1), l2 = x.lin(2);
+        V ln = mk(dot3(l0, nl), dot3(l1, nl), dot3(l2, nl));
         float height = dot(ln, n);
-        float base = x.nrm(0).w * rcp(height);
-        v = mesh ? vl : mk(dot3w(x.fwd(0), vl), dot3w(x.fwd(1), vl), dot3w(x.fwd(2), vl));
+        float base = n0.w * rcp(height);
+        if (mesh) {
+            v = vl;
+        } else {
+            const F4 f0 = x.fwd(0), f1 = x.fwd(1), f2 = x.fwd(2);
+            v = mk(dot3w(f0, vl), dot3w(f1, vl), dot3w(f2, vl));
+        }
         p = p * rcp(base);
     } else {
         v = vl;

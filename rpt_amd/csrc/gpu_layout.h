@@ -119,7 +119,8 @@ struct alignas(16) Light {
     uint32_t count;       // LS_MESH: triangle count;  LS_GROUP: number of children
     uint32_t xf;          // index into lxf (every object light has one)
     uint32_t twin_lo, twin_hi;  // hit codes of the twin object's primitives when they form one range (lo <= hi)
-    F4 color;             // Ambient: colour;  Object: material.color() * material.emittance()
+    F4 color;             // Ambient: colour;  Object: material.color() * material.emittance().  color.w (bits; Object): 1 = the scan kernels test this
+                          // light with the scan's shadow form (scan_prims<.., SHADOW>; set at commit, option "shadow_scan"), 0 = with the closest-hit scan
     F4 albedo;            // Object: material.color() (photon power, src/photon.rs:757)
 };
 // A Light::Object whose shape is a KdTree<Box<dyn Bounded>>: sampling picks a child uniformly (then a

@@ -98,6 +98,19 @@ __attribute__((weak)) hipError_t launch_debug_light_sample(const SceneView& sc, 
 __attribute__((weak)) hipError_t launch_debug_env_color(const SceneView& sc, uint64_t n, const float* d_dirs, float* d_rgb, hipStream_t s);
 __attribute__((weak)) hipError_t launch_debug_medium_distance(const SceneView& sc, uint64_t n, uint64_t seed_mixed, float* d_dmed,
                                                               float* d_limit, hipStream_t s);
+// rpt_debug_shadow_test: the scan flavours' shadow query and light decision (scan_light_visible), one segment per lane; device arrays.
+struct ShadowTestArgs {
+    uint32_t light;           // index into SceneView::lights (an L_OBJECT with a twin)
+    uint32_t pad_;
+    uint64_t n;
+    const float *o, *d;       // [3 n] origin and direction of the segment
+    const float* dist;        // [n] distance of the light's sample along d
+    int32_t* flag;            // [n] the decision: the light is visible
+    float* t;                 // [n] the closest hit's t (dist (1 + 1e-3) where the scan found none)
+};
+__attribute__((weak)) hipError_t launch_debug_shadow_test(const SceneView& sc, const ShadowTestArgs& q, hipStream_t s);
+// rpt_debug_distance_pair: the medium distance of draw k as the render kernels form it and by the guarded __logf, k = k0 .. k0 + n - 1.
+__attribute__((weak)) hipError_t launch_debug_distance_pair(float sigma_t, uint32_t k0, uint32_t n, float* d_new, float* d_guarded, hipStream_t s);
 // rpt_debug_bounce: stage_bounce<MEDIUM, false> of the render kernels, one case per lane on stream (seed, lane, 0).
 struct BounceArgs {
     Material m;

@@ -161,12 +161,28 @@ static constexpr uint32_t kCullCounters = 64u;   // counters[64..75]: scan_prima
 // src/medium.rs:133-146).  A hit beyond the sampled medium distance cannot change the event (dmed < t, or a miss with
 // dmed < 400, is a medium event either way, src/renderer.rs:197-243): the search ends there, which culls most of a
 // tree walk in fog.  The margin keeps the `dmed < t` comparison below the one that decides.
+// -ln(xi) / sigma_t of a draw xi = (2k + 1) 2^-24, k < 2^23.  __logf guards what such a draw cannot be: it scales a denormal input
+// before v_log_f32 and passes an infinite logarithm through -- 8 of its 13 instructions.  medium_distance is the rest, written out:
+// v_log_f32, then the product with ln 2 in two words exactly as the compiler forms it for __logf (product, its rounding error by
+// fma, the low word, and the sum contracted into a last fma), with contraction off so that it stays these four operations.
+// tests/test_gpu_distance_exhaustive.py holds the two bit-equal for every k.
+RPT_DEV float medium_distance_guarded(float xi, float inv_sigma_t) { return -__logf(xi) * inv_sigma_t; }
+RPT_DEV float medium_distance(float xi, float inv_sigma_t) {
+#pragma clang fp contract(off)
+    const float ln2_hi = 0x1.62e42ep-1f, ln2_lo = 0x1.efa39ep-25f;
+    const float y = __builtin_amdgcn_logf(xi);
+    const float r = y * ln2_hi;
+    const float e = __builtin_fmaf(y, ln2_hi, -r);
+    const float lo = __builtin_fmaf(y, ln2_lo, e);
+    const float ln = __builtin_fmaf(ln2_hi, y, lo);
+    return -ln * inv_sigma_t;
+}
 template <bool MEDIUM>
 RPT_DEV void stage_distance(Rng& rng, float inv_sigma_t, float& dmed, float& t) {
     dmed = kInf;
     if (MEDIUM) {
         float xi = rng.range(0.f, 1.f);
-        dmed = -__logf(xi) * inv_sigma_t;
+        dmed = medium_distance(xi, inv_sigma_t);
     }
     t = (MEDIUM && dmed < 400.f) ? dmed * (1.f + 1e-6f) : kInf;
 }
@@ -195,19 +211,43 @@ RPT_DEV void stage_event(const RenderArgs& a, const LdsTables& tab, V ro, V rd, 
 // The shadow test of an object light and its term of E (src/renderer.rs:347-353, 395-404).  Reference: contributes
 // iff the closest hit along wi lies at dist_to_light (|hit - dist| < 1e-12).  fp32 equivalent: the closest hit
 // belongs to the scene object that IS this light, at the sampled distance (rel. tol 1e-3).
+// PIN_RD (the scan flavours): wo is formed behind an opaque copy of rd, or it is formed ahead of the light loop and holds three registers
+// across the shadow scan -- one more spill in kernels that sit at their 80-register limit.
+template <bool PIN_RD = false>
+RPT_DEV void stage_light_add(const SceneView& sc, float albedo_med, V rd, bool medium, V I, V wi, V n, V mcol, const Mat& mat, V& E) {
+    if (medium) {
+        E = fma3(albedo_med * sc.medium_phase, I * mcol, E);
+    } else {
+        if constexpr (PIN_RD) asm volatile("" : "+v"(rd.x), "+v"(rd.y), "+v"(rd.z));
+        V f = bsdf(mat, n, -normalize(rd), wi);   // (wo is only needed at surface events: derived where used)
+        E = fma3(dot(wi, n), f * I, E);
+    }
+}
 template <bool MONO = false>
 RPT_DEV void stage_light_term(const SceneView& sc, const Light& L, float albedo_med, V rd, bool medium, float ts, uint32_t cs,
                               uint32_t is, float dist, V I, V wi, V n, V mcol, const Mat& mat, V& E) {
     const bool twin = (L.twin_lo <= L.twin_hi) ? (cs >= L.twin_lo && cs <= L.twin_hi)   // wave-uniform choice
                                                : (cs != CODE_MISS && code_object<MONO>(sc, cs, is) == uint32_t(L.twin_object));
-    if (cs != CODE_MISS && ts >= dist * (1.f - 1e-3f) && twin) {
-        if (medium) {
-            E = fma3(albedo_med * sc.medium_phase, I * mcol, E);
-        } else {
-            V f = bsdf(mat, n, -normalize(rd), wi);   // (wo is only needed at surface events: derived where used)
-            E = fma3(dot(wi, n), f * I, E);
-        }
+    if (cs != CODE_MISS && ts >= dist * (1.f - 1e-3f) && twin) stage_light_add(sc, albedo_med, rd, medium, I, wi, n, mcol, mat, E);
+}
+// The shadow query and the light decision of the scan flavours (BVH = 0): is the light's sample at `dist` along wi what x sees?
+// A light that the commit marked (Light::color.w; option "shadow_scan") asks the scan's shadow form for its one bit; every other
+// light -- a group light, a twin that is a shell face or a monomial surface, the option off -- runs the closest-hit scan and
+// stage_light_term's test, as before.  Wave-uniform choice.  `ts`: the closest hit's t (the end of the interval on a miss).
+template <bool MONO = false>
+RPT_DEV bool scan_light_visible(const SceneView& sc, const Light& L, V x, V wi, float dist, float& ts) {
+    ts = dist * (1.f + 1e-3f);
+    uint32_t cs = CODE_MISS;
+    if (__float_as_uint(L.color.w) != 0u) {
+        bool twin = false;
+        scan_prims<false, MONO, false, true>(sc, x, wi, ray_tmin(x), ts, cs, ~0ull, nullptr,
+                                             ShadowTwin{L.twin_lo >> 28, L.twin_lo & 0x0FFFFFFFu, L.twin_hi - L.twin_lo}, &twin);
+        return twin && ts >= dist * (1.f - 1e-3f);
     }
+    scan_prims<false, MONO>(sc, x, wi, ray_tmin(x), ts, cs);
+    const bool twin = (L.twin_lo <= L.twin_hi) ? (cs >= L.twin_lo && cs <= L.twin_hi)
+                                               : (cs != CODE_MISS && code_object<MONO>(sc, cs, 0u) == uint32_t(L.twin_object));
+    return cs != CODE_MISS && ts >= dist * (1.f - 1e-3f) && twin;
 }
 // Continue or end: Russian roulette / max_bounces, phase or BSDF sample, path weight (src/renderer.rs:222-232, 262-281, 301-313)
 template <bool MEDIUM, bool COUNT>
@@ -1268,15 +1308,23 @@ void render_kernel(const RenderArgs a) {
                 illuminate_object<GROUPS>(sc, L, x, rng, I, wi, dist, tab);
                 if (L.twin_object >= 0) {
                     SECTK(8);
-                    float ts = dist * (1.f + 1e-3f);
-                    uint32_t cs = CODE_MISS, is = 0;
-                    // tree-walking scenes: any hit in front of the light on something other than its twin settles the test
-                    const bool range = L.twin_lo <= L.twin_hi;
-                    closest_hit<BVH, COUNT, BVH != 0, MONO>(sc, x, wi, ray_tmin(x), ts, cs, is, stk, stride, c_nodes, c_btris,
-                                                     AnyHit{range ? dist * (1.f - 1e-3f) : -kInf, L.twin_lo, L.twin_hi});
-                    if (COUNT) c_rays++;
-                    SECTK(9);
-                    stage_light_term<MONO>(sc, L, albedo_med, rd, ev_medium, ts, cs, is, dist, I, wi, n, mcol, mat, E);
+                    if constexpr (BVH == 0) {
+                        float ts;
+                        const bool visible = scan_light_visible<MONO>(sc, L, x, wi, dist, ts);
+                        if (COUNT) c_rays++;
+                        SECTK(9);
+                        if (visible) stage_light_add<true>(sc, albedo_med, rd, ev_medium, I, wi, n, mcol, mat, E);
+                    } else {
+                        float ts = dist * (1.f + 1e-3f);
+                        uint32_t cs = CODE_MISS, is = 0;
+                        // tree-walking scenes: any hit in front of the light on something other than its twin settles the test
+                        const bool range = L.twin_lo <= L.twin_hi;
+                        closest_hit<BVH, COUNT, true, MONO>(sc, x, wi, ray_tmin(x), ts, cs, is, stk, stride, c_nodes, c_btris,
+                                                            AnyHit{range ? dist * (1.f - 1e-3f) : -kInf, L.twin_lo, L.twin_hi});
+                        if (COUNT) c_rays++;
+                        SECTK(9);
+                        stage_light_term<MONO>(sc, L, albedo_med, rd, ev_medium, ts, cs, is, dist, I, wi, n, mcol, mat, E);
+                    }
                 }
             }
             // Point / Directional lights can never satisfy the reference's test (dist is the
@@ -1568,6 +1616,30 @@ __global__ __launch_bounds__(256) void debug_medium_distance_kernel(const SceneV
     dmed[i] = d;
     limit[i] = t;
 }
+// rpt_debug_shadow_test: scan_light_visible -- the scan flavours' shadow query and light decision -- for light q.light, one segment
+// per lane: from o along d (as given: the render kernels hand it the unit vector to the sample) with the sample at dist.  MONO as
+// launch_render_t chooses it.  (The SceneView MUST stay the first parameter: see intersect_kernel.)
+template <bool MONO>
+__global__ __launch_bounds__(256) void debug_shadow_test_kernel(const SceneView sc, const ShadowTestArgs q) {
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= q.n) return;
+    const Light L = uload(&sc.lights[q.light]);
+    float ts;
+    const bool vis = scan_light_visible<MONO>(sc, L, mk(q.o[3 * i], q.o[3 * i + 1], q.o[3 * i + 2]), mk(q.d[3 * i], q.d[3 * i + 1], q.d[3 * i + 2]),
+                                              q.dist[i], ts);
+    q.flag[i] = vis ? 1 : 0;
+    q.t[i] = ts;
+}
+// rpt_debug_distance_pair: medium_distance and medium_distance_guarded for the draws k0 .. k0 + n - 1, inv_sigma_t as render_kernel forms it.
+__global__ __launch_bounds__(256) void debug_distance_pair_kernel(float sigma_t, uint32_t k0, uint32_t n, float* __restrict__ out_new,
+                                                                  float* __restrict__ out_guarded) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float inv_sigma_t = 1.f / sigma_t;
+    const float xi = float(((k0 + i) << 1) | 1u) * 0x1p-24f;   // Rng::uniform's value for the word's top 23 bits k0 + i (range(0, 1) returns it as it is)
+    out_new[i] = medium_distance(xi, inv_sigma_t);
+    out_guarded[i] = medium_distance_guarded(xi, inv_sigma_t);
+}
 // rpt_debug_bounce: the render kernels' own stage_bounce at a surface or a medium event.  Of the RenderArgs the stage reads
 // max_bounces alone (COUNT = false: no counters); they stay the first parameter as in render_kernel.
 template <bool MEDIUM>
@@ -1734,6 +1806,16 @@ hipError_t launch_debug_env_color(const SceneView& sc, uint64_t n, const float* 
 hipError_t launch_debug_medium_distance(const SceneView& sc, uint64_t n, uint64_t seed_mixed, float* d_dmed, float* d_limit,
                                         hipStream_t s) {
     hipLaunchKernelGGL(debug_medium_distance_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, s, sc, n, seed_mixed, d_dmed, d_limit);
+    return hipGetLastError();
+}
+hipError_t launch_debug_shadow_test(const SceneView& sc, const ShadowTestArgs& q, hipStream_t s) {
+    const dim3 grid(uint32_t((q.n + 255) / 256));
+    if (sc.n_mono) hipLaunchKernelGGL(debug_shadow_test_kernel<true>, grid, dim3(256), 0, s, sc, q);
+    else hipLaunchKernelGGL(debug_shadow_test_kernel<false>, grid, dim3(256), 0, s, sc, q);
+    return hipGetLastError();
+}
+hipError_t launch_debug_distance_pair(float sigma_t, uint32_t k0, uint32_t n, float* d_new, float* d_guarded, hipStream_t s) {
+    hipLaunchKernelGGL(debug_distance_pair_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, sigma_t, k0, n, d_new, d_guarded);
     return hipGetLastError();
 }
 hipError_t launch_debug_bounce(const BounceArgs& q, hipStream_t s) {

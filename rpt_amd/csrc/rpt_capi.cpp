@@ -64,6 +64,8 @@ struct rpt_options {
     int64_t scan_specialise = 1;    // mark y-rotated sphere / cube records and box pairs with common slabs for the unmasked scans (read by rpt_scene_commit)
     int64_t scan_cull = 1;          // primary scans in a medium leave out their tail -- boxes, rectangles, triangles -- when no lane's search interval reaches
                                     // the box around it (read by rpt_scene_commit; 0: the plain scans)
+    int64_t shadow_scan = 1;        // shadow queries of the scan flavours keep one bit, "the closest hit is a record of the light's twin", instead of the hit
+                                    // code, for every light whose twin is one range of scanned records (read by rpt_scene_commit; 0: the closest-hit scan)
     int64_t photon_skip = 0;
     int64_t photon_block_lists = 1;
     int64_t photon_coop_gather = 1; // surface gather of a pixel's samples by the wave together (0: one search per lane)
@@ -107,6 +109,7 @@ static int set_option_in(rpt_options& o, const char* name, int64_t value) {
     else if (s == "room_shell") o.room_shell = value;
     else if (s == "scan_specialise") o.scan_specialise = value;
     else if (s == "scan_cull") o.scan_cull = value;
+    else if (s == "shadow_scan") o.shadow_scan = value;
     else if (s == "photon_skip") o.photon_skip = value;
     else if (s == "photon_block_lists") o.photon_block_lists = value;
     else if (s == "photon_parts") o.photon_parts = value;
@@ -539,6 +542,7 @@ struct rpt_scene {
     int last_blocks = 0;
     uint64_t prims_per_ray = 0;
     uint32_t n_twin_lights = 0;  // Light::Objects with a twin among the scene's objects (the ones that can be visible)
+    std::vector<Light> light_records;  // the committed light list as the device has it (rpt_shadow_scan_info)
     bool twins_scanned = false;  // every Light::Object that can be visible has its twin among the scanned records, as one range of hit codes
     uint64_t stats[16] = {0};
     void* photon = nullptr;  // PhotonMapDev*, owned by photon.hip
@@ -1314,6 +1318,18 @@ struct Flattener {
             for (size_t i = 1; i < codes.size(); i++) contiguous = contiguous && codes[i] == codes[i - 1] + 1u;
             if (contiguous) { L.twin_lo = codes.front(); L.twin_hi = codes.back(); }
         }
+        // ---- the scans' shadow form (option "shadow_scan"; scan_prims<.., SHADOW>): for a light whose twin is one index range of ONE kind
+        // that the linear scan tests record by record.  Not: a range that reaches the shell's faces (their codes follow the scanned
+        // rectangles': the shell picks its face inside one test), planes (no light shape), anything in a tree, and no range at all (group
+        // lights, monomial surfaces: they get no codes above).  Those lights keep the closest-hit scan.
+        for (Light& L : lights) {
+            L.color.w = 0.f;
+            if (L.kind != L_OBJECT || L.twin_object < 0 || !(L.twin_lo <= L.twin_hi) || !s->opt.shadow_scan) continue;
+            const uint32_t kind = L.twin_lo >> 28, last = L.twin_hi & 0x0FFFFFFFu;
+            const bool one_kind = (L.twin_hi >> 28) == kind;
+            const bool scanned = kind == K_SPHERE || kind == K_CUBE || kind == K_AABB || kind == K_TRI || (kind == K_RECT && last < rect.size());
+            if (one_kind && scanned) L.color.w = bits_f(1u);
+        }
 
     }
     // (5) the scene-level tree (many-primitive scenes only)
@@ -1696,6 +1712,7 @@ struct Flattener {
         v.hdri_w = s->hdri_w;
         v.hdri_h = s->hdri_h;
         s->prims_per_ray = sph.size() + cub.size() + pln.size() + tri.size() + aabb.size() + rect.size() + (has_shell ? 1 : 0);
+        s->light_records = lights;
         s->twins_scanned = true;
         s->n_twin_lights = 0;
         for (const Light& L : lights) {
@@ -2902,6 +2919,61 @@ int rpt_debug_medium_distance(rpt_scene* s, uint64_t n, uint64_t seed, float* dm
     HIP_TRY(launch_debug_medium_distance(s->view, n, seed_mix(seed), d_m.get<float>(), d_t.get<float>(), nullptr));
     HIP_TRY(hipMemcpy(dmed, d_m.get(), n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(t_limit, d_t.get(), n * 4, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+int rpt_debug_shadow_test(rpt_scene* s, uint32_t light, uint64_t n, const float* origins, const float* dirs, const float* dist,
+                          int32_t* out_flag, float* out_t) {
+    if (!s || !origins || !dirs || !dist || !out_flag || !out_t) return fail(RPT_ERR_INVALID, "null argument");
+    if (rpti::light_kind(s, light) != int(L_OBJECT)) return fail(RPT_ERR_INVALID, "rpt_debug_shadow_test: not a Light::Object");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (s->dev.arena64) return fail(RPT_ERR_STATE, "rpt_debug_shadow_test: the scene was committed with epsilon_policy = 1");
+    if (s->view.n_nodes != 0 || s->view.scene_bvh || s->view.n_inst)
+        return fail(RPT_ERR_UNSUPPORTED, "rpt_debug_shadow_test: the scene has a tree (the query is the linear scan's)");
+    if (!launch_debug_shadow_test) return fail(RPT_ERR_UNSUPPORTED, "rpt_debug_shadow_test: built without the kernels");
+    if (n == 0) return RPT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    rpti::DevMem d_in, d_out;   // d_in: origins, dirs (3 n each), dist (n); d_out: flag, t (n each)
+    HIP_TRY(hook_scratch(d_in, n * 28));
+    HIP_TRY(hook_scratch(d_out, n * 8));
+    float* const in = d_in.get<float>();
+    HIP_TRY(hipMemcpy(in, origins, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(in + 3 * n, dirs, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(in + 6 * n, dist, n * 4, hipMemcpyHostToDevice));
+    ShadowTestArgs q{};
+    q.light = light;
+    q.n = n;
+    q.o = in; q.d = in + 3 * n; q.dist = in + 6 * n;
+    q.flag = d_out.get<int32_t>();
+    q.t = d_out.get<float>() + n;
+    HIP_TRY(launch_debug_shadow_test(s->view, q, nullptr));
+    HIP_TRY(hipMemcpy(out_flag, q.flag, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_t, q.t, n * 4, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+int rpt_shadow_scan_info(rpt_scene* s, uint32_t light, uint32_t out[4]) {
+    if (!s || !out) return fail(RPT_ERR_INVALID, "null argument");
+    if (rpti::light_kind(s, light) != int(L_OBJECT)) return fail(RPT_ERR_INVALID, "rpt_shadow_scan_info: not a Light::Object");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (s->dev.arena64) return fail(RPT_ERR_STATE, "rpt_shadow_scan_info: the scene was committed with epsilon_policy = 1");
+    if (light >= s->light_records.size()) return fail(RPT_ERR_STATE, "rpt_shadow_scan_info: the light was added after the commit");
+    const Light& L = s->light_records[light];
+    out[0] = L.twin_lo;
+    out[1] = L.twin_hi;
+    out[2] = (bits_u(L.color.w) != 0u && bvh_mode(s->view) == 0) ? 1u : 0u;   // (only the scan kernels read the mark)
+    out[3] = uint32_t(L.twin_object);
+    return RPT_OK;
+}
+int rpt_debug_distance_pair(float sigma_t, uint32_t k0, uint32_t n, float* out_new, float* out_guarded) {
+    if (!out_new || !out_guarded) return fail(RPT_ERR_INVALID, "null argument");
+    if (!(sigma_t > 0.f) || !(sigma_t < INFINITY)) return fail(RPT_ERR_INVALID, "rpt_debug_distance_pair: sigma_t must be positive and finite");
+    if (k0 >= (1u << 23) || n > (1u << 23) - k0) return fail(RPT_ERR_INVALID, "rpt_debug_distance_pair: a draw has 23 bits (k0 + n <= 2^23)");
+    if (!launch_debug_distance_pair) return fail(RPT_ERR_UNSUPPORTED, "rpt_debug_distance_pair: built without the kernels");
+    if (n == 0) return RPT_OK;
+    rpti::DevMem d_out;
+    HIP_TRY(hook_scratch(d_out, size_t(n) * 8));
+    HIP_TRY(launch_debug_distance_pair(sigma_t, k0, n, d_out.get<float>(), d_out.get<float>() + n, nullptr));
+    HIP_TRY(hipMemcpy(out_new, d_out.get<float>(), size_t(n) * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_guarded, d_out.get<float>() + n, size_t(n) * 4, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
