@@ -539,6 +539,15 @@ class Renderer {
         sample_offset_ += iterations;
     }
 
+    // The candidate trees of the reference-epsilon mode's large meshes (rpt_hip.h, rpt_f64_mesh_tree_info): meshes, triangles, nodes,
+    // depth, bytes, render uses the trees, photon passes use them, threshold.  Throws for a scene of the fp32 path.
+    std::array<uint64_t, 8> f64_mesh_tree_info() {
+        commit();
+        std::array<uint64_t, 8> out{};
+        check(rpt_f64_mesh_tree_info(handle_, out.data()));
+        return out;
+    }
+
   private:
     void commit() {
         if (handle_) return;

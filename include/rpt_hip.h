@@ -362,7 +362,7 @@ int rpt_frame_unpack_device(uint32_t width, uint32_t height, uint32_t rank, uint
  * colours, no fused multiply-adds (only the objects a ray's padded fp32 box test keeps are evaluated -- the result is that of
  * the full scan bit for bit; option "f64_cull" = 0 runs the full scan).  Same entry points (rpt_render_sample*,
  * rpt_render_into_buffer), same RNG streams, same sharding; 4-5 times slower than the fp32 path (C3: 2.9 Gsamples/s).
- * Supported: spheres, cubes, planes, meshes (scanned triangle by triangle), monomial surfaces, KdTree groups of them as objects and as
+ * Supported: spheres, cubes, planes, meshes (scanned triangle by triangle, or through a candidate tree: rpt_f64_mesh_tree_info), monomial surfaces, KdTree groups of them as objects and as
  * Light::Objects (nested at most three deep), all materials, lights and media, Environment::Color and Environment::Hdri.
  * Photon mapping (rpt_photon_map_build, rpt_photon_render_sample*): the shooting pass and the surface estimate's visibility rays run in
  * fp64 with the reference's tests (t_min = 1e-12; a gathered photon counts unless len > hit.time, src/photon.rs:357-361); the maps, the
@@ -380,6 +380,20 @@ int rpt_frame_unpack_device(uint32_t width, uint32_t height, uint32_t rank, uint
  * schedule: [8] objects evaluated in fp64 (all lanes), [9] wave-level evaluation rounds, [10] wave-level loop trips, [11] lanes
  * holding a path summed over the trips. */
 int rpt_debug_epsilon_counters(rpt_scene*, uint64_t out[12]);
+/* The candidate trees of the mode's large meshes.  Scene option "f64_mesh_tree_min" (64; read by rpt_scene_commit): every distinct
+ * mesh of at least that many triangles gets a binary tree over its triangles, in the mesh's own space (0 = never, 1 = every mesh;
+ * "f64_cull" = 0 disables the trees as well; a mesh that several shapes share has one tree; a mesh with needle triangles, whose
+ * barycentric test is ill-conditioned, keeps the scan).  A tree only chooses which triangles a ray is tested against: the test is
+ * the scan's, in fp64, and the result is that of the scan over all of them in given order -- the smallest accepted time, the
+ * smallest index among the triangles that reach it -- bit for bit.  Node boxes: the fp64 box of the vertices, padded by 1e-5 of its
+ * extent and of its coordinates, rounded outwards to fp32.  Depth limit and builder options as for the fp32 path's mesh trees
+ * ("bvh_max_depth", "bvh_leaf_max", "bvh_sweep_below"); RPT_ERR_UNSUPPORTED from rpt_scene_commit only if a balanced tree is still too deep.
+ * The render and rpt_intersect_batch_f64 walk the trees; scenes with a monomial surface or a group light, and the photon passes of
+ * the mode, scan every triangle as before.
+ * out: [0] meshes with a tree, [1] triangles under trees, [2] nodes, [3] levels below the root of the deepest tree, [4] bytes on the
+ * device, [5] 1: the render and the batch query walk the trees, 0: they scan (no tree, or a flavour without the walk), [6] the same
+ * for the photon passes (0), [7] the threshold the scene was committed with.  RPT_ERR_STATE: not committed, or an fp32 scene. */
+int rpt_f64_mesh_tree_info(rpt_scene*, uint64_t out[8]);
 
 /* ---- device self-test hooks (each runs the device function in a one-block kernel) ---- */
 int rpt_debug_rng_u32(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t n, uint32_t* out);

@@ -978,6 +978,15 @@ class Renderer:
                                                nrm.ctypes.data_as(C.c_void_p)))
         return t, obj, nrm
 
+    def f64_mesh_tree_info(self):
+        """The candidate trees of the reference-epsilon mode's large meshes (scene option "f64_mesh_tree_min") -> dict of meshes,
+        triangles, nodes, depth, bytes, render_uses_trees, photon_uses_trees (1: the pass walks the trees, 0: it scans every
+        triangle) and tree_min.  RPT_ERR_STATE for an fp32 scene."""
+        out = (C.c_uint64 * 8)()
+        _lib.check(_lib.load().rpt_f64_mesh_tree_info(self.scene._commit(self.device_), out))
+        keys = ("meshes", "triangles", "nodes", "depth", "bytes", "render_uses_trees", "photon_uses_trees", "tree_min")
+        return {k: int(v) for k, v in zip(keys, out)}
+
     # ---- per-call hooks on the committed scene (rpt_debug_*): one device-function call per case
     def debug_light_sample(self, light_index, positions, seed=0, f64=False):
         """Shape::sample and Light::illuminate of Light::Object `light_index` at n positions, case i on stream (seed, i, 0), by the

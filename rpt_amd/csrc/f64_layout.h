@@ -93,6 +93,21 @@ struct ObjShade {
 struct TriShade {
     double n1[3], n2[3], n3[3];
 };
+// ---- the candidate tree of a large mesh (scene option "f64_mesh_tree_min"; kernels_f64.hip, eval_pair<.., TREE>)
+// A binary tree over the mesh's triangles in the mesh's own space -- the space Triangle::intersect runs in, after the frames' and the
+// shape's own M^-1.  It decides only WHICH triangles a ray is tested against: the test is the fp64 one of the scan, and a visited
+// triangle replaces the running hit iff its time is smaller, or equal with a smaller index -- the result of the scan's loop in given
+// order, whatever the order of the visits.  A node's box is the fp64 box of its triangles' vertices, grown by CullBox's rule (1e-5 of
+// its largest extent and of its largest coordinate) and rounded outwards to fp32; the slab test is cull32's.  32 bytes.
+struct MeshNode {
+    float lo[3];
+    uint32_t left_or_first;   // inner: its children are nodes left, left + 1 (of Args::mnodes); leaf: first entry of Args::mleaf
+    float hi[3];
+    uint32_t count;           // 0: inner; else a leaf of `count` triangles
+};
+static constexpr uint32_t kMeshTreeStack = 24u;      // entries of a walk's stack: one per level
+static constexpr uint32_t kMeshTreeMaxDepth = 20u;   // levels below the root a committed tree may have (option "bvh_max_depth" <= 20)
+static_assert(kMeshTreeMaxDepth + 1u <= kMeshTreeStack, "a walk keeps at most one deferred sibling per level");
 
 struct Scene {
     const CullBox* cull;        // [n_objects]: one per record (a group's children are records of their own)
@@ -140,7 +155,12 @@ struct Args {
     double* slab;                   // [n_chunks][n_owned][4]: partial sums of (pixel, chunk) items
     unsigned long long* counters;   // [0] rays [1] accepted hits [2] self hits [3] shadow tests [4] passed [5] near misses [6] samples [7] vertices
                                     // [8] objects evaluated [9] evaluation rounds (wave-level) [10] trips (wave-level) [11] live lanes summed over trips; or null
-    uint32_t mono;            // some object is a MonomialSurface (its own kernel instantiation; last: the fields above keep their offsets)
+    uint32_t mono;            // some object is a MonomialSurface (its own kernel instantiation; the fields above keep their offsets)
+    // the mesh trees (behind everything else, for the same reason; read by the TREE instantiations only)
+    uint32_t tree;            // some mesh has a candidate tree and the closest-hit query of render / intersect walks it (a flavour of its own)
+    const MeshNode* mnodes;   // the nodes of every tree
+    const uint32_t* mleaf;    // the leaves' triangles: indices into Scene::trecs, i.e. the given order is kept there
+    const uint32_t* mroot;    // [n_objects]: root node + 1 of the record's mesh, 0: none (the triangles are scanned)
 };
 
 // rpt_intersect_batch_f64 (kernels_f64.hip, intersect_f64_kernel): the closest-hit query of this mode over n rays.

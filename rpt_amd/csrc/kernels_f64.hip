@@ -129,12 +129,110 @@ struct PairHit {
     uint32_t aux;
 };
 
+// The triangles of a mesh that has a candidate tree (f64_layout.h, MeshNode; the TREE instantiations): a stack walk on the lane that
+// holds the pair, in place of eval_pair's loop over all of them.
+// What the loop computes is (the smallest accepted time, the smallest index among the triangles that reach it): a triangle replaces
+// the hit iff time >= kEps, time < h.t and u, v, w >= 0, in given order.  That minimum does not depend on the order of the tests, so the
+// walk may visit triangles in any order and leave out any that the loop would not accept -- given the rule `time < h.t, or time == h.t
+// and a smaller index` and the same fp64 test.  A triangle the loop accepts at time t holds the point o + t d up to the rounding of its
+// barycentric test (the commit keeps meshes with needle triangles, whose test is ill-conditioned, on the scan), so the ray crosses every
+// box above it at a time <= t: the slab test is cull32's -- boxes padded at commit, the origin's error in `eo`, the interval widened by
+// 4e-6 relative, and a comparison that a NaN (0 * inf) makes false keeps the node.  Nodes that begin beyond the lane's search limit or
+// beyond the hit at hand (both rounded up to fp32 and widened by 1e-5; an equal time is NOT beyond: its index may be smaller) are left out.
+// The stack holds one deferred sibling per level with its entry time (kMeshTreeStack entries, in scratch: the LDS of a block is spoken
+// for -- four blocks per CU --, and only this flavour pays for it); the commit limits the depth.
+template <class TP>
+R64_DEV void mesh_tree_walk(TP trecs, uint32_t root, D ol, D dl, float tl, PairHit& h) {
+    const MeshNode* const nodes = KA.mnodes;
+    const uint32_t* const leaf = KA.mleaf;
+    const float ox = float(ol.x), oy = float(ol.y), oz = float(ol.z);
+    const float eo = 1e-6f * fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
+    // A ray that fp32 cannot hold constrains nothing: a direction component that is not zero but rounds to zero, to a denormal or to
+    // infinity gets a NaN for its reciprocal (that axis's slab is then ignored: fminf / fmaxf drop a NaN operand), an origin beyond
+    // fp32 gets three.  An exact zero keeps its infinite reciprocal: the ray is parallel to that slab, inside it or beside it.
+    const bool far = !(eo < __builtin_huge_valf());
+    auto recip = [far](double c) {
+        const float f = float(c);
+        const bool lost = (c != 0.0 && fabsf(f) < 1.17549435e-38f) || fabsf(f) == __builtin_huge_valf() || far;
+        return lost ? __builtin_nanf("") : __builtin_amdgcn_rcpf(f);
+    };
+    const float ix = recip(dl.x), iy = recip(dl.y), iz = recip(dl.z);
+    const float oxl = ox + eo, oyl = oy + eo, ozl = oz + eo, oxh = ox - eo, oyh = oy - eo, ozh = oz - eo;
+    float lim = tl;
+    // cull32's test of one node; `tn_lo`: the widened entry time (NaN: unknown, every comparison keeps the node).  The widening by 4e-6 is
+    // written as the smaller / larger of two products, so that the infinite entry time of a ray that runs parallel to a slab and beside it
+    // stays infinite (inf - 4e-6 inf would be a NaN, and the node would be visited for nothing).
+    auto out_of_reach = [&](const rptg::F4 lo, const rptg::F4 hi, float& tn_lo) {
+        const float x1 = (lo.x - oxl) * ix, x2 = (hi.x - oxh) * ix;
+        const float y1 = (lo.y - oyl) * iy, y2 = (hi.y - oyh) * iy;
+        const float z1 = (lo.z - ozl) * iz, z2 = (hi.z - ozh) * iz;
+        const float tn = fmaxf(fmaxf(fminf(x1, x2), fminf(y1, y2)), fminf(z1, z2));
+        const float tf = fminf(fminf(fmaxf(x1, x2), fmaxf(y1, y2)), fmaxf(z1, z2));
+        const float tf_hi = fmaxf(tf * (1.f - 4e-6f), tf * (1.f + 4e-6f));
+        tn_lo = fminf(tn * (1.f - 4e-6f), tn * (1.f + 4e-6f));
+        return tn_lo > tf_hi || tf_hi < 0.f || tn_lo > lim;
+    };
+    uint32_t stack_n[kMeshTreeStack];
+    float stack_t[kMeshTreeStack];
+    uint32_t sp = 0u, cur = root;
+    for (;;) {
+        const rptg::F4 a = reinterpret_cast<const rptg::F4*>(nodes + cur)[0], b = reinterpret_cast<const rptg::F4*>(nodes + cur)[1];
+        const uint32_t first = __float_as_uint(a.w), count = __float_as_uint(b.w);
+        bool descend = false;
+        if (count != 0u) {
+            for (uint32_t k = 0; k < count; k++) {   // Triangle::intersect, src/shape/mesh.rs:50-83: eval_pair's, with the order-free rule
+                const uint32_t j = leaf[first + k];
+                const auto& tr = trecs[j];
+                const D pn = ld(tr.pn), v1 = ld(tr.v1);
+                const double cosine = dot(pn, dl);
+                if (fabs(cosine) < 1e-8) continue;
+                const double time = dot(pn, v1 - ol) / cosine;
+                if (time < kEps || !(time < h.t || (time == h.t && j < h.aux))) continue;   // (a NaN time goes no further: it could not pass u, v, w >= 0)
+                const D d2 = (ol + time * dl) - v1;
+                const double d20 = dot(d2, ld(tr.d0)), d21 = dot(d2, ld(tr.d1));
+                const double v = (tr.d11 * d20 - tr.d01 * d21) / tr.denom, w = (tr.d00 * d21 - tr.d01 * d20) / tr.denom;
+                const double u = 1.0 - v - w;
+                if (u >= 0.0 && v >= 0.0 && w >= 0.0) {
+                    h.t = time;
+                    h.aux = j;
+                    lim = fminf(tl, float(time) * 1.00001f);
+                }
+            }
+        } else {
+            const rptg::F4* const c = reinterpret_cast<const rptg::F4*>(nodes + first);
+            float t0, t1;
+            const bool out0 = out_of_reach(c[0], c[1], t0), out1 = out_of_reach(c[2], c[3], t1);
+            if (!out0 && !out1) {   // the nearer child first; the other waits with its entry time (a NaN: either order)
+                const bool swap = t1 < t0;
+                if (sp < kMeshTreeStack) {   // (always: the commit limits the depth)
+                    stack_n[sp] = swap ? first : first + 1u;
+                    stack_t[sp] = swap ? t0 : t1;
+                    sp++;
+                }
+                cur = swap ? first + 1u : first;
+                descend = true;
+            } else if (!out0 || !out1) {
+                cur = out0 ? first + 1u : first;
+                descend = true;
+            }
+        }
+        if (descend) continue;
+        for (;;) {   // the next deferred node that the hit at hand has not put out of reach
+            if (sp == 0u) return;
+            sp--;
+            cur = stack_n[sp];
+            if (!(stack_t[sp] > lim)) break;
+        }
+    }
+}
+
 // Shape::intersect of object i (Transformed::intersect around it when has_xf, src/shape.rs:128-138; Ray::apply_transform
 // does not renormalise the direction, so t is shared) on an empty record.
 // MONO: the scene holds monomial surfaces (SH_MONO records: an instantiation of its own, see render_f64_kernel).
 static constexpr uint32_t kMonoHit = 0x80000000u;   // PairHit::aux / Query::aux of a monomial surface's hit (see closest_hit_wave)
-template <bool COUNT, bool MONO = false, class RP, class TP>
-R64_DEV PairHit eval_pair(RP recs, TP trecs, uint32_t i, D o, D d) {
+// TREE: some mesh has a candidate tree (Args::mroot; an instantiation of its own); `tl`: the owner's search limit in fp32 (TREE only).
+template <bool COUNT, bool MONO = false, bool TREE = false, class RP, class TP>
+R64_DEV PairHit eval_pair(RP recs, TP trecs, uint32_t i, D o, D d, float tl = 0.f) {
     SECT64(5);
     PairHit h{kInf, -kInf, 0u};
     const auto& r = recs[i];
@@ -286,6 +384,13 @@ R64_DEV PairHit eval_pair(RP recs, TP trecs, uint32_t i, D o, D d) {
             const double own = fmax(b_min, kEps);
             h.bm = fmax(bm, own);
             if (!(own > fmin(b_max, kInf))) {
+                if constexpr (TREE) {
+                    const uint32_t root = KA.mroot[i];
+                    if (root != 0u) {   // (a mesh below the threshold keeps the loop)
+                        mesh_tree_walk(trecs, root - 1u, ol, dl, tl, h);
+                        return h;
+                    }
+                }
                 for (uint32_t j = 0; j < r.tri_count; j++) {   // Triangle::intersect, src/shape/mesh.rs:50-83
                     SECT64(11);
                     const auto& tr = trecs[r.tri_first + j];
@@ -364,6 +469,7 @@ R64_DEV double lane_read(double v, uint32_t src_lane) {
     const uint32_t lo = lane_read(uint32_t(u), src_lane), hi = lane_read(uint32_t(u >> 32), src_lane);
     return __longlong_as_double((long long)((uint64_t(hi) << 32) | lo));
 }
+R64_DEV float lane_read(float v, uint32_t src_lane) { return __uint_as_float(lane_read(__float_as_uint(v), src_lane)); }
 R64_DEV D lane_read(D v, uint32_t src_lane) { return mk(lane_read(v.x, src_lane), lane_read(v.y, src_lane), lane_read(v.z, src_lane)); }
 
 // Renderer::get_closest_hit, src/renderer.rs:416-425, for the wave's queries together.  EVERY lane of the wave calls this
@@ -387,7 +493,10 @@ R64_DEV D lane_read(D v, uint32_t src_lane) { return mk(lane_read(v.x, src_lane)
 // produce --; after a NaN record only the objects whose own test lets it through replace it: another
 // monomial surface, or a mesh with a triangle hit (Triangle::intersect's `time >= record.time` is false against NaN, and the
 // first triangle hit turns the record finite again: the mesh's closest triangle is the result, as on the empty record).
-template <bool COUNT, bool MONO = false, class RP, class TP>
+//
+// TREE (scenes in which a mesh has a candidate tree): the slot lane walks that mesh's tree instead of scanning its triangles
+// (mesh_tree_walk: the same PairHit, bit for bit) and takes the owner's search limit along with its ray.
+template <bool COUNT, bool MONO = false, bool TREE = false, class RP, class TP>
 R64_DEV void closest_hit_wave(RP recs, TP trecs, volatile uint32_t* slots, bool mine, D o, D d, double tlim, Query& q, uint32_t& c_evals,
                               uint32_t& c_rounds) {
     SECT64(3);
@@ -453,10 +562,13 @@ R64_DEV void closest_hit_wave(RP recs, TP trecs, volatile uint32_t* slots, bool 
             // ---- a slot lane takes its pair's ray from the owner and evaluates the object
             const uint32_t owner = info ? (info & 0xFFu) - 1u : lane;
             const D po = lane_read(o, owner), pd = lane_read(d, owner);
+            float ptl = 0.f;
+            if constexpr (TREE) ptl = lane_read(tl, owner);   // (outside the branch below: every lane takes part in the exchange)
             PairHit ph{kInf, -kInf, 0u};
             if (info != 0u) {
                 if (COUNT) c_evals++;
-                ph = eval_pair<COUNT, MONO>(recs, trecs, info >> 8, po, pd);
+                if constexpr (TREE) ph = eval_pair<COUNT, MONO, true>(recs, trecs, info >> 8, po, pd, ptl);
+                else ph = eval_pair<COUNT, MONO>(recs, trecs, info >> 8, po, pd);
             }
             // ---- the owners collect, rank by rank = in scene order
             uint32_t cum = 0u;
@@ -821,7 +933,9 @@ static_assert(kLdsDoubles * 8u * 4u <= 160u * 1024u, "four blocks per CU");
 // megakernel -- inlined beside the wave-uniform sampler it cost C3 1.3 % through register allocation alone.
 // MONO: some object is a MonomialSurface (eval_pair's ~700-flop quartic, closest_hit_wave's tie and NaN rules): an instantiation of
 // its own for the same reason -- C3eps already spills.
-template <bool MEDIUM, bool COUNT, bool LDSTAB, bool GROUPL = false, bool MONO = false>
+// TREE: some mesh has a candidate tree (closest_hit_wave, mesh_tree_walk: a stack in scratch) -- an instantiation of its own once more, so
+// that scenes without one run the kernels they ran before there were trees.  (Not combined with GROUPL or MONO: those scenes scan.)
+template <bool MEDIUM, bool COUNT, bool LDSTAB, bool GROUPL = false, bool MONO = false, bool TREE = false>
 __global__ __launch_bounds__(256, R64_WAVES) void render_f64_kernel(const Args a_by_value) {
     (void)a_by_value;   // (read through KA)
     extern __shared__ double lds64[];
@@ -995,7 +1109,7 @@ __global__ __launch_bounds__(256, R64_WAVES) void render_f64_kernel(const Args a
         const uint32_t n_lights = KA.sc.n_lights;
         for (uint32_t sub = 0;; sub++) {
             Query q;
-            closest_hit_wave<COUNT, MONO>(recs, trecs, slots, active, ro, rd, qlim, q, c_evals, c_rounds);
+            closest_hit_wave<COUNT, MONO, TREE>(recs, trecs, slots, active, ro, rd, qlim, q, c_evals, c_rounds);
             if (active) {
                 SECT64(14);
                 if (sub == 0) {
@@ -1487,7 +1601,7 @@ __global__ __launch_bounds__(256) void resolve_photon_f64_kernel(const Args a, c
 // rpt_intersect_batch_f64: Renderer::get_closest_hit (src/renderer.rs:416-425) of this mode for n rays, one per lane -- the
 // query of the render kernel (closest_hit_wave, t_min = 1e-12) and its normal (hit_normal).
 #define KI (*rptg::kernarg_args<IsectArgs64>())
-template <bool LDSTAB, bool MONO>
+template <bool LDSTAB, bool MONO, bool TREE = false>
 __global__ __launch_bounds__(256) void intersect_f64_kernel(const IsectArgs64 by_value) {
     (void)by_value;
     extern __shared__ double lds64[];
@@ -1504,7 +1618,7 @@ __global__ __launch_bounds__(256) void intersect_f64_kernel(const IsectArgs64 by
     }
     Query q;
     uint32_t ce = 0, cr = 0;
-    closest_hit_wave<false, MONO>(recs, trecs, slots, mine, o, d, kInf, q, ce, cr);
+    closest_hit_wave<false, MONO, TREE>(recs, trecs, slots, mine, o, d, kInf, q, ce, cr);
     if (!mine) return;
     D n = mk(0, 0, 0);
     if (q.obj >= 0) n = hit_normal<MONO>(recs, trecs, q, o, d);
@@ -1608,6 +1722,9 @@ static hipError_t launch_intersect_f64(const rpt64::IsectArgs64& a, hipStream_t 
     if (a.a.mono) {
         if (tab) hipLaunchKernelGGL((rpt64::intersect_f64_kernel<true, true>), grid, dim3(256), lds, stream, a);
         else hipLaunchKernelGGL((rpt64::intersect_f64_kernel<false, true>), grid, dim3(256), lds, stream, a);
+    } else if (a.a.tree) {
+        if (tab) hipLaunchKernelGGL((rpt64::intersect_f64_kernel<true, false, true>), grid, dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL((rpt64::intersect_f64_kernel<false, false, true>), grid, dim3(256), lds, stream, a);
     } else {
         if (tab) hipLaunchKernelGGL((rpt64::intersect_f64_kernel<true, false>), grid, dim3(256), lds, stream, a);
         else hipLaunchKernelGGL((rpt64::intersect_f64_kernel<false, false>), grid, dim3(256), lds, stream, a);
@@ -1631,6 +1748,9 @@ static hipError_t launch_f64_t(const rpt64::Args& a, int n_blocks, hipStream_t s
     if (a.group_lights) {
         if (tab) hipLaunchKernelGGL((rpt64::render_f64_kernel<M, C, true, true>), dim3(n_blocks), dim3(256), lds, stream, a);
         else hipLaunchKernelGGL((rpt64::render_f64_kernel<M, C, false, true>), dim3(n_blocks), dim3(256), lds, stream, a);
+    } else if (a.tree) {   // (the host sets it only for scenes without group lights and monomial surfaces)
+        if (tab) hipLaunchKernelGGL((rpt64::render_f64_kernel<M, C, true, false, false, true>), dim3(n_blocks), dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL((rpt64::render_f64_kernel<M, C, false, false, false, true>), dim3(n_blocks), dim3(256), lds, stream, a);
     } else {
         if (tab) hipLaunchKernelGGL((rpt64::render_f64_kernel<M, C, true, false>), dim3(n_blocks), dim3(256), lds, stream, a);
         else hipLaunchKernelGGL((rpt64::render_f64_kernel<M, C, false, false>), dim3(n_blocks), dim3(256), lds, stream, a);

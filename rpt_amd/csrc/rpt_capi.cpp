@@ -92,6 +92,8 @@ struct rpt_options {
                                     // 0: they stay outside it and their walks are parked as in scenes without a scene tree (read by rpt_scene_commit)
     int64_t f64_cull = 1;           // reference-epsilon mode: 1 = a lane evaluates only the objects whose fp32 box its ray can reach (same bits), 0 = every object;
                                     // 2 = as 1, and the counters build keeps the search limits as well (its counters then describe the schedule, not the reference's work)
+    int64_t f64_mesh_tree_min = 64; // reference-epsilon mode: triangles from which a mesh gets a candidate tree (read by rpt_scene_commit; 0 = never, 1 = every mesh;
+                                    // f64_cull = 0 disables the trees as well).  Same bits as the scan of all its triangles
     int64_t f64_photon_slice = 0;   // reference-epsilon photon camera pass: samples per slice (0: as many whole chunks of 256 as fit 32 GB of per-sample selections)
     int64_t f64_surf_batch = 8;     // reference-epsilon mode, scenes with a medium: lanes of a wave that wait at a surface event before the wave runs the surface code (1..64)
     int64_t epsilon_policy = 0;     // 1: the reference-epsilon mode (read by rpt_scene_commit): fp64, generic shapes, t_min = 1e-12, |hit - dist| < 1e-12
@@ -140,6 +142,7 @@ static int set_option_in(rpt_options& o, const char* name, int64_t value) {
     else if (s == "detach_trigger") { if (value < 1 || value > 32) return fail(RPT_ERR_INVALID, "detach_trigger must be 1..32"); o.detach_trigger = value; }
     else if (s == "defer_stop") { if (value < 1 || value > 64) return fail(RPT_ERR_INVALID, "defer_stop must be 1..64"); o.defer_stop = value; }
     else if (s == "f64_cull") { if (value < 0 || value > 2) return fail(RPT_ERR_INVALID, "f64_cull must be 0, 1 or 2"); o.f64_cull = value; }
+    else if (s == "f64_mesh_tree_min") { if (value < 0 || value > (int64_t(1) << 32)) return fail(RPT_ERR_INVALID, "f64_mesh_tree_min must be 0..2^32"); o.f64_mesh_tree_min = value; }
     else if (s == "f64_photon_slice") { if (value < 0 || value > (1 << 20)) return fail(RPT_ERR_INVALID, "f64_photon_slice must be 0..2^20"); o.f64_photon_slice = value; }
     else if (s == "f64_surf_batch") { if (value < 1 || value > 64) return fail(RPT_ERR_INVALID, "f64_surf_batch must be 1..64"); o.f64_surf_batch = value; }
     else if (s == "epsilon_policy") { if (value < 0 || value > 1) return fail(RPT_ERR_INVALID, "epsilon_policy must be 0 or 1"); o.epsilon_policy = value; }
@@ -549,6 +552,10 @@ struct rpt_scene {
     // reference-epsilon mode (option "epsilon_policy" = 1 at commit): the fp64 scene of kernels_f64.hip in dev.arena64
     rpt64::Scene view64{};
     double medium_color64[3] = {0, 0, 0}, medium_color_hi64[3] = {0, 0, 0};
+    const rpt64::MeshNode* mnodes64 = nullptr;   // the candidate trees of its large meshes (f64_layout.h, Args::mnodes, mleaf, mroot), in dev.arena64
+    const uint32_t* mleaf64 = nullptr;
+    const uint32_t* mroot64 = nullptr;
+    uint64_t mesh_tree_info64[8] = {0};          // rpt_f64_mesh_tree_info
     uint64_t last_counters64[64] = {0};   // [0..11] rpt_debug_epsilon_counters, [16 + 2k], [17 + 2k] section k of kernels_f64.hip (executions, lanes)
     // mesh data interned by content (hash -> candidates), so Arc<Mesh>-style sharing survives the C ABI
     std::unordered_map<uint64_t, std::vector<std::shared_ptr<const std::vector<double>>>> mesh_pool;
@@ -2018,6 +2025,91 @@ static int fill_light_shape64(const HShape& hs, rpt64::Shape& out, std::vector<r
     }
     return RPT_OK;
 }
+// The candidate trees of the reference-epsilon mode's meshes (f64_layout.h, MeshNode; kernels_f64.hip, mesh_tree_walk).
+struct MeshTrees64 {
+    std::vector<rpt64::MeshNode> nodes;
+    std::vector<uint32_t> leaf;    // indices into trecs
+    uint32_t n_meshes = 0, n_tris = 0;
+    int depth = 0;
+};
+// One tree over triangles [first, first + count) of `tris` -- the mesh's own space, where Triangle::intersect runs --, appended to T;
+// returns its root node + 1, 0 if the mesh is to keep the scan, or -1 (error set).  The topology is the fp32 path's builder's (on the
+// triangles' boxes rounded to fp32; limited in depth the same way); the boxes are not: every node gets the fp64 box of its triangles'
+// vertices, padded by CullBox's rule and rounded outwards, so a child's box lies inside its parent's and no box has a zero extent.
+static int64_t build_mesh_tree64(const rpt_options& opt, const std::vector<rpt64::Tri>& tris, const std::vector<rpt64::TriRec>& trecs,
+                                 uint32_t first, uint32_t count, MeshTrees64& T) {
+    std::vector<BTri> bt(count);
+    for (uint32_t i = 0; i < count; i++) {
+        const rpt64::Tri& t = tris[first + i];
+        const rpt64::TriRec& r = trecs[first + i];
+        // a needle: the barycentric test of Triangle::intersect amplifies its rounding by d00 d11 / denom, and what it accepts need no longer
+        // lie within the padding of the triangle's box.  (denom == 0 or NaN: v and w are inf / NaN and nothing is accepted.)
+        if (r.denom != 0.0 && std::fabs(r.denom) < 1e-8 * r.d00 * r.d11) return 0;
+        for (int a = 0; a < 3; a++) {
+            const double lo = std::min(t.v1[a], std::min(t.v2[a], t.v3[a])), hi = std::max(t.v1[a], std::max(t.v2[a], t.v3[a]));
+            if (!std::isfinite(float(lo)) || !std::isfinite(float(hi))) return 0;   // (NaN or beyond fp32: its CullBox is unbounded too)
+            bt[i].lo[a] = float(lo);
+            bt[i].hi[a] = float(hi);
+            bt[i].c[a] = 0.5f * (bt[i].lo[a] + bt[i].hi[a]);
+        }
+        bt[i].idx = i;
+    }
+    const int max_depth = int(std::min<int64_t>(opt.bvh_max_depth, rpt64::kMeshTreeMaxDepth));
+    std::vector<TmpNode> tmp;
+    tmp.reserve(count);
+    tmp.push_back(TmpNode{});
+    int depth = 0;
+    {
+        BvhBuilder b{bt, tmp};
+        b.leaf_max = uint32_t(opt.bvh_leaf_max);
+        b.sweep_below = uint32_t(std::min<int64_t>(opt.bvh_sweep_below, 1 << 30));
+        b.build(0, 0, count, 0);
+        depth = b.max_depth;
+    }
+    if (depth > max_depth) {   // a chain-like SAH tree: the walk's stack could not hold it
+        tmp.assign(1, TmpNode{});
+        BvhBuilder b{bt, tmp};
+        b.leaf_max = uint32_t(opt.bvh_leaf_max);
+        b.balanced = true;
+        b.build(0, 0, count, 0);
+        depth = b.max_depth;
+    }
+    if (depth > max_depth) { fail(RPT_ERR_UNSUPPORTED, "mesh too large for the reference-epsilon mode's tree depth limit (raise bvh_leaf_max or bvh_max_depth)"); return -1; }
+    const uint32_t node_base = uint32_t(T.nodes.size()), leaf_base = uint32_t(T.leaf.size());
+    if (uint64_t(node_base) + tmp.size() >= (1ull << 31) || uint64_t(leaf_base) + count >= (1ull << 31)) { fail(RPT_ERR_UNSUPPORTED, "too many mesh tree nodes"); return -1; }
+    T.nodes.resize(node_base + tmp.size());
+    for (uint32_t i = 0; i < count; i++) T.leaf.push_back(first + bt[i].idx);
+    std::vector<Box64> box(tmp.size());
+    for (size_t k = tmp.size(); k-- > 0;) {   // children follow their parents in `tmp`: backwards, every child's box is known
+        Box64& b = box[k];
+        for (int a = 0; a < 3; a++) { b.lo[a] = std::numeric_limits<double>::infinity(); b.hi[a] = -b.lo[a]; }
+        const TmpNode& n = tmp[k];
+        if (n.count == 0) {
+            for (uint32_t c = n.left_or_first; c < n.left_or_first + 2; c++)
+                for (int a = 0; a < 3; a++) { b.lo[a] = std::min(b.lo[a], box[c].lo[a]); b.hi[a] = std::max(b.hi[a], box[c].hi[a]); }
+        } else {
+            for (uint32_t i = n.left_or_first; i < n.left_or_first + n.count; i++) {
+                const rpt64::Tri& t = tris[first + bt[i].idx];
+                for (const double* v : {t.v1, t.v2, t.v3})
+                    for (int a = 0; a < 3; a++) { b.lo[a] = std::min(b.lo[a], v[a]); b.hi[a] = std::max(b.hi[a], v[a]); }
+            }
+        }
+        double size = 0.0, mag = 0.0;
+        for (int a = 0; a < 3; a++) { size = std::max(size, b.hi[a] - b.lo[a]); mag = std::max(mag, std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a]))); }
+        const double pad = 1e-5 * size + 1e-5 * mag + 1e-30;
+        rpt64::MeshNode& o = T.nodes[node_base + k];
+        for (int a = 0; a < 3; a++) {
+            o.lo[a] = std::nextafter(float(b.lo[a] - pad), -HUGE_VALF);
+            o.hi[a] = std::nextafter(float(b.hi[a] + pad), HUGE_VALF);
+        }
+        o.count = n.count;
+        o.left_or_first = n.count == 0 ? node_base + n.left_or_first : leaf_base + n.left_or_first;
+    }
+    T.n_meshes++;
+    T.n_tris += count;
+    T.depth = std::max(T.depth, depth);
+    return int64_t(node_base) + 1;
+}
 static int build_scene64(rpt_scene* s) {
     static_assert(sizeof(rpt64::Tri) == 18 * sizeof(double), "a triangle is its 18 doubles");
     if (int rc = check_scene64(s)) return rc;
@@ -2053,6 +2145,26 @@ static int build_scene64(rpt_scene* s) {
             fill_mat64(hl.obj.mat, L.mat);
         }
     }
+    // the candidate trees: one per distinct mesh of at least f64_mesh_tree_min triangles (a mesh that shapes share is stored once)
+    MeshTrees64 MT;
+    std::vector<uint32_t> mroot;
+    if (s->opt.f64_mesh_tree_min > 0 && s->opt.f64_cull != 0) {
+        std::unordered_map<uint32_t, uint32_t> root_of;   // by tri_first
+        for (size_t i = 0; i < n; i++) {
+            const rpt64::ObjRec& r = recs[i];
+            if (r.kind != rpt64::SH_MESH || int64_t(r.tri_count) < s->opt.f64_mesh_tree_min) continue;
+            auto it = root_of.find(r.tri_first);
+            if (it == root_of.end()) {
+                const int64_t root = build_mesh_tree64(s->opt, tris, trecs, r.tri_first, r.tri_count, MT);
+                if (root < 0) return int(RPT_ERR_UNSUPPORTED);
+                it = root_of.emplace(r.tri_first, uint32_t(root)).first;
+            }
+            if (it->second != 0u) {
+                if (mroot.empty()) mroot.assign(n, 0u);
+                mroot[i] = it->second;
+            }
+        }
+    }
     std::vector<rpt64::CullBox> cull_groups((n + 31) / 32);
     for (size_t g = 0; g < cull_groups.size(); g++) {
         rpt64::CullBox u{};
@@ -2073,7 +2185,10 @@ static int build_scene64(rpt_scene* s) {
                     {F.frames.data(), F.frames.size() * sizeof(rpt64::FrameRec), 0}, {F.fshade.data(), F.fshade.size() * sizeof(rpt64::FrameShade), 0},
                     {s->hdri64.data(), s->hdri64.size() * sizeof(double), 0},
                     {cull_groups.data(), cull_groups.size() * sizeof(rpt64::CullBox), 0},
-                    {lshapes.data(), lshapes.size() * sizeof(rpt64::Shape), 0}};
+                    {lshapes.data(), lshapes.size() * sizeof(rpt64::Shape), 0},
+                    {MT.nodes.data(), MT.nodes.size() * sizeof(rpt64::MeshNode), 0},
+                    {MT.leaf.data(), MT.leaf.size() * sizeof(uint32_t), 0},
+                    {mroot.data(), mroot.size() * sizeof(uint32_t), 0}};
     size_t total = 0;
     for (auto& p : parts) { p.off = total; total = (total + p.bytes + 255) & ~size_t(255); }
     total = std::max<size_t>(total, 256);
@@ -2096,6 +2211,24 @@ static int build_scene64(rpt_scene* s) {
     v.hdri = reinterpret_cast<const double*>(base + parts[10].off);
     v.cull32 = reinterpret_cast<const rpt64::CullBox*>(base + parts[11].off);
     v.lshapes = reinterpret_cast<const rpt64::Shape*>(base + parts[12].off);
+    s->mnodes64 = reinterpret_cast<const rpt64::MeshNode*>(base + parts[13].off);
+    s->mleaf64 = reinterpret_cast<const uint32_t*>(base + parts[14].off);
+    s->mroot64 = mroot.empty() ? nullptr : reinterpret_cast<const uint32_t*>(base + parts[15].off);
+    {
+        // which passes walk the trees: the render and intersect kernels, unless the scene needs the group-light or the monomial flavour
+        // (those, and the photon passes of the mode, scan every triangle as before)
+        bool other_flavour = false;
+        for (const auto& l : s->lights)
+            if (l.kind == int(L_OBJECT) && l.obj.shape.d.kind == RPT_SHAPE_GROUP) other_flavour = true;
+        for (const auto& o : s->objects)
+            if (holds_monomial(o.shape)) other_flavour = true;
+        uint64_t* I = s->mesh_tree_info64;
+        I[0] = MT.n_meshes; I[1] = MT.n_tris; I[2] = MT.nodes.size(); I[3] = uint64_t(MT.depth);
+        I[4] = parts[13].bytes + parts[14].bytes + parts[15].bytes;
+        I[5] = (MT.n_meshes != 0 && !other_flavour) ? 1 : 0;
+        I[6] = 0;
+        I[7] = uint64_t(s->opt.f64_mesh_tree_min);
+    }
     v.hdri_w = s->hdri64.empty() ? 0u : s->hdri_w;
     v.hdri_h = s->hdri64.empty() ? 0u : s->hdri_h;
     v.n_objects = uint32_t(n);
@@ -2166,6 +2299,10 @@ extern "C++" void rpti::fill_args64(rpt_scene* s, const rpt_camera* cam, const r
     q.mono = 0u;
     for (const auto& o : s->objects)
         if (holds_monomial(o.shape)) q.mono = 1u;
+    q.tree = uint32_t(s->mesh_tree_info64[5]);
+    q.mnodes = s->mnodes64;
+    q.mleaf = s->mleaf64;
+    q.mroot = s->mroot64;
     if (cam) fill_camera64(cam, q.cam);
     if (prm) {
         q.width = prm->width; q.height = prm->height;
@@ -2545,6 +2682,13 @@ int rpt_render_sample(rpt_scene* s, const rpt_camera* cam, const rpt_render_para
     if (rc) return rc;
     HIP_TRY(hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost));
     return rpti::fetch_counters(s, a);
+}
+int rpt_f64_mesh_tree_info(rpt_scene* s, uint64_t out[8]) {
+    if (!s || !out) return fail(RPT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (!s->dev.arena64) return fail(RPT_ERR_STATE, "the scene was not committed with epsilon_policy = 1");
+    for (int i = 0; i < 8; i++) out[i] = s->mesh_tree_info64[i];
+    return RPT_OK;
 }
 int rpt_debug_epsilon_counters(rpt_scene* s, uint64_t out[12]) {
     if (!s || !out) return fail(RPT_ERR_INVALID, "null argument");
