@@ -456,6 +456,13 @@ int rpt_shadow_scan_info(rpt_scene*, uint32_t light, uint32_t out[4]);
  * out_new as the render kernels compute it (the bare v_log_f32 and the two-word product with ln 2), out_guarded through __logf with
  * its denormal and infinity guards, which no such draw needs.  The two are the same bits for every k. */
 int rpt_debug_distance_pair(float sigma_t, uint32_t k0, uint32_t n, float* out_new, float* out_guarded);
+/* The draws whose form the kernels changed for speed (the generator's step with three-input xors, a width that carries the draw's
+ * 2^-24, the roulette test on the raw word, the one-mask rejection test of the triangle sampler), next to the forms they replace
+ * (needs no scene; n <= 2^20).  Lane i runs each form on its own copy of stream (seed, i, 0); word w of lane i is out[w * n + i],
+ * 274 words per lane: [0, 64) the first 64 results of range(-1, 1) (float bits); [64, 128), [128, 192), [192, 256) of
+ * range(-inv, inv) for inv = 1/64, 1/1024, 1/3000; [256, 258) bit j of the pair = the roulette decision (draw < 0.8) of draw j;
+ * [258, 274) the top 23 bits of the first eight accepted pairs of the triangle sampler.  out_new and out_ref are the same bits. */
+int rpt_debug_draw_forms(uint64_t seed, uint32_t n, uint32_t* out_new, uint32_t* out_ref);
 
 /* The bounce of a path vertex, one case per lane on stream (seed, i, 0) (fp32 mode; needs no scene): the render kernels' own stage
  * (roulette or max_bounces, phase or BSDF sample, path weight) at a surface of material `m` with normal normals[i], reached along

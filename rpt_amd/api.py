@@ -1056,6 +1056,18 @@ def debug_distance_pair(sigma_t, k0, n):
     return new, guarded
 
 
+DRAW_FORM_WORDS = 274
+
+
+def debug_draw_forms(seed, n):
+    """The draw forms the kernels changed for speed and the forms they replace, lane i on stream (seed, i, 0) -> (new, ref), uint32
+    arrays of shape (274, n): rows [0, 64) range(-1, 1) as float bits, [64, 256) range(-inv, inv) for inv = 1/64, 1/1024, 1/3000,
+    [256, 258) the roulette decisions of draws 0..63 as bits, [258, 274) ku, kv of the first eight accepted triangle pairs."""
+    new, ref = np.empty((DRAW_FORM_WORDS, n), np.uint32), np.empty((DRAW_FORM_WORDS, n), np.uint32)
+    _lib.check(_lib.load().rpt_debug_draw_forms(C.c_uint64(int(seed)), int(n), _vp(new), _vp(ref)))
+    return new, ref
+
+
 def debug_bounce(material, normals, rds, max_bounces=3, depth=0, seed=0, in_medium=False, medium_event=False, albedo_med=0.0,
                  medium_color=(0.0, 0.0, 0.0)):
     """The render kernels' bounce stage (fp32 mode), case i on stream (seed, i, 0), at a surface of `material` with normal

@@ -111,7 +111,42 @@ RPT_DEV uint64_t mix64(uint64_t x) {
     x ^= x >> 31;
     return x;
 }
-struct Rng {
+// The leaner forms of the generator and its draws, one bit each so that a build can take them singly (-DRPT_RNG_FORMS=<mask>, default:
+// all).  Each is an integer identity or an exact scaling by a power of two: draw values, their number and their order stay what
+// they are, and the old form of every changed function stays next to it as *_ref (rpt_debug_draw_forms runs all the new forms, on
+// or off in this build, and the old ones).
+#define RPT_RNG_STEP 1u        // Rng::next: three xor3 (v_bitop3_b32) and one xor for six xors
+#define RPT_RNG_ONE_MASK 2u    // triangle-light rejection: one operand masked, not both
+#define RPT_RNG_RANGE 4u       // Rng::range: 2^-24 folded into the width
+#define RPT_RNG_ROULETTE 8u    // uniform() < 0.8 compared on the raw word
+#define RPT_RNG_ALL 15u
+// Default: the step alone.  Measured on C3: the step pays 0.29 ms of 18.08; the one-mask test and the
+// two draw forms lower the instruction count as predicted but each stayed inside three times the run-to-run range, so they are off.
+#ifndef RPT_RNG_FORMS
+#define RPT_RNG_FORMS RPT_RNG_STEP
+#endif
+RPT_DEV uint32_t xor3(uint32_t x, uint32_t y, uint32_t z) { return __builtin_amdgcn_bitop3_b32(x, y, z, 0x96); }
+// uniform() < p on the draw's word: with u = (2k+1) 2^-24, k = word >> 9, u < p <=> 2k+1 < p 2^24 <=> k < ceil((p 2^24 - 1) / 2) =: K
+// <=> word < K << 9 (the low nine bits do not matter, and K < 2^23).  p 2^24 and the halving are exact in fp64 for a float or a
+// double p in (0, 1); the same K serves u read as a float and as a double, since u is the same number in both.
+constexpr uint32_t roulette_k(double p) {
+    const double h = (p * 0x1p24 - 1.0) / 2.0;
+    const uint32_t k = uint32_t(h);
+    return double(k) < h ? k + 1u : k;
+}
+constexpr uint32_t roulette_word(double p) { return roulette_k(p) << 9; }
+constexpr bool roulette_exact(double p) {   // the last draw below p and the first one not below it, in the draw's own terms
+    const uint32_t k = roulette_k(p);
+    return k > 0u && k < (1u << 23) && double(2u * (k - 1u) + 1u) * 0x1p-24 < p && !(double(2u * k + 1u) * 0x1p-24 < p);
+}
+static constexpr uint32_t kRoulette08 = roulette_word(0.8f);
+static_assert(float(0x00CCCCCDu) * 0x1p-24f == 0.8f, "0.8f = 13421773 * 2^-24");
+static_assert(kRoulette08 == 0xCCCCCC00u && roulette_exact(0.8f), "uniform() < 0.8f <=> word < 0xCCCCCC00");
+static_assert(roulette_word(0.8) == kRoulette08 && roulette_exact(0.8), "the fp64 path's 0.8 cuts the draws at the same word");
+// FORMS: the forms this generator takes.  Every kernel runs Rng = RngT<RPT_RNG_FORMS> but the one flavour that names another mask
+// because a form costs it a register (photon.hip, QueryRng), and the test hook, which runs them all.
+template <uint32_t FORMS>
+struct RngT {
     uint32_t s0, s1, s2, s3;
     // `a` = mix64(seed + GOLDEN), computed on the host.
     RPT_DEV void seed(uint64_t a, uint32_t pixel, uint32_t sample) {
@@ -123,7 +158,8 @@ struct Rng {
         s2 = uint32_t(r1);
         s3 = uint32_t(r1 >> 32);
     }
-    RPT_DEV uint32_t next() {
+    // The step as the reference writes it: eight two-input operations (the compiler never fuses the xors on its own).
+    RPT_DEV uint32_t next_ref() {
         uint32_t r = s0 + s3;
         uint32_t t = s1 << 9;
         s2 ^= s0;
@@ -134,9 +170,42 @@ struct Rng {
         s3 = __builtin_rotateleft32(s3, 11);
         return r;
     }
+    // The same function of the state with the intermediate values substituted: three v_bitop3_b32 (x ^ y ^ z) and one xor,
+    // seven instructions for eight.
+    RPT_DEV uint32_t next() {
+        if constexpr ((FORMS & RPT_RNG_STEP) != 0) {
+            const uint32_t a = s0, b = s1, c = s2, d = s3;
+            const uint32_t r = a + d;
+            const uint32_t t = b << 9;
+            s1 = xor3(b, c, a);
+            s0 = xor3(a, d, b);
+            s2 = xor3(c, a, t);
+            s3 = __builtin_rotateleft32(d ^ b, 11);
+            return r;
+        } else {
+            return next_ref();
+        }
+    }
+    // The odd 24-bit integer 2k+1 of a word, k = its top 23 bits, as a float (exact).
+    RPT_DEV static float odd24(uint32_t word) { return float(((word >> 9) << 1) | 1u); }
     // (2k+1) * 2^-24 with k = top 23 bits: open interval (0,1), exact in fp32.
-    RPT_DEV float uniform() { return float(((next() >> 9) << 1) | 1u) * 0x1p-24f; }
-    RPT_DEV float range(float a, float b) { return fmaf(b - a, uniform(), a); }
+    RPT_DEV float uniform() { return odd24(next()) * 0x1p-24f; }
+    RPT_DEV float uniform_ref() { return odd24(next_ref()) * 0x1p-24f; }
+    RPT_DEV float range_ref(float a, float b) { return fmaf(b - a, uniform_ref(), a); }
+    // a + (b - a) u with the 2^-24 of u moved into the width: both scalings are exact (no b - a the kernels use comes near the
+    // denormals), the fma rounds the same real number, and the conversion's multiply is gone from every draw (constant or
+    // wave-uniform widths: the scaled width is formed once).
+    RPT_DEV float range(float a, float b) {
+        if constexpr ((FORMS & RPT_RNG_RANGE) != 0) return fmaf((b - a) * 0x1p-24f, odd24(next()), a);
+        else return fmaf(b - a, uniform(), a);
+    }
+    // uniform() < p on the word itself (see roulette_word).
+    template <uint32_t T>
+    RPT_DEV bool below(float p) {
+        if constexpr ((FORMS & RPT_RNG_ROULETTE) != 0) return next() < T;
+        else return uniform() < p;
+    }
+    RPT_DEV bool below_ref(float p) { return uniform_ref() < p; }
     RPT_DEV uint32_t index(uint32_t n) { return __umulhi(next(), n); }
     RPT_DEV void unit_disc(float& x, float& y) {  // rand_distr::UnitDisc (rejection)
         for (;;) {
@@ -146,6 +215,31 @@ struct Rng {
         }
     }
 };
+using Rng = RngT<RPT_RNG_FORMS>;
+// The accepted pair of a triangle sample, as the draws' top 23 bits (see sample_light_leaf): redraw while ku + kv >= 2^23, i.e. while
+// the sum of the two words without their low nine bits carries out of 32 bits.  One mask is enough: the low nine bits of
+// (a & ~511) + b are those of b alone and cannot carry into bit 9, so the carry out is that of (a & ~511) + (b & ~511).
+template <uint32_t FORMS>
+RPT_DEV void triangle_pair_ref(RngT<FORMS>& rng, uint32_t& ku, uint32_t& kv) {
+    uint32_t wu = rng.next_ref() & ~511u, wv = rng.next_ref() & ~511u, sum;
+    while (__builtin_add_overflow(wu, wv, &sum)) {
+        wu = rng.next_ref() & ~511u;
+        wv = rng.next_ref() & ~511u;
+    }
+    ku = wu >> 9;
+    kv = wv >> 9;
+}
+template <uint32_t FORMS = RPT_RNG_FORMS>
+RPT_DEV void triangle_pair(RngT<FORMS>& rng, uint32_t& ku, uint32_t& kv) {
+    constexpr uint32_t kMaskV = (FORMS & RPT_RNG_ONE_MASK) ? ~0u : ~511u;
+    uint32_t wu = rng.next() & ~511u, wv = rng.next() & kMaskV, sum;
+    while (__builtin_add_overflow(wu, wv, &sum)) {
+        wu = rng.next() & ~511u;
+        wv = rng.next() & kMaskV;
+    }
+    ku = wu >> 9;
+    kv = wv >> 9;
+}
 
 // ------------------------------------------------------------------ primitive tests
 // Each returns the hit parameter or a negative value for "no hit in [tmin, tmax)".
@@ -1202,12 +1296,8 @@ RPT_DEV void sample_light_leaf(const SceneView& scene_, uint32_t shape, uint32_t
         // in fp32 and u + v > 1 <=> ku + kv >= 2^23, so the rejected pairs are never converted (the wave runs the loop for its
         // unluckiest lane: ~7 rounds for 2 on average).  On the words themselves: (a & ~511) + (b & ~511) = 512 (ku + kv) carries
         // out of 32 bits exactly when ku + kv >= 2^23 -- and, and, add with carry, instead of shift, shift, add, compare.
-        uint32_t wu = rng.next() & ~511u, wv = rng.next() & ~511u, sum;
-        while (__builtin_add_overflow(wu, wv, &sum)) {
-            wu = rng.next() & ~511u;
-            wv = rng.next() & ~511u;
-        }
-        const uint32_t ku = wu >> 9, kv = wv >> 9;
+        uint32_t ku, kv;
+        triangle_pair(rng, ku, kv);
         const float u = float((ku << 1) | 1u) * 0x1p-24f, vv = float((kv << 1) | 1u) * 0x1p-24f;
         float w = 1.f - u - vv;
         vl = u * xyz(tr.v1) + vv * xyz(tr.v2) + w * xyz(tr.v3);  // already world space
@@ -1322,7 +1412,8 @@ RPT_DEV V env_color(const SceneView& scene_, V dir) {
 RPT_DEV float pixel_xn(uint32_t x, uint32_t w, float inv_dim) { return (float(2u * x + 1u) - float(w)) * inv_dim; }
 RPT_DEV float pixel_yn(uint32_t y, uint32_t h, float inv_dim) { return (float(2u * (h - y) - 1u) - float(h)) * inv_dim; }
 // Camera::cast_ray, src/camera.rs:65-82 (cot(fov/2)*direction and `right` hoisted to the host).
-RPT_DEV void cast_ray(const CameraG& c, float x, float y, Rng& rng, V& o, V& d) {
+template <class R>   // (R: Rng, or the generator of a flavour that takes other forms)
+RPT_DEV void cast_ray(const CameraG& c, float x, float y, R& rng, V& o, V& d) {
     V right = mk(c.right[0], c.right[1], c.right[2]), up = mk(c.up[0], c.up[1], c.up[2]);
     o = mk(c.eye[0], c.eye[1], c.eye[2]);
     V nd = mk(c.ddir[0], c.ddir[1], c.ddir[2]) + x * right + y * up;

@@ -111,6 +111,11 @@ struct ShadowTestArgs {
 __attribute__((weak)) hipError_t launch_debug_shadow_test(const SceneView& sc, const ShadowTestArgs& q, hipStream_t s);
 // rpt_debug_distance_pair: the medium distance of draw k as the render kernels form it and by the guarded __logf, k = k0 .. k0 + n - 1.
 __attribute__((weak)) hipError_t launch_debug_distance_pair(float sigma_t, uint32_t k0, uint32_t n, float* d_new, float* d_guarded, hipStream_t s);
+// rpt_debug_draw_forms: the draw forms behind RPT_RNG_FORMS and their *_ref twins, kDrawFormWords words per lane and side, word w of
+// lane i at [w * n + i] (layout: debug_draw_forms_kernel).
+static constexpr uint32_t kDrawFormWords = 274;
+__attribute__((weak)) hipError_t launch_debug_draw_forms(uint64_t seed_mixed, uint32_t n, const float inv[3], uint32_t* d_new, uint32_t* d_ref,
+                                                         hipStream_t s);
 // rpt_debug_bounce: stage_bounce<MEDIUM, false> of the render kernels, one case per lane on stream (seed, lane, 0).
 struct BounceArgs {
     Material m;

@@ -257,7 +257,7 @@ RPT_DEV bool stage_bounce(const RenderArgs& a, float albedo_med, V rd, uint32_t 
     SECT(10);
     if (medium) {
         SECT(11);
-        bounce = rng.uniform() < 0.8f;
+        bounce = rng.below<kRoulette08>(0.8f);
         if (bounce) {
             float ax = rng.range(-1.f, 1.f), ay = rng.range(-1.f, 1.f), az = rng.range(-1.f, 1.f);
             wi = normalize(mk(ax, ay, az));        // src/medium.rs:87-93 (cube, then normalise)
@@ -265,7 +265,7 @@ RPT_DEV bool stage_bounce(const RenderArgs& a, float albedo_med, V rd, uint32_t 
         }
     } else {
         SECT(12);
-        bounce = MEDIUM ? (rng.uniform() < 0.8f) : (depth < a.max_bounces);  // :222 / :301
+        bounce = MEDIUM ? rng.below<kRoulette08>(0.8f) : (depth < a.max_bounces);  // :222 / :301
         if (bounce) {
             float pdf;
             SECT(13);
@@ -1640,6 +1640,47 @@ __global__ __launch_bounds__(256) void debug_distance_pair_kernel(float sigma_t,
     out_new[i] = medium_distance(xi, inv_sigma_t);
     out_guarded[i] = medium_distance_guarded(xi, inv_sigma_t);
 }
+// rpt_debug_draw_forms: the draws whose form has a switch in RPT_RNG_FORMS -- all of them on, RngT<RPT_RNG_ALL> -- and their *_ref twins on the reference's step, each on its
+// own copy of stream (seed, lane, 0).  Word w of lane i is out[w * n + i]:
+//   [0, 64) range(-1, 1); [64, 128), [128, 192), [192, 256) range(-inv, inv) for the three widths given (kernel arguments, as
+//   inv_dim is in a render); [256, 258) bit j of the pair: the roulette decision of draw j; [258, 274) ku, kv of the first eight
+//   accepted pairs of the triangle sampler.
+template <bool REF>
+RPT_DEV void draw_forms(const RngT<RPT_RNG_ALL>& start, uint32_t i, uint32_t n, float inv0, float inv1, float inv2, uint32_t* __restrict__ out) {
+    const auto put = [&](uint32_t w, uint32_t v) { out[size_t(w) * n + i] = v; };
+    const auto range = [](RngT<RPT_RNG_ALL>& r, float a, float b) { return __float_as_uint(REF ? r.range_ref(a, b) : r.range(a, b)); };
+    RngT<RPT_RNG_ALL> r = start;
+    for (uint32_t j = 0; j < 64u; j++) put(j, range(r, -1.f, 1.f));
+    const float inv[3] = {inv0, inv1, inv2};
+#pragma unroll
+    for (uint32_t f = 0; f < 3u; f++) {
+        r = start;
+        for (uint32_t j = 0; j < 64u; j++) put(64u * (f + 1u) + j, range(r, -inv[f], inv[f]));
+    }
+    r = start;
+    for (uint32_t h = 0; h < 2u; h++) {
+        uint32_t bits = 0;
+        for (uint32_t j = 0; j < 32u; j++) bits |= uint32_t(REF ? r.below_ref(0.8f) : r.template below<kRoulette08>(0.8f)) << j;
+        put(256u + h, bits);
+    }
+    r = start;
+    for (uint32_t j = 0; j < 8u; j++) {
+        uint32_t ku, kv;
+        if (REF) triangle_pair_ref(r, ku, kv);
+        else triangle_pair(r, ku, kv);
+        put(258u + 2u * j, ku);
+        put(259u + 2u * j, kv);
+    }
+}
+__global__ __launch_bounds__(256) void debug_draw_forms_kernel(uint64_t seed_mixed, uint32_t n, float inv0, float inv1, float inv2,
+                                                               uint32_t* __restrict__ out_new, uint32_t* __restrict__ out_ref) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    RngT<RPT_RNG_ALL> r;   // every new form, whichever of them this build's kernels take
+    r.seed(seed_mixed, i, 0);
+    draw_forms<false>(r, i, n, inv0, inv1, inv2, out_new);
+    draw_forms<true>(r, i, n, inv0, inv1, inv2, out_ref);
+}
 // rpt_debug_bounce: the render kernels' own stage_bounce at a surface or a medium event.  Of the RenderArgs the stage reads
 // max_bounces alone (COUNT = false: no counters); they stay the first parameter as in render_kernel.
 template <bool MEDIUM>
@@ -1816,6 +1857,10 @@ hipError_t launch_debug_shadow_test(const SceneView& sc, const ShadowTestArgs& q
 }
 hipError_t launch_debug_distance_pair(float sigma_t, uint32_t k0, uint32_t n, float* d_new, float* d_guarded, hipStream_t s) {
     hipLaunchKernelGGL(debug_distance_pair_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, sigma_t, k0, n, d_new, d_guarded);
+    return hipGetLastError();
+}
+hipError_t launch_debug_draw_forms(uint64_t seed_mixed, uint32_t n, const float inv[3], uint32_t* d_new, uint32_t* d_ref, hipStream_t s) {
+    hipLaunchKernelGGL(debug_draw_forms_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, seed_mixed, n, inv[0], inv[1], inv[2], d_new, d_ref);
     return hipGetLastError();
 }
 hipError_t launch_debug_bounce(const BounceArgs& q, hipStream_t s) {

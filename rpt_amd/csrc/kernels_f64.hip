@@ -103,7 +103,17 @@ RPT_DEV uint32_t mbcnt64(uint64_t m) {
 struct Rng64 {
     rptg::Rng r;
     R64_DEV double uniform() { return double(((r.next() >> 9) << 1) | 1u) * 0x1p-24; }   // rng.gen::<f64>()
-    R64_DEV double range(double a, double b) { return a + (b - a) * uniform(); }           // rng.gen_range(a..b)
+    // rng.gen_range(a..b) = a + (b - a) u.  With the 2^-24 of u moved into the width (an exact scaling) the product, and so the sum, is
+    // the same double, and the conversion's multiply is gone from the draw.
+    R64_DEV double range(double a, double b) {
+        if constexpr ((RPT_RNG_FORMS & RPT_RNG_RANGE) != 0) return a + ((b - a) * 0x1p-24) * double(((r.next() >> 9) << 1) | 1u);
+        else return a + (b - a) * uniform();
+    }
+    // uniform() < 0.8 on the word (rptg::roulette_word: the same word for the double 0.8 as for the fp32 path's 0.8f)
+    R64_DEV bool below_08() {
+        if constexpr ((RPT_RNG_FORMS & RPT_RNG_ROULETTE) != 0) return r.next() < rptg::roulette_word(0.8);
+        else return uniform() < 0.8;
+    }
     R64_DEV uint32_t index(uint32_t n) { return __umulhi(r.next(), n); }                   // Uniform::from(0..n)
     R64_DEV void unit_disc(double& x, double& y) {                                         // rand_distr::UnitDisc
         for (;;) {
@@ -690,10 +700,15 @@ R64_DEV void sample_local(const S& s, D target, Rng64& rng, D& v, D& n, double& 
         const uint32_t idx = s.tri_first + rng.index(s.tri_count);
         // `while u + v > 1 { redraw }`: with u = (2k+1) 2^-24 the sum is exact and u + v > 1 <=> ku + kv >= 2^23, so a
         // rejected pair is never converted (same draws)
-        uint32_t ku = rng.r.next() >> 9, kv = rng.r.next() >> 9;
-        while (ku + kv >= (1u << 23)) {
-            ku = rng.r.next() >> 9;
-            kv = rng.r.next() >> 9;
+        uint32_t ku, kv;
+        if constexpr ((RPT_RNG_FORMS & RPT_RNG_ONE_MASK) != 0) {
+            rptg::triangle_pair(rng.r, ku, kv);   // the same test on the words: one and, add with carry
+        } else {
+            ku = rng.r.next() >> 9, kv = rng.r.next() >> 9;
+            while (ku + kv >= (1u << 23)) {
+                ku = rng.r.next() >> 9;
+                kv = rng.r.next() >> 9;
+            }
         }
         const double u = double((ku << 1) | 1u) * 0x1p-24, vv = double((kv << 1) | 1u) * 0x1p-24;
         const double w = 1.0 - u - vv;
@@ -1210,7 +1225,7 @@ __global__ __launch_bounds__(256, R64_WAVES) void render_f64_kernel(const Args a
         bool cont = false;
         if (ev_medium) {   // :262-281
             SECT64(21);
-            if (rng.uniform() < 0.8) {
+            if (rng.below_08()) {
                 const double ax = rng.range(-1.0, 1.0), ay = rng.range(-1.0, 1.0), az = rng.range(-1.0, 1.0);
                 wi_next = normalize(mk(ax, ay, az));   // Medium::sample_ph, src/medium.rs:87-93
                 const double scat = KA.sc.scattering;
@@ -1220,7 +1235,7 @@ __global__ __launch_bounds__(256, R64_WAVES) void render_f64_kernel(const Args a
             }
         } else {
             SECT64(22);
-            const bool go = MEDIUM ? (rng.uniform() < 0.8) : (depth < KA.max_bounces);   // :222 / :301
+            const bool go = MEDIUM ? rng.below_08() : (depth < KA.max_bounces);   // :222 / :301
             if (go) {
                 double pdf;
                 const Mat& mat = KA.sc.shade[hobj].mat;

@@ -1738,7 +1738,11 @@ __global__ __launch_bounds__(256, RPT_MIN_WAVES_QUERY) void photon_query_kernel(
         const float yn = pixel_yn(py, a.height, a.inv_dim);
         const uint32_t n_sub = (n_s + 63u) >> 6;   // trips of 64 samples
         // camera ray of sample (chunk, sub, lane) and its closest hit
-        auto gen_ray = [&](uint32_t sub, Rng& rng, V& ro, V& rd, float& tmin, float& t, uint32_t& code, uint32_t& inst) {
+        // (The surface-only flavour that hands its selections to the fp64 estimate keeps the reference's form of the generator's step:
+        // with the three-input form it needs 52 VGPRs for 51.  Same words either way.  Registers are allocated in granules of 8, so the
+        // extra one costs no occupancy: if the register budget is ever read per granule, this exception and the second generator type can go.)
+        using QueryRng = std::conditional_t<!MEDIUM && !BVH && GG && EMIT, RngT<(RPT_RNG_FORMS & ~RPT_RNG_STEP)>, Rng>;
+        auto gen_ray = [&](uint32_t sub, QueryRng& rng, V& ro, V& rd, float& tmin, float& t, uint32_t& code, uint32_t& inst) {
             const bool active = sub * 64u + lane_ < n_s;
             ro = mk(0, 0, 0); rd = mk(0, 0, 1); tmin = 0.f; t = kInf; code = CODE_MISS; inst = 0;
             rng.s0 = rng.s1 = rng.s2 = rng.s3 = 0;
@@ -1766,7 +1770,7 @@ __global__ __launch_bounds__(256, RPT_MIN_WAVES_QUERY) void photon_query_kernel(
         unsigned long long tk = tick();
         if (beam_lanes || pix_gather) {
             for (uint32_t sub = 0; sub < n_sub; sub++) {
-                Rng rng;
+                QueryRng rng;
                 V ro, rd;
                 float tmin, t;
                 uint32_t code, inst;
@@ -1818,7 +1822,7 @@ __global__ __launch_bounds__(256, RPT_MIN_WAVES_QUERY) void photon_query_kernel(
         V ro, rd;
         float tmin, t;
         uint32_t code, inst;
-        Rng rng;
+        QueryRng rng;
         const bool active = gen_ray(sub, rng, ro, rd, tmin, t, code, inst);
         { const unsigned long long t1 = tick(); diag_add(a.counters, 24 + 3, t1 - tk); tk = t1; }   // [3] second pass over the rays
         const V wo = -normalize(rd);

@@ -3121,6 +3121,22 @@ int rpt_debug_distance_pair(float sigma_t, uint32_t k0, uint32_t n, float* out_n
     return RPT_OK;
 }
 
+int rpt_debug_draw_forms(uint64_t seed, uint32_t n, uint32_t* out_new, uint32_t* out_ref) {
+    if (!out_new || !out_ref) return fail(RPT_ERR_INVALID, "null argument");
+    if (n > (1u << 20)) return fail(RPT_ERR_INVALID, "rpt_debug_draw_forms: at most 2^20 lanes");   // 1.15 GB per side on the device
+    if (!launch_debug_draw_forms) return fail(RPT_ERR_UNSUPPORTED, "rpt_debug_draw_forms: built without the kernels");
+    if (n == 0) return RPT_OK;
+    const size_t bytes = size_t(n) * kDrawFormWords * 4;
+    const float inv[3] = {1.f / 64.f, 1.f / 1024.f, 1.f / 3000.f};
+    rpti::DevMem d_new, d_ref;
+    HIP_TRY(hook_scratch(d_new, bytes));
+    HIP_TRY(hook_scratch(d_ref, bytes));
+    HIP_TRY(launch_debug_draw_forms(seed_mix(seed), n, inv, d_new.get<uint32_t>(), d_ref.get<uint32_t>(), nullptr));
+    HIP_TRY(hipMemcpy(out_new, d_new.get(), bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_ref, d_ref.get(), bytes, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
 // stage_bounce on a material descriptor: needs no scene.  (The medium enters through its albedo and colour alone.)
 int rpt_debug_bounce(const rpt_material* m, uint32_t max_bounces, uint32_t depth, int32_t in_medium, int32_t medium_event,
                      float albedo_med, const float* medium_color, uint64_t n, const float* normals, const float* rds, uint64_t seed,
