@@ -539,6 +539,30 @@ class Renderer {
         sample_offset_ += iterations;
     }
 
+    // First-hit feature planes (rpt_hip.h, rpt_render_features: an addition) of the camera samples the next sample() call traces --
+    // same seed, same sample offset, which is not advanced --: width * height * 3 doubles each, the frame's own layout.
+    struct Features {
+        std::vector<double> albedo;   // mean Material::color of the first hit, the environment's colour on a miss
+        std::vector<double> normal;   // mean normal (0 on a miss), not renormalised
+        std::vector<double> depth;    // (mean hit distance over all samples, coverage, object index + 1 of the first sample or 0)
+    };
+    Features features(uint32_t iterations) {
+        commit();
+        const size_t n = size_t(p_.width) * p_.height * 3;
+        Features f{std::vector<double>(n), std::vector<double>(n), std::vector<double>(n)};
+        rpt_camera cam = camera_.desc();
+        rpt_render_params rp{p_.width, p_.height, p_.exposure_value, p_.max_bounces, p_.shard_rank, p_.shard_count};
+        check(rpt_render_features(handle_, &cam, &rp, iterations, p_.seed, sample_offset_, f.albedo.data(), f.normal.data(), f.depth.data()));
+        return f;
+    }
+    // ... into device planes on this renderer's device (null: not computed), enqueued on hip_stream.
+    void features_device(uint32_t iterations, void* d_albedo, void* d_normal, void* d_depth, void* hip_stream = nullptr) {
+        commit();
+        rpt_camera cam = camera_.desc();
+        rpt_render_params rp{p_.width, p_.height, p_.exposure_value, p_.max_bounces, p_.shard_rank, p_.shard_count};
+        check(rpt_render_features_device(handle_, &cam, &rp, iterations, p_.seed, sample_offset_, d_albedo, d_normal, d_depth, hip_stream));
+    }
+
     // The candidate trees of the reference-epsilon mode's large meshes (rpt_hip.h, rpt_f64_mesh_tree_info): meshes, triangles, nodes,
     // depth, bytes, render uses the trees, photon passes use them, threshold.  Throws for a scene of the fp32 path.
     std::array<uint64_t, 8> f64_mesh_tree_info() {

@@ -137,6 +137,32 @@ int rpt_render_sample(rpt_scene*, const rpt_camera*, const rpt_render_params*, u
 int rpt_render_sample_device(rpt_scene*, const rpt_camera*, const rpt_render_params*, uint32_t iterations,
                              uint64_t seed, uint32_t sample_offset, void* d_out_rgb, void* hip_stream);
 
+/* First-hit feature planes of the camera samples a render of the same arguments traces (an addition: the reference renders
+ * radiance only).  Sample s in [0, iterations) of pixel (x, y) is the render's camera sample on stream (seed, y*width + x,
+ * sample_offset + s) -- rpt_debug_camera_sample / _f64 -- and its closest hit over the whole ray -- rpt_intersect_batch / _f64: t,
+ * object, normal; a medium is ignored.  On a hit a = Material::color of the object (the albedo of Lambertian and Phong, 0 for the
+ * others), n = the normal as returned (not re-oriented), z = t, c = 1; on a miss a = Environment::get_color(direction) --
+ * rpt_debug_env_color / _f64 --, n = 0, z = 0, c = 0.  Every plane is width*height*3 doubles, row-major, y = 0 top, the frame's own
+ * format (rpt_buffer_add_samples_device, rpt_frame_pack_device and rpt_gather_frame_device carry it unchanged):
+ *   albedo: mean of a;   normal: mean of n (not renormalised);
+ *   depth:  (mean of z over all samples, mean of c, id): id = object index + 1 of sample 0 of this call, 0 for a miss, as a double
+ *           (the index rpt_intersect_batch* returns); channel 0 / channel 1 = mean hit distance.
+ * Summation order: samples are cut into chunks as rpt_scene_render_chunking reports; each channel is an fp64 sum over a chunk in
+ * sample order from +0.0 (fp32 mode: every term converted from float first), the chunk sums are added in chunk order from +0.0 and
+ * the total is divided by double(iterations).  No atomics: the planes are a function of (scene, camera, params, iterations, seed,
+ * sample_offset, chunk_spp) alone.  In the reference-epsilon mode a monomial surface's hit may carry t = NaN, which propagates.
+ * Any plane may be NULL (not computed); all three NULL is RPT_ERR_INVALID.  exposure_value and max_bounces are ignored.  Sharding as
+ * for rpt_render_sample: only the owned tiles are computed, every other pixel of a requested plane is 0, and the shards' planes add
+ * up to the unsharded ones bit for bit.  Same scenes, in both modes, as rpt_render_sample. */
+int rpt_render_features(rpt_scene*, const rpt_camera*, const rpt_render_params*, uint32_t iterations,
+                        uint64_t seed, uint32_t sample_offset, double* out_albedo, double* out_normal, double* out_depth);
+/* Same, asynchronous: DEVICE pointers on the scene's device, hip_stream a hipStream_t (NULL = default stream).  The pass has its
+ * own scratch on the scene, apart from the renders': a feature pass and a render on different streams are independent; two feature
+ * passes of one scene never overlap (the second waits for the first, whatever its stream). */
+int rpt_render_features_device(rpt_scene*, const rpt_camera*, const rpt_render_params*, uint32_t iterations,
+                               uint64_t seed, uint32_t sample_offset, void* d_albedo, void* d_normal, void* d_depth,
+                               void* hip_stream);
+
 /* Renderer::get_closest_hit (src/renderer.rs:416-425) over n rays (host pointers, fp32).
  * t = +inf, object = -1 on a miss.  normal may be NULL. */
 int rpt_intersect_batch(rpt_scene*, uint64_t n, const float* origins, const float* dirs, float* t,

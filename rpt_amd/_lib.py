@@ -87,6 +87,10 @@ SYMBOLS = [
      [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P]),
     ("rpt_render_sample_device", C.c_int,
      [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P, _P]),
+    ("rpt_render_features", C.c_int,
+     [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P, _P, _P]),
+    ("rpt_render_features_device", C.c_int,
+     [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P, _P, _P, _P]),
     ("rpt_intersect_batch", C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("rpt_intersect_batch_f64", C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("rpt_intersect_segments", C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P]),

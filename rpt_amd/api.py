@@ -779,6 +779,35 @@ class Renderer:
             C.c_uint64(self.seed_), self._sample_offset, C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
         self._sample_offset += int(iterations)
 
+    # First-hit feature planes (rpt_render_features*, an addition): of the camera samples that the NEXT sample call of this renderer
+    # traces -- same seed, same sample offset; the offset is not advanced (sample_offset=...: another one).
+    def features_array(self, iterations, albedo=True, normal=True, depth=True, sample_offset=None):
+        """-> dict of the requested planes, (h, w, 3) float64 each: "albedo" (mean Material::color of the first hit, the environment's
+        colour on a miss), "normal" (mean normal, 0 on a miss, not renormalised), "depth" (mean hit distance over all samples,
+        coverage, object index + 1 of the first sample or 0).  Honours seed(), shard() and device() like sample_array."""
+        want = {"albedo": bool(albedo), "normal": bool(normal), "depth": bool(depth)}
+        if not any(want.values()):
+            raise ValueError("features_array: no plane requested")
+        lib = _lib.load()
+        h = self.scene._commit(self.device_)
+        out = {k: np.empty((self.height_, self.width_, 3), dtype=np.float64) for k, v in want.items() if v}
+        _lib.check(lib.rpt_render_features(
+            h, C.byref(camera_desc(self.camera, _lib.CameraDesc)), C.byref(self._params()), int(iterations),
+            C.c_uint64(self.seed_), self._sample_offset if sample_offset is None else int(sample_offset),
+            *[_vp(out[k]) if k in out else None for k in ("albedo", "normal", "depth")]))
+        return out
+
+    def features_device(self, iterations, d_albedo, d_normal, d_depth, stream_ptr=0, sample_offset=None):
+        """Asynchronous variant: device pointers to width*height*3 doubles each (0 / None: the plane is not computed)."""
+        if not (d_albedo or d_normal or d_depth):
+            raise ValueError("features_device: no plane requested")
+        lib = _lib.load()
+        h = self.scene._commit(self.device_)
+        _lib.check(lib.rpt_render_features_device(
+            h, C.byref(camera_desc(self.camera, _lib.CameraDesc)), C.byref(self._params()), int(iterations),
+            C.c_uint64(self.seed_), self._sample_offset if sample_offset is None else int(sample_offset),
+            C.c_void_p(d_albedo or None), C.c_void_p(d_normal or None), C.c_void_p(d_depth or None), C.c_void_p(stream_ptr)))
+
     def sample(self, iterations, buffer):
         """Renderer::sample (renderer.rs:158-171).  A DeviceBuffer receives the batch on the GPU."""
         if isinstance(buffer, DeviceBuffer) and self.shard_count_ == 1:

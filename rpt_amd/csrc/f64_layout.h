@@ -173,6 +173,12 @@ struct IsectArgs64 {
     int32_t* obj;               // [n] object index, -1: none
     double* nrm;                // [3 n] normal, or null
 };
+// rpt_render_features* in this mode (kernels_f64.hip, features_f64_kernel): one lane per (pixel slot, chunk) item of a's decomposition.
+struct FeatureArgs64 {
+    Args a;                     // scene, camera, frame, tiles, chunking, a.seed_mixed (a.queue, a.slab, a.counters unused)
+    double* slab;               // [8][n_items]: rptg::FeatureArgs::slab
+    uint32_t* ids;              // [n_owned]: rptg::FeatureArgs::ids
+};
 // rpt_debug_light_sample_f64 / rpt_debug_env_color_f64 (kernels_f64.hip): one call of the mode's device function per lane.
 struct DebugArgs64 {
     Args a;                     // scene, a.seed_mixed, a.group_lights

@@ -111,7 +111,8 @@ void photon_release(void* p);      // defined in photon.hip
 // function sizes is the one that kernel and resolve_kernel index.
 int prepare_render(rpt_scene* s, hipStream_t st, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
                    uint32_t sample_offset, rptg::RenderArgs& a, uint32_t min_chunk = 0, uint32_t fixed_chunk = 0,
-                   uint32_t slab_item_bytes = 16);   // 32: the reference-epsilon mode's partial sums are fp64
+                   uint32_t slab_item_bytes = 16,   // 32: the reference-epsilon mode's partial sums are fp64
+                   bool launch_set = true);   // false: the caller brings its own scratch (the feature pass): no launch set is taken, a.slab and a.queue stay null
 // Zeroes the queue / sharded frame, calls `launch(args, n_blocks, stream)` with a persistent grid of
 // blocks_per_cu blocks per CU, then resolves the slab into d_out.
 int run_persistent(rpt_scene* s, const rpt_render_params* prm, const rptg::RenderArgs& a, double* d_out, hipStream_t st,

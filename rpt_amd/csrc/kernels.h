@@ -71,6 +71,27 @@ __attribute__((weak)) hipError_t launch_intersect_segments(const SceneView& sc, 
                                                            float* d_t, uint32_t* d_code, hipStream_t stream);
 hipError_t launch_intersect(const SceneView& sc, uint64_t n, const float* d_o, const float* d_d, float* d_t,
                             int32_t* d_obj, float* d_n, bool bvh, hipStream_t stream);
+// rpt_render_features*: the first-hit feature pass.  One lane per (pixel slot, chunk) item of RenderArgs' decomposition (no work
+// counter: a plain grid); the lane sums its chunk's samples in fp64 and writes one record, feature_resolve_kernel adds a pixel's
+// records in chunk order, divides by the sample count and writes the requested planes.  (r.slab, r.queue and r.counters are unused.)
+struct FeatureArgs {
+    RenderArgs r;
+    double* slab;             // [8][n_items]: channel k of item i at [k * n_items + i] -- albedo rgb, normal xyz, depth, coverage
+    uint32_t* ids;            // [n_owned]: object index + 1 of the call's sample 0 (written by the items of chunk 0), 0: a miss
+};
+static_assert(offsetof(FeatureArgs, r) == 0, "FeatureArgs must begin with the SceneView");
+// The resolve of both modes (the reference-epsilon mode's feature kernel writes the same records).
+struct FeatureResolveArgs {
+    const uint32_t* tiles;
+    uint32_t tiles_x, n_owned, n_chunks, n_items;
+    uint32_t width, height, iterations, pad_;
+    const double* slab;
+    const uint32_t* ids;
+    double *albedo, *normal, *depth;   // [width * height * 3] each, or null: not requested
+};
+// (Weak: reached from rpt_render_features* alone, which report RPT_ERR_UNSUPPORTED where no kernel library is linked.)
+__attribute__((weak)) hipError_t launch_features(const FeatureArgs& a, hipStream_t stream);
+__attribute__((weak)) hipError_t launch_feature_resolve(const FeatureResolveArgs& a, hipStream_t stream);
 hipError_t launch_debug_rng(uint64_t seed_mixed, uint32_t pixel, uint32_t sample, uint32_t n, uint32_t* d_out,
                             hipStream_t stream);
 hipError_t launch_debug_sample_f(const Material& m, uint64_t n, const float* d_n, const float* d_wo,
@@ -134,7 +155,7 @@ struct BounceArgs {
 __attribute__((weak)) hipError_t launch_debug_bounce(const BounceArgs& q, hipStream_t s);
 
 }  // namespace rptg
-namespace rpt64 { struct Args; struct ShootArgs64; struct SurfArgs64; }
+namespace rpt64 { struct Args; struct ShootArgs64; struct SurfArgs64; struct FeatureArgs64; }
 namespace rptg {
 // Reference-epsilon mode (kernels_f64.hip): persistent grid over (pixel, chunk) items with an fp64 slab, then its resolve.
 hipError_t launch_render_f64(const rpt64::Args& a, int n_blocks, hipStream_t stream);
@@ -145,4 +166,6 @@ hipError_t launch_photon_shoot_f64(const rpt64::ShootArgs64& a, int n_blocks, hi
 hipError_t launch_photon_surface_f64(const rpt64::SurfArgs64& a, int n_blocks, hipStream_t stream);
 hipError_t launch_resolve_photon_f64(const rpt64::Args& a, const void* slab32, uint32_t n_chunks32, double scale_over_total, bool accumulate,
                                      double* d_out, hipStream_t stream);
+// The feature pass of that mode (records as FeatureArgs'; launch_feature_resolve resolves them).  (Weak, like launch_features.)
+__attribute__((weak)) hipError_t launch_features_f64(const rpt64::FeatureArgs64& a, hipStream_t stream);
 }  // namespace rptg

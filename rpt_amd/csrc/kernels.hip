@@ -1499,6 +1499,89 @@ __global__ __launch_bounds__(256) void intersect_kernel(const SceneView sc, uint
     }
 }
 
+// rpt_render_features*: the first-hit features of a render's camera samples.  Item i = chunk * n_owned + pixel slot, one lane each, in
+// item_pixel's layout (a wave = the 8 x 8 pixels of one block in one chunk: neighbouring rays).  Per sample of the chunk: the camera
+// sample of render_kernel (debug_camera_kernel), intersect_kernel's query and finalize_hit, then Material::color of the object or
+// Environment::get_color of the direction; each channel an fp64 sum in sample order from +0.0, every term converted from float first.
+template <int BVH, bool MONO = false>
+__global__ __launch_bounds__(256) void features_kernel(const FeatureArgs fa) {
+    extern __shared__ uint32_t dyn_lds[];
+    uint32_t* stk = BVH ? (dyn_lds + threadIdx.x) : nullptr;
+    const RenderArgs& a = fa.r;
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= a.n_items) return;
+    const uint32_t chunk = item / a.n_owned, p = item - chunk * a.n_owned;
+    uint32_t x, y;
+    item_pixel(a, p, x, y);
+    if (x >= a.width || y >= a.height) return;   // slots of clipped tiles lie outside the image
+    const uint32_t s0 = chunk * a.chunk_spp, s1 = min(s0 + a.chunk_spp, a.iterations);
+    // The sample's NDC coordinates in the form debug_camera_kernel's take (rpt_debug_camera_sample, by which the interface defines the
+    // ray): there pixel_xn's product and the jitter's sum are ONE operation, a fused multiply-add -- the compiler contracts them --, so
+    // they are written as one here, where the pixel's part is loop-invariant and would be rounded on its own.  (render_kernel keeps
+    // the product per item and rounds it: its coordinate may differ from the hook's by that rounding.)
+    const float px = float(2u * x + 1u) - float(a.width), py = float(2u * (a.height - y) - 1u) - float(a.height);   // pixel_xn, pixel_yn
+    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    uint32_t id = 0u;
+    for (uint32_t s = s0; s < s1; s++) {
+        Rng r;
+        r.seed(a.seed_mixed, y * a.width + x, a.sample_offset + s);
+        const float dx = r.range(-a.inv_dim, a.inv_dim);
+        const float dy = r.range(-a.inv_dim, a.inv_dim);
+        V ro, rd;
+        cast_ray(a.cam, __builtin_fmaf(px, a.inv_dim, dx), __builtin_fmaf(py, a.inv_dim, dy), r, ro, rd);
+        const float tmin = ray_tmin(ro);
+        float t = kInf;
+        uint32_t code = CODE_MISS, inst = 0, c0 = 0, c1 = 0;
+        closest_hit<BVH, false, false, MONO>(a.sc, ro, rd, tmin, t, code, inst, stk, 256, c0, c1);
+        V col, nn = mk(0, 0, 0);
+        float z = 0.f, cov = 0.f;
+        if (code != CODE_MISS) {
+            uint32_t obj = 0xFFFFFFFFu;
+            finalize_hit<MONO>(a.sc, ro, rd, tmin, t, code, inst, nn, obj);
+            col = mat_color(load_mat(a.sc, obj));
+            z = t;
+            cov = 1.f;
+            if (s == 0u) id = obj + 1u;
+        } else {
+            col = env_color(a.sc, rd);
+        }
+        acc[0] += double(col.x); acc[1] += double(col.y); acc[2] += double(col.z);
+        acc[3] += double(nn.x); acc[4] += double(nn.y); acc[5] += double(nn.z);
+        acc[6] += double(z);
+        acc[7] += double(cov);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; k++) fa.slab[size_t(k) * a.n_items + item] = acc[k];
+    if (chunk == 0u) fa.ids[p] = id;
+}
+// A pixel's records added in chunk order from +0.0, then / iterations (a division): the requested planes.  Depth plane: (sum of the
+// hit distances, hits) / iterations and the id.
+__global__ __launch_bounds__(256) void feature_resolve_kernel(const FeatureResolveArgs a) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= a.n_owned) return;
+    const uint32_t tl = p >> 10, within = p & 1023u, sb = within >> 6, l = within & 63u;   // item_pixel
+    const uint32_t tile = a.tiles[tl], ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    const uint32_t x = tx * 32u + (sb & 3u) * 8u + (l & 7u), y = ty * 32u + (sb >> 2) * 8u + (l >> 3);
+    if (x >= a.width || y >= a.height) return;
+    double sum[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (uint32_t c = 0; c < a.n_chunks; c++) {
+        const size_t i = size_t(c) * a.n_owned + p;
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) sum[k] += a.slab[size_t(k) * a.n_items + i];
+    }
+    const double n = double(a.iterations);
+    const size_t o = (size_t(y) * a.width + x) * 3;
+    if (a.albedo) {
+        a.albedo[o] = sum[0] / n; a.albedo[o + 1] = sum[1] / n; a.albedo[o + 2] = sum[2] / n;
+    }
+    if (a.normal) {
+        a.normal[o] = sum[3] / n; a.normal[o + 1] = sum[4] / n; a.normal[o + 2] = sum[5] / n;
+    }
+    if (a.depth) {
+        a.depth[o] = sum[6] / n; a.depth[o + 1] = sum[7] / n; a.depth[o + 2] = double(a.ids[p]);
+    }
+}
+
 // rpt_intersect_segments: the primary query of the scan flavours (culled when the view says so) over given segments, 64 to a wave.
 __global__ __launch_bounds__(256) void intersect_segments_kernel(const SceneView sc, uint64_t n, const float* __restrict__ o,
                                                                  const float* __restrict__ d, const float* __restrict__ tmax,
@@ -1805,6 +1888,25 @@ hipError_t launch_intersect(const SceneView& sc, uint64_t n, const float* d_o, c
     }
     if (bvh) hipLaunchKernelGGL(intersect_kernel<2>, dim3(blocks), dim3(256), kStackBytes, stream, sc, n, d_o, d_d, d_t, d_obj, d_n);
     else hipLaunchKernelGGL(intersect_kernel<0>, dim3(blocks), dim3(256), 0, stream, sc, n, d_o, d_d, d_t, d_obj, d_n);
+    return hipGetLastError();
+}
+// (the flavours of launch_intersect, chosen the same way)
+hipError_t launch_features(const FeatureArgs& a, hipStream_t stream) {
+    if (!a.r.n_items) return hipSuccess;
+    const dim3 grid((a.r.n_items + 255u) / 256u);
+    const bool bvh = a.r.sc.n_nodes != 0;
+    if (a.r.sc.n_mono) {
+        if (bvh) hipLaunchKernelGGL((features_kernel<2, true>), grid, dim3(256), kStackBytes, stream, a);
+        else hipLaunchKernelGGL((features_kernel<0, true>), grid, dim3(256), 0, stream, a);
+        return hipGetLastError();
+    }
+    if (bvh) hipLaunchKernelGGL(features_kernel<2>, grid, dim3(256), kStackBytes, stream, a);
+    else hipLaunchKernelGGL(features_kernel<0>, grid, dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_feature_resolve(const FeatureResolveArgs& a, hipStream_t stream) {
+    if (!a.n_owned) return hipSuccess;
+    hipLaunchKernelGGL(feature_resolve_kernel, dim3((a.n_owned + 255u) / 256u), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 hipError_t launch_intersect_segments(const SceneView& sc, uint64_t n, const float* d_o, const float* d_d, const float* d_tmax, float* d_t,

@@ -1647,6 +1647,80 @@ __global__ __launch_bounds__(256) void intersect_f64_kernel(const IsectArgs64 by
 }
 #undef KI
 
+// rpt_render_features* in this mode: the first-hit features of a render's camera samples, records as rptg::features_kernel writes
+// them (rptg::feature_resolve_kernel resolves both).  Item i = chunk * n_owned + pixel slot, one lane each; n_owned is a multiple
+// of 1024, so the 64 items of a wave are the 8 x 8 pixels of one block in ONE chunk: the sample loop's trip count is wave-uniform,
+// as closest_hit_wave needs -- every lane takes part in every query, the ones outside the image as inactive.  Per sample: the
+// camera sample of render_f64_kernel (debug_camera_f64_kernel), intersect_f64_kernel's query and hit_normal, then Material::color
+// of the object or Environment::get_color of the direction; each channel a sum in sample order from +0.0.
+#define KF (*rptg::kernarg_args<FeatureArgs64>())
+static_assert(offsetof(FeatureArgs64, a) == 0, "KA reads the Args at kernarg + 0");
+template <bool LDSTAB, bool MONO, bool TREE = false>
+__global__ __launch_bounds__(256) void features_f64_kernel(const FeatureArgs64 by_value) {
+    (void)by_value;
+    extern __shared__ double lds64[];
+    const ObjRec* recs;
+    const TriRec* trecs;
+    stage_tables<LDSTAB>(lds64, recs, trecs);
+    volatile uint32_t* const slots = reinterpret_cast<uint32_t*>(lds64 + kPhSlotBase) + (threadIdx.x >> 6) * 64u;
+    const auto& ka = KA;
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t first = __builtin_amdgcn_readfirstlane(item & ~63u);   // the wave's first item
+    if (first >= ka.n_items) return;   // (the whole wave)
+    const uint32_t chunk = first / ka.n_owned;   // wave-uniform
+    const uint32_t p = item - chunk * ka.n_owned;
+    bool mine = item < ka.n_items;
+    uint32_t x = 0u, y = 0u;
+    if (mine) {
+        const uint32_t tl = p >> 10, within = p & 1023u, sb = within >> 6, l = within & 63u;
+        const uint32_t tile = ka.tiles[tl], ty = tile / ka.tiles_x, tx = tile - ty * ka.tiles_x;
+        x = tx * 32u + (sb & 3u) * 8u + (l & 7u);
+        y = ty * 32u + (sb >> 2) * 8u + (l >> 3);
+        mine = x < ka.width && y < ka.height;   // slots of clipped tiles lie outside the image
+    }
+    const uint32_t s0 = chunk * ka.chunk_spp, s1 = min(s0 + ka.chunk_spp, ka.iterations);
+    const double dim = ka.dim;
+    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    uint32_t id = 0u;
+    for (uint32_t s = s0; s < s1; s++) {
+        D ro = mk(0, 0, 0), rd = mk(0, 0, 1);
+        if (mine) {
+            Rng64 rng;
+            rng.r.seed(ka.seed_mixed, y * ka.width + x, ka.sample_offset + s);
+            const double xn = pixel_xn(x, ka.width, dim);
+            const double yn = pixel_yn(y, ka.height, dim);
+            const double dx = rng.range(-1.0 / dim, 1.0 / dim);
+            const double dy = rng.range(-1.0 / dim, 1.0 / dim);
+            cast_ray(ka.cam, xn + dx, yn + dy, rng, ro, rd);
+        }
+        Query q;
+        uint32_t ce = 0, cr = 0;
+        closest_hit_wave<false, MONO, TREE>(recs, trecs, slots, mine, ro, rd, kInf, q, ce, cr);
+        if (mine) {
+            D col, n = mk(0, 0, 0);
+            double z = 0.0, cov = 0.0;
+            if (q.obj >= 0) {
+                n = hit_normal<MONO>(recs, trecs, q, ro, rd);
+                col = mat_color(KA.sc.shade[q.obj].mat);
+                z = q.t;
+                cov = 1.0;
+                if (s == 0u) id = uint32_t(q.obj) + 1u;
+            } else {
+                col = env_color(rd);
+            }
+            acc[0] += col.x; acc[1] += col.y; acc[2] += col.z;
+            acc[3] += n.x; acc[4] += n.y; acc[5] += n.z;
+            acc[6] += z;
+            acc[7] += cov;
+        }
+    }
+    if (!mine) return;
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; k++) KF.slab[size_t(k) * ka.n_items + item] = acc[k];
+    if (chunk == 0u) KF.ids[p] = id;
+}
+#undef KF
+
 // rpt_debug_light_sample_f64: Shape::sample of a Light::Object's shape and Light::illuminate, one position per lane, through this
 // mode's own functions -- the dispatch on GROUPL is illuminate_object's -- on two copies of stream (seed, lane, 0).  The argument
 // struct begins with the Args, as every kernel's whose code reads KA.
@@ -1743,6 +1817,24 @@ static hipError_t launch_intersect_f64(const rpt64::IsectArgs64& a, hipStream_t 
     } else {
         if (tab) hipLaunchKernelGGL((rpt64::intersect_f64_kernel<true, false>), grid, dim3(256), lds, stream, a);
         else hipLaunchKernelGGL((rpt64::intersect_f64_kernel<false, false>), grid, dim3(256), lds, stream, a);
+    }
+    return hipGetLastError();
+}
+// (the flavours of launch_intersect_f64, chosen the same way)
+hipError_t launch_features_f64(const rpt64::FeatureArgs64& a, hipStream_t stream) {
+    if (!a.a.n_items) return hipSuccess;
+    const size_t lds = size_t(rpt64::kPhLdsDoubles) * 8u;
+    const bool tab = a.a.sc.n_objects <= rpt64::kLdsObjs && a.a.sc.n_obj_tris <= rpt64::kLdsTris;
+    const dim3 grid((a.a.n_items + 255u) / 256u);
+    if (a.a.mono) {
+        if (tab) hipLaunchKernelGGL((rpt64::features_f64_kernel<true, true>), grid, dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL((rpt64::features_f64_kernel<false, true>), grid, dim3(256), lds, stream, a);
+    } else if (a.a.tree) {
+        if (tab) hipLaunchKernelGGL((rpt64::features_f64_kernel<true, false, true>), grid, dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL((rpt64::features_f64_kernel<false, false, true>), grid, dim3(256), lds, stream, a);
+    } else {
+        if (tab) hipLaunchKernelGGL((rpt64::features_f64_kernel<true, false>), grid, dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL((rpt64::features_f64_kernel<false, false>), grid, dim3(256), lds, stream, a);
     }
     return hipGetLastError();
 }

@@ -533,6 +533,11 @@ struct rpt_scene {
         LaunchSet sets[2];
         rpti::DevMem d_counters;
         rpti::DevMem d_out;
+        // the feature pass (rpt_render_features*): its records and ids, the planes of the host entry point, and the event recorded after
+        // its resolve -- one pass of a scene at a time, whatever the stream; the launch sets above are not involved
+        rpti::DevMem d_feat_slab, d_feat_out;
+        rpti::Event feat_done;
+        bool feat_used = false;
         // "timing": an event triple (before render, after render, after resolve) per launch, in a ring; nothing waits
         // for them until rpt_get_timing / rpt_get_timing_mean is called
         std::vector<rpti::Event> evs;
@@ -2471,7 +2476,8 @@ extern "C++" void rpti::fill_camera64(const rpt_camera* cam, rpt64::Camera& q) {
 }
 
 extern "C++" int rpti::prepare_render(rpt_scene* s, hipStream_t st, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations,
-                         uint64_t seed, uint32_t sample_offset, RenderArgs& a, uint32_t min_chunk, uint32_t fixed_chunk, uint32_t slab_item_bytes) {
+                         uint64_t seed, uint32_t sample_offset, RenderArgs& a, uint32_t min_chunk, uint32_t fixed_chunk, uint32_t slab_item_bytes,
+                         bool launch_set) {
     if (!s || !cam || !prm) return fail(RPT_ERR_INVALID, "null argument");
     if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called before rendering");
     if (prm->width == 0 || prm->height == 0 || iterations == 0) return fail(RPT_ERR_INVALID, "empty render");
@@ -2513,6 +2519,7 @@ extern "C++" int rpti::prepare_render(rpt_scene* s, hipStream_t st, const rpt_ca
     uint64_t n_items = uint64_t(a.n_owned) * a.n_chunks;
     if (n_items >= (1ull << 32) - (1ull << 24)) return fail(RPT_ERR_INVALID, "too many work items; raise chunk_spp");
     a.n_items = uint32_t(n_items);
+    if (!launch_set) return RPT_OK;   // (what follows configures the render kernels and their scratch)
     size_t slab_bytes = std::max<size_t>(size_t(n_items) * slab_item_bytes, 16);
     // the launch set: the one this stream used last, else the other one
     if (s->dev.sets[s->cur_set].used && s->dev.sets[s->cur_set].stream != st) s->cur_set ^= 1;
@@ -2682,6 +2689,84 @@ int rpt_render_sample(rpt_scene* s, const rpt_camera* cam, const rpt_render_para
     if (rc) return rc;
     HIP_TRY(hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost));
     return rpti::fetch_counters(s, a);
+}
+// What rpt_render_features* refuse before any device call.
+static int check_features(const rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, const void* albedo,
+                          const void* normal, const void* depth) {
+    if (!albedo && !normal && !depth) return fail(RPT_ERR_INVALID, "no feature plane requested");
+    if (!s || !cam || !prm) return fail(RPT_ERR_INVALID, "null argument");
+    if (prm->width == 0 || prm->height == 0 || iterations == 0) return fail(RPT_ERR_INVALID, "empty render");
+    if (uint64_t(prm->width) * prm->height > (1ull << 31)) return fail(RPT_ERR_INVALID, "image too large");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called before rendering");
+    return RPT_OK;
+}
+// The feature pass on stream `st` into the requested device planes: records into the scene's own feature scratch (fp32 or
+// reference-epsilon kernel, as the scene was committed), then the resolve.  A pass waits for the scene's previous one.
+static int run_features(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
+                        uint32_t sample_offset, double* d_albedo, double* d_normal, double* d_depth, hipStream_t st) {
+    if (int rc = check_features(s, cam, prm, iterations, d_albedo, d_normal, d_depth)) return rc;
+    RenderArgs a{};
+    int rc = rpti::prepare_render(s, st, cam, prm, iterations, seed, sample_offset, a, 0, 0, 0, false);
+    if (rc) return rc;
+    const bool f64 = bool(s->dev.arena64);
+    if (!launch_feature_resolve || (f64 ? !launch_features_f64 : !launch_features))
+        return fail(RPT_ERR_UNSUPPORTED, "rpt_render_features: built without the kernels");
+    if (s->dev.feat_used) HIP_TRY(hipStreamWaitEvent(st, s->dev.feat_done.get(), 0));
+    else HIP_TRY(s->dev.feat_done.create(hipEventDisableTiming));
+    s->dev.feat_used = true;
+    const size_t slab_bytes = size_t(a.n_items) * 64;
+    HIP_TRY(s->dev.d_feat_slab.reserve(std::max<size_t>(slab_bytes + size_t(a.n_owned) * 4, 16)));
+    double* const slab = s->dev.d_feat_slab.get<double>();
+    uint32_t* const ids = reinterpret_cast<uint32_t*>(s->dev.d_feat_slab.get<char>() + slab_bytes);
+    const uint32_t shard_count = prm->shard_count == 0 ? 1 : prm->shard_count;
+    if (shard_count > 1)   // the pixels of the other shards: 0 in every requested plane
+        for (double* plane : {d_albedo, d_normal, d_depth})
+            if (plane) HIP_TRY(hipMemsetAsync(plane, 0, size_t(prm->width) * prm->height * 24, st));
+    if (f64) {
+        rpt64::FeatureArgs64 q{};
+        rpti::fill_args64(s, cam, prm, &a, q.a);
+        q.slab = slab;
+        q.ids = ids;
+        HIP_TRY(launch_features_f64(q, st));
+    } else {
+        FeatureArgs q{};
+        q.r = a;
+        q.slab = slab;
+        q.ids = ids;
+        HIP_TRY(launch_features(q, st));
+    }
+    FeatureResolveArgs r{};
+    r.tiles = a.tiles; r.tiles_x = a.tiles_x; r.n_owned = a.n_owned; r.n_chunks = a.n_chunks; r.n_items = a.n_items;
+    r.width = a.width; r.height = a.height; r.iterations = a.iterations;
+    r.slab = slab; r.ids = ids;
+    r.albedo = d_albedo; r.normal = d_normal; r.depth = d_depth;
+    HIP_TRY(launch_feature_resolve(r, st));
+    HIP_TRY(hipEventRecord(s->dev.feat_done.get(), st));
+    return RPT_OK;
+}
+int rpt_render_features_device(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
+                               uint32_t sample_offset, void* d_albedo, void* d_normal, void* d_depth, void* hip_stream) {
+    return run_features(s, cam, prm, iterations, seed, sample_offset, static_cast<double*>(d_albedo), static_cast<double*>(d_normal),
+                        static_cast<double*>(d_depth), static_cast<hipStream_t>(hip_stream));
+}
+int rpt_render_features(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
+                        uint32_t sample_offset, double* out_albedo, double* out_normal, double* out_depth) {
+    if (int rc = check_features(s, cam, prm, iterations, out_albedo, out_normal, out_depth)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = size_t(prm->width) * prm->height * 24;
+    double* const outs[3] = {out_albedo, out_normal, out_depth};
+    double* d[3] = {nullptr, nullptr, nullptr};
+    size_t n_planes = 0;
+    for (int k = 0; k < 3; k++) n_planes += outs[k] ? 1 : 0;
+    // (the planes of the previous call have been copied out: its hipMemcpy waited for them)
+    HIP_TRY(s->dev.d_feat_out.reserve(n_planes * bytes));
+    for (int k = 0, i = 0; k < 3; k++)
+        if (outs[k]) d[k] = s->dev.d_feat_out.get<double>() + size_t(i++) * (bytes / 8);
+    int rc = run_features(s, cam, prm, iterations, seed, sample_offset, d[0], d[1], d[2], nullptr);
+    if (rc) return rc;
+    for (int k = 0; k < 3; k++)
+        if (outs[k]) HIP_TRY(hipMemcpy(outs[k], d[k], bytes, hipMemcpyDeviceToHost));
+    return RPT_OK;
 }
 int rpt_f64_mesh_tree_info(rpt_scene* s, uint64_t out[8]) {
     if (!s || !out) return fail(RPT_ERR_INVALID, "null argument");
