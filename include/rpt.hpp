@@ -439,12 +439,69 @@ class Buffer {
         return n;
     }
     rpt_buffer* raw() const { return h_; }
+    // rpt_buffer_mean_device (an addition): per-pixel mean of the batches and the variance of that mean, device pointers
+    // (width*height*3 and width*height doubles; d_var may be null).  Needs two batches.
+    void mean_device(void* d_rgb, void* d_var, void* hip_stream = nullptr) const {
+        if (rpt_buffer_mean_device(h_, d_rgb, d_var, hip_stream) != RPT_OK) throw Error(rpt_last_error());
+    }
+    // rpt_buffer_denoised_image (an addition): mean -> Denoiser -> color_bytes, no box filter; the feature planes are device pointers.
+    RgbImage denoised_image(class Denoiser& denoiser, const rpt_denoise_params& params, const void* d_albedo, const void* d_normal,
+                            const void* d_depth) const;
     uint32_t width, height;
     Filter filter;
 
   private:
     rpt_buffer* h_ = nullptr;
 };
+// The a-trous denoiser of rpt_hip.h (rpt_denoise*, an addition): owns the scratch of one frame size on one device.
+class Denoiser {
+  public:
+    // passes 4, demodulation and id match on, sigma_color 4, sigma_normal 0.5, depth term off (it is in scene units per pixel step)
+    static rpt_denoise_params default_params() { return {4, RPT_DENOISE_DEMODULATE | RPT_DENOISE_MATCH_ID, 4.0, 0.5, 0.0}; }
+    Denoiser(uint32_t w, uint32_t h, int device = 0) : width(w), height(h) {
+        h_ = rpt_denoiser_create(device, w, h);
+        if (!h_) throw Error(rpt_last_error());
+    }
+    Denoiser(const Denoiser&) = delete;
+    Denoiser& operator=(const Denoiser&) = delete;
+    Denoiser(Denoiser&& o) noexcept : width(o.width), height(o.height), h_(o.h_) { o.h_ = nullptr; }
+    ~Denoiser() {
+        if (h_) rpt_denoiser_destroy(h_);
+    }
+    // host arrays: rgb, albedo, normal, depth of width*height*3 doubles, var of width*height; an empty vector is a null plane
+    std::vector<double> denoise(const rpt_denoise_params& params, const std::vector<double>& rgb, const std::vector<double>& var,
+                                const std::vector<double>& albedo, const std::vector<double>& normal, const std::vector<double>& depth,
+                                std::vector<double>* out_var = nullptr) {
+        const size_t n = size_t(width) * height;
+        auto ptr = [&](const std::vector<double>& v, size_t want) -> const double* {
+            if (v.empty()) return nullptr;
+            if (v.size() != want) throw Error("Invalid plane dimension");
+            return v.data();
+        };
+        std::vector<double> out(n * 3);
+        if (out_var) out_var->assign(n, 0.0);
+        if (rpt_denoise(h_, &params, ptr(rgb, n * 3), ptr(var, n), ptr(albedo, n * 3), ptr(normal, n * 3), ptr(depth, n * 3), out.data(),
+                        out_var ? out_var->data() : nullptr) != RPT_OK)
+            throw Error(rpt_last_error());
+        return out;
+    }
+    void denoise_device(const rpt_denoise_params& params, const void* d_rgb, const void* d_var, const void* d_albedo, const void* d_normal,
+                        const void* d_depth, void* d_out, void* d_out_var = nullptr, void* hip_stream = nullptr) {
+        if (rpt_denoise_device(h_, &params, d_rgb, d_var, d_albedo, d_normal, d_depth, d_out, d_out_var, hip_stream) != RPT_OK)
+            throw Error(rpt_last_error());
+    }
+    rpt_denoiser* raw() const { return h_; }
+    uint32_t width, height;
+
+  private:
+    rpt_denoiser* h_ = nullptr;
+};
+inline RgbImage Buffer::denoised_image(Denoiser& denoiser, const rpt_denoise_params& params, const void* d_albedo, const void* d_normal,
+                                       const void* d_depth) const {
+    RgbImage img{width, height, std::vector<uint8_t>(size_t(width) * height * 3)};
+    if (rpt_buffer_denoised_image(h_, denoiser.raw(), &params, d_albedo, d_normal, d_depth, img.data.data()) != RPT_OK) throw Error(rpt_last_error());
+    return img;
+}
 
 // ---- renderer.rs
 class Renderer {

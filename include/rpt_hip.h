@@ -272,7 +272,8 @@ int rpt_scene_render_chunking(rpt_scene*, uint32_t iterations, uint32_t* chunk_s
  * "bvh_leaf_max" (read by rpt_scene_commit: triangles per leaf of a mesh tree, default 4 -- C5: 49.8 / 43.1 / 41.1 /
  * 41.1 / 41.7 ms for 1 / 2 / 4 / 6 / 8), "bvh_max_depth" (read by rpt_scene_commit: a mesh tree that the SAH builder makes deeper than this is rebuilt
  * with object-median splits, default and maximum 20 -- the traversal stack holds 21 entries per mesh tree, 32 for scene tree + mesh tree;
- * a scene that still does not fit is refused with RPT_ERR_UNSUPPORTED);
+ * a scene that still does not fit is refused with RPT_ERR_UNSUPPORTED),
+ * "denoise_stage" (a process option, read by rpt_denoiser_create: -1, 0, 1 or 2, see the denoiser below);
  * returns RPT_ERR_INVALID for unknown names. */
 int rpt_set_option(const char* name, int64_t value);
 int rpt_scene_set_option(rpt_scene*, const char* name, int64_t value);
@@ -292,6 +293,66 @@ int rpt_buffer_batches(rpt_buffer*, uint32_t* n);
  * batch and push its means into the buffer without leaving the device. */
 int rpt_render_into_buffer(rpt_scene*, const rpt_camera*, const rpt_render_params*, uint32_t iterations,
                            uint64_t seed, uint32_t sample_offset, rpt_buffer*);
+
+/* ---- denoiser on the device (an addition: the reference's only spatial filter is Filter::Box) ----
+ * An edge-avoiding a-trous wavelet filter of the SVGF family, spatial part only, guided by the first-hit feature planes
+ * (rpt_render_features*) and by the per-pixel variance of a frame's mean (rpt_buffer_mean_device).  No temporal accumulation, no
+ * reprojection.  Sharded frames are not filtered shard by shard: a shard's planes and frame are assembled first
+ * (rpt_gather_frame_device carries them) and rank 0 filters.
+ *
+ * The filter is defined as an order of fp64 operations, each rounded on its own (no fused multiply-add, IEEE division, no atomics),
+ * so the result is a function of the arguments alone, whatever the tiling, the option "denoise_stage" or the stream.  Every array
+ * is fp64, row-major, y = 0 at the top: rgb[h][w][3]; var[h][w], the variance of the pixel's mean, or NULL; albedo, normal, depth
+ * in the format rpt_render_features writes, each or NULL.  passes P in 1..8; flags RPT_DENOISE_*; a term is on iff its sigma > 0.
+ * A term or flag whose plane is NULL is RPT_ERR_INVALID: sigma_color > 0 needs var, sigma_normal > 0 normal, sigma_depth > 0 depth,
+ * RPT_DENOISE_DEMODULATE albedo, RPT_DENOISE_MATCH_ID depth.
+ *   Per pixel p:  den_k = (DEMODULATE and albedo_k > 0.0) ? albedo_k : 1.0 (false for NaN);  c_k = rgb_k / den_k;
+ *     v = var ? var[p] : 0.0;  n = normal (0 when NULL);  z = depth[..][0], id = depth[..][2] (0 when NULL).
+ *   Pass i = 0 .. P-1, step s = 2^i:
+ *     colour term only:  vhat_p = (sum (g_dy g_dx) v_q) / (sum g_dy g_dx) over the 3 x 3 neighbours (distance 1) inside the image,
+ *       g = (1/4, 1/2, 1/4), dy outer, dx inner, both sums from +0.0;  k_p = 1.0 / ((sigma_color sigma_color) (vhat_p + 1e-12)).
+ *     a_n = 1.0 / sigma_normal;  a_z = 1.0 / (sigma_depth double(s)).
+ *     For dy = -2..2 (outer), dx = -2..2 (inner), q = p + s (dx, dy); taps outside the image are skipped.
+ *       x = +0.0, then the enabled terms in the order colour, normal, depth:
+ *         colour: e_k = (c_q,k - c_p,k) den_p,k;  x = x + ((e0 e0 + e1 e1) + e2 e2) k_p
+ *         normal: e_k = (n_q,k - n_p,k) a_n;      x = x + ((e0 e0 + e1 e1) + e2 e2)
+ *         depth:  e = (z_q - z_p) a_z;            x = x + e e
+ *       The tap is skipped unless x < 4.0 and, with MATCH_ID, id_q == id_p (NaN fails both tests).
+ *       t = 1.0 - x 0.25;  t2 = t t;  w = (t2 t2) (h_dy h_dx), h = (1/16, 1/4, 3/8, 1/4, 1/16): a compactly supported stand-in for
+ *       exp(-x) without a transcendental.   W += w;  C_k += w c_q,k;  V += (w w) v_q, all from +0.0.
+ *     End of the pass: if W > 0.0, c' = C_k / W and v' = V / (W W); otherwise the pixel keeps c and v (what a NaN colour with the
+ *     colour term on, a NaN variance, depth or id with their term or flag on does to the pixel itself).
+ *   Output: out_k = c_k den_k, and optionally the filtered v.
+ * A denoiser owns the ping-pong records of one frame size on one device.  rpt_denoiser_create reads the process option
+ * "denoise_stage" (rpt_set_option): -1 the measured default (2), 0 every pass gathers its taps from global memory, n = 1 or 2 the passes
+ * of step <= n stage their tile and its halo in LDS first (larger n: RPT_ERR_INVALID) -- the same bits either way.
+ * Every argument check precedes every device call.  d_out (and d_out_var) must not be one of the inputs.  Two calls on one denoiser
+ * are ordered, whatever their streams; denoisers are independent of each other and of renders. */
+#define RPT_DENOISE_DEMODULATE 1u
+#define RPT_DENOISE_MATCH_ID 2u
+typedef struct rpt_denoise_params {
+    uint32_t passes, flags;
+    double sigma_color, sigma_normal, sigma_depth;
+} rpt_denoise_params;
+typedef struct rpt_denoiser rpt_denoiser;
+rpt_denoiser* rpt_denoiser_create(int device, uint32_t width, uint32_t height);
+void rpt_denoiser_destroy(rpt_denoiser*);
+/* DEVICE pointers on the denoiser's device, hip_stream a hipStream_t (NULL = default stream); d_out: width*height*3 doubles,
+ * d_out_var: width*height doubles or NULL. */
+int rpt_denoise_device(rpt_denoiser*, const rpt_denoise_params*, const void* d_rgb, const void* d_var, const void* d_albedo,
+                       const void* d_normal, const void* d_depth, void* d_out, void* d_out_var, void* hip_stream);
+/* The same with host pointers, synchronous. */
+int rpt_denoise(rpt_denoiser*, const rpt_denoise_params*, const double* rgb, const double* var, const double* albedo,
+                const double* normal, const double* depth, double* out, double* out_var);
+/* Per pixel of a buffer with n batches: d_rgb = sum / n in push order (width*height*3 doubles), d_var (width*height doubles, or
+ * NULL) = the variance of that mean, max(sumsq - n ((mr mr + mg mg) + mb mb), 0) / (n - 1) / n: the per-pixel expression of
+ * rpt_buffer_variance divided by n, each operation rounded on its own.  RPT_ERR_STATE with fewer than 2 batches.  Enqueued on
+ * hip_stream; batches added on other streams must have been waited for by the caller. */
+int rpt_buffer_mean_device(rpt_buffer*, void* d_rgb, void* d_var, void* hip_stream);
+/* mean -> filter -> color_bytes (src/color.rs:18-24), no box filter; synchronous, only width*height*3 bytes come back.  The planes
+ * are DEVICE pointers (each or NULL, as the parameters allow).  Buffer and denoiser of different devices or sizes: RPT_ERR_INVALID. */
+int rpt_buffer_denoised_image(rpt_buffer*, rpt_denoiser*, const rpt_denoise_params*, const void* d_albedo, const void* d_normal,
+                              const void* d_depth, uint8_t* out_rgb8);
 
 /* ---- photon mapping (next tier: src/photon.rs; config C4 = photon_point_query_beam_render) ----
  * `enum PhotonRenderKind` (src/photon.rs:631-639): point-point (photon_map_render), beam-point

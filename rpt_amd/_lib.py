@@ -65,6 +65,16 @@ class RenderParams(C.Structure):
     ]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [
+        ("passes", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("sigma_color", C.c_double),
+        ("sigma_normal", C.c_double),
+        ("sigma_depth", C.c_double),
+    ]
+
+
 # Every symbol include/rpt_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _D3 = C.POINTER(C.c_double)
@@ -114,6 +124,12 @@ SYMBOLS = [
     ("rpt_buffer_batches", C.c_int, [_P, C.POINTER(C.c_uint32)]),
     ("rpt_render_into_buffer", C.c_int,
      [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P]),
+    ("rpt_denoiser_create", _P, [C.c_int, C.c_uint32, C.c_uint32]),
+    ("rpt_denoiser_destroy", None, [_P]),
+    ("rpt_denoise_device", C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("rpt_denoise", C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P]),
+    ("rpt_buffer_mean_device", C.c_int, [_P, _P, _P, _P]),
+    ("rpt_buffer_denoised_image", C.c_int, [_P, _P, C.POINTER(DenoiseParams), _P, _P, _P, _P]),
     ("rpt_photon_map_build", C.c_int, [_P, C.c_uint64, C.c_int32, C.c_double, C.c_uint64]),
     ("rpt_photon_shoot", C.c_int,
      [_P, C.c_uint64, C.c_int32, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),

@@ -60,7 +60,7 @@ __all__ = [
     "set_option", "shard_pixels",
     "vec3", "hex_color", "color_bytes", "Sphere", "Cube", "Plane", "Triangle", "Mesh", "KdTree", "Transformed",
     "MonomialSurface", "sphere", "cube", "plane", "polygon", "monomial_surface", "Material", "Object", "Light", "Medium", "Environment",
-    "Scene", "Camera", "Filter", "Buffer", "DeviceBuffer", "Renderer", "RptError",
+    "Scene", "Camera", "Filter", "Buffer", "DeviceBuffer", "Renderer", "RptError", "DenoiseParams", "Denoiser",
 ]
 
 
@@ -679,9 +679,137 @@ class DeviceBuffer:
         _lib.check(_lib.load().rpt_buffer_variance(self._h, C.byref(v)))
         return float(v.value)
 
+    def mean_device(self, d_rgb_ptr, d_var_ptr, stream_ptr=0):
+        """rpt_buffer_mean_device: device pointers to width*height*3 and width*height doubles (d_var_ptr 0 / None: not computed)."""
+        _lib.check(_lib.load().rpt_buffer_mean_device(self._h, C.c_void_p(d_rgb_ptr or None), C.c_void_p(d_var_ptr or None),
+                                                      C.c_void_p(stream_ptr)))
+
+    def mean(self):
+        """-> (rgb, var): the per-pixel mean of the batches in push order, (h, w, 3), and the variance of that mean, (h, w): what
+        Denoiser.denoise takes.  Needs at least two batches."""
+        n = self.width * self.height
+        d = _device_zeros(4 * n, self.device)
+        _sync(self.device)                                       # batches may have been added on other streams
+        self.mean_device(d.data_ptr(), d.data_ptr() + 24 * n)
+        host = d.cpu().numpy()
+        return host[:3 * n].reshape(self.height, self.width, 3).copy(), host[3 * n:].reshape(self.height, self.width).copy()
+
+    def denoised_image(self, denoiser, planes, params=None):
+        """rpt_buffer_denoised_image: mean -> a-trous filter -> color_bytes, no box filter -> (h, w, 3) uint8.  `planes`: a dict with
+        any of "albedo", "normal", "depth" (what `params` needs), each an (h, w, 3) array as Renderer.features_array returns it or
+        a device pointer (int) as Renderer.features_device filled it."""
+        params = params or DenoiseParams()
+        unknown = set(planes) - {"albedo", "normal", "depth"}
+        if unknown:
+            raise ValueError(f"denoised_image: unknown planes {sorted(unknown)}")
+        keep, ptrs = [], []
+        for k in ("albedo", "normal", "depth"):
+            v = planes.get(k)
+            if v is None or isinstance(v, int):
+                ptrs.append(C.c_void_p(v or None))
+                continue
+            a = np.ascontiguousarray(v, dtype=np.float64)
+            if a.size != self.width * self.height * 3:
+                raise ValueError(f"denoised_image: plane {k} is not {self.height} x {self.width} x 3")
+            keep.append(_device_copy(a, self.device))
+            ptrs.append(C.c_void_p(keep[-1].data_ptr()))
+        _sync(self.device)
+        out = np.empty((self.height, self.width, 3), dtype=np.uint8)
+        _lib.check(_lib.load().rpt_buffer_denoised_image(self._h, denoiser._h, C.byref(params.desc()), *ptrs, _vp(out)))
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.load().rpt_buffer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ------------------------------------------------------------------ denoiser (rpt_denoise*, an addition)
+def _device_zeros(n_doubles, device):
+    """Device scratch of the wrappers that hand host arrays to a device-pointer entry point (torch is the allocator, imported lazily
+    as in rpt_amd.dist: `import rpt_amd` stays numpy-only)."""
+    import torch
+    return torch.zeros(int(n_doubles), dtype=torch.float64, device=f"cuda:{int(device)}")
+
+
+def _device_copy(a, device):
+    import torch
+    return torch.from_numpy(np.array(a, dtype=np.float64).reshape(-1)).to(f"cuda:{int(device)}")   # (a copy: the caller's array may be read-only)
+
+
+def _sync(device):
+    import torch
+    torch.cuda.synchronize(int(device))
+
+
+class DenoiseParams:
+    """rpt_denoise_params.  A term is on iff its sigma > 0.  The defaults are those of the CPU prototype on the oracle's renders
+    ("Denoiser"); sigma_depth is off because it is in scene units per pixel step and no default is right for
+    every scene."""
+    DEMODULATE, MATCH_ID = 1, 2
+
+    def __init__(self, passes=4, demodulate=True, match_id=True, sigma_color=4.0, sigma_normal=0.5, sigma_depth=0.0):
+        self.passes = int(passes)
+        self.demodulate, self.match_id = bool(demodulate), bool(match_id)
+        self.sigma_color, self.sigma_normal, self.sigma_depth = float(sigma_color), float(sigma_normal), float(sigma_depth)
+
+    @property
+    def flags(self):
+        return (self.DEMODULATE if self.demodulate else 0) | (self.MATCH_ID if self.match_id else 0)
+
+    def desc(self):
+        return _lib.DenoiseParams(self.passes, self.flags, self.sigma_color, self.sigma_normal, self.sigma_depth)
+
+
+class Denoiser:
+    """rpt_denoiser: the variance-guided a-trous filter of include/rpt_hip.h for frames of one size on one device."""
+
+    def __init__(self, width, height, device=0):
+        self.width, self.height, self.device = int(width), int(height), int(device)
+        if self.width <= 0 or self.height <= 0:
+            raise ValueError("Denoiser: empty frame")
+        self._h = _lib.load().rpt_denoiser_create(self.device, self.width, self.height)
+        if not self._h:
+            _lib.check(-1)
+
+    def denoise(self, rgb, var, albedo, normal, depth, params=None, return_variance=False):
+        """Host arrays: rgb, albedo, normal, depth of (h, w, 3), var of (h, w); any but rgb may be None where `params` does not
+        need it -> the filtered (h, w, 3) frame, with return_variance the filtered (h, w) variance as well."""
+        params = params or DenoiseParams()
+        n = self.width * self.height
+        arrays = []
+        for name, a, size in (("rgb", rgb, 3 * n), ("var", var, n), ("albedo", albedo, 3 * n), ("normal", normal, 3 * n), ("depth", depth, 3 * n)):
+            if a is None:
+                if name == "rgb":
+                    raise ValueError("denoise: rgb is required")
+                arrays.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != size:
+                raise ValueError(f"denoise: {name} has {a.size} values, the frame needs {size}")
+            arrays.append(a)
+        out = np.empty((self.height, self.width, 3), dtype=np.float64)
+        out_var = np.empty((self.height, self.width), dtype=np.float64) if return_variance else None
+        _lib.check(_lib.load().rpt_denoise(self._h, C.byref(params.desc()), *[_vp(a) if a is not None else None for a in arrays],
+                                           _vp(out), _vp(out_var) if return_variance else None))
+        return (out, out_var) if return_variance else out
+
+    def denoise_device(self, d_rgb, d_var, d_albedo, d_normal, d_depth, d_out, d_out_var=0, params=None, stream_ptr=0):
+        """Asynchronous variant: device pointers (0 / None: a null plane), enqueued on stream_ptr."""
+        params = params or DenoiseParams()
+        _lib.check(_lib.load().rpt_denoise_device(
+            self._h, C.byref(params.desc()), *[C.c_void_p(p or None) for p in (d_rgb, d_var, d_albedo, d_normal, d_depth, d_out, d_out_var)],
+            C.c_void_p(stream_ptr)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().rpt_denoiser_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -824,6 +952,34 @@ class Renderer:
         self._sample_offset = 0
         self.sample(self.num_samples_, buffer)
         return buffer.image()
+
+    def render_denoised(self, batches=4, params=None):
+        """An addition: num_samples in `batches` batches (at least 2; the first num_samples % batches of them one sample longer) into
+        a DeviceBuffer, the feature planes of the same num_samples camera samples, then DeviceBuffer.denoised_image: the per-pixel
+        mean and the variance of that mean, the a-trous filter, color_bytes -> (h, w, 3) uint8.  The frame, the planes and the
+        filter stay on the device; filter() is not applied.  Not for sharded renders (rank 0 filters the assembled frame)."""
+        batches = int(batches)
+        if batches < 2:
+            raise ValueError("render_denoised: the variance of the mean needs at least 2 batches")
+        if self.num_samples_ < batches:
+            raise ValueError("render_denoised: num_samples must be at least the number of batches")
+        if self.shard_count_ != 1:
+            raise ValueError("render_denoised: a sharded frame is assembled first; rank 0 filters it")
+        buffer = DeviceBuffer(self.width_, self.height_, None, self.device_)
+        denoiser = Denoiser(self.width_, self.height_, self.device_)
+        n = self.width_ * self.height_ * 3
+        planes = _device_zeros(3 * n, self.device_)
+        _sync(self.device_)
+        ptrs = [planes.data_ptr() + 8 * n * k for k in range(3)]
+        self.features_device(self.num_samples_, *ptrs, sample_offset=0)
+        self._sample_offset = 0
+        base, extra = divmod(self.num_samples_, batches)
+        for k in range(batches):
+            self.sample(base + (1 if k < extra else 0), buffer)
+        img = buffer.denoised_image(denoiser, dict(zip(("albedo", "normal", "depth"), ptrs)), params)
+        denoiser.close()
+        buffer.close()
+        return img
 
     def iterative_render(self, callback_interval, callback):
         """renderer.rs:144-156."""

@@ -92,6 +92,33 @@ struct FeatureResolveArgs {
 // (Weak: reached from rpt_render_features* alone, which report RPT_ERR_UNSUPPORTED where no kernel library is linked.)
 __attribute__((weak)) hipError_t launch_features(const FeatureArgs& a, hipStream_t stream);
 __attribute__((weak)) hipError_t launch_feature_resolve(const FeatureResolveArgs& a, hipStream_t stream);
+// rpt_denoise* (denoise.hip): the a-trous filter of include/rpt_hip.h.  Plain grids, one lane per pixel.  The prepare kernel writes one
+// record of 8 doubles per pixel (c rgb = rgb / den, v, n xyz, z) and the id beside it; a pass reads records and ids and writes the
+// next records, or -- the last one, `out` set -- the remodulated frame and, if asked, the filtered variance.
+struct DenoisePrepareArgs {
+    uint32_t n_pixels, flags;                            // RPT_DENOISE_* (DEMODULATE needs albedo)
+    const double *rgb, *var, *albedo, *normal, *depth;   // var, albedo, normal, depth: or null
+    double* rec;                                         // [n_pixels][8]
+    double* ids;                                         // [n_pixels]
+};
+struct DenoisePassArgs {
+    uint32_t width, height, step, flags;
+    uint32_t terms, pad_;                                // bit 0 colour, 1 normal, 2 depth
+    double sigma_color2, a_n, a_z;                       // sigma_color * sigma_color, 1 / sigma_normal, 1 / (sigma_depth * double(step))
+    const double* rec_in;
+    const double* ids;
+    const double* albedo;                                // den of the pixel itself (flag DEMODULATE), else unused
+    double* rec_out;                                     // every pass but the last
+    double *out, *out_var;                               // the last pass (out_var: or null)
+};
+// (Weak: reached from rpt_denoise* and rpt_buffer_mean_device / rpt_buffer_denoised_image alone, which report RPT_ERR_UNSUPPORTED
+// where no kernel library is linked.)
+__attribute__((weak)) hipError_t launch_denoise_prepare(const DenoisePrepareArgs& a, hipStream_t stream);
+__attribute__((weak)) hipError_t launch_denoise_pass(const DenoisePassArgs& a, bool staged /* tile + halo in LDS */, hipStream_t stream);
+static constexpr uint32_t kDenoiseMaxStagedStep = 2;   // the largest step whose tile + halo the staged form holds (option "denoise_stage")
+__attribute__((weak)) hipError_t launch_buffer_mean(uint32_t n_pixels, uint32_t n_batches, const double* d_sum, const double* d_sumsq,
+                                                    double* d_rgb, double* d_var /* or null */, hipStream_t st);
+__attribute__((weak)) hipError_t launch_color_bytes(uint64_t n_values, const double* d_rgb, uint8_t* d_out, hipStream_t st);
 hipError_t launch_debug_rng(uint64_t seed_mixed, uint32_t pixel, uint32_t sample, uint32_t n, uint32_t* d_out,
                             hipStream_t stream);
 hipError_t launch_debug_sample_f(const Material& m, uint64_t n, const float* d_n, const float* d_wo,
