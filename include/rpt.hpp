@@ -447,6 +447,26 @@ class Buffer {
     // rpt_buffer_denoised_image (an addition): mean -> Denoiser -> color_bytes, no box filter; the feature planes are device pointers.
     RgbImage denoised_image(class Denoiser& denoiser, const rpt_denoise_params& params, const void* d_albedo, const void* d_normal,
                             const void* d_depth) const;
+    // Adaptive sampling by tile (rpt_hip.h, an addition).  One batch for the listed 32 x 32 tiles alone (device frame, device list
+    // of distinct tile ids), and the batches each tile holds: tiles_x * tiles_y values, row-major.
+    void add_samples_tiles_device(const void* d_rgb, const void* d_tiles, uint32_t n_tiles, void* hip_stream = nullptr) {
+        if (rpt_buffer_add_samples_tiles_device(h_, d_rgb, d_tiles, n_tiles, hip_stream) != RPT_OK) throw Error(rpt_last_error());
+    }
+    std::vector<uint32_t> tile_batches() const {
+        std::vector<uint32_t> n(size_t((width + 31) / 32) * ((height + 31) / 32));
+        if (rpt_buffer_tile_batches(h_, n.data(), n.size()) != RPT_OK) throw Error(rpt_last_error());
+        return n;
+    }
+    // The tiles' errors into d_err (tiles_x * tiles_y doubles on the device); the ids of the tiles still above params.threshold and
+    // below params.max_batches into d_tiles_out (ascending) -> their number.
+    void tile_errors_device(double floor, void* d_err, void* hip_stream = nullptr) const {
+        if (rpt_buffer_tile_errors_device(h_, floor, d_err, hip_stream) != RPT_OK) throw Error(rpt_last_error());
+    }
+    uint32_t refine_tiles(const rpt_adaptive_params& params, void* d_tiles_out, void* d_err = nullptr, void* hip_stream = nullptr) {
+        uint32_t n = 0;
+        if (rpt_buffer_refine_tiles(h_, &params, d_tiles_out, &n, d_err, hip_stream) != RPT_OK) throw Error(rpt_last_error());
+        return n;
+    }
     uint32_t width, height;
     Filter filter;
 
@@ -594,6 +614,35 @@ class Renderer {
         rpt_render_params rp{p_.width, p_.height, p_.exposure_value, p_.max_bounces, p_.shard_rank, p_.shard_count};
         check(rpt_render_into_buffer(handle_, &cam, &rp, iterations, p_.seed, sample_offset_, buffer.raw()));
         sample_offset_ += iterations;
+    }
+
+    // Tile-list renders (rpt_hip.h, an addition): `iterations` samples of the listed 32 x 32 tiles alone, the bits sample() would
+    // put there; every other element of the frame is left as it is.  Not sharded.  The sample offset advances as in sample().
+    void sample_tiles_device(uint32_t iterations, const void* d_tiles, uint32_t n_tiles, void* d_frame, void* hip_stream = nullptr) {
+        commit();
+        rpt_camera cam = camera_.desc();
+        rpt_render_params rp{p_.width, p_.height, p_.exposure_value, p_.max_bounces, p_.shard_rank, p_.shard_count};
+        check(rpt_render_sample_tiles_device(handle_, &cam, &rp, iterations, p_.seed, sample_offset_, d_tiles, n_tiles, d_frame, hip_stream));
+        sample_offset_ += iterations;
+    }
+    void sample_tiles(uint32_t iterations, const std::vector<uint32_t>& tiles, std::vector<double>& frame) {
+        if (frame.size() != size_t(p_.width) * p_.height * 3) throw Error("Invalid sample dimension");
+        commit();
+        rpt_camera cam = camera_.desc();
+        rpt_render_params rp{p_.width, p_.height, p_.exposure_value, p_.max_bounces, p_.shard_rank, p_.shard_count};
+        check(rpt_render_sample_tiles(handle_, &cam, &rp, iterations, p_.seed, sample_offset_, tiles.data(), uint32_t(tiles.size()), frame.data()));
+        sample_offset_ += iterations;
+    }
+    // rpt_render_adaptive: min_batches full frames, then tile lists while a tile's error is above the threshold, into an empty buffer
+    // -> rounds, tile-batches rendered, tiles at max_batches, tiles.
+    static rpt_adaptive_params default_adaptive_params() { return {4, 4, 16, 0, 0.05, 0.05}; }
+    std::array<uint64_t, 4> render_adaptive(const rpt_adaptive_params& params, Buffer& buffer) {
+        commit();
+        rpt_camera cam = camera_.desc();
+        rpt_render_params rp{p_.width, p_.height, p_.exposure_value, p_.max_bounces, p_.shard_rank, p_.shard_count};
+        std::array<uint64_t, 4> stats{};
+        check(rpt_render_adaptive(handle_, &cam, &rp, &params, p_.seed, buffer.raw(), stats.data()));
+        return stats;
     }
 
     // First-hit feature planes (rpt_hip.h, rpt_render_features: an addition) of the camera samples the next sample() call traces --

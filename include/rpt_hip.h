@@ -136,6 +136,23 @@ int rpt_render_sample(rpt_scene*, const rpt_camera*, const rpt_render_params*, u
  * the same scene must still come from one host thread at a time. */
 int rpt_render_sample_device(rpt_scene*, const rpt_camera*, const rpt_render_params*, uint32_t iterations,
                              uint64_t seed, uint32_t sample_offset, void* d_out_rgb, void* hip_stream);
+/* Tile-list renders (an addition): exactly the listed 32 x 32 tiles, with the kernels a full render of the same scene uses, in
+ * both modes.  A tile id is ty * tiles_x + tx with tiles_x = ceil(width / 32), as in rpt_shard_tiles.  Every in-image pixel of a
+ * listed tile receives the bits rpt_render_sample* with the same arguments writes there (a pixel's value is a function of scene,
+ * camera, params, iterations, seed, sample_offset and the chunking alone, whatever tiles are rendered with it); every other element
+ * of the output is left untouched, not zeroed.  n_tiles == 0 is RPT_OK and launches nothing; shard_count > 1 is RPT_ERR_INVALID (a
+ * list is the sharding); photon-mapped renders have no such entry point.
+ * _device: d_tiles is a DEVICE array of n_tiles ids, trusted to be in range and distinct (rpt_buffer_refine_tiles writes such
+ * lists), read by the launch: it must stay unchanged until the call's work on hip_stream is done.  Stream ordering and the two
+ * launch sets as for rpt_render_sample_device.
+ * Host variant: synchronous; the ids are checked (out of range or listed twice: RPT_ERR_INVALID, before any device call); out_rgb
+ * is read first, so the caller's values outside the listed tiles survive. */
+int rpt_render_sample_tiles_device(rpt_scene*, const rpt_camera*, const rpt_render_params*, uint32_t iterations,
+                                   uint64_t seed, uint32_t sample_offset,
+                                   const void* d_tiles, uint32_t n_tiles, void* d_out_rgb, void* hip_stream);
+int rpt_render_sample_tiles(rpt_scene*, const rpt_camera*, const rpt_render_params*, uint32_t iterations,
+                            uint64_t seed, uint32_t sample_offset,
+                            const uint32_t* tiles, uint32_t n_tiles, double* out_rgb);
 
 /* First-hit feature planes of the camera samples a render of the same arguments traces (an addition: the reference renders
  * radiance only).  Sample s in [0, iterations) of pixel (x, y) is the render's camera sample on stream (seed, y*width + x,
@@ -353,6 +370,53 @@ int rpt_buffer_mean_device(rpt_buffer*, void* d_rgb, void* d_var, void* hip_stre
  * are DEVICE pointers (each or NULL, as the parameters allow).  Buffer and denoiser of different devices or sizes: RPT_ERR_INVALID. */
 int rpt_buffer_denoised_image(rpt_buffer*, rpt_denoiser*, const rpt_denoise_params*, const void* d_albedo, const void* d_normal,
                               const void* d_depth, uint8_t* out_rgb8);
+
+/* ---- adaptive sampling by tile (an addition; the reference's Buffer::add_sample(x, y, ..), src/buffer.rs:25-29, at the
+ * granularity of the render kernels' 32 x 32 tiles) ----
+ * A buffer keeps, besides its full-frame batches, a count of EXTRA batches per tile (allocated and zeroed at the first tile batch):
+ * a pixel p holds n_p = n_batches + extra[tile(p)] batches.  rpt_buffer_add_samples_tiles_device does rpt_buffer_add_samples_device's
+ * arithmetic on the in-image pixels of the listed tiles only (DEVICE list of distinct ids in range; an id out of range is skipped)
+ * and adds 1 to their counters.  rpt_buffer_batches keeps reporting the full-frame batches; rpt_buffer_tile_batches downloads
+ * n_batches + extra per tile (tiles_x * tiles_y values, row-major; a smaller capacity is RPT_ERR_INVALID).
+ * A buffer that never received a tile batch runs the kernels and gives the bits it always did.  One with extra batches:
+ *   rpt_buffer_image: the window's sums, added in the same x-outer / y-inner order, divided by the SUM of the window's n_p
+ *     (`count += samples[index].len()`, buffer.rs:75-93), then color_bytes;
+ *   rpt_buffer_variance: its per-pixel expression with n = double(n_p), summed on the host in pixel order;
+ *   rpt_buffer_mean_device (and with it rpt_buffer_denoised_image): both outputs with n = double(n_p); the check stays
+ *     n_batches >= 2, the full-frame batches. */
+int rpt_buffer_add_samples_tiles_device(rpt_buffer*, const void* d_rgb, const void* d_tiles, uint32_t n_tiles, void* hip_stream);
+int rpt_buffer_tile_batches(rpt_buffer*, uint32_t* out /* tiles_x * tiles_y */, uint64_t capacity);
+/* Tile errors and selection.  An order of fp64 operations, each rounded on its own (no fused multiply-add, IEEE division, no atomics,
+ * no sqrt).  For tile t = (tx, ty), slot j = 32 ry + rx is pixel (32 tx + rx, 32 ty + ry).  A slot outside the image contributes
+ * a_j = +0.0; otherwise, with m_k = sum_k / n and v exactly as rpt_buffer_mean_device computes them, n = double(n_p):
+ *     y = (m_0 + m_1) + m_2;   a_j = v / (y y + floor floor).
+ * The 1024 terms are reduced by halving strides: for s = 512, 256, .., 1: a_j = a_j + a_{j+s} for j < s.
+ *     E_t = a_0 / double(in-image pixels of the tile):
+ * the mean over the tile of the squared relative standard error of a pixel's mean, `floor` keeping dark pixels from dominating.
+ * A tile is SELECTED iff E_t > threshold threshold (the square formed once on the host) and n_t < max_batches; a NaN error selects
+ * nothing (such a tile would never converge).  rpt_buffer_refine_tiles writes the errors (to d_err, tiles_x * tiles_y doubles, if
+ * given), then the selected ids in ascending order to d_tiles_out (DEVICE, capacity: every tile) and, after one synchronisation of
+ * hip_stream, their number to *n_out (host): 4 bytes, the only read-back.  Both need 2 full-frame batches (RPT_ERR_STATE);
+ * min_batches < 2, max_batches < min_batches, floor <= 0 (or not finite), a negative or NaN threshold: RPT_ERR_INVALID, like every
+ * argument check before any device call. */
+typedef struct rpt_adaptive_params {
+    uint32_t spp_per_batch, min_batches, max_batches, _pad;   /* min_batches >= 2, max_batches >= min_batches */
+    double threshold;   /* relative standard error of a tile's mean at which it stops; >= 0, +inf allowed */
+    double floor;       /* > 0: added to the squared brightness, so that dark pixels do not dominate */
+} rpt_adaptive_params;
+int rpt_buffer_tile_errors_device(rpt_buffer*, double floor, void* d_err /* tiles_x*tiles_y doubles */, void* hip_stream);
+int rpt_buffer_refine_tiles(rpt_buffer*, const rpt_adaptive_params*, void* d_tiles_out /* capacity: every tile */,
+                            uint32_t* n_out /* host */, void* d_err /* or NULL */, void* hip_stream);
+/* The loop, on the default stream, synchronous.  The buffer must be empty (RPT_ERR_STATE) and match the frame and the scene's device
+ * (as for rpt_render_into_buffer); shard_count > 1 is RPT_ERR_INVALID.  Batches k = 0 .. min_batches - 1 are full-frame
+ * rpt_render_into_buffer calls of spp_per_batch samples at sample_offset = k spp_per_batch.  Round k >= min_batches: refine; stop when
+ * no tile is selected; otherwise a tile-list render of spp_per_batch samples at sample_offset = k spp_per_batch into the buffer's
+ * stage, added to the listed tiles.  (A tile's error does not change while it is not sampled: the active set only shrinks and every
+ * active tile holds k batches.)  A pixel of a tile that ended with n_t batches holds exactly the sums n_t full-frame batches would have
+ * put there.  stats (or NULL): [0] rounds that rendered a tile list, [1] tile-batches rendered (min_batches tiles + the lists'
+ * lengths), [2] tiles that ended at max_batches, [3] tiles. */
+int rpt_render_adaptive(rpt_scene*, const rpt_camera*, const rpt_render_params*, const rpt_adaptive_params*,
+                        uint64_t seed, rpt_buffer*, uint64_t stats[4] /* rounds, tile-batches rendered, tiles at max_batches, tiles */);
 
 /* ---- photon mapping (next tier: src/photon.rs; config C4 = photon_point_query_beam_render) ----
  * `enum PhotonRenderKind` (src/photon.rs:631-639): point-point (photon_map_render), beam-point

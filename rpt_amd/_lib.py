@@ -75,6 +75,17 @@ class DenoiseParams(C.Structure):
     ]
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [
+        ("spp_per_batch", C.c_uint32),
+        ("min_batches", C.c_uint32),
+        ("max_batches", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("threshold", C.c_double),
+        ("floor", C.c_double),
+    ]
+
+
 # Every symbol include/rpt_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _D3 = C.POINTER(C.c_double)
@@ -97,6 +108,10 @@ SYMBOLS = [
      [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P]),
     ("rpt_render_sample_device", C.c_int,
      [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P, _P]),
+    ("rpt_render_sample_tiles_device", C.c_int,
+     [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P, _P]),
+    ("rpt_render_sample_tiles", C.c_int,
+     [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P]),
     ("rpt_render_features", C.c_int,
      [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32, C.c_uint64, C.c_uint32, _P, _P, _P]),
     ("rpt_render_features_device", C.c_int,
@@ -130,6 +145,12 @@ SYMBOLS = [
     ("rpt_denoise", C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P]),
     ("rpt_buffer_mean_device", C.c_int, [_P, _P, _P, _P]),
     ("rpt_buffer_denoised_image", C.c_int, [_P, _P, C.POINTER(DenoiseParams), _P, _P, _P, _P]),
+    ("rpt_buffer_add_samples_tiles_device", C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    ("rpt_buffer_tile_batches", C.c_int, [_P, _P, C.c_uint64]),
+    ("rpt_buffer_tile_errors_device", C.c_int, [_P, C.c_double, _P, _P]),
+    ("rpt_buffer_refine_tiles", C.c_int, [_P, C.POINTER(AdaptiveParams), _P, C.POINTER(C.c_uint32), _P, _P]),
+    ("rpt_render_adaptive", C.c_int,
+     [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     ("rpt_photon_map_build", C.c_int, [_P, C.c_uint64, C.c_int32, C.c_double, C.c_uint64]),
     ("rpt_photon_shoot", C.c_int,
      [_P, C.c_uint64, C.c_int32, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),

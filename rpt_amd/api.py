@@ -60,7 +60,7 @@ __all__ = [
     "set_option", "shard_pixels",
     "vec3", "hex_color", "color_bytes", "Sphere", "Cube", "Plane", "Triangle", "Mesh", "KdTree", "Transformed",
     "MonomialSurface", "sphere", "cube", "plane", "polygon", "monomial_surface", "Material", "Object", "Light", "Medium", "Environment",
-    "Scene", "Camera", "Filter", "Buffer", "DeviceBuffer", "Renderer", "RptError", "DenoiseParams", "Denoiser",
+    "Scene", "Camera", "Filter", "Buffer", "DeviceBuffer", "Renderer", "RptError", "DenoiseParams", "Denoiser", "AdaptiveParams",
 ]
 
 
@@ -694,6 +694,57 @@ class DeviceBuffer:
         host = d.cpu().numpy()
         return host[:3 * n].reshape(self.height, self.width, 3).copy(), host[3 * n:].reshape(self.height, self.width).copy()
 
+    # ---- adaptive sampling by tile (an addition)
+    @property
+    def tiles(self):
+        """(tiles_x, tiles_y): the frame in 32 x 32 tiles; a tile id is ty * tiles_x + tx."""
+        return (self.width + 31) // 32, (self.height + 31) // 32
+
+    def add_samples_tiles_device(self, d_rgb_ptr, d_tiles_ptr, n_tiles, stream_ptr=0):
+        """rpt_buffer_add_samples_tiles_device: one batch for the listed tiles alone (device frame, device list of n_tiles distinct
+        uint32 ids); the tiles' batch counts go up by one."""
+        n_tiles = int(n_tiles)
+        if n_tiles < 0 or n_tiles > self.tiles[0] * self.tiles[1]:
+            raise ValueError(f"add_samples_tiles_device: {n_tiles} tiles listed, the frame has {self.tiles[0] * self.tiles[1]}")
+        if not d_rgb_ptr or (n_tiles and not d_tiles_ptr):
+            raise ValueError("add_samples_tiles_device: null pointer")
+        _lib.check(_lib.load().rpt_buffer_add_samples_tiles_device(self._h, C.c_void_p(d_rgb_ptr), C.c_void_p(d_tiles_ptr or None), n_tiles,
+                                                                   C.c_void_p(stream_ptr)))
+
+    def tile_batches(self):
+        """-> (tiles_y, tiles_x) uint32: the batches every pixel of a tile holds (full-frame batches + the tile's own)."""
+        tx, ty = self.tiles
+        out = np.empty((ty, tx), dtype=np.uint32)
+        _lib.check(_lib.load().rpt_buffer_tile_batches(self._h, _vp(out), out.size))
+        return out
+
+    def tile_errors(self, floor):
+        """rpt_buffer_tile_errors_device -> (tiles_y, tiles_x) float64: per tile, the mean of v / (y^2 + floor^2) over its pixels
+        (v the variance of the pixel's mean, y the sum of its mean's channels).  Needs at least two full-frame batches."""
+        floor = float(floor)
+        if not (floor > 0.0) or math.isinf(floor):
+            raise ValueError("tile_errors: floor must be finite and > 0")
+        tx, ty = self.tiles
+        d = _device_zeros(tx * ty, self.device)
+        _sync(self.device)                                       # batches may have been added on other streams
+        _lib.check(_lib.load().rpt_buffer_tile_errors_device(self._h, floor, C.c_void_p(d.data_ptr()), None))
+        _sync(self.device)
+        return d.cpu().numpy().reshape(ty, tx).copy()
+
+    def refine_tiles(self, params):
+        """rpt_buffer_refine_tiles -> (ids, errors): the ascending ids of the tiles whose error is above params.threshold ** 2 and
+        that hold fewer than params.max_batches batches, uint32, and every tile's error, (tiles_y, tiles_x) float64."""
+        import torch
+        tx, ty = self.tiles
+        d_err = _device_zeros(tx * ty, self.device)
+        d_ids = torch.zeros(tx * ty, dtype=torch.int32, device=f"cuda:{self.device}")
+        _sync(self.device)
+        n = C.c_uint32()
+        _lib.check(_lib.load().rpt_buffer_refine_tiles(self._h, C.byref(params.desc()), C.c_void_p(d_ids.data_ptr()), C.byref(n),
+                                                       C.c_void_p(d_err.data_ptr()), None))
+        _sync(self.device)
+        return d_ids.cpu().numpy().view(np.uint32)[:n.value].copy(), d_err.cpu().numpy().reshape(ty, tx).copy()
+
     def denoised_image(self, denoiser, planes, params=None):
         """rpt_buffer_denoised_image: mean -> a-trous filter -> color_bytes, no box filter -> (h, w, 3) uint8.  `planes`: a dict with
         any of "albedo", "normal", "depth" (what `params` needs), each an (h, w, 3) array as Renderer.features_array returns it or
@@ -765,6 +816,31 @@ class DenoiseParams:
 
     def desc(self):
         return _lib.DenoiseParams(self.passes, self.flags, self.sigma_color, self.sigma_normal, self.sigma_depth)
+
+
+class AdaptiveParams:
+    """rpt_adaptive_params: batches of spp_per_batch samples; every tile gets min_batches (>= 2) of them, then one more per round
+    while its error -- the mean over its pixels of the squared relative standard error of the pixel's mean, `floor` added to the
+    squared brightness -- is above threshold ** 2 and it holds fewer than max_batches."""
+
+    def __init__(self, spp_per_batch=4, min_batches=4, max_batches=16, threshold=0.05, floor=0.05):
+        self.spp_per_batch, self.min_batches, self.max_batches = int(spp_per_batch), int(min_batches), int(max_batches)
+        self.threshold, self.floor = float(threshold), float(floor)
+        if self.spp_per_batch < 1:
+            raise ValueError("AdaptiveParams: spp_per_batch must be at least 1")
+        if self.min_batches < 2:
+            raise ValueError("AdaptiveParams: min_batches must be at least 2")
+        if self.max_batches < self.min_batches:
+            raise ValueError("AdaptiveParams: max_batches must be at least min_batches")
+        if self.max_batches * self.spp_per_batch >= 1 << 32:
+            raise ValueError("AdaptiveParams: max_batches * spp_per_batch must fit 32 bits")
+        if not self.threshold >= 0.0:
+            raise ValueError("AdaptiveParams: threshold must be >= 0 (inf allowed)")
+        if not self.floor > 0.0 or math.isinf(self.floor):
+            raise ValueError("AdaptiveParams: floor must be finite and > 0")
+
+    def desc(self):
+        return _lib.AdaptiveParams(self.spp_per_batch, self.min_batches, self.max_batches, 0, self.threshold, self.floor)
 
 
 class Denoiser:
@@ -906,6 +982,97 @@ class Renderer:
             h, C.byref(camera_desc(self.camera, _lib.CameraDesc)), C.byref(self._params()), int(iterations),
             C.c_uint64(self.seed_), self._sample_offset, C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
         self._sample_offset += int(iterations)
+
+    # Tile-list renders (rpt_render_sample_tiles*, an addition): the listed 32 x 32 tiles alone, the bits a full render puts there.
+    def _check_tiles(self, what):
+        if self.shard_count_ != 1:
+            raise ValueError(f"{what}: a tile-list render is not sharded")
+        if self.width_ <= 0 or self.height_ <= 0:
+            raise ValueError(f"{what}: empty frame")
+        return ((self.width_ + 31) // 32) * ((self.height_ + 31) // 32)
+
+    def sample_tiles_device(self, iterations, d_tiles_ptr, n_tiles, d_out_ptr, stream_ptr=0):
+        """d_tiles_ptr: device array of n_tiles distinct uint32 tile ids (ty * tiles_x + tx); d_out_ptr: device frame of
+        width*height*3 doubles, written in the listed tiles only.  Advances the sample offset like sample_device."""
+        total, n_tiles = self._check_tiles("sample_tiles_device"), int(n_tiles)
+        if n_tiles < 0 or n_tiles > total:
+            raise ValueError(f"sample_tiles_device: {n_tiles} tiles listed, the frame has {total}")
+        if not d_out_ptr or (n_tiles and not d_tiles_ptr):
+            raise ValueError("sample_tiles_device: null pointer")
+        lib = _lib.load()
+        h = self.scene._commit(self.device_)
+        _lib.check(lib.rpt_render_sample_tiles_device(
+            h, C.byref(camera_desc(self.camera, _lib.CameraDesc)), C.byref(self._params()), int(iterations),
+            C.c_uint64(self.seed_), self._sample_offset, C.c_void_p(d_tiles_ptr or None), n_tiles, C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+        self._sample_offset += int(iterations)
+
+    def sample_tiles_array(self, iterations, tiles, out):
+        """Host variant: `tiles` a sequence of distinct tile ids, `out` a C-contiguous float64 array of width*height*3 values that is
+        updated in place in the listed tiles and keeps its values everywhere else -> out."""
+        total = self._check_tiles("sample_tiles_array")
+        tiles = np.ascontiguousarray(tiles, dtype=np.int64).reshape(-1)
+        if tiles.size and (tiles.min() < 0 or tiles.max() >= total):
+            raise ValueError(f"sample_tiles_array: tile id outside 0..{total - 1}")
+        if np.unique(tiles).size != tiles.size:
+            raise ValueError("sample_tiles_array: a tile id is listed twice")
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.flags.writeable
+                and out.size == self.width_ * self.height_ * 3):
+            raise ValueError(f"sample_tiles_array: out must be a writable C-contiguous float64 array of {self.width_ * self.height_ * 3} values")
+        ids = tiles.astype(np.uint32)
+        lib = _lib.load()
+        h = self.scene._commit(self.device_)
+        _lib.check(lib.rpt_render_sample_tiles(
+            h, C.byref(camera_desc(self.camera, _lib.CameraDesc)), C.byref(self._params()), int(iterations),
+            C.c_uint64(self.seed_), self._sample_offset, _vp(ids), ids.size, _vp(out)))
+        self._sample_offset += int(iterations)
+        return out
+
+    def sample_adaptive(self, params, buffer):
+        """rpt_render_adaptive (an addition) into an empty DeviceBuffer: params.min_batches full frames of params.spp_per_batch
+        samples, then one more batch per round for the tiles whose error is still above the threshold, at most params.max_batches.
+        A pixel of a tile that ends with n batches holds the sums n full-frame sample() calls would have put there.
+        -> (rounds that rendered a tile list, tile-batches rendered, tiles at max_batches, tiles)."""
+        if not isinstance(params, AdaptiveParams):
+            raise ValueError("sample_adaptive: params must be an AdaptiveParams")
+        if not isinstance(buffer, DeviceBuffer):
+            raise ValueError("sample_adaptive: the buffer must be a DeviceBuffer")
+        if self.shard_count_ != 1:
+            raise ValueError("sample_adaptive: an adaptive render is not sharded")
+        stats = (C.c_uint64 * 4)()
+        _lib.check(_lib.load().rpt_render_adaptive(
+            self.scene._commit(self.device_), C.byref(camera_desc(self.camera, _lib.CameraDesc)), C.byref(self._params()),
+            C.byref(params.desc()), C.c_uint64(self.seed_), buffer._h, stats))
+        return tuple(int(v) for v in stats)
+
+    def render_adaptive(self, params=None, denoise=None):
+        """sample_adaptive into a fresh DeviceBuffer -> (image, tile_batches): (h, w, 3) uint8 and the (tiles_y, tiles_x) batches each
+        tile ended with.  The image is DeviceBuffer.image() (filter() applies), or with denoise=DenoiseParams(..)
+        DeviceBuffer.denoised_image() over the feature planes of the first min_batches * spp_per_batch samples (filter() is not
+        applied).  num_samples() is not read."""
+        params = params or AdaptiveParams()
+        if not isinstance(params, AdaptiveParams):
+            raise ValueError("render_adaptive: params must be an AdaptiveParams")
+        if denoise is not None and not isinstance(denoise, DenoiseParams):
+            raise ValueError("render_adaptive: denoise must be a DenoiseParams or None")
+        if self.shard_count_ != 1:
+            raise ValueError("render_adaptive: an adaptive render is not sharded")
+        buffer = DeviceBuffer(self.width_, self.height_, None if denoise is not None else self.filter_, self.device_)
+        if denoise is not None:
+            n = self.width_ * self.height_ * 3
+            planes = _device_zeros(3 * n, self.device_)
+            _sync(self.device_)
+            ptrs = [planes.data_ptr() + 8 * n * k for k in range(3)]
+            self.features_device(params.min_batches * params.spp_per_batch, *ptrs, sample_offset=0)
+        self.sample_adaptive(params, buffer)
+        counts = buffer.tile_batches()
+        if denoise is not None:
+            denoiser = Denoiser(self.width_, self.height_, self.device_)
+            img = buffer.denoised_image(denoiser, dict(zip(("albedo", "normal", "depth"), ptrs)), denoise)
+            denoiser.close()
+        else:
+            img = buffer.image()
+        buffer.close()
+        return img, counts
 
     # First-hit feature planes (rpt_render_features*, an addition): of the camera samples that the NEXT sample call of this renderer
     # traces -- same seed, same sample offset; the offset is not advanced (sample_offset=...: another one).

@@ -119,6 +119,30 @@ static constexpr uint32_t kDenoiseMaxStagedStep = 2;   // the largest step whose
 __attribute__((weak)) hipError_t launch_buffer_mean(uint32_t n_pixels, uint32_t n_batches, const double* d_sum, const double* d_sumsq,
                                                     double* d_rgb, double* d_var /* or null */, hipStream_t st);
 __attribute__((weak)) hipError_t launch_color_bytes(uint64_t n_values, const double* d_rgb, uint8_t* d_out, hipStream_t st);
+// Adaptive sampling by tile (adaptive.hip).  A buffer whose tiles have different batch counts: a pixel of tile t holds
+// n_batches + extra[t] batches (extra null: no tile batch was ever added).
+struct TileBufferView {
+    uint32_t width, height, tiles_x, tiles_y;
+    uint32_t n_batches, pad_;
+    const uint32_t* extra;   // [tiles_x * tiles_y] or null
+};
+// (Weak: reached from rpt_buffer_add_samples_tiles_device, rpt_buffer_tile_errors_device, rpt_buffer_refine_tiles and the read-outs of a
+// buffer with extra batches alone, which report RPT_ERR_UNSUPPORTED where no kernel library is linked.)
+// buffer_add_kernel on the in-image pixels of the listed tiles (ids distinct; an id out of range is skipped), extra[id] += 1.
+__attribute__((weak)) hipError_t launch_buffer_add_tiles(const TileBufferView& b, const double* d_batch, double* d_sum, double* d_sumsq,
+                                                         uint32_t* d_extra, const uint32_t* d_tiles, uint32_t n_tiles, hipStream_t st);
+__attribute__((weak)) hipError_t launch_buffer_image_tiles(const TileBufferView& b, uint32_t radius, const double* d_sum, uint8_t* d_out,
+                                                           hipStream_t st);
+__attribute__((weak)) hipError_t launch_buffer_variance_tiles(const TileBufferView& b, const double* d_sum, const double* d_sumsq, double* d_out,
+                                                              hipStream_t st);
+__attribute__((weak)) hipError_t launch_buffer_mean_tiles(const TileBufferView& b, const double* d_sum, const double* d_sumsq, double* d_rgb,
+                                                          double* d_var /* or null */, hipStream_t st);
+// err[t] for every tile (one block each); then the ids with err > threshold2 and fewer than max_batches batches, ascending, and their
+// number (one block).
+__attribute__((weak)) hipError_t launch_tile_errors(const TileBufferView& b, double floor, const double* d_sum, const double* d_sumsq,
+                                                    double* d_err, hipStream_t st);
+__attribute__((weak)) hipError_t launch_tile_select(const TileBufferView& b, double threshold2, uint32_t max_batches, const double* d_err,
+                                                    uint32_t* d_tiles_out, uint32_t* d_n_out, hipStream_t st);
 hipError_t launch_debug_rng(uint64_t seed_mixed, uint32_t pixel, uint32_t sample, uint32_t n, uint32_t* d_out,
                             hipStream_t stream);
 hipError_t launch_debug_sample_f(const Material& m, uint64_t n, const float* d_n, const float* d_wo,

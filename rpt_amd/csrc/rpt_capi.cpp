@@ -2332,11 +2332,14 @@ extern "C++" void rpti::fill_args64(rpt_scene* s, const rpt_camera* cam, const r
 }
 // Renderer::sample in the reference-epsilon mode: the fp32 path's launch scheme (persistent grid over (pixel, chunk)
 // items, one launch set per stream) with an fp64 slab.
+static int use_tile_list(RenderArgs& a, const uint32_t* d_tiles, uint32_t n_tiles);
 static int run_render64(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
-                        uint32_t sample_offset, double* d_out, hipStream_t st) {
+                        uint32_t sample_offset, double* d_out, hipStream_t st, const uint32_t* d_tiles = nullptr, uint32_t n_tiles = 0) {
     RenderArgs a{};   // (tiles, sharding, chunking, launch sets and argument checks are shared with the fp32 path)
     int rc = rpti::prepare_render(s, st, cam, prm, iterations, seed, sample_offset, a, 0, 0, 32);
     if (rc) return rc;
+    if (d_tiles)   // rpt_render_sample_tiles*: the caller's list in place of the scene's
+        if ((rc = use_tile_list(a, d_tiles, n_tiles))) return rc;
     rpt64::Args q{};
     rpti::fill_args64(s, cam, prm, &a, q);
     q.counters = a.counters;
@@ -2695,6 +2698,82 @@ int rpt_render_sample(rpt_scene* s, const rpt_camera* cam, const rpt_render_para
     HIP_TRY(hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost));
     return rpti::fetch_counters(s, a);
 }
+// ---- rpt_render_sample_tiles*: the kernels of a full render on a caller's tile list.
+// The list replaces the scene's in the launch arguments only: the scene's cached d_tiles keeps the full frame's list, which a launch
+// on the other launch set may still be reading.  The slab prepare_render reserved is the full frame's: no smaller than the list's.
+static int use_tile_list(RenderArgs& a, const uint32_t* d_tiles, uint32_t n_tiles) {
+    if (n_tiles > a.n_tiles) return fail(RPT_ERR_INVALID, "more tiles listed than the frame has");
+    a.tiles = d_tiles;
+    a.n_tiles = n_tiles;
+    a.n_owned = n_tiles * 1024u;
+    const uint64_t n_items = uint64_t(a.n_owned) * a.n_chunks;
+    if (n_items >= (1ull << 32) - (1ull << 24)) return fail(RPT_ERR_INVALID, "too many work items; raise chunk_spp");
+    a.n_items = uint32_t(n_items);
+    return RPT_OK;
+}
+// What both entry points refuse before any device call.
+static int check_sample_tiles(const rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, const void* tiles,
+                              uint32_t n_tiles, const void* out) {
+    if (!s || !cam || !prm) return fail(RPT_ERR_INVALID, "null argument");
+    if (!out) return fail(RPT_ERR_INVALID, "null output");
+    if (n_tiles && !tiles) return fail(RPT_ERR_INVALID, "null tile list");
+    if (prm->width == 0 || prm->height == 0 || iterations == 0) return fail(RPT_ERR_INVALID, "empty render");
+    if (uint64_t(prm->width) * prm->height > (1ull << 31)) return fail(RPT_ERR_INVALID, "image too large");
+    if (prm->shard_count > 1) return fail(RPT_ERR_INVALID, "a tile-list render is not sharded: the list is the sharding");
+    const uint64_t total = uint64_t((prm->width + 31) / 32) * ((prm->height + 31) / 32);
+    if (n_tiles > total) return fail(RPT_ERR_INVALID, "more tiles listed than the frame has");
+    return RPT_OK;
+}
+static int run_sample_tiles(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
+                            uint32_t sample_offset, const uint32_t* d_tiles, uint32_t n_tiles, double* d_out, hipStream_t st) {
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called before rendering");
+    if (n_tiles == 0) return RPT_OK;
+    if (s->dev.arena64) return run_render64(s, cam, prm, iterations, seed, sample_offset, d_out, st, d_tiles, n_tiles);
+    RenderArgs a{};
+    int rc = rpti::prepare_render(s, st, cam, prm, iterations, seed, sample_offset, a);
+    if (rc) return rc;
+    if ((rc = use_tile_list(a, d_tiles, n_tiles))) return rc;
+    if ((rc = run_render(s, prm, a, d_out, st))) return rc;
+    if (a.counters) {
+        HIP_TRY(hipStreamSynchronize(st));
+        return rpti::fetch_counters(s, a);
+    }
+    return RPT_OK;
+}
+int rpt_render_sample_tiles_device(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
+                                   uint32_t sample_offset, const void* d_tiles, uint32_t n_tiles, void* d_out_rgb, void* hip_stream) {
+    if (int rc = check_sample_tiles(s, cam, prm, iterations, d_tiles, n_tiles, d_out_rgb)) return rc;
+    return run_sample_tiles(s, cam, prm, iterations, seed, sample_offset, static_cast<const uint32_t*>(d_tiles), n_tiles,
+                            static_cast<double*>(d_out_rgb), static_cast<hipStream_t>(hip_stream));
+}
+int rpt_render_sample_tiles(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
+                            uint32_t sample_offset, const uint32_t* tiles, uint32_t n_tiles, double* out_rgb) {
+    if (int rc = check_sample_tiles(s, cam, prm, iterations, tiles, n_tiles, out_rgb)) return rc;
+    {   // a host list is checked: ids in range and distinct
+        const uint32_t total = ((prm->width + 31) / 32) * ((prm->height + 31) / 32);
+        std::vector<bool> seen(total, false);
+        for (uint32_t i = 0; i < n_tiles; i++) {
+            if (tiles[i] >= total) return fail(RPT_ERR_INVALID, "tile id out of range");
+            if (seen[tiles[i]]) return fail(RPT_ERR_INVALID, "tile id listed twice");
+            seen[tiles[i]] = true;
+        }
+    }
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called before rendering");
+    if (n_tiles == 0) return RPT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = size_t(prm->width) * prm->height * 24;
+    double* d_out = rpti::scratch_out(s, bytes);
+    if (!d_out) return fail(RPT_ERR_DEVICE, "out of device memory");
+    rpti::DevMem d_list;   // this call's own upload, alive until the download below has synchronised
+    HIP_TRY(d_list.reserve(size_t(n_tiles) * 4));
+    HIP_TRY(hipMemcpy(d_list.get(), tiles, size_t(n_tiles) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_out, out_rgb, bytes, hipMemcpyHostToDevice));   // the caller's values outside the listed tiles survive
+    int rc = run_sample_tiles(s, cam, prm, iterations, seed, sample_offset, d_list.get<uint32_t>(), n_tiles, d_out, nullptr);
+    const hipError_t e = hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost);   // (also on failure: the list is freed after the stream is idle)
+    if (rc) return rc;
+    HIP_TRY(e);
+    return RPT_OK;
+}
 // What rpt_render_features* refuse before any device call.
 static int check_features(const rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, const void* albedo,
                           const void* normal, const void* depth) {
@@ -2793,6 +2872,13 @@ struct rpt_buffer {
     uint32_t width = 0, height = 0, radius = 0, n_batches = 0;
     rpti::DevMem d_sum, d_sumsq, d_stage;  // stage: one batch / per-pixel variances
     rpti::DevMem d_img;
+    // Adaptive sampling by tile (adaptive.hip): allocated at the first tile batch / the first refinement.
+    rpti::DevMem d_extra;                  // extra batches per 32 x 32 tile (u32); a pixel holds n_batches + extra[its tile]
+    rpti::DevMem d_tile_err, d_active;     // rpt_buffer_refine_tiles' errors when the caller keeps none, its count; rpt_render_adaptive's list
+    uint32_t tiles_x() const { return (width + 31) / 32; }
+    uint32_t tiles_y() const { return (height + 31) / 32; }
+    uint32_t n_tiles() const { return tiles_x() * tiles_y(); }
+    TileBufferView view() const { return TileBufferView{width, height, tiles_x(), tiles_y(), n_batches, 0, d_extra.get<uint32_t>()}; }
 };
 rpt_buffer* rpt_buffer_create(int device, uint32_t width, uint32_t height, uint32_t filter_radius) {
     int ndev = 0;
@@ -2838,7 +2924,11 @@ int rpt_buffer_image(rpt_buffer* b, uint8_t* out_rgb8) {
     if (b->n_batches == 0) return fail(RPT_ERR_STATE, "Pixel found with no samples");  // the reference's assert (buffer.rs:89)
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipDeviceSynchronize());  // batches may have been added on other streams
-    HIP_TRY(launch_buffer_image(b->width, b->height, b->radius, b->n_batches, b->d_sum.get<double>(), b->d_img.get<uint8_t>(), nullptr));
+    if (b->d_extra) {   // tiles with different batch counts: the window's sums over the window's sample count (buffer.rs:75-93)
+        if (!launch_buffer_image_tiles) return fail(RPT_ERR_UNSUPPORTED, "rpt_buffer_image: built without the kernels");
+        HIP_TRY(launch_buffer_image_tiles(b->view(), b->radius, b->d_sum.get<double>(), b->d_img.get<uint8_t>(), nullptr));
+    } else
+        HIP_TRY(launch_buffer_image(b->width, b->height, b->radius, b->n_batches, b->d_sum.get<double>(), b->d_img.get<uint8_t>(), nullptr));
     HIP_TRY(hipMemcpy(out_rgb8, b->d_img.get(), size_t(b->width) * b->height * 3, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
@@ -2848,7 +2938,11 @@ int rpt_buffer_variance(rpt_buffer* b, double* out) {
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t n = size_t(b->width) * b->height;
-    HIP_TRY(launch_buffer_variance(uint32_t(n), b->n_batches, b->d_sum.get<double>(), b->d_sumsq.get<double>(), b->d_stage.get<double>(), nullptr));
+    if (b->d_extra) {
+        if (!launch_buffer_variance_tiles) return fail(RPT_ERR_UNSUPPORTED, "rpt_buffer_variance: built without the kernels");
+        HIP_TRY(launch_buffer_variance_tiles(b->view(), b->d_sum.get<double>(), b->d_sumsq.get<double>(), b->d_stage.get<double>(), nullptr));
+    } else
+        HIP_TRY(launch_buffer_variance(uint32_t(n), b->n_batches, b->d_sum.get<double>(), b->d_sumsq.get<double>(), b->d_stage.get<double>(), nullptr));
     std::vector<double> v(n);
     HIP_TRY(hipMemcpy(v.data(), b->d_stage.get(), n * 8, hipMemcpyDeviceToHost));
     double acc = 0.0;
@@ -2883,6 +2977,109 @@ int rpt_render_into_buffer(rpt_scene* s, const rpt_camera* cam, const rpt_render
     if (a.counters) {
         HIP_TRY(hipStreamSynchronize(nullptr));
         return rpti::fetch_counters(s, a);
+    }
+    return RPT_OK;
+}
+
+// ---------------------------------------------------------------------------- adaptive sampling by tile (adaptive.hip)
+int rpt_buffer_add_samples_tiles_device(rpt_buffer* b, const void* d_rgb, const void* d_tiles, uint32_t n_tiles, void* hip_stream) {
+    if (!b || !d_rgb || (n_tiles && !d_tiles)) return fail(RPT_ERR_INVALID, "null argument");
+    if (n_tiles > b->n_tiles()) return fail(RPT_ERR_INVALID, "more tiles listed than the frame has");
+    if (n_tiles == 0) return RPT_OK;
+    if (!launch_buffer_add_tiles) return fail(RPT_ERR_UNSUPPORTED, "rpt_buffer_add_samples_tiles_device: built without the kernels");
+    HIP_TRY(hipSetDevice(b->device));
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (!b->d_extra) {
+        HIP_TRY(b->d_extra.reserve(size_t(b->n_tiles()) * 4));
+        HIP_TRY(hipMemsetAsync(b->d_extra.get(), 0, size_t(b->n_tiles()) * 4, st));
+    }
+    HIP_TRY(launch_buffer_add_tiles(b->view(), static_cast<const double*>(d_rgb), b->d_sum.get<double>(), b->d_sumsq.get<double>(),
+                                    b->d_extra.get<uint32_t>(), static_cast<const uint32_t*>(d_tiles), n_tiles, st));
+    return RPT_OK;
+}
+int rpt_buffer_tile_batches(rpt_buffer* b, uint32_t* out, uint64_t capacity) {
+    if (!b || !out) return fail(RPT_ERR_INVALID, "null argument");
+    if (capacity < b->n_tiles()) return fail(RPT_ERR_INVALID, "rpt_buffer_tile_batches: capacity below tiles_x * tiles_y");
+    std::fill(out, out + b->n_tiles(), 0u);
+    if (b->d_extra) {
+        HIP_TRY(hipSetDevice(b->device));
+        HIP_TRY(hipDeviceSynchronize());  // batches may have been added on other streams
+        HIP_TRY(hipMemcpy(out, b->d_extra.get(), size_t(b->n_tiles()) * 4, hipMemcpyDeviceToHost));
+    }
+    for (uint32_t t = 0; t < b->n_tiles(); t++) out[t] += b->n_batches;
+    return RPT_OK;
+}
+// What rpt_buffer_refine_tiles and rpt_render_adaptive refuse in their parameters, before any device call.
+static int check_adaptive(const rpt_adaptive_params* p) {
+    if (!p) return fail(RPT_ERR_INVALID, "null adaptive parameters");
+    if (p->spp_per_batch == 0) return fail(RPT_ERR_INVALID, "spp_per_batch must be at least 1");
+    if (p->min_batches < 2) return fail(RPT_ERR_INVALID, "min_batches must be at least 2: a tile's error needs a variance");
+    if (p->max_batches < p->min_batches) return fail(RPT_ERR_INVALID, "max_batches must be at least min_batches");
+    if (uint64_t(p->max_batches) * p->spp_per_batch > 0xFFFFFFFFull) return fail(RPT_ERR_INVALID, "max_batches * spp_per_batch must fit 32 bits");
+    if (!(p->threshold >= 0.0)) return fail(RPT_ERR_INVALID, "threshold must be >= 0 (+inf allowed)");
+    if (!(p->floor > 0.0) || std::isinf(p->floor)) return fail(RPT_ERR_INVALID, "floor must be finite and > 0");
+    return RPT_OK;
+}
+static int run_tile_errors(rpt_buffer* b, double floor, double* d_err, hipStream_t st) {
+    if (b->n_batches < 2) return fail(RPT_ERR_STATE, "a tile's error needs at least 2 full-frame batches");
+    if (!launch_tile_errors || !launch_tile_select) return fail(RPT_ERR_UNSUPPORTED, "adaptive sampling: built without the kernels");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(launch_tile_errors(b->view(), floor, b->d_sum.get<double>(), b->d_sumsq.get<double>(), d_err, st));
+    return RPT_OK;
+}
+int rpt_buffer_tile_errors_device(rpt_buffer* b, double floor, void* d_err, void* hip_stream) {
+    if (!(floor > 0.0) || std::isinf(floor)) return fail(RPT_ERR_INVALID, "floor must be finite and > 0");
+    if (!b || !d_err) return fail(RPT_ERR_INVALID, "null argument");
+    return run_tile_errors(b, floor, static_cast<double*>(d_err), static_cast<hipStream_t>(hip_stream));
+}
+int rpt_buffer_refine_tiles(rpt_buffer* b, const rpt_adaptive_params* p, void* d_tiles_out, uint32_t* n_out, void* d_err, void* hip_stream) {
+    if (int rc = check_adaptive(p)) return rc;
+    if (!b || !d_tiles_out || !n_out) return fail(RPT_ERR_INVALID, "null argument");
+    if (b->n_batches < 2) return fail(RPT_ERR_STATE, "a tile's error needs at least 2 full-frame batches");
+    HIP_TRY(hipSetDevice(b->device));
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    // the errors when the caller keeps none, and the count behind them
+    HIP_TRY(b->d_tile_err.reserve(size_t(b->n_tiles()) * 8 + 8));
+    double* const err = d_err ? static_cast<double*>(d_err) : b->d_tile_err.get<double>();
+    uint32_t* const d_count = reinterpret_cast<uint32_t*>(b->d_tile_err.get<double>() + b->n_tiles());
+    if (int rc = run_tile_errors(b, p->floor, err, st)) return rc;
+    HIP_TRY(launch_tile_select(b->view(), p->threshold * p->threshold, p->max_batches, err, static_cast<uint32_t*>(d_tiles_out), d_count, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the one synchronisation and the one read-back of a round, 4 bytes
+    HIP_TRY(hipMemcpy(n_out, d_count, 4, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+int rpt_render_adaptive(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, const rpt_adaptive_params* p, uint64_t seed,
+                        rpt_buffer* b, uint64_t stats[4]) {
+    if (!s || !cam || !prm) return fail(RPT_ERR_INVALID, "null argument");
+    if (int rc = check_adaptive(p)) return rc;
+    if (prm->shard_count > 1) return fail(RPT_ERR_INVALID, "an adaptive render is not sharded");
+    if (!b) return fail(RPT_ERR_INVALID, "null buffer");
+    if (prm->width != b->width || prm->height != b->height) return fail(RPT_ERR_INVALID, "Invalid sample dimension");  // buffer.rs:33-36
+    if (s->committed && s->device != b->device) return fail(RPT_ERR_INVALID, "buffer and scene live on different devices");
+    if (b->n_batches || b->d_extra) return fail(RPT_ERR_STATE, "rpt_render_adaptive needs an empty buffer");
+    for (uint32_t k = 0; k < p->min_batches; k++)
+        if (int rc = rpt_render_into_buffer(s, cam, prm, p->spp_per_batch, seed, k * p->spp_per_batch, b)) return rc;
+    HIP_TRY(b->d_active.reserve(size_t(b->n_tiles()) * 4));
+    uint32_t* const d_active = b->d_active.get<uint32_t>();
+    uint64_t rounds = 0, tile_batches = uint64_t(p->min_batches) * b->n_tiles();
+    // A tile's error does not change while it is not sampled: the active set only shrinks, and every active tile holds k batches.
+    for (uint32_t k = p->min_batches; k < p->max_batches; k++) {
+        uint32_t n_active = 0;
+        if (int rc = rpt_buffer_refine_tiles(b, p, d_active, &n_active, nullptr, nullptr)) return rc;
+        if (n_active == 0) break;
+        if (int rc = run_sample_tiles(s, cam, prm, p->spp_per_batch, seed, k * p->spp_per_batch, d_active, n_active, b->d_stage.get<double>(), nullptr))
+            return rc;
+        if (int rc = rpt_buffer_add_samples_tiles_device(b, b->d_stage.get(), d_active, n_active, nullptr)) return rc;
+        rounds++;
+        tile_batches += n_active;
+    }
+    if (stats) {
+        std::vector<uint32_t> n(b->n_tiles());
+        if (int rc = rpt_buffer_tile_batches(b, n.data(), n.size())) return rc;
+        stats[0] = rounds;
+        stats[1] = tile_batches;
+        stats[2] = uint64_t(std::count(n.begin(), n.end(), p->max_batches));
+        stats[3] = b->n_tiles();
     }
     return RPT_OK;
 }
@@ -3014,6 +3211,12 @@ int rpt_buffer_mean_device(rpt_buffer* b, void* d_rgb, void* d_var, void* hip_st
     if (b->n_batches < 2) return fail(RPT_ERR_STATE, "the variance of the mean needs at least 2 batches");
     if (!launch_buffer_mean) return fail(RPT_ERR_UNSUPPORTED, "rpt_buffer_mean_device: built without the kernels");
     HIP_TRY(hipSetDevice(b->device));
+    if (b->d_extra) {
+        if (!launch_buffer_mean_tiles) return fail(RPT_ERR_UNSUPPORTED, "rpt_buffer_mean_device: built without the kernels");
+        HIP_TRY(launch_buffer_mean_tiles(b->view(), b->d_sum.get<double>(), b->d_sumsq.get<double>(), static_cast<double*>(d_rgb),
+                                         static_cast<double*>(d_var), static_cast<hipStream_t>(hip_stream)));
+        return RPT_OK;
+    }
     HIP_TRY(launch_buffer_mean(b->width * b->height, b->n_batches, b->d_sum.get<double>(), b->d_sumsq.get<double>(), static_cast<double*>(d_rgb),
                                static_cast<double*>(d_var), static_cast<hipStream_t>(hip_stream)));
     return RPT_OK;
