@@ -260,6 +260,7 @@ int rpt_scene_render_chunking(rpt_scene*, uint32_t iterations, uint32_t* chunk_s
  * "scan_cull" 0/1 (read by rpt_scene_commit, default 1: in a medium a primary scan tests the box around the records behind the
  * shell in scan order -- boxes, rectangles, triangles -- once per lane and leaves those records out when no lane of the wave has a
  * search interval that reaches it; the frames are bit-identical either way),
+ * "scan_jit" 0/1/2 (default 1: the scan kernels compiled for the scene's record counts, see rpt_scan_jit_info; read at every render),
  * "shadow_scan" 0/1 (read by rpt_scene_commit, default 1: the shadow query of a linear scan keeps one bit, "the closest hit is a
  * record of the light's twin object", in place of the hit code, for every object light whose twin is one range of records of one
  * scanned kind; group lights, twins that are faces of the room shell or monomial surfaces, and 0 keep the closest-hit scan; the
@@ -603,6 +604,29 @@ int rpt_debug_shadow_test(rpt_scene*, uint32_t light, uint64_t n, const float* o
  * "shadow_scan" = 1, the scene is scanned, and the range is of one scanned kind -- not faces of the room shell), out[3] = the twin
  * object's index (0xFFFFFFFF: the light has none and is never visible). */
 int rpt_shadow_scan_info(rpt_scene*, uint32_t light, uint32_t out[4]);
+/* The scan kernels compiled for a scene's record counts (option "scan_jit": 0 never; 2 at the scene's first render; 1, the default: a
+ * code object found in the cache is used, and one is compiled -- synchronously, a few seconds -- at the first launch of at least 2^27
+ * camera samples).  Scenes rendered by the linear-scan kernels without group lights, monomial surfaces or counters are in scope; their
+ * shape is the number of records of each scanned kind, the shell, the y-rotation masks, the tail cull and the medium -- not the
+ * records' values.  The compiler is libhiprtc, opened at run time (RPT_HIPRTC_LIB: its path; else /opt/rocm/lib/libhiprtc.so, else libhiprtc.so); code objects are kept in the process and
+ * under $RPT_JIT_CACHE (default ~/.cache/rpt_amd/jit; unwritable: memory only).  Frames are the AOT kernel's, bit for bit, and whatever
+ * fails leaves the scene on the AOT kernel.  out[0]: state (RPT_SCAN_JIT_*), out[1]: where the code object came from
+ * (RPT_SCAN_JIT_CACHE_*), out[2]: compile time in microseconds (0 on a hit), out[3], out[4]: its VGPRs and scratch bytes per lane,
+ * out[5]: launches of the specialised kernel on this scene, out[6]: compiles in this process, out[7]: the AOT kernel's VGPRs.
+ * text (optional): "<shape>\n<reason>" (an active scene: the compiler's version and path), truncated to text_capacity. */
+#define RPT_SCAN_JIT_OFF 0           /* option scan_jit = 0 */
+#define RPT_SCAN_JIT_IDLE 1          /* nothing compiled or loaded (yet): no render so far, or option 1 below its threshold without a cached object */
+#define RPT_SCAN_JIT_ACTIVE 2        /* renders run the specialised kernel */
+#define RPT_SCAN_JIT_FALLBACK 3      /* tried and failed: the reason says why */
+#define RPT_SCAN_JIT_OUT_OF_SCOPE 4  /* a kernel flavour that is not specialised; nothing is attempted */
+#define RPT_SCAN_JIT_CACHE_NONE 0
+#define RPT_SCAN_JIT_CACHE_MEMORY 1  /* hit: compiled or loaded earlier in this process */
+#define RPT_SCAN_JIT_CACHE_DISK 2    /* hit: read from the cache directory */
+#define RPT_SCAN_JIT_CACHE_MISS 3    /* compiled for this scene */
+int rpt_scan_jit_info(rpt_scene*, int64_t out[8], char* text, uint64_t text_capacity);
+/* Drops the process's code objects (not the cache directory's): the next scene of each shape looks on disk again.  Scenes that
+ * already run a specialised kernel keep it.  Returns the number dropped. */
+int rpt_scan_jit_forget(void);
 /* The medium distance -ln(xi) / sigma_t of the draws xi = (2 k + 1) 2^-24, k = k0 .. k0 + n - 1 (k0 + n <= 2^23; needs no scene):
  * out_new as the render kernels compute it (the bare v_log_f32 and the two-word product with ln 2), out_guarded through __logf with
  * its denormal and infinity guards, which no such draw needs.  The two are the same bits for every k. */

@@ -1,11 +1,30 @@
 // device_core.h — gfx950 device functions of the path-tracing core (fp32).
 // Reference line citations are relative to the rpt source tree (src/...).
 #pragma once
+#ifndef __HIPCC_RTC__   // (runtime compilation has both built in)
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#endif
 #include "gpu_layout.h"
 
 namespace rptg {
+
+// The names of <type_traits> that the device code uses: the standard library's, or -- runtime compilation has no standard library --
+// their few lines.
+#ifndef __HIPCC_RTC__
+namespace tt = std;
+#else
+namespace tt {
+template <bool B> struct bool_constant { static constexpr bool value = B; };
+typedef bool_constant<true> true_type;
+typedef bool_constant<false> false_type;
+template <class A, class B> inline constexpr bool is_same_v = false;
+template <class A> inline constexpr bool is_same_v<A, A> = true;
+template <bool C, class A, class B> struct conditional { typedef A type; };
+template <class A, class B> struct conditional<false, A, B> { typedef B type; };
+template <bool C, class A, class B> using conditional_t = typename conditional<C, A, B>::type;
+}  // namespace tt
+#endif
 
 #define RPT_DEV __device__ __forceinline__
 
@@ -642,7 +661,48 @@ struct ShadowTwin {
     uint32_t kind, lo, span;   // twin records: kind `kind`, indices lo .. lo + span
     RPT_DEV bool has(uint32_t i) const { return i - lo <= span; }
 };
-template <bool MASKED = false, bool MONO = false, bool TAIL = false, bool SHADOW = false>
+// What a scan knows about the scene before it reads a record: how many records of each kind there are, whether there is a shell,
+// which spheres and cubes are y-rotations, whether the tail cull is on -- all fixed when the scene is committed.  SHAPE says where these
+// come from.  ScanShapeRt: from the launch's view, each read at its place of use, as ever.  ScanShapeK (builds with
+// -DRPT_SCAN_SHAPE=n_sph,n_cub,n_pln,n_aabb,n_rect_x,n_rect_y,n_rect_z,n_tri,has_shell,scan_cull,sph_yrot,cub_yrot): constants, so that
+// an empty kind's loop, its count's load and its branch are not compiled at all and a short loop has no loop control.  Record values
+// -- transforms, boxes, the tail box -- are read from memory in both.
+struct ScanShapeRt {
+    KernargView sc;
+    RPT_DEV uint32_t n_sph() const { return sc->n_sph; }
+    RPT_DEV uint32_t n_cub() const { return sc->n_cub; }
+    RPT_DEV uint32_t n_pln() const { return sc->n_pln; }
+    RPT_DEV uint32_t n_aabb() const { return sc->n_aabb; }
+    RPT_DEV uint32_t n_rect_x() const { return sc->n_rect_x; }
+    RPT_DEV uint32_t n_rect_y() const { return sc->n_rect_y; }
+    RPT_DEV uint32_t n_rect_z() const { return sc->n_rect_z; }
+    RPT_DEV uint32_t n_tri() const { return sc->n_tri; }
+    RPT_DEV uint32_t has_shell() const { return sc->has_shell; }
+    RPT_DEV uint32_t scan_cull() const { return sc->scan_cull; }
+    RPT_DEV uint64_t sph_yrot() const { return sc->sph_yrot; }
+    RPT_DEV uint64_t cub_yrot() const { return sc->cub_yrot; }
+};
+#ifdef RPT_SCAN_SHAPE
+struct ScanShapeK {
+    KernargView sc;
+    static constexpr uint64_t k[12] = {RPT_SCAN_SHAPE};
+    RPT_DEV constexpr uint32_t n_sph() const { return uint32_t(k[0]); }
+    RPT_DEV constexpr uint32_t n_cub() const { return uint32_t(k[1]); }
+    RPT_DEV constexpr uint32_t n_pln() const { return uint32_t(k[2]); }
+    RPT_DEV constexpr uint32_t n_aabb() const { return uint32_t(k[3]); }
+    RPT_DEV constexpr uint32_t n_rect_x() const { return uint32_t(k[4]); }
+    RPT_DEV constexpr uint32_t n_rect_y() const { return uint32_t(k[5]); }
+    RPT_DEV constexpr uint32_t n_rect_z() const { return uint32_t(k[6]); }
+    RPT_DEV constexpr uint32_t n_tri() const { return uint32_t(k[7]); }
+    RPT_DEV constexpr uint32_t has_shell() const { return uint32_t(k[8]); }
+    RPT_DEV constexpr uint32_t scan_cull() const { return uint32_t(k[9]); }
+    RPT_DEV constexpr uint64_t sph_yrot() const { return k[10]; }
+    RPT_DEV constexpr uint64_t cub_yrot() const { return k[11]; }
+};
+#else
+typedef ScanShapeRt ScanShapeK;
+#endif
+template <bool MASKED = false, bool MONO = false, bool TAIL = false, bool SHADOW = false, class SHAPE = ScanShapeRt>
 RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbest, uint32_t& code, uint64_t mask = ~0ull,
                         bool* tail_skipped = nullptr, ShadowTwin twin = ShadowTwin{0u, 1u, 0u}, bool* best_is_twin = nullptr) {
     static_assert(!(TAIL && MASKED), "one cull at a time");
@@ -653,42 +713,43 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
     // compiler parks the overflow in VGPR lanes, and 14 % of their VALU instructions were v_readlane / v_writelane.
     const auto& sc = *kernarg_scene();
     (void)scene;
+    const SHAPE sh{&sc};
     bool flag = false;   // (SHADOW) the best so far is a twin record
     // ... and inside the twin kind's loop: tbest as the last accepted TWIN record left it (NaN: none yet).  At the loop's end the best
     // so far is a twin record iff tbest still has that value: every later accepted record lowered it (t < tbest is strict).  A float
     // select under (lane mask & uniform bit) -- a select between a uniform and a divergent bool is compiled to four vector instructions.
     float t_twin = __builtin_nanf("");
     // An accepted record (`ok` holds t < tbest): the new tbest, and its code or -- SHADOW -- whether it is a twin record (`is_twin`: a
-    // std::false_type outside the twin kind's loop, a wave-uniform bool inside).
+    // tt::false_type outside the twin kind's loop, a wave-uniform bool inside).
     auto acc = [&](bool ok, float t, uint32_t c, auto is_twin) {
         if (ok) tbest = t;
         asm volatile("" : "+v"(tbest));   // one tbest: without the pin the loops carry a second copy of it (a third select per record)
         if constexpr (!SHADOW) { if (ok) code = c; }
-        else if constexpr (std::is_same_v<decltype(is_twin), std::false_type>) flag = flag && !ok;
+        else if constexpr (tt::is_same_v<decltype(is_twin), tt::false_type>) flag = flag && !ok;
         else if (ok && is_twin) t_twin = t;
     };
     // twin_at(tw, i): acc's last argument for record i of a kind whose loop was entered as the twin kind's (tw: true_type) or not.
     auto twin_at = [&](auto tw, uint32_t i) {
         if constexpr (decltype(tw)::value) return twin.has(i);
-        else return std::false_type{};
+        else return tt::false_type{};
     };
     // A kind's loop: SHADOW compiles it twice, for the twin's kind (its records ask twin.has(i)) and for every other kind.
     auto kind_loop = [&](uint32_t kind, auto&& loop) {
         if constexpr (SHADOW) {
             if (twin.kind == kind) {   // (wave-uniform)
-                loop(std::true_type{});
+                loop(tt::true_type{});
                 flag = t_twin == tbest;
                 return;
             }
         }
-        loop(std::false_type{});
+        loop(tt::false_type{});
     };
     uint32_t bit = 0;  // wave-uniform record number
     auto on = [&](uint32_t i) { return !MASKED || ((mask >> ((bit + i) & 63u)) & 1ull) != 0ull; };
     // Unmasked scans: records the commit found to be rotations about the vertical axis take to_local_y (wave-uniform branches).
-    const uint64_t sph_yrot = MASKED ? 0ull : sc.sph_yrot, cub_yrot = MASKED ? 0ull : sc.cub_yrot;
+    const uint64_t sph_yrot = MASKED ? 0ull : sh.sph_yrot(), cub_yrot = MASKED ? 0ull : sh.cub_yrot();
     kind_loop(K_SPHERE, [&](auto tw) {
-        for (uint32_t i = 0; i < sc.n_sph; i++) {
+        for (uint32_t i = 0; i < sh.n_sph(); i++) {
             if (!on(i)) continue;
             const XfScan x = uload(&sc.sph[i]);
             V ol, dl;
@@ -698,11 +759,11 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
             acc(sphere_closer(ol, dl, tmin, tbest, t), t, (K_SPHERE << 28) | i, twin_at(tw, i));
         }
     });
-    bit += sc.n_sph;
+    bit += sh.n_sph();
     kind_loop(K_CUBE, [&](auto tw) {   // two records per iteration: independent instruction streams for the scheduler (unmasked scans)
         uint32_t i = 0;
         if (!MASKED)
-            for (; i + 1u < sc.n_cub; i += 2u) {
+            for (; i + 1u < sh.n_cub(); i += 2u) {
                 const XfScan x0 = uload(&sc.cub[i]), x1 = uload(&sc.cub[i + 1u]);
                 V ol0, dl0, ol1, dl1;
                 float t0, t1;
@@ -716,7 +777,7 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
                 acc(cube_closer(ol0, dl0, tmin, tbest, t0), t0, (K_CUBE << 28) | i, twin_at(tw, i));
                 acc(cube_closer(ol1, dl1, tmin, tbest, t1), t1, (K_CUBE << 28) | (i + 1u), twin_at(tw, i + 1u));
             }
-        for (; i < sc.n_cub; i++) {
+        for (; i < sh.n_cub(); i++) {
             if (!on(i)) continue;
             const XfScan x = uload(&sc.cub[i]);
             V ol, dl;
@@ -726,22 +787,22 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
             acc(cube_closer(ol, dl, tmin, tbest, t), t, (K_CUBE << 28) | i, twin_at(tw, i));
         }
     });
-    bit += sc.n_cub;
-    for (uint32_t i = 0; i < sc.n_pln; i++) {   // (a plane is never a twin: no light shape is one)
+    bit += sh.n_cub();
+    for (uint32_t i = 0; i < sh.n_pln(); i++) {   // (a plane is never a twin: no light shape is one)
         const F4 nv = uload(&sc.pln[i]).nv;
         float t;
-        acc(plane_closer(nv, o, d, tmin, tbest, t), t, (K_PLANE << 28) | i, std::false_type{});
+        acc(plane_closer(nv, o, d, tmin, tbest, t), t, (K_PLANE << 28) | i, tt::false_type{});
     }
-    const uint32_t n_rect = sc.n_rect_x + sc.n_rect_y + sc.n_rect_z;
-    if (sc.n_aabb + n_rect + sc.has_shell != 0) {  // wave-uniform: these kinds share one reciprocal direction per ray
+    const uint32_t n_rect = sh.n_rect_x() + sh.n_rect_y() + sh.n_rect_z();
+    if (sh.n_aabb() + n_rect + sh.has_shell() != 0) {  // wave-uniform: these kinds share one reciprocal direction per ray
         const V inv = mk(rcp(d.x), rcp(d.y), rcp(d.z));
-        if (sc.has_shell)   // (SHADOW: a light whose twin is a shell face takes the closest-hit form)
+        if (sh.has_shell())   // (SHADOW: a light whose twin is a shell face takes the closest-hit form)
             shell_closer(uload(sc.shell), o, inv, tmin, tbest, [&](bool ok, float t, auto code_of) {
-                if constexpr (SHADOW) acc(ok, t, 0u, std::false_type{});
+                if constexpr (SHADOW) acc(ok, t, 0u, tt::false_type{});
                 else { if (ok) { tbest = t; code = code_of(); } }
             });
         if constexpr (TAIL) {
-            if (sc.scan_cull) {   // (wave-uniform)
+            if (sh.scan_cull()) {   // (wave-uniform)
                 const SceneView::ScanBox tb = kernarg_load(&sc.scan_tail);
                 if (__ballot(interval_meets_box<false>(tb, o, inv, tmin, tbest)) == 0ull) {
                     if (tail_skipped) *tail_skipped = true;
@@ -752,28 +813,28 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
         kind_loop(K_AABB, [&](auto tw) {
             uint32_t i = 0;
             if (!MASKED)
-                for (; i + 1u < sc.n_aabb; i += 2u) {
+                for (; i + 1u < sh.n_aabb(); i += 2u) {
                     const AabbScan b0 = uload(&sc.aabb[i]), b1 = uload(&sc.aabb[i + 1u]);
                     aabb_pair_closer(b0, b1, __float_as_uint(b0.hi.w), o, inv, tmin, tbest, i,   // hi.w: the slabs they have in common
                                      [&](bool ok, float t, uint32_t k) { acc(ok, t, (K_AABB << 28) | k, twin_at(tw, k)); });
                 }
-            for (; i < sc.n_aabb; i++) {
+            for (; i < sh.n_aabb(); i++) {
                 if (!on(i)) continue;
                 const AabbScan b = uload(&sc.aabb[i]);
                 float t;
                 acc(aabb_closer(b.lo, b.hi, o, inv, tmin, tbest, t), t, (K_AABB << 28) | i, twin_at(tw, i));
             }
         });
-        bit += sc.n_aabb;
+        bit += sh.n_aabb();
         kind_loop(K_RECT, [&](auto tw) {
             uint32_t i = 0;
-            for (uint32_t e = sc.n_rect_x; i < e; i++) {
+            for (uint32_t e = sh.n_rect_x(); i < e; i++) {
                 if (!on(i)) continue;
                 const RectScan r = uload(&sc.rect[i]);
                 float t;
                 acc(rect_closer(r.a, r.b.x, o.x, inv.x, o.y, d.y, o.z, d.z, tmin, tbest, t), t, (K_RECT << 28) | i, twin_at(tw, i));
             }
-            for (uint32_t e = sc.n_rect_x + sc.n_rect_y; i < e; i++) {
+            for (uint32_t e = sh.n_rect_x() + sh.n_rect_y(); i < e; i++) {
                 if (!on(i)) continue;
                 const RectScan r = uload(&sc.rect[i]);
                 float t;
@@ -788,10 +849,10 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
         });
         bit += n_rect;
     } else {
-        bit += sc.n_aabb + n_rect;
+        bit += sh.n_aabb() + n_rect;
     }
     kind_loop(K_TRI, [&](auto tw) {
-        for (uint32_t i = 0; i < sc.n_tri; i++) {
+        for (uint32_t i = 0; i < sh.n_tri(); i++) {
             if (!on(i)) continue;
             const TriScan tr = uload(&sc.tri[i]);
             float t;
@@ -805,7 +866,7 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
             V ol, dl;
             to_local(XfScan{m.r0, m.r1, m.r2}, o, d, ol, dl);
             float t;
-            acc(mono_closer(ol, dl, m.h, tmin, tbest, t), t, (K_MONO << 28) | i, std::false_type{});
+            acc(mono_closer(ol, dl, m.h, tmin, tbest, t), t, (K_MONO << 28) | i, tt::false_type{});
         }
     }
     if constexpr (SHADOW) *best_is_twin = flag;
@@ -848,7 +909,7 @@ RPT_DEV uint64_t scan_mask_for_ball(const SceneView& scene_, bool live, V c, flo
 // rpt_scan_cull_counters): cnt[0..4] trips by the number of lanes whose interval reaches the box around all scanned records (0, 1-2,
 // 3-4, 5-8, more), cnt[5..8] trips with such a lane in which none of them reaches the box of record group g (SceneView::scan_groups:
 // the candidates of a finer cull, measured and not built: DESIGN.md section 4, round 6), cnt[9] trips that left out the tail.
-template <bool COUNT>
+template <bool COUNT, class SHAPE = ScanShapeRt>
 RPT_DEV void scan_primary(const SceneView& scene, V o, V d, float tmin, float& tbest, uint32_t& code, unsigned long long* cnt) {
     if constexpr (COUNT) {
         const auto& sc = *kernarg_scene();
@@ -867,10 +928,10 @@ RPT_DEV void scan_primary(const SceneView& scene, V o, V d, float tmin, float& t
                 }
         }
         bool skipped = false;
-        scan_prims<false, false, true>(scene, o, d, tmin, tbest, code, ~0ull, &skipped);
+        scan_prims<false, false, true, false, SHAPE>(scene, o, d, tmin, tbest, code, ~0ull, &skipped);
         if (skipped && first) atomicAdd(&cnt[9], 1ull);
     } else {
-        scan_prims<false, false, true>(scene, o, d, tmin, tbest, code);
+        scan_prims<false, false, true, false, SHAPE>(scene, o, d, tmin, tbest, code);
     }
 }
 
@@ -987,7 +1048,7 @@ RPT_DEV void walk_meshes_resumable(const SceneView& scene_, V o, V d, float tmin
 }
 
 // BVH: 0 = no tree in the scene, 1 = per-mesh trees only, 2 = scene-level tree possible.
-template <int BVH, bool COUNT, bool ANY = false, bool MONO = false>
+template <int BVH, bool COUNT, bool ANY = false, bool MONO = false, class SHAPE = ScanShapeRt>
 RPT_DEV void closest_hit(const SceneView& scene_, V o, V d, float tmin, float& tbest, uint32_t& code, uint32_t& inst,
                          uint32_t* stk, uint32_t stride, uint32_t& c_nodes, uint32_t& c_tris,
                          AnyHit any = AnyHit{-kInf, 1u, 0u}) {
@@ -1002,7 +1063,7 @@ RPT_DEV void closest_hit(const SceneView& scene_, V o, V d, float tmin, float& t
         if (sc.mesh_deferred) walk_meshes<COUNT, ANY>(scene_, o, d, tmin, tbest, code, inst, stk, stride, c_nodes, c_tris, any);   // (wave-uniform)
         return;
     }
-    scan_prims<false, MONO>(scene_, o, d, tmin, tbest, code);
+    scan_prims<false, MONO, false, false, SHAPE>(scene_, o, d, tmin, tbest, code);
     if (BVH) walk_meshes<COUNT, ANY>(scene_, o, d, tmin, tbest, code, inst, stk, stride, c_nodes, c_tris, any);
 }
 

@@ -8,7 +8,19 @@
 //     (normal transform, vertex normals, object -> material).
 //   * large meshes are a BVH2 (64-byte two-box nodes) + the same 48-byte triangle records, walked per lane.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <stdint.h>
+#else   // runtime compilation has no C library headers: the compiler's own types (a repeated typedef of the same type is legal)
+typedef __INT8_TYPE__ int8_t;
+typedef __UINT8_TYPE__ uint8_t;
+typedef __INT16_TYPE__ int16_t;
+typedef __UINT16_TYPE__ uint16_t;
+typedef __INT32_TYPE__ int32_t;
+typedef __UINT32_TYPE__ uint32_t;
+typedef __INT64_TYPE__ int64_t;
+typedef __UINT64_TYPE__ uint64_t;
+typedef __UINTPTR_TYPE__ uintptr_t;
+#endif
 
 namespace rptg {
 

@@ -5,6 +5,7 @@
 #include <functional>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "../../include/rpt_hip.h"
 #include "kernels.h"
@@ -89,6 +90,38 @@ inline float elapsed_ms(const Event& a, const Event& b) {
 }
 
 int fail(int code, const std::string& msg);
+// What the scans of a committed scene know before they read a record (device_core.h, ScanShapeK), and which of the two scan kernels
+// runs them.  Two scenes with the same shape share one specialised code object; record values are not part of it.
+struct ScanShape {
+    uint32_t n_sph, n_cub, n_pln, n_aabb, n_rect_x, n_rect_y, n_rect_z, n_tri, has_shell, scan_cull, medium;
+    uint64_t sph_yrot, cub_yrot;
+};
+bool scan_shape_of(const rptg::SceneView& v, ScanShape* out, std::string* why);   // false: a flavour outside the scope (tree, group light, monomial surface)
+std::string scan_shape_string(const ScanShape& h);
+std::string scan_jit_program(const ScanShape& h);        // the program text: the shape block and #include "kernels.hip"
+std::string scan_jit_kernel_name(const ScanShape& h);    // the name expression of the one instantiation it emits
+const std::vector<std::string>& scan_jit_options();
+bool scan_jit_sources(const std::string& dir, std::vector<std::pair<std::string, std::string>>* out, std::string* why);
+std::string scan_jit_key(const std::string& program, const std::vector<std::pair<std::string, std::string>>& sources,
+                         const std::vector<std::string>& options, int rtc_major, int rtc_minor);
+bool scan_jit_compile(const ScanShape& shape, const std::vector<std::pair<std::string, std::string>>& sources, std::vector<char>* code,
+                      std::string* lowered, double* ms, std::string* why);
+bool scan_jit_resources(const std::vector<char>& code, int* vgprs, int* scratch);
+bool scan_jit_cache_read(const std::string& path, std::vector<char>* code, std::string* lowered, std::string* why);
+bool scan_jit_cache_write(const std::string& dir, const std::string& path, const std::vector<char>& code, const std::string& lowered);
+// A scene's state of it (rpt_scan_jit_info).
+struct ScanJit {
+    int state = 1, cache = 0;   // RPT_SCAN_JIT_IDLE, RPT_SCAN_JIT_CACHE_NONE
+    bool probed = false;
+    ScanShape shape{};
+    std::string shape_text, reason, key, compiler;
+    std::vector<std::pair<std::string, std::string>> sources;
+    double compile_ms = 0;
+    int vgprs = 0, scratch = 0, aot_vgprs = 0;
+    size_t lds = 0;
+    hipFunction_t fn = nullptr;
+    uint64_t launches = 0;
+};
 uint64_t seed_mix(uint64_t seed);
 struct SceneDev {
     bool committed;

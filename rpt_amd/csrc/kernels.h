@@ -1,8 +1,10 @@
 // kernels.h — host-callable launchers of the HIP kernels (implemented in kernels.hip).
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 #include <stdint.h>
+#endif
 #include "gpu_layout.h"
 
 namespace rptg {
@@ -42,7 +44,9 @@ struct RenderArgs {
 
 // The device functions read the scene view at kernarg + 0 (kernarg_scene in device_core.h): every kernel that calls them
 // takes ONE argument struct that begins with the SceneView.
-static_assert(offsetof(RenderArgs, sc) == 0, "RenderArgs must begin with the SceneView");
+static_assert(__builtin_offsetof(RenderArgs, sc) == 0, "RenderArgs must begin with the SceneView");
+
+#ifndef __HIPCC_RTC__   // (runtime compilation takes the argument struct alone)
 
 struct KernelInfo {
     int vgprs, sgprs, lds, max_blocks_per_cu;
@@ -52,6 +56,9 @@ struct KernelInfo {
 hipError_t launch_render(const RenderArgs& a, int n_blocks, hipStream_t stream);
 hipError_t render_occupancy(bool medium, int bvh, int* blocks_per_cu, int detach = 0);  // bvh: bvh_mode(); detach: RenderArgs::detach
 size_t stream_scratch_bytes_per_block();
+// Registers, scratch bytes per lane and dynamic LDS of the AOT scan kernel render_kernel<medium, 0, false>: what a specialised twin
+// (rpt_capi.cpp, scan JIT) is launched with and must not exceed.  (Weak: the host-only test builds have no kernels.)
+__attribute__((weak)) hipError_t scan_render_info(bool medium, int* vgprs, int* scratch, size_t* lds);
 int bvh_mode(const SceneView& sc);  // 0 no tree, 1 per-mesh trees, 2 scene-level tree
 // out[pixel] = sum_chunks slab / iterations * scale for owned pixels (others untouched).
 hipError_t launch_buffer_add(uint32_t n_pixels, const double* d_batch, double* d_sum, double* d_sumsq, hipStream_t st);
@@ -219,4 +226,6 @@ hipError_t launch_resolve_photon_f64(const rpt64::Args& a, const void* slab32, u
                                      double* d_out, hipStream_t stream);
 // The feature pass of that mode (records as FeatureArgs'; launch_feature_resolve resolves them).  (Weak, like launch_features.)
 __attribute__((weak)) hipError_t launch_features_f64(const rpt64::FeatureArgs64& a, hipStream_t stream);
+#endif  // __HIPCC_RTC__
+
 }  // namespace rptg

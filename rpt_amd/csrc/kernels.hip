@@ -234,17 +234,17 @@ RPT_DEV void stage_light_term(const SceneView& sc, const Light& L, float albedo_
 // A light that the commit marked (Light::color.w; option "shadow_scan") asks the scan's shadow form for its one bit; every other
 // light -- a group light, a twin that is a shell face or a monomial surface, the option off -- runs the closest-hit scan and
 // stage_light_term's test, as before.  Wave-uniform choice.  `ts`: the closest hit's t (the end of the interval on a miss).
-template <bool MONO = false>
+template <bool MONO = false, class SHAPE = ScanShapeRt>
 RPT_DEV bool scan_light_visible(const SceneView& sc, const Light& L, V x, V wi, float dist, float& ts) {
     ts = dist * (1.f + 1e-3f);
     uint32_t cs = CODE_MISS;
     if (__float_as_uint(L.color.w) != 0u) {
         bool twin = false;
-        scan_prims<false, MONO, false, true>(sc, x, wi, ray_tmin(x), ts, cs, ~0ull, nullptr,
+        scan_prims<false, MONO, false, true, SHAPE>(sc, x, wi, ray_tmin(x), ts, cs, ~0ull, nullptr,
                                              ShadowTwin{L.twin_lo >> 28, L.twin_lo & 0x0FFFFFFFu, L.twin_hi - L.twin_lo}, &twin);
         return twin && ts >= dist * (1.f - 1e-3f);
     }
-    scan_prims<false, MONO>(sc, x, wi, ray_tmin(x), ts, cs);
+    scan_prims<false, MONO, false, false, SHAPE>(sc, x, wi, ray_tmin(x), ts, cs);
     const bool twin = (L.twin_lo <= L.twin_hi) ? (cs >= L.twin_lo && cs <= L.twin_hi)
                                                : (cs != CODE_MISS && code_object<MONO>(sc, cs, 0u) == uint32_t(L.twin_object));
     return cs != CODE_MISS && ts >= dist * (1.f - 1e-3f) && twin;
@@ -298,6 +298,9 @@ void render_kernel(const RenderArgs a) {
 #endif
     static_assert(DETACH == 0 || (MEDIUM && BVH == 1 && !GROUPS), "detached tree walks: per-mesh-tree kernels in a medium only");
     static_assert(DETACH == 0 || !MONO, "no detached tree walks in scenes with monomial surfaces");
+    // The scan flavours without group lights, monomial surfaces or counters take the scene's record counts as constants where the
+    // build gives them (ScanShapeK); every other flavour, and every build without them, reads them from the view.
+    using Shape = tt::conditional_t<BVH == 0 && !COUNT && !GROUPS && DETACH == 0 && !MONO, ScanShapeK, ScanShapeRt>;
     extern __shared__ uint32_t dyn_lds[];
     const SceneView& sc = a.sc;
     uint32_t* stk = BVH ? (dyn_lds + threadIdx.x) : nullptr;
@@ -1270,9 +1273,9 @@ void render_kernel(const RenderArgs a) {
         const float tmin = ray_tmin(ro);
         uint32_t code = CODE_MISS, inst = 0;
         if constexpr (MEDIUM && BVH == 0 && !MONO)   // (the interval mostly ends at the medium distance: the scan's tail is seldom in reach)
-            scan_primary<COUNT>(sc, ro, rd, tmin, t, code, COUNT ? a.counters + kCullCounters : nullptr);
+            scan_primary<COUNT, Shape>(sc, ro, rd, tmin, t, code, COUNT ? a.counters + kCullCounters : nullptr);
         else
-            closest_hit<BVH, COUNT, false, MONO>(sc, ro, rd, tmin, t, code, inst, stk, stride, c_nodes, c_btris);
+            closest_hit<BVH, COUNT, false, MONO, Shape>(sc, ro, rd, tmin, t, code, inst, stk, stride, c_nodes, c_btris);
         if (COUNT) c_rays++;
         SECTK(3);
         const bool hit = code != CODE_MISS;
@@ -1310,7 +1313,7 @@ void render_kernel(const RenderArgs a) {
                     SECTK(8);
                     if constexpr (BVH == 0) {
                         float ts;
-                        const bool visible = scan_light_visible<MONO>(sc, L, x, wi, dist, ts);
+                        const bool visible = scan_light_visible<MONO, Shape>(sc, L, x, wi, dist, ts);
                         if (COUNT) c_rays++;
                         SECTK(9);
                         if (visible) stage_light_add<true>(sc, albedo_med, rd, ev_medium, I, wi, n, mcol, mat, E);
@@ -1379,6 +1382,9 @@ void render_kernel(const RenderArgs a) {
     }
 }
 
+// Runtime compilation (the scan JIT of rpt_capi.cpp): the program is a shape block (RPT_SCAN_SHAPE) and this file, and what it needs of
+// it ends here -- the one render_kernel instantiation it names.  Every other kernel and the host launchers are left out.
+#ifndef __HIPCC_RTC__
 __global__ __launch_bounds__(256) void resolve_kernel(const RenderArgs a, double scale, double* __restrict__ out) {
     uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= a.n_owned) return;
@@ -1831,6 +1837,16 @@ hipError_t launch_render(const RenderArgs& a, int n_blocks, hipStream_t stream) 
     if (m) return c ? launch_render_b<true, true>(a, b, n_blocks, stream) : launch_render_b<true, false>(a, b, n_blocks, stream);
     return c ? launch_render_b<false, true>(a, b, n_blocks, stream) : launch_render_b<false, false>(a, b, n_blocks, stream);
 }
+hipError_t scan_render_info(bool medium, int* vgprs, int* scratch, size_t* lds) {
+    hipFuncAttributes fa{};
+    const hipError_t e = medium ? hipFuncGetAttributes(&fa, (const void*)render_kernel<true, 0, false>)
+                                : hipFuncGetAttributes(&fa, (const void*)render_kernel<false, 0, false>);
+    if (e != hipSuccess) return e;
+    *vgprs = fa.numRegs;
+    *scratch = int(fa.localSizeBytes);
+    *lds = kStateBytes;
+    return hipSuccess;
+}
 size_t stream_scratch_bytes_per_block() { return size_t(kWaveScratchDwords) * 4u * 4u; }
 hipError_t render_occupancy(bool medium, int bvh, int* blocks_per_cu, int detach) {
 #ifdef RPT_EXPERIMENTS
@@ -1973,5 +1989,7 @@ hipError_t launch_debug_bounce(const BounceArgs& q, hipStream_t s) {
     else hipLaunchKernelGGL(debug_bounce_kernel<false>, grid, dim3(256), 0, s, a, q);
     return hipGetLastError();
 }
+
+#endif  // __HIPCC_RTC__
 
 }  // namespace rptg

@@ -2,16 +2,24 @@
 // the fp32 device layout (gpu_layout.h), BVH build for large meshes, launches.
 #include <hip/hip_runtime_api.h>
 
+#include <dlfcn.h>
+#include <unistd.h>
+
 #include <algorithm>
+#include <atomic>
 #include <cfloat>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <filesystem>
 #include <functional>
 #include <limits>
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -64,6 +72,8 @@ struct rpt_options {
     int64_t scan_specialise = 1;    // mark y-rotated sphere / cube records and box pairs with common slabs for the unmasked scans (read by rpt_scene_commit)
     int64_t scan_cull = 1;          // primary scans in a medium leave out their tail -- boxes, rectangles, triangles -- when no lane's search interval reaches
                                     // the box around it (read by rpt_scene_commit; 0: the plain scans)
+    int64_t scan_jit = 1;           // the scan flavours' render kernel compiled for the scene's record counts (hiprtc): 0 never, 2 always; 1: a cached code
+                                    // object is used, and one is compiled at the first launch of at least 2^27 camera samples (rpt_scan_jit_info)
     int64_t shadow_scan = 1;        // shadow queries of the scan flavours keep one bit, "the closest hit is a record of the light's twin", instead of the hit
                                     // code, for every light whose twin is one range of scanned records (read by rpt_scene_commit; 0: the closest-hit scan)
     int64_t photon_skip = 0;
@@ -113,6 +123,7 @@ static int set_option_in(rpt_options& o, const char* name, int64_t value) {
     else if (s == "scan_specialise") o.scan_specialise = value;
     else if (s == "scan_cull") o.scan_cull = value;
     else if (s == "shadow_scan") o.shadow_scan = value;
+    else if (s == "scan_jit") { if (value < 0 || value > 2) return fail(RPT_ERR_INVALID, "scan_jit must be 0, 1 or 2"); o.scan_jit = value; }
     else if (s == "photon_skip") o.photon_skip = value;
     else if (s == "photon_block_lists") o.photon_block_lists = value;
     else if (s == "photon_parts") o.photon_parts = value;
@@ -558,6 +569,7 @@ struct rpt_scene {
     std::vector<Light> light_records;  // the committed light list as the device has it (rpt_shadow_scan_info)
     bool twins_scanned = false;  // every Light::Object that can be visible has its twin among the scanned records, as one range of hit codes
     uint64_t stats[16] = {0};
+    rpti::ScanJit jit;   // the specialised render kernel of this scene, if any (option "scan_jit")
     void* photon = nullptr;  // PhotonMapDev*, owned by photon.hip
     // reference-epsilon mode (option "epsilon_policy" = 1 at commit): the fp64 scene of kernels_f64.hip in dev.arena64
     rpt64::Scene view64{};
@@ -668,6 +680,7 @@ static void release_device(rpt_scene* s) {
     if (s->photon) rpti::photon_release(s->photon);
     s->photon = nullptr;
     s->committed = false;
+    s->jit = rpti::ScanJit{};   // (the modules belong to the process, not to the scene)
 }
 
 void rpt_scene_destroy(rpt_scene* s) {
@@ -2617,6 +2630,362 @@ extern "C++" int rpti::run_persistent(rpt_scene* s, const rpt_render_params* prm
     HIP_TRY(hipEventRecord(mine.done.get(), st));
     return RPT_OK;
 }
+// ---------------------------------------------------------------------------- scan JIT
+// The scan flavours' render kernel compiled for one scene's record counts.  What a scan knows before it
+// reads a record -- the counts per kind, the shell, the y-rotation masks, the tail cull -- is fixed at commit and costs the generic
+// kernel a chain of scalar loads, waits, compares and branches per kind, twice per wave trip.  hiprtc (opened with dlopen: no link
+// dependency) compiles kernels.hip with these as constants (device_core.h, ScanShapeK); record VALUES stay data, so scenes of one shape
+// share one code object.  Everything that goes wrong -- library absent, sources absent, compile or load error, more registers than the
+// AOT twin -- leaves the scene on the AOT kernel and is said by rpt_scan_jit_info.
+extern "C++" {
+namespace rpti {
+bool scan_shape_of(const SceneView& v, ScanShape* out, std::string* why) {
+    if (why) why->clear();
+    const char* w = nullptr;
+    if (v.n_lparts) w = "a group is a light (GROUPS)";
+    else if (v.n_mono) w = "the scene has monomial surfaces (MONO)";
+    else if (v.scene_bvh || v.n_nodes) w = "the scene has a tree (BVH != 0)";
+    if (w) { if (why) *why = w; return false; }
+    *out = ScanShape{v.n_sph, v.n_cub, v.n_pln, v.n_aabb, v.n_rect_x, v.n_rect_y, v.n_rect_z, v.n_tri, v.has_shell ? 1u : 0u,
+                     v.scan_cull ? 1u : 0u, v.has_medium ? 1u : 0u, v.sph_yrot, v.cub_yrot};
+    return true;
+}
+// The constants in ScanShapeK's order (device_core.h), as they stand behind "#define RPT_SCAN_SHAPE".
+std::string scan_shape_constants(const ScanShape& h) {
+    char b[256];
+    std::snprintf(b, sizeof b, "%u,%u,%u,%u,%u,%u,%u,%u,%u,%u,0x%llxull,0x%llxull", h.n_sph, h.n_cub, h.n_pln, h.n_aabb, h.n_rect_x, h.n_rect_y,
+                  h.n_rect_z, h.n_tri, h.has_shell, h.scan_cull, (unsigned long long)h.sph_yrot, (unsigned long long)h.cub_yrot);
+    return b;
+}
+std::string scan_shape_string(const ScanShape& h) { return scan_shape_constants(h) + (h.medium ? ";medium=1" : ";medium=0"); }
+std::string scan_jit_kernel_name(const ScanShape& h) {
+    return std::string("rptg::render_kernel<") + (h.medium ? "true" : "false") + ", 0, false, false, 0, false>";
+}
+std::string scan_jit_program(const ScanShape& h) {
+    return "#define RPT_SCAN_SHAPE " + scan_shape_constants(h) + "\n#include \"kernels.hip\"\n";
+}
+const std::vector<std::string>& scan_jit_options() {   // the library's own device flags (__graft_entry__.FLAGS)
+    static const std::vector<std::string> o = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize"};
+    return o;
+}
+// kernels.hip and every file it includes with quotes, transitively, as read from `dir`: (include name, contents) in the order found.
+// They are handed to the compiler from memory, so what is hashed is what is compiled.
+bool scan_jit_sources(const std::string& dir, std::vector<std::pair<std::string, std::string>>* out, std::string* why) {
+    out->clear();
+    std::vector<std::string> todo = {"kernels.hip"};
+    while (!todo.empty()) {
+        const std::string name = todo.back();
+        todo.pop_back();
+        bool have = false;
+        for (auto& f : *out) have = have || f.first == name;
+        if (have) continue;
+        FILE* f = std::fopen((dir + "/" + name).c_str(), "rb");
+        if (!f) { *why = "source not found: " + dir + "/" + name; return false; }
+        std::string text;
+        char buf[65536];
+        for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, n);
+        std::fclose(f);
+        for (size_t p = 0; (p = text.find("#include \"", p)) != std::string::npos;) {
+            p += 10;
+            const size_t e = text.find('"', p);
+            if (e == std::string::npos) break;
+            const std::string inc = text.substr(p, e - p);
+            if (inc.find('/') == std::string::npos) todo.push_back(inc);   // (the program needs no file outside csrc/)
+            p = e;
+        }
+        out->emplace_back(name, std::move(text));
+    }
+    return true;
+}
+// 128 bits (two FNV-1a streams with different offsets) over the exact program text, every source as read, the options and the hiprtc
+// version: a cache key, not a signature.
+std::string scan_jit_key(const std::string& program, const std::vector<std::pair<std::string, std::string>>& sources,
+                         const std::vector<std::string>& options, int rtc_major, int rtc_minor) {
+    uint64_t h0 = 0xCBF29CE484222325ULL, h1 = 0x84222325CBF29CE4ULL;
+    auto eat = [&](const std::string& s) {
+        const uint64_t n = s.size();
+        for (int i = 0; i < 8; i++) { h0 = (h0 ^ ((n >> (8 * i)) & 255u)) * 0x100000001B3ULL; h1 = (h1 ^ ((n >> (8 * i)) & 255u)) * 0x100000001B3ULL; }
+        for (unsigned char c : s) { h0 = (h0 ^ c) * 0x100000001B3ULL; h1 = (h1 ^ c) * 0x100000001B3ULL; h1 ^= h1 >> 29; }
+    };
+    eat(program);
+    for (auto& f : sources) { eat(f.first); eat(f.second); }
+    for (auto& o : options) eat(o);
+    eat("hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor));
+    char b[40];
+    std::snprintf(b, sizeof b, "%016llx%016llx", (unsigned long long)h0, (unsigned long long)h1);
+    return b;
+}
+// VGPRs and scratch bytes per lane of the (one) kernel of a code object, from its metadata note: the MessagePack map entries
+// ".vgpr_count" and ".private_segment_fixed_size" (a string key followed by an unsigned integer).
+bool scan_jit_resources(const std::vector<char>& code, int* vgprs, int* scratch) {
+    auto find = [&](const char* key, int* out) {
+        const size_t kl = std::strlen(key);
+        for (size_t i = 0; i + kl + 1 <= code.size(); i++) {
+            if (std::memcmp(code.data() + i, key, kl) != 0) continue;
+            const unsigned char* p = reinterpret_cast<const unsigned char*>(code.data()) + i + kl;
+            const size_t left = code.size() - i - kl;
+            if (left >= 1 && p[0] < 0x80) { *out = p[0]; return true; }
+            if (left >= 2 && p[0] == 0xCC) { *out = p[1]; return true; }
+            if (left >= 3 && p[0] == 0xCD) { *out = (p[1] << 8) | p[2]; return true; }
+            if (left >= 5 && p[0] == 0xCE) { *out = int((uint32_t(p[1]) << 24) | (p[2] << 16) | (p[3] << 8) | p[4]); return true; }
+        }
+        return false;
+    };
+    return find(".vgpr_count", vgprs) && find(".private_segment_fixed_size", scratch);
+}
+
+namespace {
+struct Hiprtc {   // the entry points of libhiprtc this file uses (signatures of hip/hiprtc.h; the header is not needed)
+    void* lib = nullptr;
+    std::string path;
+    int major = 0, minor = 0;
+    int (*version)(int*, int*) = nullptr;
+    int (*create)(void**, const char*, const char*, int, const char* const*, const char* const*) = nullptr;
+    int (*destroy)(void**) = nullptr;
+    int (*add_name)(void*, const char*) = nullptr;
+    int (*compile)(void*, int, const char* const*) = nullptr;
+    int (*lowered)(void*, const char*, const char**) = nullptr;
+    int (*log_size)(void*, size_t*) = nullptr;
+    int (*log)(void*, char*) = nullptr;
+    int (*code_size)(void*, size_t*) = nullptr;
+    int (*code)(void*, char*) = nullptr;
+};
+struct HipModules {   // the module entry points of the HIP runtime this library is linked to, looked up by name: a build that stubs the
+    bool looked = false, ok = false;   // runtime (tests/host) has none of them and simply has no JIT
+    hipError_t (*load_data)(hipModule_t*, const void*) = nullptr;
+    hipError_t (*get_function)(hipFunction_t*, hipModule_t, const char*) = nullptr;
+    hipError_t (*launch)(hipFunction_t, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t, void**, void**) = nullptr;
+};
+struct JitObject {
+    std::vector<char> code;
+    std::string lowered;
+    int vgprs = 0, scratch = 0;
+    double compile_ms = 0;
+    std::string rejected;   // not empty: compiled (or failed to) and not to be used, why
+    std::unordered_map<int, hipFunction_t> fn;   // per device; modules stay loaded for the life of the process
+};
+std::mutex g_jit_mutex;   // everything below
+std::unordered_map<std::string, Hiprtc> g_hiprtc;   // by path (RPT_HIPRTC_LIB may change between scenes)
+HipModules g_modules;
+std::unordered_map<std::string, JitObject> g_jit_objects;   // by key
+uint64_t g_jit_compiles = 0;
+
+const Hiprtc* hiprtc_open(std::string* why) {
+    const char* env = std::getenv("RPT_HIPRTC_LIB");
+    const std::vector<std::string> paths = env && *env ? std::vector<std::string>{env} : std::vector<std::string>{"/opt/rocm/lib/libhiprtc.so", "libhiprtc.so"};   // (the compiler the library was built with first)
+    for (const std::string& path : paths) {
+        auto it = g_hiprtc.find(path);
+        if (it != g_hiprtc.end()) { if (it->second.lib) return &it->second; continue; }
+        Hiprtc& h = g_hiprtc[path];
+        void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        if (!lib) continue;
+        bool ok = true;
+        auto sym = [&](auto& fn, const char* name) { fn = reinterpret_cast<std::remove_reference_t<decltype(fn)>>(dlsym(lib, name)); ok = ok && fn; };
+        sym(h.version, "hiprtcVersion"); sym(h.create, "hiprtcCreateProgram"); sym(h.destroy, "hiprtcDestroyProgram");
+        sym(h.add_name, "hiprtcAddNameExpression"); sym(h.compile, "hiprtcCompileProgram"); sym(h.lowered, "hiprtcGetLoweredName");
+        sym(h.log_size, "hiprtcGetProgramLogSize"); sym(h.log, "hiprtcGetProgramLog"); sym(h.code_size, "hiprtcGetCodeSize");
+        sym(h.code, "hiprtcGetCode");
+        if (!ok || h.version(&h.major, &h.minor) != 0) { dlclose(lib); continue; }
+        h.lib = lib;
+        h.path = path;
+        return &h;
+    }
+    *why = "hiprtc not available (" + paths[0] + ")";
+    return nullptr;
+}
+const HipModules& hip_modules() {
+    HipModules& m = g_modules;
+    if (m.looked) return m;
+    m.looked = true;
+    Dl_info di{};
+    if (!dladdr(reinterpret_cast<void*>(&hipGetDeviceCount), &di) || !di.dli_fname) return m;
+    void* lib = dlopen(di.dli_fname, RTLD_NOW | RTLD_NOLOAD);
+    if (!lib) return m;
+    m.load_data = reinterpret_cast<decltype(m.load_data)>(dlsym(lib, "hipModuleLoadData"));
+    m.get_function = reinterpret_cast<decltype(m.get_function)>(dlsym(lib, "hipModuleGetFunction"));
+    m.launch = reinterpret_cast<decltype(m.launch)>(dlsym(lib, "hipModuleLaunchKernel"));
+    m.ok = m.load_data && m.get_function && m.launch;
+    return m;
+}
+std::string jit_source_dir() {
+    if (const char* env = std::getenv("RPT_JIT_SRC")) if (*env) return env;
+    Dl_info di{};
+    if (!dladdr(reinterpret_cast<void*>(&rpt_last_error), &di) || !di.dli_fname) return "";
+    const std::string lib = di.dli_fname;
+    const size_t slash = lib.rfind('/');
+    return (slash == std::string::npos ? std::string(".") : lib.substr(0, slash)) + "/csrc";
+}
+std::string jit_cache_dir() {
+    if (const char* env = std::getenv("RPT_JIT_CACHE")) if (*env) return env;
+    const char* home = std::getenv("HOME");
+    return home && *home ? std::string(home) + "/.cache/rpt_amd/jit" : std::string();
+}
+uint64_t fnv_bytes(const void* p, size_t n, uint64_t h = 0xCBF29CE484222325ULL) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 0x100000001B3ULL;
+    return h;
+}
+}  // namespace
+
+// A cache file: "RPTJIT01", code bytes, name bytes, FNV-1a of name + code (three u64), the lowered name, the code object.
+bool scan_jit_cache_read(const std::string& path, std::vector<char>* code, std::string* lowered, std::string* why) {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) { *why = "no cache file"; return false; }
+    char magic[8];
+    uint64_t hd[3] = {0, 0, 0};
+    bool ok = std::fread(magic, 1, 8, f) == 8 && std::memcmp(magic, "RPTJIT01", 8) == 0 && std::fread(hd, 8, 3, f) == 3 && hd[0] > 0 &&
+              hd[0] < (uint64_t(1) << 28) && hd[1] > 0 && hd[1] < 4096;
+    if (ok) {
+        lowered->resize(size_t(hd[1]));
+        code->resize(size_t(hd[0]));
+        ok = std::fread(&(*lowered)[0], 1, lowered->size(), f) == lowered->size() && std::fread(code->data(), 1, code->size(), f) == code->size() &&
+             fnv_bytes(code->data(), code->size(), fnv_bytes(lowered->data(), lowered->size())) == hd[2];
+    }
+    std::fclose(f);
+    if (!ok) *why = "cache file truncated or damaged";
+    return ok;
+}
+bool scan_jit_cache_write(const std::string& dir, const std::string& path, const std::vector<char>& code, const std::string& lowered) {
+    std::error_code ec;
+    std::filesystem::create_directories(dir, ec);
+    static std::atomic<unsigned> serial{0};
+    const std::string tmp = path + ".tmp." + std::to_string(uint64_t(getpid())) + "." + std::to_string(serial++);   // (the ranks of one job write the same file at once)
+    FILE* f = std::fopen(tmp.c_str(), "wb");
+    if (!f) return false;
+    const uint64_t hd[3] = {code.size(), lowered.size(), fnv_bytes(code.data(), code.size(), fnv_bytes(lowered.data(), lowered.size()))};
+    bool ok = std::fwrite("RPTJIT01", 1, 8, f) == 8 && std::fwrite(hd, 8, 3, f) == 3 && std::fwrite(lowered.data(), 1, lowered.size(), f) == lowered.size() &&
+              std::fwrite(code.data(), 1, code.size(), f) == code.size();
+    ok = (std::fclose(f) == 0) && ok;
+    if (ok) ok = std::rename(tmp.c_str(), path.c_str()) == 0;
+    if (!ok) std::remove(tmp.c_str());
+    return ok;
+}
+// One compile, in this process.  `rtc` null: the library is opened here (tests/host).
+bool scan_jit_compile(const ScanShape& shape, const std::vector<std::pair<std::string, std::string>>& sources, std::vector<char>* code,
+                      std::string* lowered, double* ms, std::string* why) {
+    std::string w;
+    const Hiprtc* rtc = hiprtc_open(&w);
+    if (!rtc) { *why = w; return false; }
+    const std::string program = scan_jit_program(shape), name = scan_jit_kernel_name(shape);
+    std::vector<const char*> texts, names, opts;
+    for (auto& f : sources) { names.push_back(f.first.c_str()); texts.push_back(f.second.c_str()); }
+    for (auto& o : scan_jit_options()) opts.push_back(o.c_str());
+    void* prog = nullptr;
+    if (rtc->create(&prog, program.c_str(), "rpt_scan_jit.hip", int(texts.size()), texts.data(), names.data()) != 0) { *why = "hiprtcCreateProgram failed"; return false; }
+    const auto t0 = std::chrono::steady_clock::now();
+    bool ok = rtc->add_name(prog, name.c_str()) == 0;
+    if (!ok) *why = "hiprtcAddNameExpression failed";
+    if (ok && rtc->compile(prog, int(opts.size()), opts.data()) != 0) {
+        ok = false;
+        size_t n = 0;
+        std::string log;
+        if (rtc->log_size(prog, &n) == 0 && n > 1) { log.resize(n); rtc->log(prog, &log[0]); }
+        *why = "compile error: " + log.substr(0, 600);
+    }
+    *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const char* low = nullptr;
+    size_t n = 0;
+    if (ok && (rtc->lowered(prog, name.c_str(), &low) != 0 || !low)) { ok = false; *why = "no lowered name for " + name; }
+    if (ok) *lowered = low;
+    if (ok && (rtc->code_size(prog, &n) != 0 || n == 0)) { ok = false; *why = "empty code object"; }
+    if (ok) { code->resize(n); if (rtc->code(prog, code->data()) != 0) { ok = false; *why = "hiprtcGetCode failed"; } }
+    rtc->destroy(&prog);
+    return ok;
+}
+}  // namespace rpti
+
+// The specialised function for this launch, or null: the AOT kernel.  Called with the scene's device current.
+static hipFunction_t scan_jit_function(rpt_scene* s, const RenderArgs& a) {
+    using namespace rpti;
+    ScanJit& j = s->jit;
+    if (s->opt.scan_jit == 0 || a.counters) return nullptr;   // (the counters build is a flavour of its own)
+    if (j.fn) return j.fn;
+    if (j.state == RPT_SCAN_JIT_FALLBACK || j.state == RPT_SCAN_JIT_OUT_OF_SCOPE) return nullptr;
+    std::lock_guard<std::mutex> lock(g_jit_mutex);
+    auto give_up = [&](int state, const std::string& why) { j.state = state; j.reason = why; return nullptr; };
+    if (!j.probed) {   // once per scene: shape, sources, key, and a look into both caches
+        j.probed = true;
+        ScanShape shape;
+        std::string why;
+        if (!scan_shape_of(s->view, &shape, &why)) return give_up(RPT_SCAN_JIT_OUT_OF_SCOPE, why);
+        j.shape = shape;
+        j.shape_text = scan_shape_string(shape);
+        if (!scan_render_info) return give_up(RPT_SCAN_JIT_FALLBACK, "this build has no AOT twin to compare with");
+        if (!hip_modules().ok) return give_up(RPT_SCAN_JIT_FALLBACK, "the HIP runtime has no module entry points");
+        const Hiprtc* rtc = hiprtc_open(&why);
+        if (!rtc) return give_up(RPT_SCAN_JIT_FALLBACK, why);
+        if (!scan_jit_sources(jit_source_dir(), &j.sources, &why)) return give_up(RPT_SCAN_JIT_FALLBACK, why);
+        j.key = scan_jit_key(scan_jit_program(shape), j.sources, scan_jit_options(), rtc->major, rtc->minor);
+        j.compiler = "hiprtc " + std::to_string(rtc->major) + "." + std::to_string(rtc->minor) + " (" + rtc->path + ")";
+        int aot_scratch = 0;
+        if (scan_render_info(shape.medium != 0, &j.aot_vgprs, &aot_scratch, &j.lds) != hipSuccess || j.aot_vgprs <= 0)
+            return give_up(RPT_SCAN_JIT_FALLBACK, "the AOT twin's registers are unknown");
+    }
+    const int aot_vgprs = j.aot_vgprs;
+    auto it = g_jit_objects.find(j.key);
+    int cache = RPT_SCAN_JIT_CACHE_MEMORY;
+    const std::string dir = jit_cache_dir(), path = dir.empty() ? std::string() : dir + "/" + j.key + ".co";
+    std::string note;
+    if (it == g_jit_objects.end() && !path.empty()) {
+        JitObject o;
+        std::string why;
+        if (scan_jit_cache_read(path, &o.code, &o.lowered, &why) && scan_jit_resources(o.code, &o.vgprs, &o.scratch)) {
+            it = g_jit_objects.emplace(j.key, std::move(o)).first;
+            cache = RPT_SCAN_JIT_CACHE_DISK;
+        } else if (why != "no cache file") {
+            std::remove(path.c_str());   // a file that does not load is discarded and compiled again
+            note = "cache file discarded (" + (why.empty() ? std::string("no resource note") : why) + "); ";
+        }
+    }
+    if (it == g_jit_objects.end()) {
+        const uint64_t samples = uint64_t(a.n_owned) * a.iterations;
+        if (s->opt.scan_jit == 1 && samples < (uint64_t(1) << 27)) {   // (not final: a larger launch compiles)
+            j.state = RPT_SCAN_JIT_IDLE;
+            j.reason = note + "no cached code object, and the launch is below the compile threshold of 2^27 camera samples";
+            return nullptr;
+        }
+        JitObject o;
+        std::string why;
+        g_jit_compiles++;
+        if (!scan_jit_compile(j.shape, j.sources, &o.code, &o.lowered, &o.compile_ms, &why)) o.rejected = why;
+        else if (!scan_jit_resources(o.code, &o.vgprs, &o.scratch)) o.rejected = "no resource note in the code object";
+        else if (!path.empty()) (void)scan_jit_cache_write(dir, path, o.code, o.lowered);   // (an unwritable directory: memory only)
+        it = g_jit_objects.emplace(j.key, std::move(o)).first;
+        cache = RPT_SCAN_JIT_CACHE_MISS;
+    }
+    JitObject& o = it->second;
+    j.cache = cache;
+    j.compile_ms = cache == RPT_SCAN_JIT_CACHE_MISS ? o.compile_ms : 0.0;
+    j.vgprs = o.vgprs;
+    j.scratch = o.scratch;
+    if (!o.rejected.empty()) return give_up(RPT_SCAN_JIT_FALLBACK, note + o.rejected);
+    if (o.vgprs > aot_vgprs)
+        return give_up(RPT_SCAN_JIT_FALLBACK, note + std::to_string(o.vgprs) + " VGPRs against the AOT kernel's " + std::to_string(aot_vgprs));
+    auto fn = o.fn.find(s->device);
+    if (fn == o.fn.end()) {
+        hipModule_t mod = nullptr;
+        hipFunction_t f = nullptr;
+        hipError_t e = hip_modules().load_data(&mod, o.code.data());
+        if (e == hipSuccess) e = hip_modules().get_function(&f, mod, o.lowered.c_str());
+        if (e != hipSuccess || !f) {
+            if (cache == RPT_SCAN_JIT_CACHE_DISK) { std::remove(path.c_str()); g_jit_objects.erase(it); }
+            return give_up(RPT_SCAN_JIT_FALLBACK, note + "load error: " + hipGetErrorString(e));
+        }
+        fn = o.fn.emplace(s->device, f).first;
+    }
+    j.fn = fn->second;
+    j.state = RPT_SCAN_JIT_ACTIVE;
+    j.reason = note + j.compiler;
+    return j.fn;
+}
+static hipError_t launch_render_jit(rpt_scene* s, hipFunction_t fn, const RenderArgs& a, int n_blocks, hipStream_t stream) {
+    size_t size = sizeof(RenderArgs);
+    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<RenderArgs*>(&a), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    s->jit.launches++;
+    return rpti::hip_modules().launch(fn, unsigned(n_blocks), 1, 1, 256, 1, 1, unsigned(s->jit.lds), stream, nullptr, extra);
+}
+}  // extern "C++"
+
 static int run_render(rpt_scene* s, const rpt_render_params* prm, const RenderArgs& a_in, double* d_out, hipStream_t st) {
     RenderArgs a = a_in;
     int bpc = int(s->opt.blocks_per_cu);
@@ -2629,8 +2998,12 @@ static int run_render(rpt_scene* s, const rpt_render_params* prm, const RenderAr
         HIP_TRY(ls.d_stream.reserve(size_t(s->n_cus) * size_t(bpc) * stream_scratch_bytes_per_block()));
         a.stream_scratch = ls.d_stream.get<uint32_t>();
     }
+    // (grid, streams, events, max_blocks and the tile list are the AOT kernel's: only the function differs)
+    const hipFunction_t jit = a.n_items ? scan_jit_function(s, a) : nullptr;
     return rpti::run_persistent(s, prm, a, d_out, st, bpc,
-                                [](const RenderArgs& ra, int nb, hipStream_t stream) { return launch_render(ra, nb, stream); }, true);
+                                [s, jit](const RenderArgs& ra, int nb, hipStream_t stream) {
+                                    return jit ? launch_render_jit(s, jit, ra, nb, stream) : launch_render(ra, nb, stream);
+                                }, true);
 }
 extern "C++" rpti::SceneDev rpti::scene_dev(rpt_scene* s) {
     int first = -1;
@@ -3555,6 +3928,44 @@ int rpt_shadow_scan_info(rpt_scene* s, uint32_t light, uint32_t out[4]) {
     out[2] = (bits_u(L.color.w) != 0u && bvh_mode(s->view) == 0) ? 1u : 0u;   // (only the scan kernels read the mark)
     out[3] = uint32_t(L.twin_object);
     return RPT_OK;
+}
+int rpt_scan_jit_info(rpt_scene* s, int64_t out[8], char* text, uint64_t text_capacity) {
+    if (!s || !out) return fail(RPT_ERR_INVALID, "null argument");
+    if (!text && text_capacity) return fail(RPT_ERR_INVALID, "rpt_scan_jit_info: a capacity without a buffer");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    const rpti::ScanJit& j = s->jit;
+    std::string shape = j.shape_text, reason = j.reason;
+    int state = j.state;
+    if (!j.probed) {   // no render yet: the shape the first one will see
+        rpti::ScanShape h;
+        if (rpti::scan_shape_of(s->view, &h, &reason)) shape = rpti::scan_shape_string(h);
+        else state = RPT_SCAN_JIT_OUT_OF_SCOPE;
+    }
+    if (s->opt.scan_jit == 0) { state = RPT_SCAN_JIT_OFF; reason = "option scan_jit = 0"; }
+    out[0] = state;
+    out[1] = j.cache;
+    out[2] = int64_t(j.compile_ms * 1000.0);
+    out[3] = j.vgprs;
+    out[4] = j.scratch;
+    out[5] = int64_t(j.launches);
+    {
+        std::lock_guard<std::mutex> lock(rpti::g_jit_mutex);
+        out[6] = int64_t(rpti::g_jit_compiles);
+    }
+    out[7] = j.aot_vgprs;
+    if (text_capacity) {
+        const std::string t = shape + "\n" + reason;
+        const size_t n = std::min<size_t>(t.size(), size_t(text_capacity) - 1);
+        std::memcpy(text, t.data(), n);
+        text[n] = 0;
+    }
+    return RPT_OK;
+}
+int rpt_scan_jit_forget(void) {
+    std::lock_guard<std::mutex> lock(rpti::g_jit_mutex);
+    const int n = int(rpti::g_jit_objects.size());
+    rpti::g_jit_objects.clear();   // (loaded modules stay: scenes that run them keep their functions)
+    return n;
 }
 int rpt_debug_distance_pair(float sigma_t, uint32_t k0, uint32_t n, float* out_new, float* out_guarded) {
     if (!out_new || !out_guarded) return fail(RPT_ERR_INVALID, "null argument");
