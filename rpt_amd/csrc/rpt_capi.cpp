@@ -545,7 +545,18 @@ struct rpt_scene {
         rpti::DevMem arena;      // the flattened scene (view's arrays)
         rpti::DevMem arena64;    // reference-epsilon mode: view64's arrays
         // per-render cached buffers
-        rpti::DevMem d_tiles;
+        // The owned-tile lists, one per (width, height, shard rank, shard count) a render asked for.  A list is uploaded once, into
+        // memory of its own, and never rewritten: the render and resolve kernels of a launch queued on a non-blocking stream read it
+        // long after the call has returned, and the next call may ask for another frame.  (prepare_render; a scene that goes
+        // through more than kTileLists frames frees the list it has not used for longest -- hipFree waits for the device.)
+        struct TileList {
+            rpti::DevMem ids;
+            uint32_t w = 0, h = 0, rank = 0, count = 0, n_tiles = 0;
+            uint64_t used = 0;   // tile_clock of the call that switched to it last
+        };
+        static constexpr size_t kTileLists = 16;
+        std::vector<TileList> tile_lists;
+        const uint32_t* d_tiles = nullptr;   // the current one (tk_* below), in tile_lists
         LaunchSet sets[2];
         rpti::DevMem d_counters;
         rpti::DevMem d_out;
@@ -581,8 +592,9 @@ struct rpt_scene {
     uint64_t last_counters64[64] = {0};   // [0..11] rpt_debug_epsilon_counters, [16 + 2k], [17 + 2k] section k of kernels_f64.hip (executions, lanes)
     // mesh data interned by content (hash -> candidates), so Arc<Mesh>-style sharing survives the C ABI
     std::unordered_map<uint64_t, std::vector<std::shared_ptr<const std::vector<double>>>> mesh_pool;
-    // tile cache key
+    // tile cache key: the list dev.d_tiles points to
     uint32_t tk_w = 0, tk_h = 0, tk_rank = 0, tk_count = 0, n_tiles = 0, tiles_x = 0;
+    uint64_t tile_clock = 0;
 };
 
 using MeshCallCache = std::unordered_map<const double*, std::pair<uint64_t, std::shared_ptr<const std::vector<double>>>>;
@@ -2524,16 +2536,39 @@ extern "C++" int rpti::prepare_render(rpt_scene* s, hipStream_t st, const rpt_ca
     (void)tiles_y;
     if (s->tk_w != prm->width || s->tk_h != prm->height || s->tk_rank != prm->shard_rank || s->tk_count != shard_count ||
         !s->dev.d_tiles) {
-        std::vector<uint32_t> tiles(size_t(tiles_x) * tiles_y);
-        tiles.resize(size_t(rpt_shard_tiles(prm->width, prm->height, prm->shard_rank, shard_count, tiles.data(),
-                                            tiles.size())));
-        HIP_TRY(s->dev.d_tiles.reserve(tiles.size() * 4));
-        if (!tiles.empty()) HIP_TRY(hipMemcpy(s->dev.d_tiles.get(), tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice));
+        // Another frame than the last call's: the list this scene already holds for it, else a new one.  Earlier launches may
+        // still be reading the lists they were given, so none is written after its upload.
+        auto& lists = s->dev.tile_lists;
+        size_t at = 0;
+        while (at < lists.size() && !(lists[at].w == prm->width && lists[at].h == prm->height && lists[at].rank == prm->shard_rank &&
+                                      lists[at].count == shard_count))
+            at++;
+        if (at == lists.size()) {
+            std::vector<uint32_t> tiles(size_t(tiles_x) * tiles_y);
+            tiles.resize(size_t(rpt_shard_tiles(prm->width, prm->height, prm->shard_rank, shard_count, tiles.data(),
+                                                tiles.size())));
+            if (lists.size() >= rpt_scene::Device::kTileLists) {   // full: the least recently used one goes
+                size_t old = 0;
+                for (size_t i = 1; i < lists.size(); i++)
+                    if (lists[i].used < lists[old].used) old = i;
+                if (lists[old].ids.get() == s->dev.d_tiles) s->dev.d_tiles = nullptr;
+                lists.erase(lists.begin() + old);   // (hipFree: synchronises the device, no launch reads it any more)
+                at = lists.size();
+            }
+            rpt_scene::Device::TileList fresh;
+            HIP_TRY(fresh.ids.reserve(std::max<size_t>(tiles.size() * 4, 4)));
+            if (!tiles.empty()) HIP_TRY(hipMemcpy(fresh.ids.get(), tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice));
+            fresh.w = prm->width; fresh.h = prm->height; fresh.rank = prm->shard_rank; fresh.count = shard_count;
+            fresh.n_tiles = uint32_t(tiles.size());
+            lists.push_back(std::move(fresh));
+        }
+        lists[at].used = ++s->tile_clock;
+        s->dev.d_tiles = lists[at].ids.get<uint32_t>();
         s->tk_w = prm->width; s->tk_h = prm->height; s->tk_rank = prm->shard_rank; s->tk_count = shard_count;
-        s->n_tiles = uint32_t(tiles.size());
+        s->n_tiles = lists[at].n_tiles;
         s->tiles_x = tiles_x;
     }
-    a.tiles = s->dev.d_tiles.get<uint32_t>();
+    a.tiles = s->dev.d_tiles;
     a.n_tiles = s->n_tiles;
     a.tiles_x = s->tiles_x;
     a.n_owned = a.n_tiles * 1024u;

@@ -163,16 +163,36 @@ def test_launches_on_two_streams_overlap_without_sharing_their_slab():
         r._sample_offset = offset
         return r.sample_array(spp).copy()
     expect = [lone(0), lone(spp), lone(2 * spp)]
+    # a second size, between the launches of the first and on the stream after theirs: the same tiles_x, half the height, other
+    # sample counts and offsets, and one shard of two -- its tile list [1, 3, 5] is no prefix of the first size's [0 .. 5], so a launch
+    # that read the other size's list would show (the lone frames come from a scene of their own: this one's history is under test)
+    h2, spp2 = 48, 5
+    s2, c2, _ = scenes.lampshade()
+    r2 = Renderer(s2, c2).width(w).height(h2).max_bounces(10).seed(4).shard(1, 2)
+
+    def lone_small(offset):
+        r2._sample_offset = offset
+        return r2.sample_array(spp2).copy()
+    expect_small = [lone_small(7), lone_small(7 + spp2), lone_small(7 + 2 * spp2)]
+    small = Renderer(scene, cam).width(w).height(h2).max_bounces(10).seed(4).shard(1, 2)   # the same scene handle as r
     streams = [torch.cuda.Stream() for _ in range(3)]
     frames = [torch.zeros(w * h * 3, dtype=torch.float64, device="cuda") for _ in range(6)]
+    small_frames = [torch.zeros(w * h2 * 3, dtype=torch.float64, device="cuda") for _ in range(6)]
+    torch.cuda.synchronize()
     for i, f in enumerate(frames):                             # 6 launches queued back to back: streams 0 1 2 0 1 2
         st = streams[i % 3]
         r._sample_offset = (i % 3) * spp
         with torch.cuda.stream(st):
             r.sample_device(spp, f.data_ptr(), st.cuda_stream)
+        st = streams[(i + 1) % 3]                              # ... each followed by one of the other size: streams 1 2 0 1 2 0
+        small._sample_offset = 7 + (i % 3) * spp2
+        with torch.cuda.stream(st):
+            small.sample_device(spp2, small_frames[i].data_ptr(), st.cuda_stream)
     torch.cuda.synchronize()
     for i, f in enumerate(frames):
         assert np.array_equal(f.cpu().numpy().reshape(-1, 3), expect[i % 3])
+    for i, f in enumerate(small_frames):
+        assert np.array_equal(f.cpu().numpy().reshape(-1, 3), expect_small[i % 3]), i
 
 
 def test_no_tree_walk_ever_finds_its_stack_full():
