@@ -23,7 +23,7 @@
 
 #include "device_core.h"   // Rng (the fp32 path's stream, bit for bit)
 #include "f64_layout.h"
-#include "host_internal.h"   // (rpt_intersect_batch_f64, at the end of the file)
+#include "scene_host.h"   // (rpt_intersect_batch_f64, at the end of the file)
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -1921,11 +1921,10 @@ hipError_t launch_resolve_photon_f64(const rpt64::Args& a, const void* slab32, u
 extern "C" int rpt_intersect_batch_f64(rpt_scene* s, uint64_t n, const double* origins, const double* dirs, double* t, int32_t* object,
                                        double* normal) {
     if (!s || !origins || !dirs || !t || !object) return rpti::fail(RPT_ERR_INVALID, "null argument");
-    const rpti::SceneDev sd = rpti::scene_dev(s);
-    if (!sd.committed) return rpti::fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
-    if (!sd.epsilon64) return rpti::fail(RPT_ERR_STATE, "rpt_intersect_batch_f64 needs a scene committed with epsilon_policy = 1");
+    if (!s->committed) return rpti::fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (!s->dev.arena64) return rpti::fail(RPT_ERR_STATE, "rpt_intersect_batch_f64 needs a scene committed with epsilon_policy = 1");
     if (n == 0) return RPT_OK;
-    RPTI_HIP_TRY(hipSetDevice(sd.device));
+    RPTI_HIP_TRY(hipSetDevice(s->device));
     rpti::DevMem d_o, d_d, d_t, d_obj, d_nrm;
     RPTI_HIP_TRY(d_o.reserve(n * 24));
     RPTI_HIP_TRY(d_d.reserve(n * 24));
@@ -1955,12 +1954,11 @@ extern "C" int rpt_debug_light_sample_f64(rpt_scene* s, uint32_t light, uint64_t
                                           double* nrm, double* pdf, double* intensity, double* wi, double* dist, uint32_t* next_word) {
     if (!s || !positions || !v || !nrm || !pdf || !intensity || !wi || !dist || !next_word) return rpti::fail(RPT_ERR_INVALID, "null argument");
     if (rpti::light_kind(s, light) != int(rpt64::LT_OBJECT)) return rpti::fail(RPT_ERR_INVALID, "rpt_debug_light_sample_f64: not a Light::Object");
-    const rpti::SceneDev sd = rpti::scene_dev(s);
-    if (!sd.committed) return rpti::fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
-    if (!sd.epsilon64) return rpti::fail(RPT_ERR_STATE, "rpt_debug_light_sample_f64 needs a scene committed with epsilon_policy = 1");
+    if (!s->committed) return rpti::fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (!s->dev.arena64) return rpti::fail(RPT_ERR_STATE, "rpt_debug_light_sample_f64 needs a scene committed with epsilon_policy = 1");
     if (n == 0) return RPT_OK;
     if (n > 0xFFFFFFFFull) return rpti::fail(RPT_ERR_INVALID, "rpt_debug_light_sample_f64: the case number keys a 32-bit stream field");
-    RPTI_HIP_TRY(hipSetDevice(sd.device));
+    RPTI_HIP_TRY(hipSetDevice(s->device));
     rpti::DevMem d_pos, d_out;   // d_out: v, nrm, intensity, wi (3 n each), pdf, dist (n each), next_word (n dwords)
     RPTI_HIP_TRY(d_pos.reserve(n * 24));
     RPTI_HIP_TRY(d_out.reserve(n * (14 * 8 + 4)));
@@ -1991,11 +1989,10 @@ extern "C" int rpt_debug_light_sample_f64(rpt_scene* s, uint32_t light, uint64_t
 }
 extern "C" int rpt_debug_env_color_f64(rpt_scene* s, uint64_t n, const double* dirs, double* rgb) {
     if (!s || !dirs || !rgb) return rpti::fail(RPT_ERR_INVALID, "null argument");
-    const rpti::SceneDev sd = rpti::scene_dev(s);
-    if (!sd.committed) return rpti::fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
-    if (!sd.epsilon64) return rpti::fail(RPT_ERR_STATE, "rpt_debug_env_color_f64 needs a scene committed with epsilon_policy = 1");
+    if (!s->committed) return rpti::fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (!s->dev.arena64) return rpti::fail(RPT_ERR_STATE, "rpt_debug_env_color_f64 needs a scene committed with epsilon_policy = 1");
     if (n == 0) return RPT_OK;
-    RPTI_HIP_TRY(hipSetDevice(sd.device));
+    RPTI_HIP_TRY(hipSetDevice(s->device));
     rpti::DevMem d_d, d_c;
     RPTI_HIP_TRY(d_d.reserve(n * 24));
     RPTI_HIP_TRY(d_c.reserve(n * 24));

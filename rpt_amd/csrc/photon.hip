@@ -18,7 +18,7 @@
 
 #include "device_core.h"
 #include "f64_layout.h"
-#include "host_internal.h"
+#include "scene_host.h"
 #include "kernels.h"
 #include "sort_scan.h"
 
@@ -2208,19 +2208,18 @@ extern "C" {
 // chains traced by kernels_f64.hip (t_min = 1e-12, fp64), which also keeps every surface photon's position in fp64 (pm->pos64).
 static int shoot_range(rpt_scene* s, PhotonMapDev* pm, uint64_t photon_count, uint64_t first, uint64_t n, int32_t kind,
                        double watts, uint64_t seed) {
-    const rpti::SceneDev sd = rpti::scene_dev(s);
-    const bool f64 = sd.epsilon64;
+    const bool f64 = bool(s->dev.arena64);
     hipStream_t st = nullptr;
     rpti::Event e0, e1;
     RPTI_HIP_TRY(e0.create());
     RPTI_HIP_TRY(e1.create());
     ShootArgs a{};
-    a.sc = sd.view;
+    a.sc = s->view;
     a.n_photons = n;
     a.first_photon = first;
     a.seed_mixed = rpti::seed_mix(seed);
     a.power = float(watts / double(photon_count));
-    a.light_index = uint32_t(sd.first_object_light);
+    a.light_index = uint32_t(rpti::first_object_light(s));
     a.kind = uint32_t(kind);
     rpt64::ShootArgs64 a64{};
     if (f64) {
@@ -2239,9 +2238,9 @@ static int shoot_range(rpt_scene* s, PhotonMapDev* pm, uint64_t photon_count, ui
     a.cnt_s = cnt_s.get();
     a.cnt_v = cnt_v.get();
     if (f64) RPTI_HIP_TRY(queue.alloc(*pm->pool, 1));
-    const bool medium = sd.view.has_medium != 0, bvh = sd.view.n_nodes != 0;
-    int blocks = int(std::min<uint64_t>((n + 255) / 256, uint64_t(sd.n_cus) * (f64 ? 4 : 8)));
-    if (const int64_t cap = rpti::option_max_blocks(s)) blocks = int(std::min<int64_t>(blocks, cap));
+    const bool medium = s->view.has_medium != 0, bvh = s->view.n_nodes != 0;
+    int blocks = int(std::min<uint64_t>((n + 255) / 256, uint64_t(s->n_cus) * (f64 ? 4 : 8)));
+    if (const int64_t cap = s->opt.max_blocks) blocks = int(std::min<int64_t>(blocks, cap));
     pm->shoot_blocks = blocks;
     PoolMem<uint32_t> d_mismatch;   // fp64 write pass: raised by a chain that does not store exactly the records the count pass counted
     if (f64) {
@@ -2320,25 +2319,24 @@ static int build_maps(PhotonMapDev* pm, const PhotonRec* d_s, uint64_t n_s, cons
 
 static int photon_args_ok(rpt_scene* s, uint64_t photon_count, int32_t kind) {
     if (!s) return rpti::fail(RPT_ERR_INVALID, "null scene");
-    rpti::SceneDev sd = rpti::scene_dev(s);
-    if (!sd.committed) return rpti::fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    if (!s->committed) return rpti::fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
     if (photon_count == 0) return rpti::fail(RPT_ERR_INVALID, "photon_count must be > 0");
     if (kind != RPT_PHOTON_POINT_BEAM && kind != RPT_PHOTON_MAP && kind != RPT_PHOTON_BEAM_BEAM)
         return rpti::fail(RPT_ERR_INVALID, "unknown PhotonRenderKind");
-    if (sd.has_monomial)   // (every photon.hip flavour would need the monomial surfaces' kernel flag)
+    if (rpti::has_monomial(s))   // (every photon.hip flavour would need the monomial surfaces' kernel flag)
         return rpti::fail(RPT_ERR_UNSUPPORTED, "photon mapping does not support scenes with a MonomialSurface");
-    if (sd.first_object_light < 0)
+    if (rpti::first_object_light(s) < 0)
         return rpti::fail(RPT_ERR_INVALID, "Only found non-object lights while photon mapping");  // the reference's panic
-    RPTI_HIP_TRY(hipSetDevice(sd.device));
+    RPTI_HIP_TRY(hipSetDevice(s->device));
     return RPT_OK;
 }
 static PhotonMapDev* fresh_map(rpt_scene* s, uint64_t photon_count, int32_t kind) {
-    void*& slot = rpti::photon_slot(s);
+    void*& slot = s->photon;
     std::shared_ptr<DevPool> pool;
     if (slot) {
         // the old map's buffers go back to the pool and may be handed out at once: nothing may still be reading them
         // (hipFree used to wait for the device here)
-        (void)hipSetDevice(rpti::scene_dev(s).device);
+        (void)hipSetDevice(s->device);
         (void)hipDeviceSynchronize();
         pool = static_cast<PhotonMapDev*>(slot)->pool;
         rpti::photon_release(slot);
@@ -2347,14 +2345,14 @@ static PhotonMapDev* fresh_map(rpt_scene* s, uint64_t photon_count, int32_t kind
     }
     auto* pm = new PhotonMapDev();
     if (pool) pm->pool = pool;
-    pm->device = rpti::scene_dev(s).device;
+    pm->device = s->device;
     pm->kind = kind;
     pm->photon_count = photon_count;
     slot = pm;
     return pm;
 }
 static void drop_map(rpt_scene* s) {
-    void*& slot = rpti::photon_slot(s);
+    void*& slot = s->photon;
     rpti::photon_release(slot);
     slot = nullptr;
 }
@@ -2374,7 +2372,7 @@ int rpt_photon_shoot(rpt_scene* s, uint64_t photon_count, int32_t kind, double w
                      uint32_t shard_count, uint64_t n_out[2]) {
     int rc = photon_args_ok(s, photon_count, kind);
     if (rc) return rc;
-    if (rpti::scene_dev(s).epsilon64) return rpti::fail(RPT_ERR_UNSUPPORTED, "the reference-epsilon mode keeps the surface photons' positions in fp64 beside the 48-byte records: build the map with rpt_photon_map_build (on every rank)");
+    if (s->dev.arena64) return rpti::fail(RPT_ERR_UNSUPPORTED, "the reference-epsilon mode keeps the surface photons' positions in fp64 beside the 48-byte records: build the map with rpt_photon_map_build (on every rank)");
     if (shard_count == 0) shard_count = 1;
     if (shard_rank >= shard_count) return rpti::fail(RPT_ERR_INVALID, "shard_rank must be < shard_count");
     // contiguous blocks, so that the shards concatenated in rank order ARE the single-GPU record arrays
@@ -2388,7 +2386,7 @@ int rpt_photon_shoot(rpt_scene* s, uint64_t photon_count, int32_t kind, double w
 
 int rpt_photon_records(rpt_scene* s, int32_t which, void** d_records, uint64_t* n) {
     if (!s || !d_records || !n) return rpti::fail(RPT_ERR_INVALID, "null argument");
-    auto* pm = static_cast<PhotonMapDev*>(rpti::photon_slot(s));
+    auto* pm = static_cast<PhotonMapDev*>(s->photon);
     if (!pm || pm->built) return rpti::fail(RPT_ERR_STATE, "no shot photons: call rpt_photon_shoot first");
     *d_records = which == 0 ? pm->raw_s.get() : pm->raw_v.get();
     *n = which == 0 ? pm->n_raw_s : pm->n_raw_v;
@@ -2400,8 +2398,8 @@ int rpt_photon_map_from_records(rpt_scene* s, uint64_t photon_count, int32_t kin
     int rc = photon_args_ok(s, photon_count, kind);
     if (rc) return rc;
     if ((n_surface && !d_surface) || (n_volume && !d_volume)) return rpti::fail(RPT_ERR_INVALID, "null record array");
-    if (rpti::scene_dev(s).epsilon64) return rpti::fail(RPT_ERR_UNSUPPORTED, "the reference-epsilon mode keeps the surface photons' positions in fp64 beside the 48-byte records: build the map with rpt_photon_map_build (on every rank)");
-    auto* old = static_cast<PhotonMapDev*>(rpti::photon_slot(s));
+    if (s->dev.arena64) return rpti::fail(RPT_ERR_UNSUPPORTED, "the reference-epsilon mode keeps the surface photons' positions in fp64 beside the 48-byte records: build the map with rpt_photon_map_build (on every rank)");
+    auto* old = static_cast<PhotonMapDev*>(s->photon);
     // the arrays may be this scene's own shot records: keep them alive until the maps are built (they go back to the pool
     // the new map takes over from the old one, before a failed map takes that pool with it)
     PoolMem<PhotonRec> keep_s, keep_v;
@@ -2418,7 +2416,7 @@ int rpt_photon_map_from_records(rpt_scene* s, uint64_t photon_count, int32_t kin
 
 int rpt_photon_map_stats(rpt_scene* s, uint64_t out[8]) {
     if (!s || !out) return rpti::fail(RPT_ERR_INVALID, "null argument");
-    auto* pm = static_cast<PhotonMapDev*>(rpti::photon_slot(s));
+    auto* pm = static_cast<PhotonMapDev*>(s->photon);
     if (!pm || !pm->built) return rpti::fail(RPT_ERR_STATE, "no photon map: call rpt_photon_map_build first");
     out[0] = pm->surf.n;
     out[1] = pm->vol.n;
@@ -2435,7 +2433,7 @@ int rpt_photon_map_stats(rpt_scene* s, uint64_t out[8]) {
 // power, radius.
 int rpt_photon_map_download(rpt_scene* s, int32_t which, float* out, uint64_t capacity) {
     if (!s || !out) return rpti::fail(RPT_ERR_INVALID, "null argument");
-    auto* pm = static_cast<PhotonMapDev*>(rpti::photon_slot(s));
+    auto* pm = static_cast<PhotonMapDev*>(s->photon);
     if (!pm || !pm->built) return rpti::fail(RPT_ERR_STATE, "no photon map: call rpt_photon_map_build first");
     const DevLbvh& l = which == 0 ? pm->surf : pm->vol;
     if (capacity < l.n) return rpti::fail(RPT_ERR_INVALID, "output buffer too small");
@@ -2462,7 +2460,7 @@ struct EpsSlice {
 static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint64_t gather_size,
                               uint64_t gather_size_volume, uint32_t num_samples, uint64_t seed, uint32_t sample_offset,
                               double* d_out, hipStream_t st, bool sync_counters, const EpsSlice* eps = nullptr) {
-    auto* pm = s ? static_cast<PhotonMapDev*>(rpti::photon_slot(s)) : nullptr;
+    auto* pm = s ? static_cast<PhotonMapDev*>(s->photon) : nullptr;
     if (!pm || !pm->built) return rpti::fail(RPT_ERR_STATE, "no photon map: call rpt_photon_map_build first");
     const uint64_t gather_max = pm->kind == RPT_PHOTON_MAP ? std::max(gather_size, gather_size_volume) : gather_size;
     if (gather_max > kGatherMax) return rpti::fail(RPT_ERR_UNSUPPORTED, "gather sizes above 1024 are not supported");
@@ -2477,7 +2475,7 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
     if (rc) return rc;
     rc = rpti::serialize_with_other_streams(s, st);  // candidate lists and the overflow flag exist once per scene
     if (rc) return rc;
-    const int64_t parts = rpti::option_photon_parts(s);
+    const int64_t parts = s->opt.photon_parts;
     if (parts != 1 && parts != 2 && parts != 4 && parts != 8) return rpti::fail(RPT_ERR_INVALID, "photon_parts must be 1, 2, 4 or 8");
     q.parts = uint32_t(parts);
     const uint64_t n_items = uint64_t(q.r.n_owned / 64u) * q.parts * q.r.n_chunks;
@@ -2486,7 +2484,7 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
     q.s_nodes = pm->surf.nodes.get(); q.s_ph = pm->surf.sorted.get(); q.n_s = pm->surf.n;
     q.v_nodes = pm->vol.nodes.get(); q.v_ph = pm->vol.sorted.get(); q.n_v = pm->vol.n;
     q.kind = uint32_t(pm->kind);
-    q.skip = uint32_t(rpti::option_photon_skip(s));
+    q.skip = uint32_t(s->opt.photon_skip);
     q.gather_size = uint32_t(gather_size);
     q.gather_size_volume = pm->kind == RPT_PHOTON_MAP ? uint32_t(gather_size_volume) : 0u;  // only the point-point estimate gathers in the volume
     const bool medium = q.r.sc.has_medium != 0, bvh = q.r.sc.n_nodes != 0;
@@ -2494,7 +2492,7 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
     const size_t coop_base = size_t(gather_size) * 64u + kBallStack;
     q.region_dwords = uint32_t(std::max<size_t>({size_t(gather_lds) * 64u * 2u, size_t(kBeamCap) + 64u * 16u, size_t(kSuper) * 4u + 2u * kPendCap,
                                                  gg ? 0u : coop_base + 5u * 160u}));
-    q.coop_cap = (gg || !rpti::option_photon_coop_gather(s)) ? 0u : uint32_t(std::min<size_t>(kCoopCap, ((q.region_dwords - coop_base) / 5u) & ~size_t(3)));
+    q.coop_cap = (gg || !s->opt.photon_coop_gather) ? 0u : uint32_t(std::min<size_t>(kCoopCap, ((q.region_dwords - coop_base) / 5u) & ~size_t(3)));
     const size_t lds = (bvh ? 32u * 256u * 4u : 0u) + 4u * size_t(q.region_dwords) * 4u;
     RPTI_HIP_TRY(pm->d_overflow.reserve(*pm->pool, 16));   // (64 bytes)
     RPTI_HIP_TRY(hipMemsetAsync(pm->d_overflow.get(), 0, 4, st));
@@ -2519,8 +2517,8 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
         sa.skip = q.skip;
         if (uint64_t(n_groups) * q.r.n_owned >= (1ull << 32)) return rpti::fail(RPT_ERR_INVALID, "too many work items");
     }
-    int surf64_blocks = rpti::scene_dev(s).n_cus * 4;
-    if (const int64_t cap = rpti::option_max_blocks(s)) surf64_blocks = int(std::min<int64_t>(surf64_blocks, cap));
+    int surf64_blocks = s->n_cus * 4;
+    if (const int64_t cap = s->opt.max_blocks) surf64_blocks = int(std::min<int64_t>(surf64_blocks, cap));
     if (eps) pm->surf64_blocks = surf64_blocks;
     auto launch = [&](const RenderArgs& ra, int nb, hipStream_t stream) -> hipError_t {
         QueryArgs qq = q;
@@ -2541,11 +2539,11 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
         };
     int bpc = int(std::max<size_t>(1, std::min<size_t>(4, (160u * 1024u) / std::max<size_t>(lds, 1))));
     if (gg) {  // one [2][K][64]-dword region per wave of the largest grid run_persistent may launch
-        RPTI_HIP_TRY(pm->d_gather.reserve(*pm->pool, size_t(rpti::scene_dev(s).n_cus) * size_t(bpc) * 4u * size_t(gather_max) * 128u));
+        RPTI_HIP_TRY(pm->d_gather.reserve(*pm->pool, size_t(s->n_cus) * size_t(bpc) * 4u * size_t(gather_max) * 128u));
         q.gather = pm->d_gather.get();
     }
-    if (pm->kind == RPT_PHOTON_POINT_BEAM && medium && pm->vol.n && rpti::option_photon_block_lists(s)) {
-        RPTI_HIP_TRY(pm->d_cand.reserve(*pm->pool, size_t(rpti::scene_dev(s).n_cus) * size_t(bpc) * 4u * kCandCap));
+    if (pm->kind == RPT_PHOTON_POINT_BEAM && medium && pm->vol.n && s->opt.photon_block_lists) {
+        RPTI_HIP_TRY(pm->d_cand.reserve(*pm->pool, size_t(s->n_cus) * size_t(bpc) * 4u * kCandCap));
         q.cand = pm->d_cand.get();
         q.cand_cap = kCandCap;
     }
@@ -2553,13 +2551,19 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
     // one kernel's mix of waves does: 112 ms against 95 on C4): a second slab for the surface term
     q.r.slab2 = nullptr;
 #ifndef RPT_EXPERIMENTS
-    if (rpti::option_photon_split(s)) return rpti::fail(RPT_ERR_UNSUPPORTED, "photon_split: a rejected prototype, built with -DRPT_EXPERIMENTS only");
+    if (s->opt.photon_split) return rpti::fail(RPT_ERR_UNSUPPORTED, "photon_split: a rejected prototype, built with -DRPT_EXPERIMENTS only");
 #endif
-    if (medium && !gg && pm->kind != RPT_PHOTON_MAP && rpti::option_photon_split(s)) {
+    if (medium && !gg && pm->kind != RPT_PHOTON_MAP && s->opt.photon_split) {
         RPTI_HIP_TRY(pm->d_slab2.reserve(*pm->pool, std::max<size_t>(size_t(q.r.n_chunks) * q.r.n_owned * 4u, 4u)));   // 16 bytes per item
         q.r.slab2 = pm->d_slab2.get();
     }
-    rc = rpti::run_persistent(s, prm, q.r, d_out, st, bpc, launch, false, true, resolve, !eps || eps->first);
+    rpti::PersistentLaunch pl;
+    pl.blocks_per_cu = bpc;
+    pl.launch = launch;
+    pl.resolve = resolve;
+    pl.wave_items = true;
+    pl.clear_sharded = !eps || eps->first;
+    rc = rpti::run_persistent(s, prm, q.r, d_out, st, pl);
     if (rc == RPT_OK && sync_counters) {
         uint32_t ov = 0;
         RPTI_HIP_TRY(hipMemcpyAsync(&ov, pm->d_overflow.get(), 4, hipMemcpyDeviceToHost, st));
@@ -2575,7 +2579,7 @@ static constexpr size_t kEmitBudget = size_t(32) << 30;
 static int photon_render_any(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint64_t gather_size,
                              uint64_t gather_size_volume, uint32_t num_samples, uint64_t seed, uint32_t sample_offset, double* d_out,
                              hipStream_t st) {
-    if (!s || !rpti::scene_dev(s).epsilon64)
+    if (!s || !s->dev.arena64)
         return photon_render_impl(s, cam, prm, gather_size, gather_size_volume, num_samples, seed, sample_offset, d_out, st, true);
     if (!prm || num_samples == 0) return rpti::fail(RPT_ERR_INVALID, "empty render");
     // slices: whole chunks of kSuper samples while the selections fit the budget, else fewer samples.  The selections are kept for the
@@ -2585,7 +2589,7 @@ static int photon_render_any(rpt_scene* s, const rpt_camera* cam, const rpt_rend
     const size_t per_sample = std::max<size_t>(size_t(n_tiles) * 1024u * (size_t(gather_size) + 2u) * 4u, 1);
     uint32_t slice = uint32_t(std::min<uint64_t>(num_samples, std::max<uint64_t>(kEmitBudget / per_sample, 1)));
     if (slice >= kSuper) slice -= slice % kSuper;
-    if (const int64_t forced = rpti::option_f64_photon_slice(s)) slice = uint32_t(std::min<int64_t>(forced, slice));
+    if (const int64_t forced = s->opt.f64_photon_slice) slice = uint32_t(std::min<int64_t>(forced, slice));
     if (per_sample * slice > kEmitBudget)   // (a slice is at least one sample)
         return rpti::fail(RPT_ERR_UNSUPPORTED, "reference-epsilon photon camera pass: the selections of one sample exceed the budget of a slice; render a smaller frame or more shards");
     // (a sharded frame is cleared before its first slice only, photon_render_impl: the resolve adds each slice to what the earlier ones left)
@@ -2622,7 +2626,7 @@ int rpt_photon_render_sample_device(rpt_scene* s, const rpt_camera* cam, const r
 
 int rpt_debug_photon_positions64(rpt_scene* s, double* out, uint64_t capacity) {
     if (!s || !out) return rpti::fail(RPT_ERR_INVALID, "null argument");
-    auto* pm = static_cast<PhotonMapDev*>(rpti::photon_slot(s));
+    auto* pm = static_cast<PhotonMapDev*>(s->photon);
     if (!pm || !pm->built) return rpti::fail(RPT_ERR_STATE, "no photon map: call rpt_photon_map_build first");
     if (pm->surf.n && !pm->pos64.get()) return rpti::fail(RPT_ERR_STATE, "this photon map was not shot in the reference-epsilon mode");
     if (capacity < pm->surf.n) return rpti::fail(RPT_ERR_INVALID, "output buffer too small");
@@ -2632,7 +2636,7 @@ int rpt_debug_photon_positions64(rpt_scene* s, double* out, uint64_t capacity) {
 
 int rpt_debug_photon_selections(rpt_scene* s, uint32_t* out, uint64_t capacity_words, uint64_t dims[3]) {
     if (!s || !dims) return rpti::fail(RPT_ERR_INVALID, "null argument");
-    auto* pm = static_cast<PhotonMapDev*>(rpti::photon_slot(s));
+    auto* pm = static_cast<PhotonMapDev*>(s->photon);
     if (!pm || !pm->d_emit.get()) return rpti::fail(RPT_ERR_STATE, "no camera pass in the reference-epsilon mode yet");
     for (int i = 0; i < 3; i++) dims[i] = pm->emit_dims[i];
     const uint64_t words = dims[0] * dims[1] * dims[2];

@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "../../include/rpt_hip.h"
-#include "host_internal.h"
+#include "scene_host.h"
 #include "kernels.h"
 #include "f64_layout.h"
 
@@ -57,58 +57,6 @@ uint64_t seed_mix(uint64_t seed) {
             return fail(RPT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e__));       \
     } while (0)
 
-// Options.  Every scene carries its own set, copied from the process defaults when it is created
-// (rpt_scene_create) and changed with rpt_scene_set_option; rpt_set_option changes the defaults, i.e. the scenes
-// created afterwards.  Nothing a render or commit reads is process-global, so scenes with different options can
-// be driven from different host threads.
-struct rpt_options {
-    int64_t counters = 0;
-    int64_t chunk_spp = 0;          // 0 = auto: ceil(iterations / 16) clamped to [2, 32]
-    int64_t blocks_per_cu = 0;      // 0 = occupancy query
-    int64_t max_blocks = 0;         // cap on the blocks of every persistent launch (renders, photon camera pass, fp64 shooting and surface passes); 0 = no cap.
-                                    // A small grid gives every lane / wave many work items: what the schedule tests run (the frame bits do not depend on it)
-    int64_t timing = 0;
-    int64_t room_shell = 1;         // fold rectangles that are the faces of one box into a single slab test
-    int64_t scan_specialise = 1;    // mark y-rotated sphere / cube records and box pairs with common slabs for the unmasked scans (read by rpt_scene_commit)
-    int64_t scan_cull = 1;          // primary scans in a medium leave out their tail -- boxes, rectangles, triangles -- when no lane's search interval reaches
-                                    // the box around it (read by rpt_scene_commit; 0: the plain scans)
-    int64_t scan_jit = 1;           // the scan flavours' render kernel compiled for the scene's record counts (hiprtc): 0 never, 2 always; 1: a cached code
-                                    // object is used, and one is compiled at the first launch of at least 2^27 camera samples (rpt_scan_jit_info)
-    int64_t shadow_scan = 1;        // shadow queries of the scan flavours keep one bit, "the closest hit is a record of the light's twin", instead of the hit
-                                    // code, for every light whose twin is one range of scanned records (read by rpt_scene_commit; 0: the closest-hit scan)
-    int64_t photon_skip = 0;
-    int64_t photon_block_lists = 1;
-    int64_t photon_coop_gather = 1; // surface gather of a pixel's samples by the wave together (0: one search per lane)
-    int64_t photon_split = 0;       // camera pass of the beam kinds in a medium: volume estimate and surface estimate as two launches (no scratch in
-                                    // either, but 112 ms instead of 95 on C4: in one kernel the LDS-bound and the VALU-bound estimate overlap)
-    int64_t photon_parts = 4;       // work items per (8x8 pixel block, sample chunk) of the photon camera pass: the block's rows in strips
-    int64_t instancing = 1;         // meshes shared by several shapes are stored once and instanced
-    int64_t bvh_leaf_max = 4;       // triangles per leaf of a mesh tree (read by rpt_scene_commit)
-    int64_t bvh_max_depth = 20;     // a mesh tree deeper than this is rebuilt balanced (read by rpt_scene_commit)
-    int64_t bvh_sweep_below = 4096; // ranges of at most this many triangles are split by an exact SAH sweep instead of 16 bins (read by rpt_scene_commit; 0 = bins only)
-    int64_t defer_stop = 16;        // still-walking lanes below which a wave leaves the walk (the rest resume later)
-    int64_t walk_leaf_quarters = 6; // deferred walks: test the leaves when 4 x (lanes at a leaf) >= this x (lanes still descending); 0 = when all are there
-    int64_t defer_lanes = 32;       // parked tree walks per wave that trigger a walk (per-mesh-tree kernels)
-    int64_t detach_shadows = 1;     // per-mesh-tree kernels in a medium: 1 = shadow queries that need a tree walk leave their path (0: they park
-                                    // the lane), 2 = every tree walk leaves its path ("streamed walks": ring + parked paths in memory)
-    int64_t stream_backlog = 48;    // detach_shadows = 2: queries in a wave's ring that trigger a walk session
-    int64_t stream_contexts = 1;    // detach_shadows = 2: paths a lane can have waiting in memory (1..6; C5: 272 / 279 / 290 ms for 1 / 2 / 4 at
-                                    // 2048x2048x128 -- every parked path is a round trip to the fabric --, 234 with detach_shadows = 1)
-    int64_t detach_lanes = 44;      // ... parked primary + queued shadow queries per wave that trigger a walk session
-    int64_t pull_batch = 2;         // lanes waiting for a new work item before a wave runs its item bookkeeping (1..64)
-    int64_t detach_trigger = 28;    // ... or this many queued shadow queries alone (the queue holds 32)
-    int64_t scene_bvh_min = 64;     // bounded primitives + BVH meshes from which the scene-level BVH is built
-    int64_t scene_tree_meshes = 0;  // 1: meshes with trees of their own are leaves of the scene tree (every query walks to completion);
-                                    // 0: they stay outside it and their walks are parked as in scenes without a scene tree (read by rpt_scene_commit)
-    int64_t f64_cull = 1;           // reference-epsilon mode: 1 = a lane evaluates only the objects whose fp32 box its ray can reach (same bits), 0 = every object;
-                                    // 2 = as 1, and the counters build keeps the search limits as well (its counters then describe the schedule, not the reference's work)
-    int64_t f64_mesh_tree_min = 64; // reference-epsilon mode: triangles from which a mesh gets a candidate tree (read by rpt_scene_commit; 0 = never, 1 = every mesh;
-                                    // f64_cull = 0 disables the trees as well).  Same bits as the scan of all its triangles
-    int64_t f64_photon_slice = 0;   // reference-epsilon photon camera pass: samples per slice (0: as many whole chunks of 256 as fit 32 GB of per-sample selections)
-    int64_t f64_surf_batch = 8;     // reference-epsilon mode, scenes with a medium: lanes of a wave that wait at a surface event before the wave runs the surface code (1..64)
-    int64_t denoise_stage = -1;     // read by rpt_denoiser_create: passes of step <= this stage their tile + halo in LDS (0: none, -1: the measured default, kDenoiseStageDefault)
-    int64_t epsilon_policy = 0;     // 1: the reference-epsilon mode (read by rpt_scene_commit): fp64, generic shapes, t_min = 1e-12, |hit - dist| < 1e-12
-};
 static rpt_options g_defaults;
 static std::mutex g_defaults_mutex;
 static int set_option_in(rpt_options& o, const char* name, int64_t value) {
@@ -289,29 +237,6 @@ uint64_t mix64_(uint64_t x) {
 }
 uint64_t seed_mix(uint64_t seed) { return rpti::seed_mix(seed); }
 
-// ---------------------------------------------------------------------------- host scene
-struct HShape {
-    rpt_shape_desc d;            // tris / children pointers rewritten to own storage
-    std::shared_ptr<const std::vector<double>> mesh;  // interned per scene: shapes sharing a mesh share this
-    const std::vector<double>& T() const {
-        static const std::vector<double> none;
-        return mesh ? *mesh : none;
-    }
-    std::vector<HShape> children;  // RPT_SHAPE_GROUP
-};
-struct HObject {
-    HShape shape;
-    rpt_material mat;
-};
-struct HLight {
-    int kind;
-    double color[3], vec[3];
-    HObject obj;
-};
-struct HMedium {
-    int kind;
-    double absorption, scattering;
-};
 bool same_shape(const HShape& a, const HShape& b) {
     if (a.d.kind != b.d.kind || a.d.has_transform != b.d.has_transform) return false;
     if (a.d.has_transform && std::memcmp(a.d.transform, b.d.transform, sizeof(a.d.transform)) != 0) return false;
@@ -513,89 +438,6 @@ struct DevBuf {
 
 }  // namespace
 
-// ---------------------------------------------------------------------------- rpt_scene
-struct rpt_scene {
-    std::vector<HObject> objects;
-    std::vector<HLight> lights;
-    std::vector<HMedium> media;
-    double env[3] = {0, 0, 0};
-    uint32_t hdri_w = 0, hdri_h = 0;
-    std::vector<float> hdri;  // w*h*4
-    std::vector<double> hdri64;  // w*h*3: the texels as they were given (the reference-epsilon mode reads these)
-    bool committed = false;
-    rpt_options opt;  // this scene's options (rpt_scene_set_option; starts as a copy of the process defaults)
-    int device = 0;
-    int n_cus = 256;
-    SceneView view{};
-    // What one launch owns until its resolve has run: the slab of partial sums and the work counter.  Two sets, so
-    // that a caller who alternates between two streams (consecutive frames of an iterative render) gets launches
-    // that overlap -- the next frame's blocks fill the CUs that the last paths of this frame no longer keep busy,
-    // ~0.35 ms per launch -- while launches on one stream keep using one set.
-    struct LaunchSet {
-        rpti::DevMem d_slab;
-        rpti::DevMem d_queue;
-        rpti::DevMem d_stream;   // streamed walks (detach = 2): rings and parked paths of the grid's waves
-        rpti::Event done;        // recorded after the resolve of the last launch that used the set
-        rpti::Event launched;    // recorded right before its render kernel
-        hipStream_t stream = nullptr;
-        bool used = false;
-    };
-    // Everything a commit and the renders after it put on the device: release_device replaces it with an empty one.
-    struct Device {
-        rpti::DevMem arena;      // the flattened scene (view's arrays)
-        rpti::DevMem arena64;    // reference-epsilon mode: view64's arrays
-        // per-render cached buffers
-        // The owned-tile lists, one per (width, height, shard rank, shard count) a render asked for.  A list is uploaded once, into
-        // memory of its own, and never rewritten: the render and resolve kernels of a launch queued on a non-blocking stream read it
-        // long after the call has returned, and the next call may ask for another frame.  (prepare_render; a scene that goes
-        // through more than kTileLists frames frees the list it has not used for longest -- hipFree waits for the device.)
-        struct TileList {
-            rpti::DevMem ids;
-            uint32_t w = 0, h = 0, rank = 0, count = 0, n_tiles = 0;
-            uint64_t used = 0;   // tile_clock of the call that switched to it last
-        };
-        static constexpr size_t kTileLists = 16;
-        std::vector<TileList> tile_lists;
-        const uint32_t* d_tiles = nullptr;   // the current one (tk_* below), in tile_lists
-        LaunchSet sets[2];
-        rpti::DevMem d_counters;
-        rpti::DevMem d_out;
-        // the feature pass (rpt_render_features*): its records and ids, the planes of the host entry point, and the event recorded after
-        // its resolve -- one pass of a scene at a time, whatever the stream; the launch sets above are not involved
-        rpti::DevMem d_feat_slab, d_feat_out;
-        rpti::Event feat_done;
-        bool feat_used = false;
-        // "timing": an event triple (before render, after render, after resolve) per launch, in a ring; nothing waits
-        // for them until rpt_get_timing / rpt_get_timing_mean is called
-        std::vector<rpti::Event> evs;
-    } dev;
-    int cur_set = 0;
-    uint64_t last_counters[64] = {0};  // [0..7] counters, [8..63] diagnostic trip stamps
-    uint64_t last_cull[12] = {0};      // rpt_scan_cull_counters (device counters [64..75])
-    static constexpr size_t kTimedLaunches = 1024;
-    size_t ev_count = 0;  // timed launches since the last rpt_get_timing_mean
-    int last_blocks = 0;
-    uint64_t prims_per_ray = 0;
-    uint32_t n_twin_lights = 0;  // Light::Objects with a twin among the scene's objects (the ones that can be visible)
-    std::vector<Light> light_records;  // the committed light list as the device has it (rpt_shadow_scan_info)
-    bool twins_scanned = false;  // every Light::Object that can be visible has its twin among the scanned records, as one range of hit codes
-    uint64_t stats[16] = {0};
-    rpti::ScanJit jit;   // the specialised render kernel of this scene, if any (option "scan_jit")
-    void* photon = nullptr;  // PhotonMapDev*, owned by photon.hip
-    // reference-epsilon mode (option "epsilon_policy" = 1 at commit): the fp64 scene of kernels_f64.hip in dev.arena64
-    rpt64::Scene view64{};
-    double medium_color64[3] = {0, 0, 0}, medium_color_hi64[3] = {0, 0, 0};
-    const rpt64::MeshNode* mnodes64 = nullptr;   // the candidate trees of its large meshes (f64_layout.h, Args::mnodes, mleaf, mroot), in dev.arena64
-    const uint32_t* mleaf64 = nullptr;
-    const uint32_t* mroot64 = nullptr;
-    uint64_t mesh_tree_info64[8] = {0};          // rpt_f64_mesh_tree_info
-    uint64_t last_counters64[64] = {0};   // [0..11] rpt_debug_epsilon_counters, [16 + 2k], [17 + 2k] section k of kernels_f64.hip (executions, lanes)
-    // mesh data interned by content (hash -> candidates), so Arc<Mesh>-style sharing survives the C ABI
-    std::unordered_map<uint64_t, std::vector<std::shared_ptr<const std::vector<double>>>> mesh_pool;
-    // tile cache key: the list dev.d_tiles points to
-    uint32_t tk_w = 0, tk_h = 0, tk_rank = 0, tk_count = 0, n_tiles = 0, tiles_x = 0;
-    uint64_t tile_clock = 0;
-};
 
 using MeshCallCache = std::unordered_map<const double*, std::pair<uint64_t, std::shared_ptr<const std::vector<double>>>>;
 static std::shared_ptr<const std::vector<double>> intern_mesh(rpt_scene* s, const double* p, uint64_t n_tris,
@@ -644,12 +486,6 @@ static bool copy_shape(rpt_scene* s, MeshCallCache& seen, const rpt_shape_desc* 
     Xf x;
     if (!make_xf(*d, x)) { why = "singular transform"; return false; }
     return true;
-}
-static bool holds_monomial(const HShape& h) {
-    if (h.d.kind == RPT_SHAPE_MONOMIAL) return true;
-    for (const HShape& c : h.children)
-        if (holds_monomial(c)) return true;
-    return false;
 }
 static bool check_material(const rpt_material* m, std::string& why) {
     if (!m) { why = "null material"; return false; }
@@ -2331,9 +2167,7 @@ extern "C++" void rpti::fill_args64(rpt_scene* s, const rpt_camera* cam, const r
     q.group_lights = 0u;
     for (const auto& l : s->lights)
         if (l.kind == int(L_OBJECT) && l.obj.shape.d.kind == RPT_SHAPE_GROUP) q.group_lights = 1u;
-    q.mono = 0u;
-    for (const auto& o : s->objects)
-        if (holds_monomial(o.shape)) q.mono = 1u;
+    q.mono = rpti::has_monomial(s) ? 1u : 0u;
     q.tree = uint32_t(s->mesh_tree_info64[5]);
     q.mnodes = s->mnodes64;
     q.mleaf = s->mleaf64;
@@ -2354,40 +2188,6 @@ extern "C++" void rpti::fill_args64(rpt_scene* s, const rpt_camera* cam, const r
         q.slab = reinterpret_cast<double*>(a->slab);
     }
     q.counters = nullptr;
-}
-// Renderer::sample in the reference-epsilon mode: the fp32 path's launch scheme (persistent grid over (pixel, chunk)
-// items, one launch set per stream) with an fp64 slab.
-static int use_tile_list(RenderArgs& a, const uint32_t* d_tiles, uint32_t n_tiles);
-static int run_render64(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
-                        uint32_t sample_offset, double* d_out, hipStream_t st, const uint32_t* d_tiles = nullptr, uint32_t n_tiles = 0) {
-    RenderArgs a{};   // (tiles, sharding, chunking, launch sets and argument checks are shared with the fp32 path)
-    int rc = rpti::prepare_render(s, st, cam, prm, iterations, seed, sample_offset, a, 0, 0, 32);
-    if (rc) return rc;
-    if (d_tiles)   // rpt_render_sample_tiles*: the caller's list in place of the scene's
-        if ((rc = use_tile_list(a, d_tiles, n_tiles))) return rc;
-    rpt64::Args q{};
-    rpti::fill_args64(s, cam, prm, &a, q);
-    q.counters = a.counters;
-    int bpc = int(s->opt.blocks_per_cu);
-    if (bpc <= 0) {
-        HIP_TRY(render_f64_occupancy(q.sc.has_medium != 0, &bpc));
-        if (bpc < 1) bpc = 1;
-    }
-    rc = rpti::run_persistent(s, prm, a, d_out, st, bpc,
-                              [&q](const RenderArgs&, int nb, hipStream_t stream) { return launch_render_f64(q, nb, stream); }, true, false,
-                              [&q](double scale, double* out, hipStream_t stream) { return launch_resolve_f64(q, scale, out, stream); });
-    if (rc) return rc;
-    if (q.counters) {
-        HIP_TRY(hipStreamSynchronize(st));
-        std::memset(s->last_counters, 0, sizeof(s->last_counters));
-        HIP_TRY(hipMemcpy(s->last_counters64, q.counters, sizeof(s->last_counters64), hipMemcpyDeviceToHost));
-        s->last_counters[0] = s->last_counters64[6];   // rpt_get_counters: samples, rays, vertices
-        s->last_counters[1] = s->last_counters64[0];
-        s->last_counters[2] = s->last_counters64[7];
-        s->last_counters[3] = s->last_counters64[10];   // wave-level loop trips
-        for (int i = 0; i < 48; i++) s->last_counters[8 + i] = s->last_counters64[16 + i];   // rpt_debug_section_counters
-    }
-    return RPT_OK;
 }
 
 int rpt_scene_commit(rpt_scene* s, int device) {
@@ -2599,7 +2399,7 @@ extern "C++" int rpti::prepare_render(rpt_scene* s, hipStream_t st, const rpt_ca
     a.stream_backlog = uint32_t(s->opt.stream_backlog);
     a.stream_contexts = uint32_t(s->opt.stream_contexts);
     a.n_twin_lights = s->n_twin_lights;
-    a.stream_scratch = nullptr;   // (run_render sizes it for the grid)
+    a.stream_scratch = nullptr;   // (render_frame sizes it for the grid)
     a.pull_batch = uint32_t(s->opt.pull_batch);
     a.detach_trigger = uint32_t(s->opt.detach_trigger);
     if (a.detach) {
@@ -2618,9 +2418,7 @@ extern "C++" int rpti::serialize_with_other_streams(rpt_scene* s, hipStream_t st
 }
 
 extern "C++" int rpti::run_persistent(rpt_scene* s, const rpt_render_params* prm, const RenderArgs& a, double* d_out, hipStream_t st,
-                         int blocks_per_cu, const std::function<hipError_t(const RenderArgs&, int, hipStream_t)>& launch,
-                         bool indexed_start, bool wave_items, const std::function<hipError_t(double, double*, hipStream_t)>& resolve,
-                         bool clear_sharded) {
+                         const PersistentLaunch& pl) {
     const int k = s->dev.sets[0].d_queue.get() == a.queue ? 0 : 1;
     rpt_scene::LaunchSet& mine = s->dev.sets[k];
     rpt_scene::LaunchSet& other = s->dev.sets[k ^ 1];
@@ -2632,15 +2430,15 @@ extern "C++" int rpti::run_persistent(rpt_scene* s, const rpt_render_params* prm
     HIP_TRY(hipMemsetAsync(a.queue, 0, 8, st));
     if (a.counters) HIP_TRY(hipMemsetAsync(a.counters, 0, 640, st));
     uint32_t shard_count = prm->shard_count == 0 ? 1 : prm->shard_count;
-    if (shard_count > 1 && clear_sharded) HIP_TRY(hipMemsetAsync(d_out, 0, size_t(prm->width) * prm->height * 24, st));
+    if (shard_count > 1 && pl.clear_sharded) HIP_TRY(hipMemsetAsync(d_out, 0, size_t(prm->width) * prm->height * 24, st));
     if (a.n_items) {
-        uint64_t want = wave_items ? (uint64_t(a.n_items) + 3) / 4 : (uint64_t(a.n_items) + 255) / 256;
-        int n_blocks = int(std::min<uint64_t>(uint64_t(s->n_cus) * std::max(blocks_per_cu, 1), want));
+        uint64_t want = pl.wave_items ? (uint64_t(a.n_items) + 3) / 4 : (uint64_t(a.n_items) + 255) / 256;
+        int n_blocks = int(std::min<uint64_t>(uint64_t(s->n_cus) * std::max(pl.blocks_per_cu, 1), want));
         if (s->opt.max_blocks > 0) n_blocks = int(std::min<int64_t>(n_blocks, s->opt.max_blocks));   // (scratch per wave is sized for the uncapped grid)
         s->last_blocks = n_blocks;
         // indexed_start: every wave of the grid takes the batch with its own index first (render_kernel's work
         // pull), so the counter starts behind those batches
-        if (indexed_start) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)a.queue, int(uint32_t(n_blocks) * 4u * 64u), 1, st));
+        if (pl.indexed_start) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)a.queue, int(uint32_t(n_blocks) * 4u * 64u), 1, st));
         const rpti::Event* ev = nullptr;
         if (s->opt.timing) {
             const size_t slot = s->ev_count % rpt_scene::kTimedLaunches;
@@ -2653,9 +2451,9 @@ extern "C++" int rpti::run_persistent(rpt_scene* s, const rpt_render_params* prm
             HIP_TRY(hipEventRecord(ev[0].get(), st));
         }
         HIP_TRY(hipEventRecord(mine.launched.get(), st));
-        HIP_TRY(launch(a, n_blocks, st));
+        HIP_TRY(pl.launch(a, n_blocks, st));
         if (ev) HIP_TRY(hipEventRecord(ev[1].get(), st));
-        if (resolve) HIP_TRY(resolve(std::pow(2.0, prm->exposure_value), d_out, st));
+        if (pl.resolve) HIP_TRY(pl.resolve(std::pow(2.0, prm->exposure_value), d_out, st));
         else HIP_TRY(launch_resolve(a, std::pow(2.0, prm->exposure_value), d_out, st));
         if (ev) {
             HIP_TRY(hipEventRecord(ev[2].get(), st));
@@ -3021,41 +2819,6 @@ static hipError_t launch_render_jit(rpt_scene* s, hipFunction_t fn, const Render
 }
 }  // extern "C++"
 
-static int run_render(rpt_scene* s, const rpt_render_params* prm, const RenderArgs& a_in, double* d_out, hipStream_t st) {
-    RenderArgs a = a_in;
-    int bpc = int(s->opt.blocks_per_cu);
-    if (bpc <= 0) {
-        HIP_TRY(render_occupancy(a.sc.has_medium != 0, bvh_mode(a.sc), &bpc, int(a.detach)));
-        if (bpc < 1) bpc = 1;
-    }
-    if (a.detach == 2) {   // the waves' rings and parked paths: per launch set, like the slab (two launches may be in flight)
-        rpt_scene::LaunchSet& ls = s->dev.sets[s->dev.sets[0].d_queue.get() == a.queue ? 0 : 1];
-        HIP_TRY(ls.d_stream.reserve(size_t(s->n_cus) * size_t(bpc) * stream_scratch_bytes_per_block()));
-        a.stream_scratch = ls.d_stream.get<uint32_t>();
-    }
-    // (grid, streams, events, max_blocks and the tile list are the AOT kernel's: only the function differs)
-    const hipFunction_t jit = a.n_items ? scan_jit_function(s, a) : nullptr;
-    return rpti::run_persistent(s, prm, a, d_out, st, bpc,
-                                [s, jit](const RenderArgs& ra, int nb, hipStream_t stream) {
-                                    return jit ? launch_render_jit(s, jit, ra, nb, stream) : launch_render(ra, nb, stream);
-                                }, true);
-}
-extern "C++" rpti::SceneDev rpti::scene_dev(rpt_scene* s) {
-    int first = -1;
-    for (size_t i = 0; i < s->lights.size(); i++)
-        if (s->lights[i].kind == L_OBJECT) { first = int(i); break; }
-    bool mono = false;
-    for (const auto& o : s->objects) mono = mono || holds_monomial(o.shape);
-    return SceneDev{s->committed, s->device, s->n_cus, s->view, first, bool(s->dev.arena64), mono};
-}
-extern "C++" void*& rpti::photon_slot(rpt_scene* s) { return s->photon; }
-extern "C++" int64_t rpti::option_photon_skip(rpt_scene* s) { return s->opt.photon_skip; }
-extern "C++" int64_t rpti::option_max_blocks(rpt_scene* s) { return s->opt.max_blocks; }
-extern "C++" int64_t rpti::option_f64_photon_slice(rpt_scene* s) { return s->opt.f64_photon_slice; }
-extern "C++" int64_t rpti::option_photon_block_lists(rpt_scene* s) { return s->opt.photon_block_lists; }
-extern "C++" int64_t rpti::option_photon_parts(rpt_scene* s) { return s->opt.photon_parts; }
-extern "C++" int64_t rpti::option_photon_split(rpt_scene* s) { return s->opt.photon_split; }
-extern "C++" int64_t rpti::option_photon_coop_gather(rpt_scene* s) { return s->opt.photon_coop_gather; }
 extern "C++" double* rpti::scratch_out(rpt_scene* s, size_t bytes) {
     return s->dev.d_out.reserve(bytes) == hipSuccess ? s->dev.d_out.get<double>() : nullptr;
 }
@@ -3069,43 +2832,18 @@ extern "C++" int rpti::fetch_counters(rpt_scene* s, const RenderArgs& a) {
     }
     return RPT_OK;
 }
-
-int rpt_render_sample_device(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations,
-                             uint64_t seed, uint32_t sample_offset, void* d_out_rgb, void* hip_stream) {
-    if (!d_out_rgb) return fail(RPT_ERR_INVALID, "null output");
-    if (s && s->dev.arena64) return run_render64(s, cam, prm, iterations, seed, sample_offset, static_cast<double*>(d_out_rgb), static_cast<hipStream_t>(hip_stream));
-    RenderArgs a{};
-    int rc = rpti::prepare_render(s, static_cast<hipStream_t>(hip_stream), cam, prm, iterations, seed, sample_offset, a);
-    if (rc) return rc;
-    rc = run_render(s, prm, a, static_cast<double*>(d_out_rgb), static_cast<hipStream_t>(hip_stream));
-    if (rc) return rc;
-    if (a.counters) {
-        HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(hip_stream)));
-        return rpti::fetch_counters(s, a);
-    }
+// The reference-epsilon kernels' counters, after the stream has been synchronised.
+static int fetch_counters64(rpt_scene* s, const RenderArgs& a) {
+    std::memset(s->last_counters, 0, sizeof(s->last_counters));
+    HIP_TRY(hipMemcpy(s->last_counters64, a.counters, sizeof(s->last_counters64), hipMemcpyDeviceToHost));
+    s->last_counters[0] = s->last_counters64[6];   // rpt_get_counters: samples, rays, vertices
+    s->last_counters[1] = s->last_counters64[0];
+    s->last_counters[2] = s->last_counters64[7];
+    s->last_counters[3] = s->last_counters64[10];   // wave-level loop trips
+    for (int i = 0; i < 48; i++) s->last_counters[8 + i] = s->last_counters64[16 + i];   // rpt_debug_section_counters
     return RPT_OK;
 }
 
-int rpt_render_sample(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations,
-                      uint64_t seed, uint32_t sample_offset, double* out_rgb) {
-    if (!out_rgb) return fail(RPT_ERR_INVALID, "null output");
-    RenderArgs a{};
-    int rc = rpti::prepare_render(s, nullptr, cam, prm, iterations, seed, sample_offset, a);
-    if (rc) return rc;
-    size_t bytes = size_t(prm->width) * prm->height * 24;
-    double* d_out = rpti::scratch_out(s, bytes);
-    if (!d_out) return fail(RPT_ERR_DEVICE, "out of device memory");
-    if (s->dev.arena64) {
-        rc = run_render64(s, cam, prm, iterations, seed, sample_offset, d_out, nullptr);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost));
-        return RPT_OK;
-    }
-    rc = run_render(s, prm, a, d_out, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost));
-    return rpti::fetch_counters(s, a);
-}
 // ---- rpt_render_sample_tiles*: the kernels of a full render on a caller's tile list.
 // The list replaces the scene's in the launch arguments only: the scene's cached d_tiles keeps the full frame's list, which a launch
 // on the other launch set may still be reading.  The slab prepare_render reserved is the full frame's: no smaller than the list's.
@@ -3117,6 +2855,70 @@ static int use_tile_list(RenderArgs& a, const uint32_t* d_tiles, uint32_t n_tile
     const uint64_t n_items = uint64_t(a.n_owned) * a.n_chunks;
     if (n_items >= (1ull << 32) - (1ull << 24)) return fail(RPT_ERR_INVALID, "too many work items; raise chunk_spp");
     a.n_items = uint32_t(n_items);
+    return RPT_OK;
+}
+
+// Renderer::sample, one frame: a persistent grid over (pixel, chunk) items, one launch set per stream, the slab resolved into d_out.
+// The mode the scene was committed in is asked here and nowhere else: the reference-epsilon mode runs the same launch scheme with
+// an fp64 slab and its own kernels, occupancy and counters.  d_out null: the scene's cached frame (the host entry point), reserved
+// where it always was, after prepare_render.
+static int render_frame(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
+                        uint32_t sample_offset, double* d_out, hipStream_t st, const uint32_t* d_tiles = nullptr, uint32_t n_tiles = 0) {
+    const bool f64 = s && s->dev.arena64;
+    RenderArgs a{};   // (tiles, sharding, chunking, launch sets and argument checks are the same in both modes)
+    int rc = rpti::prepare_render(s, st, cam, prm, iterations, seed, sample_offset, a, 0, 0, f64 ? 32 : 16);
+    if (rc) return rc;
+    if (!d_out && !(d_out = rpti::scratch_out(s, size_t(prm->width) * prm->height * 24))) return fail(RPT_ERR_DEVICE, "out of device memory");
+    if (d_tiles)   // rpt_render_sample_tiles*: the caller's list in place of the scene's
+        if ((rc = use_tile_list(a, d_tiles, n_tiles))) return rc;
+    rpt64::Args q{};
+    if (f64) {
+        rpti::fill_args64(s, cam, prm, &a, q);
+        q.counters = a.counters;
+    }
+    rpti::PersistentLaunch pl;
+    pl.indexed_start = true;
+    pl.blocks_per_cu = int(s->opt.blocks_per_cu);
+    if (pl.blocks_per_cu <= 0) {
+        int bpc = 0;
+        if (f64) HIP_TRY(render_f64_occupancy(q.sc.has_medium != 0, &bpc));
+        else HIP_TRY(render_occupancy(a.sc.has_medium != 0, bvh_mode(a.sc), &bpc, int(a.detach)));
+        pl.blocks_per_cu = std::max(bpc, 1);
+    }
+    if (f64) {
+        pl.launch = [&q](const RenderArgs&, int nb, hipStream_t stream) { return launch_render_f64(q, nb, stream); };
+        pl.resolve = [&q](double scale, double* out, hipStream_t stream) { return launch_resolve_f64(q, scale, out, stream); };
+    } else {
+        if (a.detach == 2) {   // the waves' rings and parked paths: per launch set, like the slab (two launches may be in flight)
+            rpt_scene::LaunchSet& ls = s->dev.sets[s->dev.sets[0].d_queue.get() == a.queue ? 0 : 1];
+            HIP_TRY(ls.d_stream.reserve(size_t(s->n_cus) * size_t(pl.blocks_per_cu) * stream_scratch_bytes_per_block()));
+            a.stream_scratch = ls.d_stream.get<uint32_t>();
+        }
+        // (grid, streams, events, max_blocks and the tile list are the AOT kernel's: only the function differs)
+        const hipFunction_t jit = a.n_items ? scan_jit_function(s, a) : nullptr;
+        pl.launch = [s, jit](const RenderArgs& ra, int nb, hipStream_t stream) {
+            return jit ? launch_render_jit(s, jit, ra, nb, stream) : launch_render(ra, nb, stream);
+        };
+    }
+    if ((rc = rpti::run_persistent(s, prm, a, d_out, st, pl))) return rc;
+    if (!a.counters) return RPT_OK;
+    HIP_TRY(hipStreamSynchronize(st));
+    return f64 ? fetch_counters64(s, a) : rpti::fetch_counters(s, a);
+}
+
+int rpt_render_sample_device(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations,
+                             uint64_t seed, uint32_t sample_offset, void* d_out_rgb, void* hip_stream) {
+    if (!d_out_rgb) return fail(RPT_ERR_INVALID, "null output");
+    return render_frame(s, cam, prm, iterations, seed, sample_offset, static_cast<double*>(d_out_rgb), static_cast<hipStream_t>(hip_stream));
+}
+
+int rpt_render_sample(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations,
+                      uint64_t seed, uint32_t sample_offset, double* out_rgb) {
+    if (!out_rgb) return fail(RPT_ERR_INVALID, "null output");
+    if (int rc = render_frame(s, cam, prm, iterations, seed, sample_offset, nullptr, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(out_rgb, s->dev.d_out.get(), size_t(prm->width) * prm->height * 24, hipMemcpyDeviceToHost));
+    // as ever: an fp32 render through this entry without counters leaves none behind (rpt_get_counters, rpt_scan_cull_counters: zeros)
+    if (!s->opt.counters && !s->dev.arena64) return rpti::fetch_counters(s, RenderArgs{});
     return RPT_OK;
 }
 // What both entry points refuse before any device call.
@@ -3132,27 +2934,13 @@ static int check_sample_tiles(const rpt_scene* s, const rpt_camera* cam, const r
     if (n_tiles > total) return fail(RPT_ERR_INVALID, "more tiles listed than the frame has");
     return RPT_OK;
 }
-static int run_sample_tiles(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
-                            uint32_t sample_offset, const uint32_t* d_tiles, uint32_t n_tiles, double* d_out, hipStream_t st) {
-    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called before rendering");
-    if (n_tiles == 0) return RPT_OK;
-    if (s->dev.arena64) return run_render64(s, cam, prm, iterations, seed, sample_offset, d_out, st, d_tiles, n_tiles);
-    RenderArgs a{};
-    int rc = rpti::prepare_render(s, st, cam, prm, iterations, seed, sample_offset, a);
-    if (rc) return rc;
-    if ((rc = use_tile_list(a, d_tiles, n_tiles))) return rc;
-    if ((rc = run_render(s, prm, a, d_out, st))) return rc;
-    if (a.counters) {
-        HIP_TRY(hipStreamSynchronize(st));
-        return rpti::fetch_counters(s, a);
-    }
-    return RPT_OK;
-}
 int rpt_render_sample_tiles_device(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
                                    uint32_t sample_offset, const void* d_tiles, uint32_t n_tiles, void* d_out_rgb, void* hip_stream) {
     if (int rc = check_sample_tiles(s, cam, prm, iterations, d_tiles, n_tiles, d_out_rgb)) return rc;
-    return run_sample_tiles(s, cam, prm, iterations, seed, sample_offset, static_cast<const uint32_t*>(d_tiles), n_tiles,
-                            static_cast<double*>(d_out_rgb), static_cast<hipStream_t>(hip_stream));
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called before rendering");
+    if (n_tiles == 0) return RPT_OK;
+    return render_frame(s, cam, prm, iterations, seed, sample_offset, static_cast<double*>(d_out_rgb), static_cast<hipStream_t>(hip_stream),
+                        static_cast<const uint32_t*>(d_tiles), n_tiles);
 }
 int rpt_render_sample_tiles(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, uint32_t iterations, uint64_t seed,
                             uint32_t sample_offset, const uint32_t* tiles, uint32_t n_tiles, double* out_rgb) {
@@ -3176,7 +2964,7 @@ int rpt_render_sample_tiles(rpt_scene* s, const rpt_camera* cam, const rpt_rende
     HIP_TRY(d_list.reserve(size_t(n_tiles) * 4));
     HIP_TRY(hipMemcpy(d_list.get(), tiles, size_t(n_tiles) * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_out, out_rgb, bytes, hipMemcpyHostToDevice));   // the caller's values outside the listed tiles survive
-    int rc = run_sample_tiles(s, cam, prm, iterations, seed, sample_offset, d_list.get<uint32_t>(), n_tiles, d_out, nullptr);
+    int rc = render_frame(s, cam, prm, iterations, seed, sample_offset, d_out, nullptr, d_list.get<uint32_t>(), n_tiles);
     const hipError_t e = hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost);   // (also on failure: the list is freed after the stream is idle)
     if (rc) return rc;
     HIP_TRY(e);
@@ -3275,19 +3063,6 @@ int rpt_debug_epsilon_counters(rpt_scene* s, uint64_t out[12]) {
 }
 
 // ---------------------------------------------------------------------------- Buffer on the device
-struct rpt_buffer {
-    int device = 0;
-    uint32_t width = 0, height = 0, radius = 0, n_batches = 0;
-    rpti::DevMem d_sum, d_sumsq, d_stage;  // stage: one batch / per-pixel variances
-    rpti::DevMem d_img;
-    // Adaptive sampling by tile (adaptive.hip): allocated at the first tile batch / the first refinement.
-    rpti::DevMem d_extra;                  // extra batches per 32 x 32 tile (u32); a pixel holds n_batches + extra[its tile]
-    rpti::DevMem d_tile_err, d_active;     // rpt_buffer_refine_tiles' errors when the caller keeps none, its count; rpt_render_adaptive's list
-    uint32_t tiles_x() const { return (width + 31) / 32; }
-    uint32_t tiles_y() const { return (height + 31) / 32; }
-    uint32_t n_tiles() const { return tiles_x() * tiles_y(); }
-    TileBufferView view() const { return TileBufferView{width, height, tiles_x(), tiles_y(), n_batches, 0, d_extra.get<uint32_t>()}; }
-};
 rpt_buffer* rpt_buffer_create(int device, uint32_t width, uint32_t height, uint32_t filter_radius) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { fail(RPT_ERR_INVALID, "device index out of range"); return nullptr; }
@@ -3370,23 +3145,8 @@ int rpt_render_into_buffer(rpt_scene* s, const rpt_camera* cam, const rpt_render
     if (!s || !prm) return fail(RPT_ERR_INVALID, "null argument");
     if (prm->width != b->width || prm->height != b->height) return fail(RPT_ERR_INVALID, "Invalid sample dimension");  // buffer.rs:33-36
     if (s->committed && s->device != b->device) return fail(RPT_ERR_INVALID, "buffer and scene live on different devices");
-    if (s->dev.arena64) {
-        int rc64 = run_render64(s, cam, prm, iterations, seed, sample_offset, b->d_stage.get<double>(), nullptr);
-        return rc64 ? rc64 : rpt_buffer_add_samples_device(b, b->d_stage.get(), nullptr);
-    }
-    RenderArgs a{};
-    int rc = rpti::prepare_render(s, nullptr, cam, prm, iterations, seed, sample_offset, a);
-    if (rc) return rc;
-    if (prm->shard_count > 1) HIP_TRY(hipMemsetAsync(b->d_stage.get(), 0, size_t(b->width) * b->height * 24, nullptr));
-    rc = run_render(s, prm, a, b->d_stage.get<double>(), nullptr);
-    if (rc) return rc;
-    rc = rpt_buffer_add_samples_device(b, b->d_stage.get(), nullptr);
-    if (rc) return rc;
-    if (a.counters) {
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        return rpti::fetch_counters(s, a);
-    }
-    return RPT_OK;
+    if (int rc = render_frame(s, cam, prm, iterations, seed, sample_offset, b->d_stage.get<double>(), nullptr)) return rc;
+    return rpt_buffer_add_samples_device(b, b->d_stage.get(), nullptr);
 }
 
 // ---------------------------------------------------------------------------- adaptive sampling by tile (adaptive.hip)
@@ -3475,7 +3235,7 @@ int rpt_render_adaptive(rpt_scene* s, const rpt_camera* cam, const rpt_render_pa
         uint32_t n_active = 0;
         if (int rc = rpt_buffer_refine_tiles(b, p, d_active, &n_active, nullptr, nullptr)) return rc;
         if (n_active == 0) break;
-        if (int rc = run_sample_tiles(s, cam, prm, p->spp_per_batch, seed, k * p->spp_per_batch, d_active, n_active, b->d_stage.get<double>(), nullptr))
+        if (int rc = rpt_render_sample_tiles_device(s, cam, prm, p->spp_per_batch, seed, k * p->spp_per_batch, d_active, n_active, b->d_stage.get(), nullptr))
             return rc;
         if (int rc = rpt_buffer_add_samples_tiles_device(b, b->d_stage.get(), d_active, n_active, nullptr)) return rc;
         rounds++;
@@ -3856,7 +3616,6 @@ int rpt_debug_camera_rays(const rpt_camera* cam, const rpt_render_params* prm, u
 }
 // The per-call hooks on a committed scene.  What the caller got wrong (null arrays, the light's kind, a scene without a medium) is
 // reported before the scene's state, so those answers need no device.
-extern "C++" int rpti::light_kind(rpt_scene* s, uint32_t light) { return light < s->lights.size() ? int(s->lights[light].kind) : -1; }
 int rpt_debug_light_sample(rpt_scene* s, uint32_t light, uint64_t n, const float* positions, uint64_t seed, float* v, float* nrm,
                            float* pdf, float* intensity, float* wi, float* dist, uint32_t* next_word) {
     if (!s || !positions || !v || !nrm || !pdf || !intensity || !wi || !dist || !next_word) return fail(RPT_ERR_INVALID, "null argument");
