@@ -522,6 +522,81 @@ inline RgbImage Buffer::denoised_image(Denoiser& denoiser, const rpt_denoise_par
     if (rpt_buffer_denoised_image(h_, denoiser.raw(), &params, d_albedo, d_normal, d_depth, img.data.data()) != RPT_OK) throw Error(rpt_last_error());
     return img;
 }
+// Temporal accumulation with reprojection (rpt_temporal_*, an addition): owns the history of a frame sequence of one size on one
+// device.  For a camera that moves over a scene whose objects keep their places and indices.
+class Temporal {
+  public:
+    // history of 16 frames, id match on, depth_tol 0.1 (relative, on squared distances), normal_tol 0.5
+    static rpt_temporal_params default_params() { return {16, RPT_TEMPORAL_MATCH_ID, 0.1, 0.5}; }
+    // eye, direction, right, up, d: what the accumulation takes of a camera (a host function)
+    static std::array<double, 13> camera_record(const Camera& camera) {
+        std::array<double, 13> r{};
+        const rpt_camera c = camera.desc();
+        if (rpt_temporal_camera_record(&c, r.data()) != RPT_OK) throw Error(rpt_last_error());
+        return r;
+    }
+    Temporal(uint32_t w, uint32_t h, int device = 0) : width(w), height(h) {
+        h_ = rpt_temporal_create(device, w, h);
+        if (!h_) throw Error(rpt_last_error());
+    }
+    Temporal(const Temporal&) = delete;
+    Temporal& operator=(const Temporal&) = delete;
+    Temporal(Temporal&& o) noexcept : width(o.width), height(o.height), h_(o.h_) { o.h_ = nullptr; }
+    ~Temporal() {
+        if (h_) rpt_temporal_destroy(h_);
+    }
+    // host arrays: rgb, normal, depth of width*height*3 doubles, var of width*height; an empty vector is a null plane (normal is
+    // empty iff params.normal_tol == 0) -> the accumulated frame; its variance and the history lengths where asked for
+    std::vector<double> accumulate(const rpt_temporal_params& params, const Camera& camera, const std::vector<double>& rgb,
+                                   const std::vector<double>& var, const std::vector<double>& normal, const std::vector<double>& depth,
+                                   std::vector<double>* out_var = nullptr, std::vector<double>* out_len = nullptr) {
+        const size_t n = size_t(width) * height;
+        auto ptr = [&](const std::vector<double>& v, size_t want) -> const double* {
+            if (v.empty()) return nullptr;
+            if (v.size() != want) throw Error("Invalid plane dimension");
+            return v.data();
+        };
+        std::vector<double> out(n * 3);
+        if (out_var) out_var->assign(n, 0.0);
+        if (out_len) out_len->assign(n, 0.0);
+        const rpt_camera c = camera.desc();
+        if (rpt_temporal_accumulate(h_, &params, &c, ptr(rgb, n * 3), ptr(var, n), ptr(normal, n * 3), ptr(depth, n * 3), out.data(),
+                                    out_var ? out_var->data() : nullptr, out_len ? out_len->data() : nullptr) != RPT_OK)
+            throw Error(rpt_last_error());
+        return out;
+    }
+    void accumulate_device(const rpt_temporal_params& params, const Camera& camera, const void* d_rgb, const void* d_var, const void* d_normal,
+                           const void* d_depth, void* d_out, void* d_out_var = nullptr, void* d_out_len = nullptr, void* hip_stream = nullptr) {
+        const rpt_camera c = camera.desc();
+        if (rpt_temporal_accumulate_device(h_, &params, &c, d_rgb, d_var, d_normal, d_depth, d_out, d_out_var, d_out_len, hip_stream) != RPT_OK)
+            throw Error(rpt_last_error());
+    }
+    // rpt_temporal_frame_image: the buffer's mean and variance -> accumulate -> (with a denoiser: the a-trous filter with the
+    // accumulated variance) -> color_bytes; the feature planes are device pointers.
+    RgbImage frame_image(const rpt_temporal_params& params, const Camera& camera, const Buffer& buffer, const void* d_albedo,
+                         const void* d_normal, const void* d_depth, Denoiser* denoiser = nullptr,
+                         const rpt_denoise_params& denoise = Denoiser::default_params()) {
+        RgbImage img{width, height, std::vector<uint8_t>(size_t(width) * height * 3)};
+        const rpt_camera c = camera.desc();
+        if (rpt_temporal_frame_image(h_, &params, &c, buffer.raw(), denoiser ? denoiser->raw() : nullptr, &denoise, d_albedo, d_normal, d_depth,
+                                     img.data.data()) != RPT_OK)
+            throw Error(rpt_last_error());
+        return img;
+    }
+    void reset() {  // forget the history
+        if (rpt_temporal_reset(h_) != RPT_OK) throw Error(rpt_last_error());
+    }
+    uint32_t frames() const {  // since the creation or the last reset
+        uint32_t n = 0;
+        if (rpt_temporal_frames(h_, &n) != RPT_OK) throw Error(rpt_last_error());
+        return n;
+    }
+    rpt_temporal* raw() const { return h_; }
+    uint32_t width, height;
+
+  private:
+    rpt_temporal* h_ = nullptr;
+};
 
 // ---- renderer.rs
 class Renderer {

@@ -314,8 +314,8 @@ int rpt_render_into_buffer(rpt_scene*, const rpt_camera*, const rpt_render_param
 
 /* ---- denoiser on the device (an addition: the reference's only spatial filter is Filter::Box) ----
  * An edge-avoiding a-trous wavelet filter of the SVGF family, spatial part only, guided by the first-hit feature planes
- * (rpt_render_features*) and by the per-pixel variance of a frame's mean (rpt_buffer_mean_device).  No temporal accumulation, no
- * reprojection.  Sharded frames are not filtered shard by shard: a shard's planes and frame are assembled first
+ * (rpt_render_features*) and by the per-pixel variance of a frame's mean (rpt_buffer_mean_device).  Temporal accumulation and
+ * reprojection are rpt_temporal_* below.  Sharded frames are not filtered shard by shard: a shard's planes and frame are assembled first
  * (rpt_gather_frame_device carries them) and rank 0 filters.
  *
  * The filter is defined as an order of fp64 operations, each rounded on its own (no fused multiply-add, IEEE division, no atomics),
@@ -371,6 +371,85 @@ int rpt_buffer_mean_device(rpt_buffer*, void* d_rgb, void* d_var, void* hip_stre
  * are DEVICE pointers (each or NULL, as the parameters allow).  Buffer and denoiser of different devices or sizes: RPT_ERR_INVALID. */
 int rpt_buffer_denoised_image(rpt_buffer*, rpt_denoiser*, const rpt_denoise_params*, const void* d_albedo, const void* d_normal,
                               const void* d_depth, uint8_t* out_rgb8);
+
+/* ---- temporal accumulation with reprojection (an addition with no counterpart in the reference, whose frame sequences --
+ * examples/simple_video.rs, marbles.rs -- render every frame from nothing) ----
+ * For a camera that moves over a scene whose objects keep their places and indices: a frame's pixel is blended with what the previous
+ * frames saw at the same surface point.  The point comes from the depth plane and the camera, its place in the previous frame from the
+ * camera stored with the history; id, depth and normal tests reject history of another surface, so where objects move the
+ * sequence degrades to no reuse, not to ghosting.  No motion vectors, no demodulation (materials are one colour per object and ids
+ * are matched).  With a thin lens (aperture > 0) depths are measured from lens samples but reprojected from `eye`: an approximation
+ * that the depth test absorbs.
+ *
+ * Defined, like the denoiser, as an order of fp64 operations, each rounded on its own: no contraction, IEEE division, sqrt the
+ * correctly rounded square root, no atomics; tan is evaluated on the host only.  Arrays are row-major, y = 0 at the top; rgb, var,
+ * normal and depth in the formats rpt_buffer_mean_device and rpt_render_features* write.
+ *
+ * The camera record: rpt_temporal_camera_record (pure host function, no device is touched) writes eye[3], direction[3], right[3],
+ * up[3], d with right = normalize(cross(direction, up)) and d = 1 / tan(fov / 2) (src/camera.rs:67-68); RPT_ERR_INVALID for a field
+ * that is not finite, fov outside (0, pi) or a zero cross product.  The accumulation takes records, never a camera.
+ *
+ * Per pixel p = (x, y) of a W x H frame; dim = double(max(W, H)); R the call's camera record, R' the one stored with the history;
+ * v_in = var ? var[p] : 0.0.
+ *   1. Pixel centre (src/renderer.rs:174-176 without jitter):
+ *        xn = (double(2x+1) - double(W)) / dim;   yn = (double(2(H-y)-1) - double(H)) / dim
+ *        v_k = (d direction_k + xn right_k) + yn up_k;   l = sqrt((v0 v0 + v1 v1) + v2 v2)
+ *   2. cov = depth[p][1]; hit = cov > 0.0 (false for NaN); zc = depth[p][0] / cov; id = depth[p][2]; n = normal[p] (0 when NULL).
+ *   3. History is looked up only if the accumulator holds a frame and hit:
+ *        s = zc / l;  P_k = eye_k + s v_k;  q_k = P_k - eye'_k;  zq = (q0 dir'0 + q1 dir'1) + q2 dir'2;  require zq > 0.0
+ *        u = (((q0 r'0 + q1 r'1) + q2 r'2) d') / zq, and w likewise with up'
+ *        fx = ((u dim + double(W)) - 1.0) 0.5;   fy = ((double(H) - 1.0) - w dim) 0.5
+ *        require fx > -1.0 && fx < double(W), and the same for fy against H (NaN fails)
+ *        ix = floor(fx), ax = fx - ix; iy, ay likewise;  qq = (q0 q0 + q1 q1) + q2 q2
+ *   4. Taps j = 0, 1 (outer), i = 0, 1 (inner) at (ix+i, iy+j); taps outside the image are skipped.
+ *        b = (i ? ax : 1.0 - ax) (j ? ay : 1.0 - ay).  The tap's history record h is skipped unless h.len > 0.0; with MATCH_ID unless
+ *        h.id == id; with depth_tol > 0, r = h.z h.z, unless fabs(r - qq) <= depth_tol qq; with normal_tol > 0, e_k = h.n_k - n_k,
+ *        unless ((e0 e0 + e1 e1) + e2 e2) <= normal_tol normal_tol.  NaN fails every test.
+ *        B += b;  C_k += b h.c_k;  V += (b b) h.v;  L += b h.len, all from +0.0.
+ *   5. If B > 0.0:  hc_k = C_k / B;  hv = V / (B B);  hl = L / B;  len = min(hl + 1.0, double(max_history));  a = 1.0 / len
+ *        out_k = hc_k + (rgb_k - hc_k) a;   om = 1.0 - a;   out_v = (om om) hv + (a a) v_in
+ *      (the variance of a blend of independent terms, in the units rpt_denoise_device expects).
+ *      Otherwise out = rgb, out_v = v_in, len = 1.0.
+ *   6. The new history record: c = out, v = out_v, n, z = zc, id, len.  If the pixel is not a hit, or any of out_k, out_v is not
+ *      finite (t - t != 0.0), len = 0.0 is stored (the len written to d_out_len is unchanged): a NaN or a firefly at inf never outlives
+ *      its frame, and a miss carries no history.
+ *
+ * max_history 1..4096 (1: no reuse); the tolerances finite and >= 0 (0: the test is off); depth_tol is relative, on SQUARED distances;
+ * normal_tol on the distance of the normal planes.  d_normal is NULL iff normal_tol == 0.  Defaults: 16, MATCH_ID, 0.1, 0.5.
+ * An accumulator owns the history of one frame size on one device: two arrays of 80-byte records (c[3], v, len, n[3], z, id) that swap
+ * per call -- a call reads its neighbours' old records while it writes new ones -- and the camera record of the last call.  Every
+ * argument check precedes every device call, the parameters' and the planes' before the handle's.  Outputs must not alias inputs or
+ * each other.  The calls of one accumulator are ordered, whatever their streams; accumulators share nothing with each other, with
+ * scenes or with denoisers. */
+#define RPT_TEMPORAL_MATCH_ID 1u
+typedef struct rpt_temporal_params {
+    uint32_t max_history;   /* 1..4096; 1 = no reuse */
+    uint32_t flags;         /* RPT_TEMPORAL_MATCH_ID */
+    double depth_tol;       /* on SQUARED distances, relative; 0 = test off */
+    double normal_tol;      /* on the distance of the normal planes; 0 = off */
+} rpt_temporal_params;
+int rpt_temporal_camera_record(const rpt_camera*, double out[13]);
+typedef struct rpt_temporal rpt_temporal;
+rpt_temporal* rpt_temporal_create(int device, uint32_t width, uint32_t height);
+void rpt_temporal_destroy(rpt_temporal*);
+int rpt_temporal_reset(rpt_temporal*);                 /* forget the history */
+int rpt_temporal_frames(rpt_temporal*, uint32_t* n);   /* frames since create / reset */
+/* DEVICE pointers on the accumulator's device, hip_stream a hipStream_t (NULL = default stream).  d_out_rgb: width*height*3 doubles;
+ * d_out_var, d_out_len: width*height doubles each, or NULL. */
+int rpt_temporal_accumulate_device(rpt_temporal*, const rpt_temporal_params*, const rpt_camera*, const void* d_rgb, const void* d_var,
+                                   const void* d_normal, const void* d_depth, void* d_out_rgb, void* d_out_var, void* d_out_len,
+                                   void* hip_stream);
+/* The same with host pointers, synchronous. */
+int rpt_temporal_accumulate(rpt_temporal*, const rpt_temporal_params*, const rpt_camera*, const double* rgb, const double* var,
+                            const double* normal, const double* depth, double* out_rgb, double* out_var, double* out_len);
+/* The sequence counterpart of rpt_buffer_denoised_image: mean and variance of the buffer -> accumulate -> (with a denoiser: the a-trous
+ * filter with the accumulated variance) -> color_bytes; synchronous, only width*height*3 bytes come back.  The planes are DEVICE
+ * pointers; d_depth always, d_normal where normal_tol > 0 or the filter needs it (the accumulation reads it only with normal_tol > 0),
+ * d_albedo as the filter needs it.  Without a denoiser the denoise parameters are ignored.  Buffer, denoiser and accumulator of different
+ * devices or sizes: RPT_ERR_INVALID; fewer than 2 batches: RPT_ERR_STATE. */
+int rpt_temporal_frame_image(rpt_temporal*, const rpt_temporal_params*, const rpt_camera*, rpt_buffer*, rpt_denoiser*,
+                             const rpt_denoise_params*, const void* d_albedo, const void* d_normal, const void* d_depth,
+                             uint8_t* out_rgb8);
 
 /* ---- adaptive sampling by tile (an addition; the reference's Buffer::add_sample(x, y, ..), src/buffer.rs:25-29, at the
  * granularity of the render kernels' 32 x 32 tiles) ----

@@ -75,6 +75,15 @@ class DenoiseParams(C.Structure):
     ]
 
 
+class TemporalParams(C.Structure):
+    _fields_ = [
+        ("max_history", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("depth_tol", C.c_double),
+        ("normal_tol", C.c_double),
+    ]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [
         ("spp_per_batch", C.c_uint32),
@@ -145,6 +154,16 @@ SYMBOLS = [
     ("rpt_denoise", C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P]),
     ("rpt_buffer_mean_device", C.c_int, [_P, _P, _P, _P]),
     ("rpt_buffer_denoised_image", C.c_int, [_P, _P, C.POINTER(DenoiseParams), _P, _P, _P, _P]),
+    ("rpt_temporal_camera_record", C.c_int, [C.POINTER(CameraDesc), _D3]),
+    ("rpt_temporal_create", _P, [C.c_int, C.c_uint32, C.c_uint32]),
+    ("rpt_temporal_destroy", None, [_P]),
+    ("rpt_temporal_reset", C.c_int, [_P]),
+    ("rpt_temporal_frames", C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ("rpt_temporal_accumulate_device", C.c_int,
+     [_P, C.POINTER(TemporalParams), C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("rpt_temporal_accumulate", C.c_int, [_P, C.POINTER(TemporalParams), C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P, _P]),
+    ("rpt_temporal_frame_image", C.c_int,
+     [_P, C.POINTER(TemporalParams), C.POINTER(CameraDesc), _P, _P, C.POINTER(DenoiseParams), _P, _P, _P, _P]),
     ("rpt_buffer_add_samples_tiles_device", C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     ("rpt_buffer_tile_batches", C.c_int, [_P, _P, C.c_uint64]),
     ("rpt_buffer_tile_errors_device", C.c_int, [_P, C.c_double, _P, _P]),

@@ -61,6 +61,7 @@ __all__ = [
     "vec3", "hex_color", "color_bytes", "Sphere", "Cube", "Plane", "Triangle", "Mesh", "KdTree", "Transformed",
     "MonomialSurface", "sphere", "cube", "plane", "polygon", "monomial_surface", "Material", "Object", "Light", "Medium", "Environment",
     "Scene", "Camera", "Filter", "Buffer", "DeviceBuffer", "Renderer", "RptError", "DenoiseParams", "Denoiser", "AdaptiveParams",
+    "TemporalParams", "TemporalAccumulator", "temporal_camera_record",
 ]
 
 
@@ -745,14 +746,12 @@ class DeviceBuffer:
         _sync(self.device)
         return d_ids.cpu().numpy().view(np.uint32)[:n.value].copy(), d_err.cpu().numpy().reshape(ty, tx).copy()
 
-    def denoised_image(self, denoiser, planes, params=None):
-        """rpt_buffer_denoised_image: mean -> a-trous filter -> color_bytes, no box filter -> (h, w, 3) uint8.  `planes`: a dict with
-        any of "albedo", "normal", "depth" (what `params` needs), each an (h, w, 3) array as Renderer.features_array returns it or
-        a device pointer (int) as Renderer.features_device filled it."""
-        params = params or DenoiseParams()
+    def _plane_pointers(self, planes, what):
+        """`planes`: a dict with any of "albedo", "normal", "depth", each an (h, w, 3) array as Renderer.features_array returns it or a
+        device pointer (int) as Renderer.features_device filled it -> (what keeps the uploads alive, the three pointers)."""
         unknown = set(planes) - {"albedo", "normal", "depth"}
         if unknown:
-            raise ValueError(f"denoised_image: unknown planes {sorted(unknown)}")
+            raise ValueError(f"{what}: unknown planes {sorted(unknown)}")
         keep, ptrs = [], []
         for k in ("albedo", "normal", "depth"):
             v = planes.get(k)
@@ -761,12 +760,35 @@ class DeviceBuffer:
                 continue
             a = np.ascontiguousarray(v, dtype=np.float64)
             if a.size != self.width * self.height * 3:
-                raise ValueError(f"denoised_image: plane {k} is not {self.height} x {self.width} x 3")
+                raise ValueError(f"{what}: plane {k} is not {self.height} x {self.width} x 3")
             keep.append(_device_copy(a, self.device))
             ptrs.append(C.c_void_p(keep[-1].data_ptr()))
         _sync(self.device)
+        return keep, ptrs
+
+    def denoised_image(self, denoiser, planes, params=None):
+        """rpt_buffer_denoised_image: mean -> a-trous filter -> color_bytes, no box filter -> (h, w, 3) uint8.  `planes`: a dict with
+        any of "albedo", "normal", "depth" (what `params` needs), each an (h, w, 3) array as Renderer.features_array returns it or
+        a device pointer (int) as Renderer.features_device filled it."""
+        params = params or DenoiseParams()
+        keep, ptrs = self._plane_pointers(planes, "denoised_image")
         out = np.empty((self.height, self.width, 3), dtype=np.uint8)
         _lib.check(_lib.load().rpt_buffer_denoised_image(self._h, denoiser._h, C.byref(params.desc()), *ptrs, _vp(out)))
+        return out
+
+    def temporal_image(self, accumulator, camera, planes, temporal=None, denoiser=None, denoise=None):
+        """rpt_temporal_frame_image: mean and variance -> the accumulation -> (with `denoiser`: the a-trous filter with the
+        accumulated variance, parameters `denoise`) -> color_bytes -> (h, w, 3) uint8.  `camera` is the camera the batches and the
+        planes were rendered with; `planes` as for denoised_image, "depth" always, "normal" where temporal.normal_tol > 0 or the
+        filter needs it."""
+        temporal = temporal or TemporalParams()
+        if denoiser is not None:
+            denoise = denoise or DenoiseParams()
+        keep, ptrs = self._plane_pointers(planes, "temporal_image")
+        out = np.empty((self.height, self.width, 3), dtype=np.uint8)
+        _lib.check(_lib.load().rpt_temporal_frame_image(
+            accumulator._h, C.byref(temporal.desc()), C.byref(camera_desc(camera, _lib.CameraDesc)), self._h,
+            denoiser._h if denoiser is not None else None, C.byref(denoise.desc()) if denoise is not None else None, *ptrs, _vp(out)))
         return out
 
     def close(self):
@@ -886,6 +908,102 @@ class Denoiser:
     def close(self):
         if getattr(self, "_h", None):
             _lib.load().rpt_denoiser_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ------------------------------------------------------------------ temporal accumulation (rpt_temporal_*, an addition)
+class TemporalParams:
+    """rpt_temporal_params.  max_history 1..4096 caps the history length (1: no reuse); a test is on iff its tolerance > 0:
+    depth_tol relative, on squared distances, normal_tol on the distance of the normal planes."""
+    MATCH_ID = 1
+
+    def __init__(self, max_history=16, match_id=True, depth_tol=0.1, normal_tol=0.5):
+        self.max_history, self.match_id = int(max_history), bool(match_id)
+        self.depth_tol, self.normal_tol = float(depth_tol), float(normal_tol)
+        if not 1 <= self.max_history <= 4096:
+            raise ValueError("TemporalParams: max_history must be 1..4096")
+        for t in (self.depth_tol, self.normal_tol):
+            if not t >= 0.0 or math.isinf(t):
+                raise ValueError("TemporalParams: a tolerance must be finite and >= 0")
+
+    @property
+    def flags(self):
+        return self.MATCH_ID if self.match_id else 0
+
+    def desc(self):
+        return _lib.TemporalParams(self.max_history, self.flags, self.depth_tol, self.normal_tol)
+
+
+def temporal_camera_record(camera):
+    """rpt_temporal_camera_record -> the 13 doubles eye, direction, right, up, d that the accumulation takes (a host function)."""
+    out = np.empty(13, dtype=np.float64)
+    _lib.check(_lib.load().rpt_temporal_camera_record(C.byref(camera_desc(camera, _lib.CameraDesc)), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+class TemporalAccumulator:
+    """rpt_temporal: the history of a frame sequence of one size on one device, and the accumulation of include/rpt_hip.h."""
+
+    def __init__(self, width, height, device=0):
+        self.width, self.height, self.device = int(width), int(height), int(device)
+        if self.width <= 0 or self.height <= 0:
+            raise ValueError("TemporalAccumulator: empty frame")
+        self._h = _lib.load().rpt_temporal_create(self.device, self.width, self.height)
+        if not self._h:
+            _lib.check(-1)
+
+    def accumulate(self, camera, rgb, var, normal, depth, params=None, return_variance=False, return_length=False):
+        """Host arrays: rgb, normal, depth of (h, w, 3), var of (h, w); var may be None, normal is None iff params.normal_tol == 0
+        -> the accumulated (h, w, 3) frame, then as asked its (h, w) variance and the (h, w) history lengths."""
+        params = params or TemporalParams()
+        n = self.width * self.height
+        arrays = []
+        for name, a, size in (("rgb", rgb, 3 * n), ("var", var, n), ("normal", normal, 3 * n), ("depth", depth, 3 * n)):
+            if a is None:
+                if name in ("rgb", "depth"):
+                    raise ValueError(f"accumulate: {name} is required")
+                arrays.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != size:
+                raise ValueError(f"accumulate: {name} has {a.size} values, the frame needs {size}")
+            arrays.append(a)
+        out = np.empty((self.height, self.width, 3), dtype=np.float64)
+        out_var = np.empty((self.height, self.width), dtype=np.float64) if return_variance else None
+        out_len = np.empty((self.height, self.width), dtype=np.float64) if return_length else None
+        _lib.check(_lib.load().rpt_temporal_accumulate(
+            self._h, C.byref(params.desc()), C.byref(camera_desc(camera, _lib.CameraDesc)), *[_vp(a) if a is not None else None for a in arrays],
+            _vp(out), _vp(out_var) if return_variance else None, _vp(out_len) if return_length else None))
+        res = (out,) + ((out_var,) if return_variance else ()) + ((out_len,) if return_length else ())
+        return res if len(res) > 1 else out
+
+    def accumulate_device(self, camera, d_rgb, d_var, d_normal, d_depth, d_out, d_out_var=0, d_out_len=0, params=None, stream_ptr=0):
+        """Asynchronous variant: device pointers (0 / None: a null plane), enqueued on stream_ptr."""
+        params = params or TemporalParams()
+        _lib.check(_lib.load().rpt_temporal_accumulate_device(
+            self._h, C.byref(params.desc()), C.byref(camera_desc(camera, _lib.CameraDesc)),
+            *[C.c_void_p(p or None) for p in (d_rgb, d_var, d_normal, d_depth, d_out, d_out_var, d_out_len)], C.c_void_p(stream_ptr)))
+
+    def reset(self):
+        """Forget the history: the next frame passes through."""
+        _lib.check(_lib.load().rpt_temporal_reset(self._h))
+
+    @property
+    def frames(self):
+        """Frames accumulated since the creation or the last reset."""
+        n = C.c_uint32()
+        _lib.check(_lib.load().rpt_temporal_frames(self._h, C.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().rpt_temporal_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -1147,6 +1265,56 @@ class Renderer:
         denoiser.close()
         buffer.close()
         return img
+
+    def render_sequence(self, cameras, batches=4, temporal=None, denoise=None):
+        """An addition: a generator of one (h, w, 3) uint8 frame per camera of `cameras`, for a camera that moves over this scene.
+        Frame f renders num_samples in `batches` batches (as render_denoised) at the sample offsets f * num_samples .. (fresh random
+        streams per frame) into a DeviceBuffer, the feature planes of the same camera samples, then DeviceBuffer.temporal_image
+        with one TemporalAccumulator for the sequence: mean and variance, accumulation over the previous frames (`temporal`: a
+        TemporalParams or None for the defaults), with denoise=DenoiseParams(..) the a-trous filter, color_bytes.  Everything but
+        the bytes stays on the device; filter() is not applied; self.camera is left as it was.  Not for sharded renders."""
+        batches = int(batches)
+        if batches < 2:
+            raise ValueError("render_sequence: the variance of the mean needs at least 2 batches")
+        if self.num_samples_ < batches:
+            raise ValueError("render_sequence: num_samples must be at least the number of batches")
+        if self.shard_count_ != 1:
+            raise ValueError("render_sequence: a sharded frame is assembled first; rank 0 accumulates it")
+        if temporal is not None and not isinstance(temporal, TemporalParams):
+            raise ValueError("render_sequence: temporal must be a TemporalParams or None")
+        if denoise is not None and not isinstance(denoise, DenoiseParams):
+            raise ValueError("render_sequence: denoise must be a DenoiseParams or None")
+        cameras = list(cameras)
+        if len(cameras) * self.num_samples_ >= 1 << 32:
+            raise ValueError("render_sequence: frames * num_samples must fit 32 bits")
+        return self._render_sequence(cameras, batches, temporal or TemporalParams(), denoise)
+
+    def _render_sequence(self, cameras, batches, temporal, denoise):
+        accumulator = TemporalAccumulator(self.width_, self.height_, self.device_)
+        denoiser = Denoiser(self.width_, self.height_, self.device_) if denoise is not None else None
+        n = self.width_ * self.height_ * 3
+        planes = _device_zeros(3 * n, self.device_)
+        _sync(self.device_)
+        ptrs = [planes.data_ptr() + 8 * n * k for k in range(3)]
+        base, extra = divmod(self.num_samples_, batches)
+        own = self.camera
+        try:
+            for f, cam in enumerate(cameras):
+                self.camera = cam
+                buffer = DeviceBuffer(self.width_, self.height_, None, self.device_)
+                self.features_device(self.num_samples_, *ptrs, sample_offset=f * self.num_samples_)
+                self._sample_offset = f * self.num_samples_
+                for k in range(batches):
+                    self.sample(base + (1 if k < extra else 0), buffer)
+                img = buffer.temporal_image(accumulator, cam, dict(zip(("albedo", "normal", "depth"), ptrs)), temporal, denoiser, denoise)
+                buffer.close()
+                self.camera = own
+                yield img
+        finally:
+            self.camera = own
+            accumulator.close()
+            if denoiser is not None:
+                denoiser.close()
 
     def iterative_render(self, callback_interval, callback):
         """renderer.rs:144-156."""

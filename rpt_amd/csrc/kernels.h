@@ -126,6 +126,26 @@ static constexpr uint32_t kDenoiseMaxStagedStep = 2;   // the largest step whose
 __attribute__((weak)) hipError_t launch_buffer_mean(uint32_t n_pixels, uint32_t n_batches, const double* d_sum, const double* d_sumsq,
                                                     double* d_rgb, double* d_var /* or null */, hipStream_t st);
 __attribute__((weak)) hipError_t launch_color_bytes(uint64_t n_values, const double* d_rgb, uint8_t* d_out, hipStream_t st);
+// rpt_temporal_* (temporal.hip): the accumulation of include/rpt_hip.h, one kernel, one lane per pixel.  The history is one record of
+// kTemporalRecDoubles doubles per pixel (c rgb, v, len, n xyz, z, id); a call reads the old records of its four taps and writes the new
+// ones elsewhere.  The two camera records are rpt_temporal_camera_record's 13 doubles.
+static constexpr uint32_t kTemporalRecDoubles = 10;
+struct TemporalCam {
+    double eye[3], dir[3], right[3], up[3], d;
+};
+struct TemporalArgs {
+    uint32_t width, height, max_history, flags;          // RPT_TEMPORAL_MATCH_ID
+    uint32_t have_history, pad_;                         // 0: hist_in holds no frame (the first call, or the first after a reset)
+    double depth_tol, normal_tol;                        // 0: the test is off
+    TemporalCam cur, prev;                               // prev: the record stored with hist_in
+    const double *rgb, *var, *normal, *depth;            // var, normal: or null
+    const double* hist_in;                               // [n_pixels][kTemporalRecDoubles]
+    double* hist_out;
+    double *out_rgb, *out_var, *out_len;                 // out_var, out_len: or null
+};
+// (Weak: reached from rpt_temporal_accumulate* / rpt_temporal_frame_image alone, which report RPT_ERR_UNSUPPORTED where no kernel
+// library is linked.)
+__attribute__((weak)) hipError_t launch_temporal_accumulate(const TemporalArgs& a, hipStream_t stream);
 // Adaptive sampling by tile (adaptive.hip).  A buffer whose tiles have different batch counts: a pixel of tile t holds
 // n_batches + extra[t] batches (extra null: no tile batch was ever added).
 struct TileBufferView {

@@ -3414,6 +3414,193 @@ int rpt_buffer_denoised_image(rpt_buffer* b, rpt_denoiser* d, const rpt_denoise_
     return RPT_OK;
 }
 
+// ---------------------------------------------------------------------------- temporal accumulation (temporal.hip)
+int rpt_temporal_camera_record(const rpt_camera* cam, double out[13]) {
+    if (!cam || !out) return fail(RPT_ERR_INVALID, "null argument");
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(cam->eye[i]) || !std::isfinite(cam->direction[i]) || !std::isfinite(cam->up[i]))
+            return fail(RPT_ERR_INVALID, "camera: a field is not finite");
+    if (!std::isfinite(cam->fov) || !std::isfinite(cam->aperture) || !std::isfinite(cam->focal_distance))
+        return fail(RPT_ERR_INVALID, "camera: a field is not finite");
+    if (!(cam->fov > 0.0 && cam->fov < M_PI)) return fail(RPT_ERR_INVALID, "camera: fov must be in (0, pi)");
+    const D3 c = cross(d3(cam->direction), d3(cam->up));
+    const double l = std::sqrt((c.x * c.x + c.y * c.y) + c.z * c.z);
+    if (!(l > 0.0) || std::isinf(l)) return fail(RPT_ERR_INVALID, "camera: direction and up have no cross product");
+    for (int i = 0; i < 3; i++) {
+        out[i] = cam->eye[i];
+        out[3 + i] = cam->direction[i];
+        out[6 + i] = comp(c, i) / l;
+        out[9 + i] = cam->up[i];
+    }
+    out[12] = 1.0 / std::tan(cam->fov / 2.0);
+    return RPT_OK;
+}
+struct rpt_temporal {
+    int device = 0;
+    uint32_t width = 0, height = 0;
+    rpti::DevMem d_rec[2];             // the history: records of kTemporalRecDoubles doubles; d_rec[cur] is read, the other written
+    int cur = 0;
+    uint32_t frames = 0;               // since create / reset; 0: d_rec[cur] holds no frame
+    TemporalCam cam{};                 // the record of the call that wrote d_rec[cur]
+    rpti::DevMem d_host;               // rpt_temporal_accumulate: the planes of the host entry point
+    rpti::DevMem d_frame;              // rpt_temporal_frame_image: mean, variance, accumulated frame and variance, filtered frame
+    rpti::Event done;                  // recorded after the kernel of a call: the next call waits for it, whatever its stream
+    bool used = false;
+};
+rpt_temporal* rpt_temporal_create(int device, uint32_t width, uint32_t height) {
+    if (width == 0 || height == 0 || uint64_t(width) * height >= (1ull << 31)) { fail(RPT_ERR_INVALID, "bad accumulator size"); return nullptr; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { fail(RPT_ERR_INVALID, "device index out of range"); return nullptr; }
+    auto* t = new rpt_temporal();
+    t->device = device;
+    t->width = width;
+    t->height = height;
+    const size_t bytes = size_t(width) * height * kTemporalRecDoubles * sizeof(double);
+    const bool ok = hipSetDevice(device) == hipSuccess && t->d_rec[0].reserve(bytes) == hipSuccess && t->d_rec[1].reserve(bytes) == hipSuccess &&
+                    t->done.create(hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        fail(RPT_ERR_DEVICE, "rpt_temporal_create: device allocation failed");
+        rpt_temporal_destroy(t);
+        return nullptr;
+    }
+    return t;
+}
+void rpt_temporal_destroy(rpt_temporal* t) {
+    if (!t) return;
+    (void)hipSetDevice(t->device);
+    delete t;
+}
+int rpt_temporal_reset(rpt_temporal* t) {
+    if (!t) return fail(RPT_ERR_INVALID, "null accumulator");
+    t->frames = 0;                     // the next call looks nothing up; what the arrays hold is never read
+    return RPT_OK;
+}
+int rpt_temporal_frames(rpt_temporal* t, uint32_t* n) {
+    if (!t || !n) return fail(RPT_ERR_INVALID, "null argument");
+    *n = t->frames;
+    return RPT_OK;
+}
+// What rpt_temporal_* refuse before any device call; the call's camera record to *rec.
+static int check_temporal(const rpt_temporal* t, const rpt_temporal_params* prm, const rpt_camera* cam, const void* rgb, const void* var,
+                          const void* normal, const void* depth, const void* out, const void* out_var, const void* out_len, TemporalCam* rec) {
+    if (!prm) return fail(RPT_ERR_INVALID, "null temporal parameters");
+    if (prm->max_history < 1 || prm->max_history > 4096) return fail(RPT_ERR_INVALID, "max_history must be 1..4096");
+    if (prm->flags & ~RPT_TEMPORAL_MATCH_ID) return fail(RPT_ERR_INVALID, "unknown temporal flag");
+    for (double tol : {prm->depth_tol, prm->normal_tol})
+        if (!(tol >= 0.0) || std::isinf(tol)) return fail(RPT_ERR_INVALID, "a tolerance must be finite and >= 0 (0: the test is off)");
+    if (!cam) return fail(RPT_ERR_INVALID, "null camera");
+    static_assert(sizeof(TemporalCam) == 13 * sizeof(double), "the camera record is 13 doubles");
+    if (int rc = rpt_temporal_camera_record(cam, reinterpret_cast<double*>(rec))) return rc;
+    if (!rgb || !out) return fail(RPT_ERR_INVALID, "null frame");
+    if (!depth) return fail(RPT_ERR_INVALID, "the accumulation needs the depth plane");
+    if (prm->normal_tol > 0.0 && !normal) return fail(RPT_ERR_INVALID, "normal_tol > 0 needs the normal plane");
+    if (!(prm->normal_tol > 0.0) && normal) return fail(RPT_ERR_INVALID, "normal_tol == 0 takes no normal plane");
+    for (const void* o : {out, out_var, out_len})
+        for (const void* in : {rgb, var, normal, depth})
+            if (o && o == in) return fail(RPT_ERR_INVALID, "an output must not be one of the inputs");
+    if (out == out_var || out == out_len || (out_var && out_var == out_len)) return fail(RPT_ERR_INVALID, "the outputs must differ");
+    if (!t) return fail(RPT_ERR_INVALID, "null accumulator");
+    return RPT_OK;
+}
+// (The arguments have passed check_temporal.)
+static int run_temporal(rpt_temporal* t, const rpt_temporal_params* prm, const TemporalCam& rec, const double* d_rgb, const double* d_var,
+                        const double* d_normal, const double* d_depth, double* d_out, double* d_out_var, double* d_out_len, hipStream_t st) {
+    if (!launch_temporal_accumulate) return fail(RPT_ERR_UNSUPPORTED, "rpt_temporal_accumulate: built without the kernels");
+    HIP_TRY(hipSetDevice(t->device));
+    if (t->used) HIP_TRY(hipStreamWaitEvent(st, t->done.get(), 0));
+    t->used = true;
+    TemporalArgs a{};
+    a.width = t->width; a.height = t->height; a.max_history = prm->max_history; a.flags = prm->flags;
+    a.have_history = t->frames ? 1u : 0u;
+    a.depth_tol = prm->depth_tol; a.normal_tol = prm->normal_tol;
+    a.cur = rec;
+    a.prev = t->cam;
+    a.rgb = d_rgb; a.var = d_var; a.normal = d_normal; a.depth = d_depth;
+    a.hist_in = t->d_rec[t->cur].get<double>();
+    a.hist_out = t->d_rec[t->cur ^ 1].get<double>();
+    a.out_rgb = d_out; a.out_var = d_out_var; a.out_len = d_out_len;
+    HIP_TRY(launch_temporal_accumulate(a, st));
+    HIP_TRY(hipEventRecord(t->done.get(), st));
+    t->cur ^= 1;
+    t->cam = rec;
+    if (t->frames != 0xFFFFFFFFu) t->frames++;
+    return RPT_OK;
+}
+int rpt_temporal_accumulate_device(rpt_temporal* t, const rpt_temporal_params* prm, const rpt_camera* cam, const void* d_rgb, const void* d_var,
+                                   const void* d_normal, const void* d_depth, void* d_out_rgb, void* d_out_var, void* d_out_len,
+                                   void* hip_stream) {
+    TemporalCam rec;
+    if (int rc = check_temporal(t, prm, cam, d_rgb, d_var, d_normal, d_depth, d_out_rgb, d_out_var, d_out_len, &rec)) return rc;
+    return run_temporal(t, prm, rec, static_cast<const double*>(d_rgb), static_cast<const double*>(d_var), static_cast<const double*>(d_normal),
+                        static_cast<const double*>(d_depth), static_cast<double*>(d_out_rgb), static_cast<double*>(d_out_var),
+                        static_cast<double*>(d_out_len), static_cast<hipStream_t>(hip_stream));
+}
+int rpt_temporal_accumulate(rpt_temporal* t, const rpt_temporal_params* prm, const rpt_camera* cam, const double* rgb, const double* var,
+                            const double* normal, const double* depth, double* out_rgb, double* out_var, double* out_len) {
+    TemporalCam rec;
+    if (int rc = check_temporal(t, prm, cam, rgb, var, normal, depth, out_rgb, out_var, out_len, &rec)) return rc;
+    HIP_TRY(hipSetDevice(t->device));
+    const size_t n = size_t(t->width) * t->height;
+    // rgb, normal, depth, out: 3 n each; var, out_var, out_len: n each
+    HIP_TRY(t->d_host.reserve(15 * n * 8));
+    double* const base = t->d_host.get<double>();
+    const double* const ins[4] = {rgb, normal, depth, var};
+    double* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; k++)
+        if (ins[k]) {
+            dev[k] = base + size_t(k) * 3 * n;
+            HIP_TRY(hipMemcpy(dev[k], ins[k], (k == 3 ? n : 3 * n) * 8, hipMemcpyHostToDevice));
+        }
+    double* const d_out = base + 10 * n;
+    double* const d_out_var = out_var ? base + 13 * n : nullptr;
+    double* const d_out_len = out_len ? base + 14 * n : nullptr;
+    if (int rc = run_temporal(t, prm, rec, dev[0], dev[3], dev[1], dev[2], d_out, d_out_var, d_out_len, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(out_rgb, d_out, 3 * n * 8, hipMemcpyDeviceToHost));
+    if (out_var) HIP_TRY(hipMemcpy(out_var, d_out_var, n * 8, hipMemcpyDeviceToHost));
+    if (out_len) HIP_TRY(hipMemcpy(out_len, d_out_len, n * 8, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+int rpt_temporal_frame_image(rpt_temporal* t, const rpt_temporal_params* prm, const rpt_camera* cam, rpt_buffer* b, rpt_denoiser* d,
+                             const rpt_denoise_params* dprm, const void* d_albedo, const void* d_normal, const void* d_depth,
+                             uint8_t* out_rgb8) {
+    // (the frame and its variance come from the buffer, the accumulated ones from the accumulator: placeholders that are no plane of
+    // the caller's.  The accumulation reads the normal plane only where its test is on.)
+    TemporalCam rec;
+    const void* const t_normal = prm && prm->normal_tol > 0.0 ? d_normal : nullptr;
+    if (int rc = check_temporal(t, prm, cam, &rec, nullptr, t_normal, d_depth, out_rgb8, nullptr, nullptr, &rec)) return rc;
+    if (d)
+        if (int rc = check_denoise(d, dprm, &rec, dprm && dprm->sigma_color > 0.0 ? t : nullptr, d_albedo, d_normal, d_depth, out_rgb8, nullptr)) return rc;
+    if (!b) return fail(RPT_ERR_INVALID, "null buffer");
+    if (b->device != t->device || (d && d->device != t->device)) return fail(RPT_ERR_INVALID, "buffer, denoiser and accumulator live on different devices");
+    if (b->width != t->width || b->height != t->height || (d && (d->width != t->width || d->height != t->height)))
+        return fail(RPT_ERR_INVALID, "buffer, denoiser and accumulator have different sizes");
+    if (b->n_batches < 2) return fail(RPT_ERR_STATE, "the variance of the mean needs at least 2 batches");
+    if (!launch_buffer_mean || !launch_color_bytes || !launch_temporal_accumulate)
+        return fail(RPT_ERR_UNSUPPORTED, "rpt_temporal_frame_image: built without the kernels");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipDeviceSynchronize());  // batches and planes may have been written on other streams
+    const size_t n = size_t(b->width) * b->height;
+    HIP_TRY(t->d_frame.reserve(11 * n * 8));
+    double* const mean = t->d_frame.get<double>();
+    double* const var = mean + 3 * n;
+    double* const acc = mean + 4 * n;
+    double* const acc_var = mean + 7 * n;
+    double* out = acc;
+    if (int rc = rpt_buffer_mean_device(b, mean, var, nullptr)) return rc;
+    if (int rc = run_temporal(t, prm, rec, mean, var, static_cast<const double*>(t_normal), static_cast<const double*>(d_depth), acc, acc_var,
+                              nullptr, nullptr))
+        return rc;
+    if (d) {
+        out = mean + 8 * n;
+        if (int rc = run_denoise(d, dprm, acc, acc_var, static_cast<const double*>(d_albedo), static_cast<const double*>(d_normal),
+                                 static_cast<const double*>(d_depth), out, nullptr, nullptr))
+            return rc;
+    }
+    HIP_TRY(launch_color_bytes(3 * n, out, b->d_img.get<uint8_t>(), nullptr));
+    HIP_TRY(hipMemcpy(out_rgb8, b->d_img.get(), n * 3, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
 int rpt_get_timing(rpt_scene* s, double* render_ms, double* resolve_ms, int32_t* grid_blocks) {
     if (!s) return fail(RPT_ERR_INVALID, "null scene");
     if (!s->ev_count) return fail(RPT_ERR_STATE, "no timed render: rpt_set_option(\"timing\", 1) first");

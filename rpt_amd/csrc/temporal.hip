@@ -1,0 +1,140 @@
+// temporal.hip — rpt_temporal_*: temporal accumulation with reprojection for a camera moving over a scene whose objects keep their
+// places and indices (an addition: the reference renders every frame of a sequence from nothing).  The arithmetic is the order of fp64
+// operations that include/rpt_hip.h states, every one rounded on its own (contraction off, IEEE division and square root, no atomics):
+// tests/temporal_ref.py restates it in numpy and the kernel's output is compared with it bit for bit.
+//
+// One kernel, a plain grid of 16 x 16 pixel blocks (a wave = 16 x 4 neighbouring pixels), one lane per pixel: the pixel's surface point
+// from the depth plane and the current camera record, its place in the previous frame from the stored record, up to four taps of the
+// old history (one contiguous 80-byte record each; neighbouring lanes land on neighbouring records, so the taps of a wave overlap in
+// L2), the blend, and the pixel's new record written to the other array.  Both camera records are kernel arguments, uniform over the
+// grid.  A NULL plane is a uniform branch that yields the value the definition names (0.0), so the bits do not depend on it.
+#include <hip/hip_runtime.h>
+
+#include "../../include/rpt_hip.h"
+#include "kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace rptg {
+namespace {
+
+struct alignas(16) TemporalRec {
+    double c[3], v, len, n[3], z, id;
+};
+static_assert(sizeof(TemporalRec) == kTemporalRecDoubles * sizeof(double), "one record is 80 contiguous bytes");
+
+constexpr uint32_t kTile = 16;         // pixels per block edge
+
+__device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+__device__ __forceinline__ bool finite(double t) { return !(t - t != 0.0); }
+
+__global__ __launch_bounds__(256) void temporal_accumulate_kernel(const TemporalArgs a) {
+    const uint32_t x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
+    if (x >= a.width || y >= a.height) return;
+    const size_t p = size_t(y) * a.width + x;
+    const double fw = double(a.width), fh = double(a.height), dim = double(a.width > a.height ? a.width : a.height);
+    const double rgb[3] = {a.rgb[3 * p], a.rgb[3 * p + 1], a.rgb[3 * p + 2]};
+    const double v_in = a.var ? a.var[p] : 0.0;
+    // 2: the current surface point
+    const double cov = a.depth[3 * p + 1];
+    const bool hit = cov > 0.0;                                         // (false for NaN)
+    const double zc = a.depth[3 * p] / cov, id = a.depth[3 * p + 2];
+    double n[3] = {0.0, 0.0, 0.0};
+    if (a.normal)
+        for (int k = 0; k < 3; k++) n[k] = a.normal[3 * p + k];
+    double B = 0.0, C[3] = {0.0, 0.0, 0.0}, V = 0.0, L = 0.0;
+    if (a.have_history && hit) {
+        // 1: the pixel centre's ray
+        const double xn = (double(2u * x + 1u) - fw) / dim;
+        const double yn = (double(2u * (a.height - y) - 1u) - fh) / dim;
+        double v[3];
+        for (int k = 0; k < 3; k++) v[k] = (a.cur.d * a.cur.dir[k] + xn * a.cur.right[k]) + yn * a.cur.up[k];
+        const double l = __dsqrt_rn(dot3(v, v));
+        // 3: where the history saw that point
+        const double s = zc / l;
+        double q[3];
+        for (int k = 0; k < 3; k++) q[k] = (a.cur.eye[k] + s * v[k]) - a.prev.eye[k];
+        const double zq = dot3(q, a.prev.dir);
+        if (zq > 0.0) {
+            const double u = (dot3(q, a.prev.right) * a.prev.d) / zq;
+            const double w = (dot3(q, a.prev.up) * a.prev.d) / zq;
+            const double fx = ((u * dim + fw) - 1.0) * 0.5;
+            const double fy = ((fh - 1.0) - w * dim) * 0.5;
+            if (fx > -1.0 && fx < fw && fy > -1.0 && fy < fh) {          // (NaN fails)
+                const double flx = floor(fx), fly = floor(fy);
+                const double ax = fx - flx, ay = fy - fly;
+                const int ix = int(flx), iy = int(fly);                   // -1 .. width - 1, -1 .. height - 1
+                const double qq = dot3(q, q);
+                const TemporalRec* const hist = reinterpret_cast<const TemporalRec*>(a.hist_in);
+                const bool match = a.flags & RPT_TEMPORAL_MATCH_ID, depth = a.depth_tol > 0.0, normal = a.normal_tol > 0.0;
+                const double nt2 = a.normal_tol * a.normal_tol;
+#pragma unroll
+                for (int j = 0; j < 2; j++)
+#pragma unroll
+                    for (int i = 0; i < 2; i++) {
+                        const uint32_t tx = uint32_t(ix + i), ty = uint32_t(iy + j);   // (below 0 wraps to a large value)
+                        if (tx >= a.width || ty >= a.height) continue;
+                        const double b = (i ? ax : 1.0 - ax) * (j ? ay : 1.0 - ay);
+                        const TemporalRec h = hist[size_t(ty) * a.width + tx];
+                        bool ok = h.len > 0.0;                            // (every test: false for NaN)
+                        if (match) ok = ok && h.id == id;
+                        if (depth) {
+                            const double r = h.z * h.z;
+                            ok = ok && fabs(r - qq) <= a.depth_tol * qq;
+                        }
+                        if (normal) {
+                            const double e0 = h.n[0] - n[0], e1 = h.n[1] - n[1], e2 = h.n[2] - n[2];
+                            ok = ok && ((e0 * e0 + e1 * e1) + e2 * e2) <= nt2;
+                        }
+                        if (ok) {
+                            B = B + b;
+                            C[0] = C[0] + b * h.c[0];
+                            C[1] = C[1] + b * h.c[1];
+                            C[2] = C[2] + b * h.c[2];
+                            V = V + (b * b) * h.v;
+                            L = L + b * h.len;
+                        }
+                    }
+            }
+        }
+    }
+    // 5: the blend
+    TemporalRec out;
+    double len = 1.0;
+    if (B > 0.0) {
+        const double hv = V / (B * B), hl = L / B;
+        len = fmin(hl + 1.0, double(a.max_history));
+        const double al = 1.0 / len, om = 1.0 - al;
+        for (int k = 0; k < 3; k++) {
+            const double hc = C[k] / B;
+            out.c[k] = hc + (rgb[k] - hc) * al;
+        }
+        out.v = (om * om) * hv + (al * al) * v_in;
+    } else {
+        out.c[0] = rgb[0]; out.c[1] = rgb[1]; out.c[2] = rgb[2];
+        out.v = v_in;
+    }
+    a.out_rgb[3 * p] = out.c[0];
+    a.out_rgb[3 * p + 1] = out.c[1];
+    a.out_rgb[3 * p + 2] = out.c[2];
+    if (a.out_var) a.out_var[p] = out.v;
+    if (a.out_len) a.out_len[p] = len;
+    // 6: the new record; a miss or a value that is not finite carries no history
+    const bool keep = hit && finite(out.c[0]) && finite(out.c[1]) && finite(out.c[2]) && finite(out.v);
+    out.len = keep ? len : 0.0;
+    out.n[0] = n[0]; out.n[1] = n[1]; out.n[2] = n[2];
+    out.z = zc;
+    out.id = id;
+    reinterpret_cast<TemporalRec*>(a.hist_out)[p] = out;
+}
+
+}  // namespace
+
+hipError_t launch_temporal_accumulate(const TemporalArgs& a, hipStream_t stream) {
+    if (!a.width || !a.height) return hipSuccess;
+    const dim3 grid((a.width + kTile - 1) / kTile, (a.height + kTile - 1) / kTile), block(kTile, kTile);
+    hipLaunchKernelGGL(temporal_accumulate_kernel, grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace rptg
