@@ -305,7 +305,7 @@ RPT_DEV bool aabb_closer(const F4& lo, const F4& hi, V o, V inv, float tmin, flo
     return slabs_closer((lo.x - o.x) * inv.x, (hi.x - o.x) * inv.x, (lo.y - o.y) * inv.y, (hi.y - o.y) * inv.y,
                         (lo.z - o.z) * inv.z, (hi.z - o.z) * inv.z, tmin, tbest, t);
 }
-// Unit cube [-1/2,1/2]^3, src/shape/cube.rs:22-74: t of the accepted root (the face is found from the hit point: box_face_normal).
+// Unit cube [-1/2,1/2]^3, src/shape/cube.rs:22-74: t of the accepted root (the face is found afterwards, for the winner alone: box_face_normal).
 RPT_DEV float hit_cube(V ol, V dl, float tmin) {
     float t;
     return cube_closer(ol, dl, tmin, __builtin_inff(), t) ? t : -1.f;
@@ -1087,12 +1087,36 @@ RPT_DEV void scan_or_tree(const SceneView& scene_, V o, V d, float tmin, float& 
 
 // Outward normal of the face of the axis-aligned box [lo, hi] that the surface point p lies on: the axis whose nearer face
 // plane is closest to p.
-RPT_DEV V box_face_normal(V p, V lo, V hi) {
-    const float xl = fabsf(p.x - lo.x), xh = fabsf(p.x - hi.x), yl = fabsf(p.y - lo.y), yh = fabsf(p.y - hi.y);
-    const float zl = fabsf(p.z - lo.z), zh = fabsf(p.z - hi.z);
-    const float ex = fminf(xl, xh), ey = fminf(yl, yh), ez = fminf(zl, zh);
-    const bool ax0 = ex <= ey && ex <= ez, ax1 = !ax0 && ey <= ez;
-    return mk(ax0 ? (xh < xl ? 1.f : -1.f) : 0.f, ax1 ? (yh < yl ? 1.f : -1.f) : 0.f, (!ax0 && !ax1) ? (zh < zl ? 1.f : -1.f) : 0.f);
+// The face of a box [lo, hi] that bounds the accepted root t of its slab test (src/shape/cube.rs:37-55).  Away from the edges that is
+// the face nearest to the hit point, six subtractions.  Within rounding of an edge the nearest face can be the hidden one, a normal
+// that faces away from the ray: where the two nearest faces are closer than 1e-5 (1 + |p|) to each other the slab test is run again
+// and decides as the reference does -- the slab entered last when the entry lies at or beyond tmin, else the slab left first; among
+// equal times x before y before z.  (A lane in 10^4 takes that branch.)
+RPT_DEV V slab_face_normal(V o, V d, V lo, V hi, float tmin);
+RPT_DEV V box_face_normal(V o, V d, V lo, V hi, float t, float tmin) {
+    const V p = fma3(t, d, o);
+    const float pxl = fabsf(p.x - lo.x), pxh = fabsf(p.x - hi.x), pyl = fabsf(p.y - lo.y), pyh = fabsf(p.y - hi.y);
+    const float pzl = fabsf(p.z - lo.z), pzh = fabsf(p.z - hi.z);
+    const float ex = fminf(pxl, pxh), ey = fminf(pyl, pyh), ez = fminf(pzl, pzh);
+    if (__builtin_amdgcn_fmed3f(ex, ey, ez) > 1e-5f * (1.f + max3(fabsf(p.x), fabsf(p.y), fabsf(p.z)))) {
+        const bool ax0 = ex <= ey && ex <= ez, ax1 = !ax0 && ey <= ez;
+        return mk(ax0 ? (pxh < pxl ? 1.f : -1.f) : 0.f, ax1 ? (pyh < pyl ? 1.f : -1.f) : 0.f, (!ax0 && !ax1) ? (pzh < pzl ? 1.f : -1.f) : 0.f);
+    }
+    return slab_face_normal(o, d, lo, hi, tmin);
+}
+RPT_DEV V slab_face_normal(V o, V d, V lo, V hi, float tmin) {
+#pragma clang fp contract(off)
+    const float ix = rcp(d.x), iy = rcp(d.y), iz = rcp(d.z);
+    const float x1 = (lo.x - o.x) * ix, x2 = (hi.x - o.x) * ix, y1 = (lo.y - o.y) * iy, y2 = (hi.y - o.y) * iy;
+    const float z1 = (lo.z - o.z) * iz, z2 = (hi.z - o.z) * iz;
+    const bool sx = x1 > x2, sy = y1 > y2, sz = z1 > z2;
+    const float xl = fminf(x1, x2), xh = fmaxf(x1, x2), yl = fminf(y1, y2), yh = fmaxf(y1, y2), zl = fminf(z1, z2), zh = fmaxf(z1, z2);
+    const bool in = !(max3(xl, yl, zl) < tmin);   // slabs_closer's choice of the root
+    const bool ax0 = in ? (xl > yl && xl > zl) : (xh < yh && xh < zh);
+    const bool ax1 = !ax0 && (in ? yl > zl : yh < zh);
+    const bool swapped = ax0 ? sx : (ax1 ? sy : sz);
+    const float sg = (in == swapped) ? 1.f : -1.f;   // in through the lo face, out through the hi face, unless the direction is negative there
+    return mk(ax0 ? sg : 0.f, ax1 ? sg : 0.f, (!ax0 && !ax1) ? sg : 0.f);
 }
 // Normal and object of the winning primitive (per lane).
 template <bool MONO = false>
@@ -1145,14 +1169,12 @@ RPT_DEV void finalize_hit(const SceneView& scene_, V o, V d, float tmin, float t
         const XfShade s = sc.cub_sh[idx];
         V ol, dl;
         to_local(x, o, d, ol, dl);
-        // the face the hit point lies on (src/shape/cube.rs:37-55 picks the slab that bounds the root: the same face except
-        // within rounding of an edge), from the point instead of a second run of the slab test
-        const V nl = box_face_normal(fma3(t, dl, ol), mk(-0.5f, -0.5f, -0.5f), mk(0.5f, 0.5f, 0.5f));
+        const V nl = box_face_normal(ol, dl, mk(-0.5f, -0.5f, -0.5f), mk(0.5f, 0.5f, 0.5f), t, tmin);
         n = (s.r1.w != 0.f) ? normalize(mk(dot3(s.r0, nl), dot3(s.r1, nl), dot3(s.r2, nl))) : nl;
         obj = __float_as_uint(s.r0.w);
     } else if (kind == K_AABB) {
         const AabbScan b = sc.aabb[idx];
-        n = box_face_normal(fma3(t, d, o), xyz(b.lo), xyz(b.hi));   // (as for the cube)
+        n = box_face_normal(o, d, xyz(b.lo), xyz(b.hi), t, tmin);   // (as for the cube)
         obj = __float_as_uint(b.lo.w);
     } else if (kind == K_RECT) {
         const F4 s = sc.rect_sh[idx].n_obj;

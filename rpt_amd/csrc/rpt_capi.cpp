@@ -695,10 +695,20 @@ static void push_tri(const double* t, const Xf& x, uint32_t obj, std::vector<Tri
     double denom = d00 * d11 - d01 * d01;
     D3 A = (1.0 / denom) * (d11 * d0 - d01 * d1);
     D3 B = (1.0 / denom) * (d00 * d1 - d01 * d0);
+    // tri_closer accepts u, v, w >= 0 of these functionals, evaluated in fp32 at an fp32 hit point: an error of about 1 ulp of the terms'
+    // sum.  Two triangles that share an edge err independently there, and a ray within that error of the edge was rejected by both and
+    // passed through the mesh.  So the functionals are those of the triangle enlarged about its centroid by e in every barycentric
+    // coordinate ((v + e) / (1 + 3 e), likewise w and u), e = 4e-7 x the magnitude of the terms: neighbours overlap by the error.
+    double aw = -dot(A, v1), bw = -dot(B, v1);
+    const double big = std::max({std::fabs(v1.x), std::fabs(v1.y), std::fabs(v1.z), std::fabs(v2.x), std::fabs(v2.y), std::fabs(v2.z),
+                                 std::fabs(v3.x), std::fabs(v3.y), std::fabs(v3.z)});
+    const double sa = (std::fabs(A.x) + std::fabs(A.y) + std::fabs(A.z)) * big + std::fabs(aw) + 1.0;
+    const double sb = (std::fabs(B.x) + std::fabs(B.y) + std::fabs(B.z)) * big + std::fabs(bw) + 1.0;
+    const double e = 4e-7 * std::max(sa, sb), k = 1.0 / (1.0 + 3.0 * e);
     TriScan ts;
     ts.pn = f4(pn, dot(pn, v1));
-    ts.A = f4(A, -dot(A, v1));
-    ts.B = f4(B, -dot(B, v1));
+    ts.A = f4(k * A, k * (aw + e));
+    ts.B = f4(k * B, k * (bw + e));
     TriShade sh;
     if (flat) {
         sh.n1 = f4(normalize(w1), 0);
@@ -1165,6 +1175,14 @@ struct Flattener {
                 }
             }
         }
+        // The scanned rectangles reach 2e-6 of their coordinates beyond their edges: rect_closer compares each rectangle's own fp32 hit point
+        // with its own bounds, and where two walls meet in an edge of a room a ray at that edge overshot both (by up to 3 ulp of the
+        // coordinate) and left the room.  (The shell's faces are gone from these lists: its slab test is closed.)
+        for (int a = 0; a < 3; a++)
+            for (RectScan& r : rect_axis[a]) {
+                const float pu = 2e-6f * std::max(std::fabs(r.a.y), std::fabs(r.a.z)), pv = 2e-6f * std::max(std::fabs(r.a.w), std::fabs(r.b.x));
+                r.a.y -= pu; r.a.z += pu; r.a.w -= pv; r.b.x += pv;
+            }
         for (int a = 0; a < 3; a++) {
             rect.insert(rect.end(), rect_axis[a].begin(), rect_axis[a].end());
             rect_sh.insert(rect_sh.end(), rect_sh_axis[a].begin(), rect_sh_axis[a].end());
