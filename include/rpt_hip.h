@@ -516,7 +516,10 @@ int rpt_photon_map_build(rpt_scene*, uint64_t photon_count, int32_t kind, double
  *      shooting order); the caller all-gathers them in rank order (RCCL), which reproduces the
  *      single-GPU arrays exactly because the blocks are contiguous.
  *   3. rpt_photon_map_from_records: build the maps of rpt_photon_map_build from device arrays
- *      (the gathered ones; they are read, not kept).  Invalidates the pointers of step 2. */
+ *      (the gathered ones; they are read, not kept).  Invalidates the pointers of step 2.
+ * The records may be any photons.  The volume map of kinds RPT_PHOTON_MAP and RPT_PHOTON_POINT_BEAM is searched with a stack of 64
+ * pending nodes per lane: a map whose k-nearest tree has more than 64 inner nodes on a path (thousands of coincident photons next
+ * to far outliers; a shot map has about 15) is refused with RPT_ERR_UNSUPPORTED, the depth in the message -- by both builds. */
 #define RPT_PHOTON_RECORD_BYTES 48
 int rpt_photon_shoot(rpt_scene*, uint64_t photon_count, int32_t kind, double watts, uint64_t seed,
                      uint32_t shard_rank, uint32_t shard_count, uint64_t n_out[2]);

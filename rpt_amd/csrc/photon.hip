@@ -376,6 +376,22 @@ __global__ void pack_kernel(const PhotonRec* p, int n, const uint32_t* left, con
     nodes[i] = w;
 }
 
+// Inner nodes on the deepest root-to-leaf path of the tree pack_kernel writes with `leaf_max` (a collapsed subtree is a leaf
+// entry: its inner nodes are never walked): what the per-lane stack of knn_walk has to hold, one pending sibling per inner
+// node on the way down.  One thread per inner node climbs to the root; depth_max is pre-set to 0.
+static constexpr uint32_t kKnnStack = 64;
+__global__ void tree_depth_kernel(int n, const uint32_t* parent_int, const uint32_t* range_lo, const uint32_t* range_hi, uint32_t leaf_max,
+                                  uint32_t* depth_max) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t d = 0;
+    if (i < n - 1 && (i == 0 || range_hi[i] - range_lo[i] + 1u > leaf_max)) {
+        d = 1;
+        for (uint32_t j = parent_int[i]; j != 0xFFFFFFFFu && d < uint32_t(n); j = parent_int[j]) d++;
+    }
+    for (int off = 32; off; off >>= 1) d = max(d, uint32_t(__shfl_xor(int(d), off)));
+    if ((threadIdx.x & 63) == 0 && d != 0u) atomicMax(depth_max, d);
+}
+
 RPT_DEV float box_dist2(const float lo[3], const float hi[3], V q) {
     float dx = fmaxf(fmaxf(lo[0] - q.x, q.x - hi[0]), 0.f);
     float dy = fmaxf(fmaxf(lo[1] - q.y, q.y - hi[1]), 0.f);
@@ -383,6 +399,9 @@ RPT_DEV float box_dist2(const float lo[3], const float hi[3], V q) {
     return fmaf(dx, dx, fmaf(dy, dy, dz * dz));
 }
 // k-nearest walk.  visit(index, d2) returns the current pruning bound (d2 of the k-th best, or +inf).
+// The stack holds one pending sibling per inner node on the way down: a tree with more than kKnnStack inner nodes on a path
+// would lose the deepest ones -- the query's nearest neighbours.  build_lbvh refuses such a tree (tree_depth_kernel), so the
+// guard below never drops a push.
 template <class F>
 RPT_DEV void knn_walk(const BvhNode* nodes, const PhotonRec* p, uint32_t n, V q, float& bound, F&& visit) {
     if (n == 0) return;
@@ -391,7 +410,7 @@ RPT_DEV void knn_walk(const BvhNode* nodes, const PhotonRec* p, uint32_t n, V q,
         bound = visit(0u, dot(d, d));
         return;
     }
-    uint32_t stack[64];
+    uint32_t stack[kKnnStack];
     int sp = 0;
     uint32_t cur = 0;
     for (;;) {
@@ -407,7 +426,7 @@ RPT_DEV void knn_walk(const BvhNode* nodes, const PhotonRec* p, uint32_t n, V q,
             bool h0 = d0 <= bound, h1 = d1 <= bound;
             if (h0 && h1) {
                 bool first0 = d0 <= d1;
-                if (sp < 64) stack[sp++] = first0 ? nd.e1 : nd.e0;
+                if (sp < int(kKnnStack)) stack[sp++] = first0 ? nd.e1 : nd.e0;
                 cur = first0 ? nd.e0 : nd.e1;
                 continue;
             }
@@ -1101,7 +1120,9 @@ RPT_DEV V beam_estimate_photon_lanes(QueryK q, const uint32_t* cand, uint32_t ca
         if (lane_ < nb) {
             const PhotonRec raw = q.v_ph[list[lane_]];
             const V c = xyz(raw.pos_r) - eye0;
-            const float r2 = raw.pos_r.w * raw.pos_r.w, ir2 = rcp(r2), c2 = dot(c, c), len = sqrt1(c2);
+            // (a radius of exactly 0 -- ten coincident photons, a map of one -- reaches no ray: its weights sum to 0, and 1 / r^2 = inf
+            // would turn the photon's term into 0 * inf)
+            const float r2 = raw.pos_r.w * raw.pos_r.w, ir2 = r2 > 0.f ? rcp(r2) : 0.f, c2 = dot(c, c), len = sqrt1(c2);
             const float kk = (3.f * kInvPi) * phase * ir2 * __expf(-sigma_t * len);
             const V pw = kk * xyz(raw.pow);
             const float one_plus = fmaf(sigma_t, len, 1.f);
@@ -1165,7 +1186,7 @@ RPT_DEV V beam_estimate_photon_lanes(QueryK q, const uint32_t* cand, uint32_t ca
             const float cc2 = dot(cc, cc), along = dot(cc, fs.axis);
             take = take && cc2 <= far2;  // the per-ray test rejects centres beyond the ray's hit
             // in front of every ray of the pixel (within 89.4 degrees of its axis; the pixel's cone is ~1e-3 wide)
-            plain = have_fs && cc2 <= near2 && along > 0.f && along * along > 1e-4f * cc2;
+            plain = have_fs && cc2 <= near2 && along > 0.f && along * along > 1e-4f * cc2 && pr.w > 0.f;
         }
         const uint64_t tp = __ballot(take && plain), tg = __ballot(take && !plain);
         if (take && plain) pend_list[pend + prefix(tp)] = idx;
@@ -1370,7 +1391,7 @@ RPT_DEV bool gather_serve(QueryK q, const SceneView& sc_arg, const GatherLds& l,
     lane_clear = lane_clear && shell.holds(x);
     const float reach2 = __builtin_sqrtf(r2k) + rho;
     const float thr2 = ok ? reach2 * reach2 * (1.f + 1e-5f) : -1.f;
-    bool more = __ballot(ok) != 0ull && !(q.skip & 16u);   // diagnostic: 16 = no second pass
+    const bool more0 = __ballot(ok) != 0ull && !(q.skip & 16u);   // diagnostic: 16 = no second pass
     const float thr2_max = wave_max(thr2);
     // Most terms need no visibility scan and sit on diffuse surfaces: what bsdf() returns for a Lambertian surface whenever
     // n.wi >= 0 is a constant of the lane (src/material.rs:268-275; for n.wi < 0 the cosine factor is zero anyway), and the
@@ -1379,6 +1400,15 @@ RPT_DEV bool gather_serve(QueryK q, const SceneView& sc_arg, const GatherLds& l,
     const V f_diffuse = (lambert && !__builtin_signbit(dot(s.n, s.wo))) ? kInvPi * s.mat.albedo : mk(0.f, 0.f, 0.f);
     const bool all_diffuse = __ballot(ok && !lambert) == 0ull;   // wave-uniform
     lap(8);
+    // Of the photons AT the K-th distance the estimate takes as many as the list of the K nearest holds -- identical records, or two
+    // that fp32 places equally far -- as the search per lane and the reference do; the first ones in candidate order.  Such ties are
+    // rare: the terms are added under the plain test d2 <= r2k while every lane counts its own, and only when a lane has counted
+    // more than its list holds does the wave add them once more (cut = 1) with the number of ties to take at hand.
+    const V sc_before = s.sc_col;
+    uint32_t ties = 0u;
+    for (uint32_t cut = 0u; cut < 2u; cut++) {   // wave-uniform
+    uint32_t n_in = 0u;
+    bool more = more0;
     for (uint32_t base = 0; base < M && more; base += 64u) {
         // lane l fetches what the term needs of candidate base + l; the records are then handed round by readlane
         F4 fdir{}, fpow{};
@@ -1404,8 +1434,15 @@ RPT_DEV bool gather_serve(QueryK q, const SceneView& sc_arg, const GatherLds& l,
             if (__ballot(kj <= thr2) == 0ull) { more = false; break; }
             if (a.counters) diag_add(q.r.counters, 15, 1ull);
             const V dd = po - x;
-            const bool in = ok && dot(dd, dd) <= r2k;
+            const float dj = dot(dd, dd);
+            bool in = ok && dj <= r2k;
+            if (cut != 0u) {
+                const bool tie = in && dj == r2k;
+                in = in && (!tie || ties != 0u);
+                if (tie && ties != 0u) ties--;
+            }
             if (__ballot(in) == 0ull) continue;
+            n_in += in ? 1u : 0u;
             if constexpr (EMIT) {   // the selection is handed over instead of being evaluated (at most K: ties at the K-th distance are cut)
                 if (in && s.n_em < K) {
                     s.em[size_t(s.n_em) * a.iterations] = pidx;
@@ -1429,6 +1466,10 @@ RPT_DEV bool gather_serve(QueryK q, const SceneView& sc_arg, const GatherLds& l,
             }
         }
     }
+    if (EMIT || cut != 0u || __ballot(ok && n_in > found) == 0ull) break;
+    s.sc_col = sc_before;
+    if (ok) for (uint32_t k = 0; k < found; k++) ties += gd[k * 64u] == r2k ? 1u : 0u;
+    }   // cut
     lap(9);
     if (ok) {
         s.max_d2 = r2k;
@@ -2050,7 +2091,9 @@ struct PhotonMapDev {
 // Build the LBVH of `n` photons in `raw` (consumed: the sorted copy is kept).  radius_k > 0: also
 // compute the k-NN radii and refit the boxes with them (sphere map for the beam query).
 // mode 0: point map; 1: point map + k-NN radii, then sphere boxes; 2: beam map (boxes of whole beams)
-int build_lbvh(DevPool& pool, PhotonRec* raw, uint32_t n, int mode, DevLbvh& out, hipStream_t st) {
+// lane_walk: the point tree is searched by knn_walk (the radii; the point x point volume gather), whose per-lane stack holds
+// kKnnStack pending siblings: a deeper tree is refused here, where the map is built, and costs the camera pass nothing.
+int build_lbvh(DevPool& pool, PhotonRec* raw, uint32_t n, int mode, DevLbvh& out, hipStream_t st, bool lane_walk = false) {
     const bool with_radius = mode == 1;
     const int first_mode = mode == 2 ? 2 : 0;
     out = DevLbvh{};
@@ -2058,7 +2101,7 @@ int build_lbvh(DevPool& pool, PhotonRec* raw, uint32_t n, int mode, DevLbvh& out
     if (n == 0) return RPT_OK;
     PoolMem<float> m_lohi, m_box, m_radius;
     PoolMem<uint64_t> m_keys, m_keys2;
-    PoolMem<uint32_t> m_vals, m_vals2, m_left, m_right, m_par_i, m_par_l, m_flags, m_rlo, m_rhi;
+    PoolMem<uint32_t> m_vals, m_vals2, m_left, m_right, m_par_i, m_par_l, m_flags, m_rlo, m_rhi, m_depth;
     PoolMem<char> m_temp;
     RPTI_HIP_TRY(m_lohi.alloc(pool, 6));
     RPTI_HIP_TRY(m_keys.alloc(pool, n));
@@ -2099,6 +2142,11 @@ int build_lbvh(DevPool& pool, PhotonRec* raw, uint32_t n, int mode, DevLbvh& out
         // point trees are walked by the k-NN search only (radii, gathers): collapsed leaves
         hipLaunchKernelGGL(pack_kernel, dim3(blocks), dim3(256), 0, st, sorted, int(n), left, right, box, rlo, rhi, par_i, out.nodes.get(),
                            first_mode, first_mode == 0 ? kKnnLeaf : 1u);
+        if (lane_walk && first_mode == 0) {
+            RPTI_HIP_TRY(m_depth.alloc(pool, 1));
+            RPTI_HIP_TRY(hipMemsetAsync(m_depth.get(), 0, 4, st));
+            hipLaunchKernelGGL(tree_depth_kernel, dim3(blocks), dim3(256), 0, st, int(n), par_i, rlo, rhi, kKnnLeaf, m_depth.get());
+        }
     }
     if (with_radius) {
         RPTI_HIP_TRY(m_radius.alloc(pool, n));
@@ -2114,7 +2162,13 @@ int build_lbvh(DevPool& pool, PhotonRec* raw, uint32_t n, int mode, DevLbvh& out
         }
     }
     RPTI_HIP_TRY(hipGetLastError());
+    uint32_t depth = 0;
+    if (m_depth.get()) RPTI_HIP_TRY(hipMemcpyAsync(&depth, m_depth.get(), 4, hipMemcpyDeviceToHost, st));
     RPTI_HIP_TRY(hipStreamSynchronize(st));
+    if (depth > kKnnStack)
+        return rpti::fail(RPT_ERR_UNSUPPORTED, "photon map: the volume photons' k-nearest tree has " + std::to_string(depth) +
+                                                   " inner nodes on its deepest path (tree depth), the search's stack holds " +
+                                                   std::to_string(kKnnStack) + ": photons too unevenly spread (many coincident ones next to far outliers)");
     return RPT_OK;
 }
 
@@ -2307,7 +2361,7 @@ static int build_maps(PhotonMapDev* pm, const PhotonRec* d_s, uint64_t n_s, cons
     int rc = build_lbvh(*pm->pool, const_cast<PhotonRec*>(d_s), uint32_t(n_s), 0, pm->surf, st);
     if (rc == RPT_OK)
         rc = build_lbvh(*pm->pool, const_cast<PhotonRec*>(d_v), uint32_t(n_v),
-                        kind == RPT_PHOTON_POINT_BEAM ? 1 : (kind == RPT_PHOTON_BEAM_BEAM ? 2 : 0), pm->vol, st);
+                        kind == RPT_PHOTON_POINT_BEAM ? 1 : (kind == RPT_PHOTON_BEAM_BEAM ? 2 : 0), pm->vol, st, kind != RPT_PHOTON_BEAM_BEAM);
     if (rc != RPT_OK) return rc;
     RPTI_HIP_TRY(hipEventRecord(e2.get(), st));
     RPTI_HIP_TRY(hipEventSynchronize(e2.get()));
