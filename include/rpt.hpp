@@ -535,6 +535,22 @@ class Temporal {
         if (rpt_temporal_camera_record(&c, r.data()) != RPT_OK) throw Error(rpt_last_error());
         return r;
     }
+    // A (3 x 4), G (3 x 3), three zeros: the motion record of an object whose composed object-to-world matrices (row-major 4 x 4)
+    // are `cur` in the current and `prev` in the previous frame (a host function)
+    static std::array<double, RPT_TEMPORAL_MOTION_DOUBLES> motion_record(const std::array<double, 16>& cur, const std::array<double, 16>& prev) {
+        std::array<double, RPT_TEMPORAL_MOTION_DOUBLES> r{};
+        if (rpt_temporal_motion_record(cur.data(), prev.data(), r.data()) != RPT_OK) throw Error(rpt_last_error());
+        return r;
+    }
+    // the one-shot motion table of the next accumulate / accumulate_device / frame_image: record i for the object with id i + 1
+    // (copied; an empty vector clears it)
+    void set_motion(const std::vector<std::array<double, RPT_TEMPORAL_MOTION_DOUBLES>>& records) {
+        if (rpt_temporal_set_motion(h_, records.empty() ? nullptr : records[0].data(), uint32_t(records.size())) != RPT_OK) throw Error(rpt_last_error());
+    }
+    // ... as a device table that the caller owns and leaves unchanged until the consuming call's work is done
+    void set_motion_device(const void* d_records, uint32_t n_objects) {
+        if (rpt_temporal_set_motion_device(h_, d_records, n_objects) != RPT_OK) throw Error(rpt_last_error());
+    }
     Temporal(uint32_t w, uint32_t h, int device = 0) : width(w), height(h) {
         h_ = rpt_temporal_create(device, w, h);
         if (!h_) throw Error(rpt_last_error());

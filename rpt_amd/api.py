@@ -61,7 +61,7 @@ __all__ = [
     "vec3", "hex_color", "color_bytes", "Sphere", "Cube", "Plane", "Triangle", "Mesh", "KdTree", "Transformed",
     "MonomialSurface", "sphere", "cube", "plane", "polygon", "monomial_surface", "Material", "Object", "Light", "Medium", "Environment",
     "Scene", "Camera", "Filter", "Buffer", "DeviceBuffer", "Renderer", "RptError", "DenoiseParams", "Denoiser", "AdaptiveParams",
-    "TemporalParams", "TemporalAccumulator", "temporal_camera_record",
+    "TemporalParams", "TemporalAccumulator", "temporal_camera_record", "temporal_motion_record",
 ]
 
 
@@ -947,6 +947,20 @@ def temporal_camera_record(camera):
     return out
 
 
+MOTION_DOUBLES = 24
+
+
+def temporal_motion_record(cur, prev):
+    """rpt_temporal_motion_record -> the 24 doubles A (3 x 4), G (3 x 3), three zeros of an object whose object-to-world matrices
+    are `cur` in the current and `prev` in the previous frame (4 x 4, as Shape.matrix() gives them; None: the identity).  A host
+    function."""
+    mats = [np.ascontiguousarray(np.eye(4) if m is None else m, dtype=np.float64).reshape(16) for m in (cur, prev)]
+    out = np.empty(MOTION_DOUBLES, dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    _lib.check(_lib.load().rpt_temporal_motion_record(mats[0].ctypes.data_as(dp), mats[1].ctypes.data_as(dp), out.ctypes.data_as(dp)))
+    return out
+
+
 class TemporalAccumulator:
     """rpt_temporal: the history of a frame sequence of one size on one device, and the accumulation of include/rpt_hip.h."""
 
@@ -990,8 +1004,24 @@ class TemporalAccumulator:
             self._h, C.byref(params.desc()), C.byref(camera_desc(camera, _lib.CameraDesc)),
             *[C.c_void_p(p or None) for p in (d_rgb, d_var, d_normal, d_depth, d_out, d_out_var, d_out_len)], C.c_void_p(stream_ptr)))
 
+    def set_motion(self, records):
+        """rpt_temporal_set_motion: an (n, 24) array of motion records (temporal_motion_record), record i for the object with id
+        i + 1, or None to clear.  One-shot: the next accumulate, accumulate_device or temporal_image consumes the table."""
+        if records is None:
+            _lib.check(_lib.load().rpt_temporal_set_motion(self._h, None, 0))
+            return
+        records = np.ascontiguousarray(records, dtype=np.float64)
+        if records.ndim != 2 or records.shape[1] != MOTION_DOUBLES:
+            raise ValueError("set_motion: records must be an (n, 24) array")
+        _lib.check(_lib.load().rpt_temporal_set_motion(self._h, records.ctypes.data_as(C.POINTER(C.c_double)), records.shape[0]))
+
+    def set_motion_device(self, ptr, n):
+        """rpt_temporal_set_motion_device: a device table of n records that the caller owns and leaves unchanged until the
+        consuming call's work is done.  One-shot, like set_motion."""
+        _lib.check(_lib.load().rpt_temporal_set_motion_device(self._h, C.c_void_p(ptr or None), int(n)))
+
     def reset(self):
-        """Forget the history: the next frame passes through."""
+        """Forget the history (and a motion table that was not consumed): the next frame passes through."""
         _lib.check(_lib.load().rpt_temporal_reset(self._h))
 
     @property
@@ -1266,8 +1296,12 @@ class Renderer:
         buffer.close()
         return img
 
-    def render_sequence(self, cameras, batches=4, temporal=None, denoise=None):
-        """An addition: a generator of one (h, w, 3) uint8 frame per camera of `cameras`, for a camera that moves over this scene.
+    def render_sequence(self, cameras, batches=4, temporal=None, denoise=None, scenes=None):
+        """An addition: a generator of one (h, w, 3) uint8 frame per camera of `cameras`, for a camera that moves over this scene
+        or, with `scenes` (one Scene per camera, as the reference builds one per frame: the same number of objects with the same
+        base shape kinds in the same order, else ValueError), over objects that move: frame f renders scenes[f], committed when its
+        turn comes, and for f > 0 the accumulation gets the motion table built by temporal_motion_record from
+        objects[i].shape.matrix() of scenes[f] and scenes[f - 1]; self.scene is left as it was.
         Frame f renders num_samples in `batches` batches (as render_denoised) at the sample offsets f * num_samples .. (fresh random
         streams per frame) into a DeviceBuffer, the feature planes of the same camera samples, then DeviceBuffer.temporal_image
         with one TemporalAccumulator for the sequence: mean and variance, accumulation over the previous frames (`temporal`: a
@@ -1287,9 +1321,18 @@ class Renderer:
         cameras = list(cameras)
         if len(cameras) * self.num_samples_ >= 1 << 32:
             raise ValueError("render_sequence: frames * num_samples must fit 32 bits")
-        return self._render_sequence(cameras, batches, temporal or TemporalParams(), denoise)
+        if scenes is not None:
+            scenes = list(scenes)
+            if len(scenes) != len(cameras):
+                raise ValueError("render_sequence: scenes must hold one Scene per camera")
+            if any(not isinstance(sc, Scene) for sc in scenes):
+                raise ValueError("render_sequence: scenes must hold Scene objects")
+            kinds = [[o.shape.base().KIND for o in sc.objects] for sc in scenes]
+            if any(k != kinds[0] for k in kinds[1:]):
+                raise ValueError("render_sequence: every scene must hold the same base shape kinds in the same order")
+        return self._render_sequence(cameras, batches, temporal or TemporalParams(), denoise, scenes)
 
-    def _render_sequence(self, cameras, batches, temporal, denoise):
+    def _render_sequence(self, cameras, batches, temporal, denoise, scenes=None):
         accumulator = TemporalAccumulator(self.width_, self.height_, self.device_)
         denoiser = Denoiser(self.width_, self.height_, self.device_) if denoise is not None else None
         n = self.width_ * self.height_ * 3
@@ -1297,10 +1340,16 @@ class Renderer:
         _sync(self.device_)
         ptrs = [planes.data_ptr() + 8 * n * k for k in range(3)]
         base, extra = divmod(self.num_samples_, batches)
-        own = self.camera
+        own, own_scene = self.camera, self.scene
         try:
             for f, cam in enumerate(cameras):
                 self.camera = cam
+                if scenes is not None:
+                    self.scene = scenes[f]
+                    if f > 0:
+                        accumulator.set_motion(np.stack([temporal_motion_record(c.shape.matrix(), p.shape.matrix())
+                                                         for c, p in zip(scenes[f].objects, scenes[f - 1].objects)])
+                                               if scenes[f].objects else None)
                 buffer = DeviceBuffer(self.width_, self.height_, None, self.device_)
                 self.features_device(self.num_samples_, *ptrs, sample_offset=f * self.num_samples_)
                 self._sample_offset = f * self.num_samples_
@@ -1308,10 +1357,10 @@ class Renderer:
                     self.sample(base + (1 if k < extra else 0), buffer)
                 img = buffer.temporal_image(accumulator, cam, dict(zip(("albedo", "normal", "depth"), ptrs)), temporal, denoiser, denoise)
                 buffer.close()
-                self.camera = own
+                self.camera, self.scene = own, own_scene
                 yield img
         finally:
-            self.camera = own
+            self.camera, self.scene = own, own_scene
             accumulator.close()
             if denoiser is not None:
                 denoiser.close()

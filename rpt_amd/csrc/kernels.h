@@ -142,10 +142,16 @@ struct TemporalArgs {
     const double* hist_in;                               // [n_pixels][kTemporalRecDoubles]
     double* hist_out;
     double *out_rgb, *out_var, *out_len;                 // out_var, out_len: or null
+    const double* motion;                                // [n_motion][kTemporalMotionDoubles] motion records, or null: no table is set
+    uint32_t n_motion, pad2_;                            // (with a table the launcher takes the kernel's second instantiation)
 };
+static constexpr uint32_t kTemporalMotionDoubles = 24;   // RPT_TEMPORAL_MOTION_DOUBLES: A 3 x 4, G 3 x 3, three zeros
 // (Weak: reached from rpt_temporal_accumulate* / rpt_temporal_frame_image alone, which report RPT_ERR_UNSUPPORTED where no kernel
 // library is linked.)
 __attribute__((weak)) hipError_t launch_temporal_accumulate(const TemporalArgs& a, hipStream_t stream);
+// rpt_temporal_set_motion's table on its way to the device: `bytes` from host memory to d_table, enqueued on `stream` (the host
+// array may be reused as soon as the call returns).  (Weak, like the launcher above.)
+__attribute__((weak)) hipError_t launch_temporal_motion_upload(void* d_table, const double* records, size_t bytes, hipStream_t stream);
 // Adaptive sampling by tile (adaptive.hip).  A buffer whose tiles have different batch counts: a pixel of tile t holds
 // n_batches + extra[t] batches (extra null: no tile batch was ever added).
 struct TileBufferView {

@@ -3464,6 +3464,13 @@ struct rpt_temporal {
     rpti::DevMem d_frame;              // rpt_temporal_frame_image: mean, variance, accumulated frame and variance, filtered frame
     rpti::Event done;                  // recorded after the kernel of a call: the next call waits for it, whatever its stream
     bool used = false;
+    // The one-shot motion table of the next call that passes its checks (motion_set: 0 none, 1 host records, 2 the caller's device table).
+    int motion_set = 0;
+    uint32_t n_motion = 0;
+    std::vector<double> motion_host;   // rpt_temporal_set_motion's copy, uploaded by the consuming call on its stream
+    std::vector<double> motion_sent;   // ... and the copy the last upload read (never the one a later set writes)
+    const double* motion_dev = nullptr;  // rpt_temporal_set_motion_device's table
+    rpti::DevMem d_motion;             // the uploaded table
 };
 rpt_temporal* rpt_temporal_create(int device, uint32_t width, uint32_t height) {
     if (width == 0 || height == 0 || uint64_t(width) * height >= (1ull << 31)) { fail(RPT_ERR_INVALID, "bad accumulator size"); return nullptr; }
@@ -3491,11 +3498,77 @@ void rpt_temporal_destroy(rpt_temporal* t) {
 int rpt_temporal_reset(rpt_temporal* t) {
     if (!t) return fail(RPT_ERR_INVALID, "null accumulator");
     t->frames = 0;                     // the next call looks nothing up; what the arrays hold is never read
+    t->motion_set = 0;                 // a table that was not consumed belongs to the sequence that ends here
     return RPT_OK;
 }
 int rpt_temporal_frames(rpt_temporal* t, uint32_t* n) {
     if (!t || !n) return fail(RPT_ERR_INVALID, "null argument");
     *n = t->frames;
+    return RPT_OK;
+}
+// The nine cofactors k (the adjugate: inverse = k / det) and the determinant of a 3 x 3 matrix m, in the order include/rpt_hip.h states.
+static double cofactors3(const double m[3][3], double k[3][3]) {
+    k[0][0] = m[1][1] * m[2][2] - m[1][2] * m[2][1]; k[0][1] = m[0][2] * m[2][1] - m[0][1] * m[2][2]; k[0][2] = m[0][1] * m[1][2] - m[0][2] * m[1][1];
+    k[1][0] = m[1][2] * m[2][0] - m[1][0] * m[2][2]; k[1][1] = m[0][0] * m[2][2] - m[0][2] * m[2][0]; k[1][2] = m[0][2] * m[1][0] - m[0][0] * m[1][2];
+    k[2][0] = m[1][0] * m[2][1] - m[1][1] * m[2][0]; k[2][1] = m[0][1] * m[2][0] - m[0][0] * m[2][1]; k[2][2] = m[0][0] * m[1][1] - m[0][1] * m[1][0];
+    return (m[0][0] * k[0][0] + m[0][1] * k[1][0]) + m[0][2] * k[2][0];
+}
+// (No operation below may be contracted into an fma: the pragma above check_scene64 holds to the end of the file.)
+int rpt_temporal_motion_record(const double cur[16], const double prev[16], double out[24]) {
+    if (!cur || !prev || !out) return fail(RPT_ERR_INVALID, "null argument");
+    bool same = true;
+    for (int i = 0; i < 16; i++) {
+        if (!std::isfinite(cur[i]) || !std::isfinite(prev[i])) return fail(RPT_ERR_INVALID, "motion record: a matrix value is not finite");
+        same = same && cur[i] == prev[i];
+    }
+    for (const double* m : {cur, prev})
+        if (m[12] != 0.0 || m[13] != 0.0 || m[14] != 0.0 || m[15] != 1.0) return fail(RPT_ERR_INVALID, "motion record: the bottom row must be 0 0 0 1");
+    double c[3][3], k[3][3], a[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) c[i][j] = cur[4 * i + j];
+    const double det = cofactors3(c, k);
+    if (det == 0.0 || !std::isfinite(det)) return fail(RPT_ERR_INVALID, "motion record: the current matrix has no inverse");
+    for (int i = 0; i < 24; i++) out[i] = 0.0;
+    if (same) {
+        out[0] = out[5] = out[10] = out[12] = out[16] = out[20] = 1.0;
+        return RPT_OK;
+    }
+    double inv[3][3], u[3];
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) inv[i][j] = k[i][j] / det;
+        u[i] = -((inv[i][0] * cur[3] + inv[i][1] * cur[7]) + inv[i][2] * cur[11]);
+    }
+    for (int i = 0; i < 3; i++) {
+        const double* const p = prev + 4 * i;
+        for (int j = 0; j < 3; j++) a[i][j] = out[4 * i + j] = (p[0] * inv[0][j] + p[1] * inv[1][j]) + p[2] * inv[2][j];
+        out[4 * i + 3] = ((p[0] * u[0] + p[1] * u[1]) + p[2] * u[2]) + p[3];
+    }
+    const double det_a = cofactors3(a, k);
+    if (det_a == 0.0 || !std::isfinite(det_a)) {
+        for (int i = 0; i < 24; i++) out[i] = 0.0;
+        return fail(RPT_ERR_INVALID, "motion record: the map between the frames has no inverse");
+    }
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) out[12 + 3 * i + j] = k[j][i] / det_a;
+    return RPT_OK;
+}
+int rpt_temporal_set_motion(rpt_temporal* t, const double* records, uint32_t n_objects) {
+    if (!records && n_objects) return fail(RPT_ERR_INVALID, "null motion records");
+    for (size_t o = 0; o < n_objects; o++)
+        for (int i = 0; i < 21; i++)
+            if (!std::isfinite(records[o * kTemporalMotionDoubles + i])) return fail(RPT_ERR_INVALID, "motion records: a value is not finite");
+    if (!t) return fail(RPT_ERR_INVALID, "null accumulator");
+    t->motion_set = n_objects ? 1 : 0;
+    t->n_motion = n_objects;
+    t->motion_host.assign(records, records + size_t(n_objects) * kTemporalMotionDoubles);
+    return RPT_OK;
+}
+int rpt_temporal_set_motion_device(rpt_temporal* t, const void* d_records, uint32_t n_objects) {
+    if (!d_records && n_objects) return fail(RPT_ERR_INVALID, "null motion records");
+    if (!t) return fail(RPT_ERR_INVALID, "null accumulator");
+    t->motion_set = n_objects ? 2 : 0;
+    t->n_motion = n_objects;
+    t->motion_dev = static_cast<const double*>(d_records);
     return RPT_OK;
 }
 // What rpt_temporal_* refuse before any device call; the call's camera record to *rec.
@@ -3537,6 +3610,22 @@ static int run_temporal(rpt_temporal* t, const rpt_temporal_params* prm, const T
     a.hist_in = t->d_rec[t->cur].get<double>();
     a.hist_out = t->d_rec[t->cur ^ 1].get<double>();
     a.out_rgb = d_out; a.out_var = d_out_var; a.out_len = d_out_len;
+    if (t->motion_set == 1) {
+        // behind the predecessor's event on this call's stream: the kernel of an earlier call may still be reading d_motion
+        if (!launch_temporal_motion_upload) return fail(RPT_ERR_UNSUPPORTED, "rpt_temporal_set_motion: built without the kernels");
+        const size_t bytes = size_t(t->n_motion) * kTemporalMotionDoubles * sizeof(double);
+        HIP_TRY(t->d_motion.reserve(bytes));
+        t->motion_sent.swap(t->motion_host);
+        if (hipError_t e = launch_temporal_motion_upload(t->d_motion.get(), t->motion_sent.data(), bytes, st); e != hipSuccess) {
+            t->motion_sent.swap(t->motion_host);   // the table stays set for the next call
+            return fail(RPT_ERR_DEVICE, std::string("the motion table's upload: ") + hipGetErrorString(e));
+        }
+        a.motion = t->d_motion.get<double>();
+    } else if (t->motion_set == 2) {
+        a.motion = t->motion_dev;
+    }
+    a.n_motion = a.motion ? t->n_motion : 0u;
+    t->motion_set = 0;                 // one-shot: the table describes this frame's motion only
     HIP_TRY(launch_temporal_accumulate(a, st));
     HIP_TRY(hipEventRecord(t->done.get(), st));
     t->cur ^= 1;

@@ -1,7 +1,8 @@
 // temporal.hip — rpt_temporal_*: temporal accumulation with reprojection for a camera moving over a scene whose objects keep their
-// places and indices (an addition: the reference renders every frame of a sequence from nothing).  The arithmetic is the order of fp64
-// operations that include/rpt_hip.h states, every one rounded on its own (contraction off, IEEE division and square root, no atomics):
-// tests/temporal_ref.py restates it in numpy and the kernel's output is compared with it bit for bit.
+// indices and either keep their places or move by a motion record per object (an addition: the reference renders every frame of a
+// sequence from nothing).  The arithmetic is the order of fp64 operations that include/rpt_hip.h states, every one rounded on its
+// own (contraction off, IEEE division and square root, no atomics): tests/temporal_ref.py and tests/temporal_motion_ref.py restate it
+// in numpy and the kernel's output is compared with them bit for bit.
 //
 // One kernel, a plain grid of 16 x 16 pixel blocks (a wave = 16 x 4 neighbouring pixels), one lane per pixel: the pixel's surface point
 // from the depth plane and the current camera record, its place in the previous frame from the stored record, up to four taps of the
@@ -28,6 +29,10 @@ constexpr uint32_t kTile = 16;         // pixels per block edge
 __device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 __device__ __forceinline__ bool finite(double t) { return !(t - t != 0.0); }
 
+// MOTION: a table of motion records is set for the call (a.motion, a.n_motion): the pixel's point and normal go through the record
+// of the pixel's object before the history is looked up.  Every lane loads its own record with plain vector loads: a wave is 16 x 4
+// neighbouring pixels that nearly always see one or two ids, so the 21 loads of its lanes fall on the same few cache lines.
+template <bool MOTION>
 __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const TemporalArgs a) {
     const uint32_t x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
     if (x >= a.width || y >= a.height) return;
@@ -53,7 +58,22 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const Temporal
         // 3: where the history saw that point
         const double s = zc / l;
         double q[3];
-        for (int k = 0; k < 3; k++) q[k] = (a.cur.eye[k] + s * v[k]) - a.prev.eye[k];
+        double nm[3] = {n[0], n[1], n[2]};                              // the normal the taps are tested against
+        if constexpr (MOTION) {
+            double P[3];
+            for (int k = 0; k < 3; k++) P[k] = a.cur.eye[k] + s * v[k];
+            if (id >= 1.0 && id <= double(a.n_motion)) {                // (false for NaN)
+                const double* const r = a.motion + size_t(uint32_t(id) - 1u) * kTemporalMotionDoubles;
+                const double P0 = P[0], P1 = P[1], P2 = P[2];
+                for (int k = 0; k < 3; k++) {
+                    P[k] = ((r[4 * k] * P0 + r[4 * k + 1] * P1) + r[4 * k + 2] * P2) + r[4 * k + 3];
+                    nm[k] = (r[12 + 3 * k] * n[0] + r[13 + 3 * k] * n[1]) + r[14 + 3 * k] * n[2];
+                }
+            }
+            for (int k = 0; k < 3; k++) q[k] = P[k] - a.prev.eye[k];
+        } else {
+            for (int k = 0; k < 3; k++) q[k] = (a.cur.eye[k] + s * v[k]) - a.prev.eye[k];
+        }
         const double zq = dot3(q, a.prev.dir);
         if (zq > 0.0) {
             const double u = (dot3(q, a.prev.right) * a.prev.d) / zq;
@@ -83,7 +103,7 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const Temporal
                             ok = ok && fabs(r - qq) <= a.depth_tol * qq;
                         }
                         if (normal) {
-                            const double e0 = h.n[0] - n[0], e1 = h.n[1] - n[1], e2 = h.n[2] - n[2];
+                            const double e0 = h.n[0] - nm[0], e1 = h.n[1] - nm[1], e2 = h.n[2] - nm[2];
                             ok = ok && ((e0 * e0 + e1 * e1) + e2 * e2) <= nt2;
                         }
                         if (ok) {
@@ -133,8 +153,15 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const Temporal
 hipError_t launch_temporal_accumulate(const TemporalArgs& a, hipStream_t stream) {
     if (!a.width || !a.height) return hipSuccess;
     const dim3 grid((a.width + kTile - 1) / kTile, (a.height + kTile - 1) / kTile), block(kTile, kTile);
-    hipLaunchKernelGGL(temporal_accumulate_kernel, grid, block, 0, stream, a);
+    if (a.motion)
+        hipLaunchKernelGGL(temporal_accumulate_kernel<true>, grid, block, 0, stream, a);
+    else
+        hipLaunchKernelGGL(temporal_accumulate_kernel<false>, grid, block, 0, stream, a);
     return hipGetLastError();
+}
+
+hipError_t launch_temporal_motion_upload(void* d_table, const double* records, size_t bytes, hipStream_t stream) {
+    return hipMemcpyAsync(d_table, records, bytes, hipMemcpyHostToDevice, stream);
 }
 
 }  // namespace rptg

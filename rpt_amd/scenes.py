@@ -275,6 +275,22 @@ def monomial_glass(env=(0.6, 0.65, 0.7)):
     return scene, Camera(), {"width": 800, "height": 600, "spp": 100, "max_bounces": 1}
 
 
+def simple_video(frame, step=0.01):
+    """examples/simple_video.rs:10-55 (800x600x100, max_bounces(1) there): frame `frame` of a sequence in which a cube slides towards
+    the default camera, z = 4.0 + step * frame (the example: step 0.01, frames 0..59, one Scene per frame), past a unit sphere, two
+    small spheres and a floor.  Not in CONFIGS (bench.py reads that)."""
+    scene = Scene()
+    scene.add(Object(sphere()))
+    scene.add(Object(cube().rotate_y(math.pi / 6.0).scale(vec3(0.5, 0.3, 0.4)).translate(vec3(0.4, -0.8, 4.0 + step * frame)))
+              .material(Material.specular(hex_color(0xFF00FF), 0.5)))
+    scene.add(Object(sphere().scale(vec3(0.5, 0.5, 0.5)).translate(vec3(1.5, -0.5, 1.0))).material(Material.specular(hex_color(0x0000FF), 0.1)))
+    scene.add(Object(sphere().scale(vec3(0.5, 0.5, 0.5)).translate(vec3(-1.5, -0.5, 1.0))).material(Material.specular(hex_color(0x00FF00), 0.1)))
+    scene.add(Object(plane(vec3(0.0, 1.0, 0.0), -1.0)).material(Material.specular(hex_color(0xAAAAAA), 0.5)))
+    scene.add(Light.Ambient(vec3(0.01, 0.01, 0.01)))
+    scene.add(Light.Point(vec3(100.0, 100.0, 100.0), vec3(0.0, 5.0, 5.0)))
+    return scene, Camera(), {"width": 800, "height": 600, "spp": 100, "max_bounces": 1}
+
+
 CONFIGS = {
     "C1": spheres,
     "C2": cornell,
