@@ -551,6 +551,11 @@ class Temporal {
     void set_motion_device(const void* d_records, uint32_t n_objects) {
         if (rpt_temporal_set_motion_device(h_, d_records, n_objects) != RPT_OK) throw Error(rpt_last_error());
     }
+    // the settings of RPT_TEMPORAL_CLIP (params.flags): window radius 1..3, gamma >= 0, the history length a clipped pixel keeps
+    // (0: all of it); they persist over calls and resets
+    void set_clip(uint32_t radius = 1, double gamma = 0.5, uint32_t clip_history = 1) {
+        if (rpt_temporal_set_clip(h_, radius, gamma, clip_history) != RPT_OK) throw Error(rpt_last_error());
+    }
     Temporal(uint32_t w, uint32_t h, int device = 0) : width(w), height(h) {
         h_ = rpt_temporal_create(device, w, h);
         if (!h_) throw Error(rpt_last_error());

@@ -463,12 +463,36 @@ int rpt_buffer_denoised_image(rpt_buffer*, rpt_denoiser*, const rpt_denoise_para
  * place, rpt_temporal_reset drops it, a second set before consumption replaces the first: a stale table is wrong for every later
  * frame, so it never persists.  The host variant's upload is ordered like every call of the accumulator: on the consuming call's
  * stream, behind the predecessor's event, so a set issued while an earlier call is still queued does not change what that call
- * reads. */
+ * reads.
+ *
+ * History clipping (flag RPT_TEMPORAL_CLIP).  The reprojection follows geometry: it cannot see that the LIGHTING of an unchanged
+ * surface point has changed (the shadow of a moving object on a static floor, a light that moves), and blends the old lighting in for
+ * up to max_history frames.  With the flag, the reprojected history colour is clamped to mean +- gamma . sigma of the CURRENT frame's
+ * (2r + 1)^2 window around the pixel itself (not around the reprojected place), and a clipped pixel gives up most of its history
+ * length.  Three settings live on the accumulator (rpt_temporal_set_clip): radius r 1..3, gamma finite and >= 0, clip_history 0..4096
+ * (0: a clipped pixel keeps its length); anything else is RPT_ERR_INVALID, a NULL handle after that.  Defaults (1, 0.5, 1).  Host state
+ * only, no device is touched; the settings persist across calls and across rpt_temporal_reset (a setting, not data, unlike the
+ * one-shot motion table); they are read when a call with the flag passes its checks and ignored without the flag.
+ * A new step between 4 and 5, only with the flag and B > 0.0, in the arithmetic of the other steps; fmax(a, b) here is a if
+ * a >= b or b is NaN, else b, and fmin(a, b) is a if a <= b or b is NaN, else b (the operand that is not NaN; of two that compare
+ * equal, the first):
+ *        hc_k = C_k / B;  hl = L / B  (as step 5 forms them)
+ *        Window dy = -r..r (outer), dx = -r..r (inner), p' = (x + dx, y + dy); pixels outside the image are skipped.  A pixel counts
+ *        iff all three rgb[p']_k are finite (t - t == 0.0) and, with MATCH_ID, depth[p'][2] == id (false for NaN: a NaN id counts nothing).
+ *        n += 1.0;  S_k += c_k;  Q_k += c_k c_k  with c = rgb[p'], all from +0.0.
+ *        If n > 0.0:  m_k = S_k / n;  s_k = fmax(Q_k / n - m_k m_k, 0.0);  sd_k = sqrt(s_k)
+ *                     lo_k = m_k - gamma sd_k;  hi_k = m_k + gamma sd_k;  hc'_k = fmin(fmax(hc_k, lo_k), hi_k)
+ *                     clipped = some hc'_k != hc_k;  if clipped && clip_history > 0: hl = fmin(hl, double(clip_history))
+ *        otherwise hc' = hc.
+ * Step 5 continues with hc' and this hl.  hv is unchanged: the variance of a clipped pixel's history is NOT corrected (it describes
+ * the history before the clamp).  There are no new outputs: a clipped pixel shows in d_out_len.  The motion path (P', n') is
+ * untouched.  gamma = 0.5 over a 3 x 3 window also pulls history towards the local mean, which is a spatial blur. */
 #define RPT_TEMPORAL_MATCH_ID 1u
+#define RPT_TEMPORAL_CLIP 2u
 #define RPT_TEMPORAL_MOTION_DOUBLES 24u
 typedef struct rpt_temporal_params {
     uint32_t max_history;   /* 1..4096; 1 = no reuse */
-    uint32_t flags;         /* RPT_TEMPORAL_MATCH_ID */
+    uint32_t flags;         /* RPT_TEMPORAL_MATCH_ID | RPT_TEMPORAL_CLIP */
     double depth_tol;       /* on SQUARED distances, relative; 0 = test off */
     double normal_tol;      /* on the distance of the normal planes; 0 = off */
 } rpt_temporal_params;
@@ -481,6 +505,7 @@ int rpt_temporal_frames(rpt_temporal*, uint32_t* n);   /* frames since create / 
 int rpt_temporal_motion_record(const double cur[16], const double prev[16], double out[24]);
 int rpt_temporal_set_motion(rpt_temporal*, const double* records, uint32_t n_objects);          /* host array, copied; one-shot */
 int rpt_temporal_set_motion_device(rpt_temporal*, const void* d_records, uint32_t n_objects);   /* caller-owned device table; one-shot */
+int rpt_temporal_set_clip(rpt_temporal*, uint32_t radius, double gamma, uint32_t clip_history);      /* RPT_TEMPORAL_CLIP's settings; persistent */
 /* DEVICE pointers on the accumulator's device, hip_stream a hipStream_t (NULL = default stream).  d_out_rgb: width*height*3 doubles;
  * d_out_var, d_out_len: width*height doubles each, or NULL. */
 int rpt_temporal_accumulate_device(rpt_temporal*, const rpt_temporal_params*, const rpt_camera*, const void* d_rgb, const void* d_var,

@@ -162,6 +162,7 @@ SYMBOLS = [
     ("rpt_temporal_motion_record", C.c_int, [_D3, _D3, _D3]),
     ("rpt_temporal_set_motion", C.c_int, [_P, _D3, C.c_uint32]),
     ("rpt_temporal_set_motion_device", C.c_int, [_P, _P, C.c_uint32]),
+    ("rpt_temporal_set_clip", C.c_int, [_P, C.c_uint32, C.c_double, C.c_uint32]),
     ("rpt_temporal_accumulate_device", C.c_int,
      [_P, C.POINTER(TemporalParams), C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     ("rpt_temporal_accumulate", C.c_int, [_P, C.POINTER(TemporalParams), C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P, _P]),

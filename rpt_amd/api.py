@@ -920,11 +920,14 @@ class Denoiser:
 # ------------------------------------------------------------------ temporal accumulation (rpt_temporal_*, an addition)
 class TemporalParams:
     """rpt_temporal_params.  max_history 1..4096 caps the history length (1: no reuse); a test is on iff its tolerance > 0:
-    depth_tol relative, on squared distances, normal_tol on the distance of the normal planes."""
+    depth_tol relative, on squared distances, normal_tol on the distance of the normal planes.  clip=True sets RPT_TEMPORAL_CLIP:
+    the history colour is clamped to the current frame's window around the pixel, with the accumulator's settings
+    (TemporalAccumulator.set_clip)."""
     MATCH_ID = 1
+    CLIP = 2
 
-    def __init__(self, max_history=16, match_id=True, depth_tol=0.1, normal_tol=0.5):
-        self.max_history, self.match_id = int(max_history), bool(match_id)
+    def __init__(self, max_history=16, match_id=True, depth_tol=0.1, normal_tol=0.5, clip=False):
+        self.max_history, self.match_id, self.clip = int(max_history), bool(match_id), bool(clip)
         self.depth_tol, self.normal_tol = float(depth_tol), float(normal_tol)
         if not 1 <= self.max_history <= 4096:
             raise ValueError("TemporalParams: max_history must be 1..4096")
@@ -934,7 +937,7 @@ class TemporalParams:
 
     @property
     def flags(self):
-        return self.MATCH_ID if self.match_id else 0
+        return (self.MATCH_ID if self.match_id else 0) | (self.CLIP if self.clip else 0)
 
     def desc(self):
         return _lib.TemporalParams(self.max_history, self.flags, self.depth_tol, self.normal_tol)
@@ -1019,6 +1022,12 @@ class TemporalAccumulator:
         """rpt_temporal_set_motion_device: a device table of n records that the caller owns and leaves unchanged until the
         consuming call's work is done.  One-shot, like set_motion."""
         _lib.check(_lib.load().rpt_temporal_set_motion_device(self._h, C.c_void_p(ptr or None), int(n)))
+
+    def set_clip(self, radius=1, gamma=0.5, history=1):
+        """rpt_temporal_set_clip: the settings of TemporalParams(clip=True) -- the window's radius 1..3, the width gamma >= 0 of the
+        clamp in standard deviations of the window, and the history length 0..4096 a clipped pixel keeps (0: all of it).  A host
+        setting that persists over calls and over reset(); without clip=True it is ignored."""
+        _lib.check(_lib.load().rpt_temporal_set_clip(self._h, int(radius), float(gamma), int(history)))
 
     def reset(self):
         """Forget the history (and a motion table that was not consumed): the next frame passes through."""

@@ -134,7 +134,7 @@ struct TemporalCam {
     double eye[3], dir[3], right[3], up[3], d;
 };
 struct TemporalArgs {
-    uint32_t width, height, max_history, flags;          // RPT_TEMPORAL_MATCH_ID
+    uint32_t width, height, max_history, flags;          // RPT_TEMPORAL_MATCH_ID | RPT_TEMPORAL_CLIP
     uint32_t have_history, pad_;                         // 0: hist_in holds no frame (the first call, or the first after a reset)
     double depth_tol, normal_tol;                        // 0: the test is off
     TemporalCam cur, prev;                               // prev: the record stored with hist_in
@@ -144,7 +144,11 @@ struct TemporalArgs {
     double *out_rgb, *out_var, *out_len;                 // out_var, out_len: or null
     const double* motion;                                // [n_motion][kTemporalMotionDoubles] motion records, or null: no table is set
     uint32_t n_motion, pad2_;                            // (with a table the launcher takes the kernel's second instantiation)
+    // RPT_TEMPORAL_CLIP (flags): rpt_temporal_set_clip's settings; without the flag they are 0 and never read
+    uint32_t clip_radius, clip_history;                  // 1..kTemporalClipMaxRadius; 0..4096, 0: a clipped pixel keeps its length
+    double clip_gamma;
 };
+static constexpr uint32_t kTemporalClipMaxRadius = 3;    // the largest window radius whose halo the kernel's tile holds
 static constexpr uint32_t kTemporalMotionDoubles = 24;   // RPT_TEMPORAL_MOTION_DOUBLES: A 3 x 4, G 3 x 3, three zeros
 // (Weak: reached from rpt_temporal_accumulate* / rpt_temporal_frame_image alone, which report RPT_ERR_UNSUPPORTED where no kernel
 // library is linked.)

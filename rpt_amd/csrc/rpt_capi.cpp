@@ -3471,6 +3471,9 @@ struct rpt_temporal {
     std::vector<double> motion_sent;   // ... and the copy the last upload read (never the one a later set writes)
     const double* motion_dev = nullptr;  // rpt_temporal_set_motion_device's table
     rpti::DevMem d_motion;             // the uploaded table
+    // rpt_temporal_set_clip's settings, read by a call with RPT_TEMPORAL_CLIP: a setting, kept over calls and resets
+    uint32_t clip_radius = 1, clip_history = 1;
+    double clip_gamma = 0.5;
 };
 rpt_temporal* rpt_temporal_create(int device, uint32_t width, uint32_t height) {
     if (width == 0 || height == 0 || uint64_t(width) * height >= (1ull << 31)) { fail(RPT_ERR_INVALID, "bad accumulator size"); return nullptr; }
@@ -3571,12 +3574,22 @@ int rpt_temporal_set_motion_device(rpt_temporal* t, const void* d_records, uint3
     t->motion_dev = static_cast<const double*>(d_records);
     return RPT_OK;
 }
+int rpt_temporal_set_clip(rpt_temporal* t, uint32_t radius, double gamma, uint32_t clip_history) {
+    if (radius < 1 || radius > kTemporalClipMaxRadius) return fail(RPT_ERR_INVALID, "clip radius must be 1..3");
+    if (!(gamma >= 0.0) || std::isinf(gamma)) return fail(RPT_ERR_INVALID, "clip gamma must be finite and >= 0");
+    if (clip_history > 4096) return fail(RPT_ERR_INVALID, "clip_history must be 0..4096 (0: a clipped pixel keeps its length)");
+    if (!t) return fail(RPT_ERR_INVALID, "null accumulator");
+    t->clip_radius = radius;
+    t->clip_gamma = gamma;
+    t->clip_history = clip_history;
+    return RPT_OK;
+}
 // What rpt_temporal_* refuse before any device call; the call's camera record to *rec.
 static int check_temporal(const rpt_temporal* t, const rpt_temporal_params* prm, const rpt_camera* cam, const void* rgb, const void* var,
                           const void* normal, const void* depth, const void* out, const void* out_var, const void* out_len, TemporalCam* rec) {
     if (!prm) return fail(RPT_ERR_INVALID, "null temporal parameters");
     if (prm->max_history < 1 || prm->max_history > 4096) return fail(RPT_ERR_INVALID, "max_history must be 1..4096");
-    if (prm->flags & ~RPT_TEMPORAL_MATCH_ID) return fail(RPT_ERR_INVALID, "unknown temporal flag");
+    if (prm->flags & ~(RPT_TEMPORAL_MATCH_ID | RPT_TEMPORAL_CLIP)) return fail(RPT_ERR_INVALID, "unknown temporal flag");
     for (double tol : {prm->depth_tol, prm->normal_tol})
         if (!(tol >= 0.0) || std::isinf(tol)) return fail(RPT_ERR_INVALID, "a tolerance must be finite and >= 0 (0: the test is off)");
     if (!cam) return fail(RPT_ERR_INVALID, "null camera");
@@ -3590,7 +3603,8 @@ static int check_temporal(const rpt_temporal* t, const rpt_temporal_params* prm,
         for (const void* in : {rgb, var, normal, depth})
             if (o && o == in) return fail(RPT_ERR_INVALID, "an output must not be one of the inputs");
     if (out == out_var || out == out_len || (out_var && out_var == out_len)) return fail(RPT_ERR_INVALID, "the outputs must differ");
-    if (!t) return fail(RPT_ERR_INVALID, "null accumulator");
+    // (with RPT_TEMPORAL_CLIP the call would read its three settings from the accumulator: the refusal names the flag that needs them)
+    if (!t) return fail(RPT_ERR_INVALID, (prm->flags & RPT_TEMPORAL_CLIP) ? "null accumulator: the flag RPT_TEMPORAL_CLIP reads its settings from it" : "null accumulator");
     return RPT_OK;
 }
 // (The arguments have passed check_temporal.)
@@ -3610,6 +3624,9 @@ static int run_temporal(rpt_temporal* t, const rpt_temporal_params* prm, const T
     a.hist_in = t->d_rec[t->cur].get<double>();
     a.hist_out = t->d_rec[t->cur ^ 1].get<double>();
     a.out_rgb = d_out; a.out_var = d_out_var; a.out_len = d_out_len;
+    if (prm->flags & RPT_TEMPORAL_CLIP) {
+        a.clip_radius = t->clip_radius; a.clip_gamma = t->clip_gamma; a.clip_history = t->clip_history;
+    }
     if (t->motion_set == 1) {
         // behind the predecessor's event on this call's stream: the kernel of an earlier call may still be reading d_motion
         if (!launch_temporal_motion_upload) return fail(RPT_ERR_UNSUPPORTED, "rpt_temporal_set_motion: built without the kernels");

@@ -9,6 +9,10 @@
 // old history (one contiguous 80-byte record each; neighbouring lanes land on neighbouring records, so the taps of a wave overlap in
 // L2), the blend, and the pixel's new record written to the other array.  Both camera records are kernel arguments, uniform over the
 // grid.  A NULL plane is a uniform branch that yields the value the definition names (0.0), so the bits do not depend on it.
+//
+// RPT_TEMPORAL_CLIP is a third and fourth instantiation of the same kernel: before anything else the block stages the current frame's
+// (16 + 2r)^2 halo -- the three colour planes and one "key" per cell that folds the count rule's inside-the-image, finite and id
+// parts into one comparison -- in LDS; a pixel that took history then sums its window from LDS in the definition's order.
 #include <hip/hip_runtime.h>
 
 #include "../../include/rpt_hip.h"
@@ -25,16 +29,49 @@ struct alignas(16) TemporalRec {
 static_assert(sizeof(TemporalRec) == kTemporalRecDoubles * sizeof(double), "one record is 80 contiguous bytes");
 
 constexpr uint32_t kTile = 16;         // pixels per block edge
+// The clip halo: at most (16 + 2 * 3)^2 cells of four doubles (r, g, b, key) as two arrays of rows of 48 doubles, r | b in columns
+// 0..21 and g | key in columns 24..45.  A 32-lane half of a wave is two rows of 16 neighbouring pixels; it reads 16 consecutive
+// doubles (32 banks of the 64 that an 8-byte LDS read sees) of two consecutive rows, and a pitch of 48 doubles = 96 dwords = 32
+// (mod 64) puts the second row on the other 32 banks: no conflict at any radius or window offset.  (22, the smallest pitch, would
+// overlap 12 banks: 2-way.)  16.5 KiB per block, nine blocks per CU.
+constexpr uint32_t kHaloSide = kTile + 2 * kTemporalClipMaxRadius, kHaloPitch = 48, kHaloSecond = 24;
+static_assert(kHaloSecond >= kHaloSide && kHaloSecond + kHaloSide <= kHaloPitch && (2 * kHaloPitch) % 64 == 32, "the halo's layout");
 
 __device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 __device__ __forceinline__ bool finite(double t) { return !(t - t != 0.0); }
+// fmax and fmin as the clipping step defines them: the operand that is not NaN; of two that compare equal, the first
+__device__ __forceinline__ double clip_max(double a, double b) { return (a >= b || b != b) ? a : b; }
+__device__ __forceinline__ double clip_min(double a, double b) { return (a <= b || b != b) ? a : b; }
 
 // MOTION: a table of motion records is set for the call (a.motion, a.n_motion): the pixel's point and normal go through the record
 // of the pixel's object before the history is looked up.  Every lane loads its own record with plain vector loads: a wave is 16 x 4
 // neighbouring pixels that nearly always see one or two ids, so the 21 loads of its lanes fall on the same few cache lines.
-template <bool MOTION>
+// CLIP: flag RPT_TEMPORAL_CLIP.  The key of a halo cell is NaN where the cell lies outside the image or its colour is not finite,
+// else its id with MATCH_ID and 0.0 without; a cell counts iff key == (MATCH_ID ? the pixel's id : 0.0), which is false for NaN.
+template <bool MOTION, bool CLIP>
 __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const TemporalArgs a) {
     const uint32_t x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
+    __shared__ double halo[CLIP ? 2 : 1][CLIP ? kHaloSide : 1][CLIP ? kHaloPitch : 1];
+    if constexpr (CLIP) {
+        // every thread of the block, the ones outside the image included, stages and reaches the barrier
+        const uint32_t r = a.clip_radius, side = kTile + 2u * r;
+        const bool match = a.flags & RPT_TEMPORAL_MATCH_ID;
+        for (uint32_t i = threadIdx.y * kTile + threadIdx.x; i < side * side; i += kTile * kTile) {
+            const uint32_t cy = i / side, cx = i - cy * side;
+            const uint32_t gx = blockIdx.x * kTile + cx - r, gy = blockIdx.y * kTile + cy - r;   // (left of / above the image wraps to a large value)
+            double c0 = 0.0, c1 = 0.0, c2 = 0.0, key = __builtin_nan("");
+            if (gx < a.width && gy < a.height) {
+                const size_t g = size_t(gy) * a.width + gx;
+                c0 = a.rgb[3 * g]; c1 = a.rgb[3 * g + 1]; c2 = a.rgb[3 * g + 2];
+                if (finite(c0) && finite(c1) && finite(c2)) key = match ? a.depth[3 * g + 2] : 0.0;
+            }
+            halo[0][cy][cx] = c0;
+            halo[0][cy][kHaloSecond + cx] = c1;
+            halo[1][cy][cx] = c2;
+            halo[1][cy][kHaloSecond + cx] = key;
+        }
+        __syncthreads();
+    }
     if (x >= a.width || y >= a.height) return;
     const size_t p = size_t(y) * a.width + x;
     const double fw = double(a.width), fh = double(a.height), dim = double(a.width > a.height ? a.width : a.height);
@@ -122,13 +159,43 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const Temporal
     TemporalRec out;
     double len = 1.0;
     if (B > 0.0) {
-        const double hv = V / (B * B), hl = L / B;
+        const double hv = V / (B * B);
+        double hl = L / B;
+        double hc[3] = {C[0] / B, C[1] / B, C[2] / B};
+        if constexpr (CLIP) {
+            // between 4 and 5: the history colour clamped to the window of the current frame around the pixel itself
+            const int r = int(a.clip_radius);
+            const double want = (a.flags & RPT_TEMPORAL_MATCH_ID) ? id : 0.0;
+            double n_w = 0.0, S[3] = {0.0, 0.0, 0.0}, Q[3] = {0.0, 0.0, 0.0};
+            for (int dy = 0; dy <= 2 * r; dy++)
+                for (int dx = 0; dx <= 2 * r; dx++) {
+                    const uint32_t cy = threadIdx.y + dy, cx = threadIdx.x + dx;
+                    if (halo[1][cy][kHaloSecond + cx] == want) {
+                        const double c[3] = {halo[0][cy][cx], halo[0][cy][kHaloSecond + cx], halo[1][cy][cx]};
+                        n_w = n_w + 1.0;
+                        for (int k = 0; k < 3; k++) {
+                            S[k] = S[k] + c[k];
+                            Q[k] = Q[k] + c[k] * c[k];
+                        }
+                    }
+                }
+            if (n_w > 0.0) {
+                bool clipped = false;
+                for (int k = 0; k < 3; k++) {
+                    const double m = S[k] / n_w;
+                    const double s = clip_max(Q[k] / n_w - m * m, 0.0);
+                    const double g = a.clip_gamma * __dsqrt_rn(s);
+                    const double lo = m - g, hi = m + g;
+                    const double t = clip_min(clip_max(hc[k], lo), hi);
+                    clipped = clipped || t != hc[k];
+                    hc[k] = t;
+                }
+                if (clipped && a.clip_history > 0u) hl = clip_min(hl, double(a.clip_history));
+            }
+        }
         len = fmin(hl + 1.0, double(a.max_history));
         const double al = 1.0 / len, om = 1.0 - al;
-        for (int k = 0; k < 3; k++) {
-            const double hc = C[k] / B;
-            out.c[k] = hc + (rgb[k] - hc) * al;
-        }
+        for (int k = 0; k < 3; k++) out.c[k] = hc[k] + (rgb[k] - hc[k]) * al;
         out.v = (om * om) * hv + (al * al) * v_in;
     } else {
         out.c[0] = rgb[0]; out.c[1] = rgb[1]; out.c[2] = rgb[2];
@@ -153,10 +220,17 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const Temporal
 hipError_t launch_temporal_accumulate(const TemporalArgs& a, hipStream_t stream) {
     if (!a.width || !a.height) return hipSuccess;
     const dim3 grid((a.width + kTile - 1) / kTile, (a.height + kTile - 1) / kTile), block(kTile, kTile);
-    if (a.motion)
-        hipLaunchKernelGGL(temporal_accumulate_kernel<true>, grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL(temporal_accumulate_kernel<false>, grid, block, 0, stream, a);
+    if (a.flags & RPT_TEMPORAL_CLIP) {
+        if (a.clip_radius < 1 || a.clip_radius > kTemporalClipMaxRadius) return hipErrorInvalidValue;   // the halo would not hold the window
+        if (a.motion)
+            hipLaunchKernelGGL((temporal_accumulate_kernel<true, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((temporal_accumulate_kernel<false, true>), grid, block, 0, stream, a);
+    } else if (a.motion) {
+        hipLaunchKernelGGL((temporal_accumulate_kernel<true, false>), grid, block, 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((temporal_accumulate_kernel<false, false>), grid, block, 0, stream, a);
+    }
     return hipGetLastError();
 }
 

@@ -291,6 +291,36 @@ def simple_video(frame, step=0.01):
     return scene, Camera(), {"width": 800, "height": 600, "spp": 100, "max_bounces": 1}
 
 
+def _lit_video(cube_at, light_at):
+    """simple_video's five objects with a diffuse floor, under a sphere light that is also the sixth object (as spheres_lit: the
+    reference's visibility test passes no light without geometry, so simple_video's point light lights nothing)."""
+    scene = Scene()
+    scene.add(Object(sphere()))
+    scene.add(Object(cube().rotate_y(math.pi / 6.0).scale(vec3(0.5, 0.3, 0.4)).translate(vec3(*cube_at)))
+              .material(Material.specular(hex_color(0xFF00FF), 0.5)))
+    scene.add(Object(sphere().scale(vec3(0.5, 0.5, 0.5)).translate(vec3(1.5, -0.5, 1.0))).material(Material.specular(hex_color(0x0000FF), 0.1)))
+    scene.add(Object(sphere().scale(vec3(0.5, 0.5, 0.5)).translate(vec3(-1.5, -0.5, 1.0))).material(Material.specular(hex_color(0x00FF00), 0.1)))
+    scene.add(Object(plane(vec3(0.0, 1.0, 0.0), -1.0)).material(Material.diffuse(hex_color(0xAAAAAA))))
+    scene.add(Light.Ambient(vec3(0.01, 0.01, 0.01)))
+    light_mtl = Material.light(hex_color(0xFFFFFF), 20.0)
+    scene.add(Light.Object(Object(sphere().scale(vec3(0.5, 0.5, 0.5)).translate(vec3(*light_at))).material(light_mtl)))
+    scene.add(Object(sphere().scale(vec3(0.5, 0.5, 0.5)).translate(vec3(*light_at))).material(light_mtl))
+    return scene, Camera(), {"width": 800, "height": 600, "spp": 100, "max_bounces": 1}
+
+
+def sliding_shadow(frame, step=0.4):
+    """Frame `frame` of a sequence in which simple_video's cube slides in x over a diffuse floor, x = -1.5 + step * frame, under a
+    fixed sphere light at (0, 4, 4): its shadow moves over floor pixels whose geometry does not change.  The cube is object 2, the
+    light object 6.  Not in CONFIGS (bench.py reads that)."""
+    return _lit_video((-1.5 + step * frame, -0.7, 4.0), (0.0, 4.0, 4.0))
+
+
+def moving_light(frame, step=0.75):
+    """The same scene with the cube at rest at (0.4, -0.7, 4.0) and the light sliding in x, x = -3 + step * frame: the lighting of
+    every static pixel changes.  Not in CONFIGS."""
+    return _lit_video((0.4, -0.7, 4.0), (-3.0 + step * frame, 4.0, 4.0))
+
+
 CONFIGS = {
     "C1": spheres,
     "C2": cornell,
