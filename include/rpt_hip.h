@@ -778,6 +778,13 @@ int rpt_shadow_scan_info(rpt_scene*, uint32_t light, uint32_t out[4]);
 #define RPT_SCAN_JIT_CACHE_DISK 2    /* hit: read from the cache directory */
 #define RPT_SCAN_JIT_CACHE_MISS 3    /* compiled for this scene */
 int rpt_scan_jit_info(rpt_scene*, int64_t out[8], char* text, uint64_t text_capacity);
+/* The second block of constants such a kernel is compiled with: what the code around the scans knows when the scene is committed.
+ * text: "groups=<lights+tables+mats+small+pairs | none>;lights=<n>:<kind[/shape[/xf][/twin][/lo-hi]]>|...;mats=0x<mask of material
+ * kinds>;medium_kind=<k>;hdri=<0|1>;pairs=0x<three common-slab bits per pair of boxes>", truncated to text_capacity; a group that is
+ * not in effect for this scene (more than 4 lights, a table too large for LDS, more than 21 box pairs) says "view": its questions
+ * are answered from the scene's records at run time.  Scenes of one shape and one structure share a code object; record values --
+ * colours, transforms, boxes, light triangles -- are part of neither.  Empty for a scene outside the JIT's scope. */
+int rpt_scan_jit_structure(rpt_scene*, char* text, uint64_t text_capacity);
 /* Drops the process's code objects (not the cache directory's): the next scene of each shape looks on disk again.  Scenes that
  * already run a specialised kernel keep it.  Returns the number dropped. */
 int rpt_scan_jit_forget(void);

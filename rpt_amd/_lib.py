@@ -222,6 +222,7 @@ SYMBOLS = [
     ("rpt_debug_draw_forms", C.c_int, [C.c_uint64, C.c_uint32, _P, _P]),
     ("rpt_shadow_scan_info", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("rpt_scan_jit_info", C.c_int, [_P, C.POINTER(C.c_int64), _P, C.c_uint64]),
+    ("rpt_scan_jit_structure", C.c_int, [_P, _P, C.c_uint64]),
     ("rpt_scan_jit_forget", C.c_int, []),
     ("rpt_debug_material_f64", C.c_int, [C.POINTER(MaterialDesc), C.c_uint64, _P, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("rpt_debug_material_bsdf_f64", C.c_int, [C.POINTER(MaterialDesc), C.c_uint64, _P, _P, _P, _P]),

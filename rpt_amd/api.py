@@ -1627,14 +1627,16 @@ class Renderer:
     def scan_jit_info(self):
         """rpt_scan_jit_info: the scan kernel compiled for this scene's record counts (option "scan_jit") -> dict of state ("off", "idle",
         "active", "fallback", "out_of_scope"), cache ("none", "memory", "disk", "miss"), compile_ms, vgprs, scratch (bytes per lane),
-        launches (of the specialised kernel on this scene), compiles (in this process), aot_vgprs, shape and reason."""
+        launches (of the specialised kernel on this scene), compiles (in this process), aot_vgprs, shape, reason and structure
+        (rpt_scan_jit_structure: the second block of constants, "groups=...;lights=...;mats=...;medium_kind=...;hdri=...;pairs=...")."""
         out = (C.c_int64 * 8)()
-        text = C.create_string_buffer(2048)
+        text, structure = C.create_string_buffer(2048), C.create_string_buffer(512)
         _lib.check(_lib.load().rpt_scan_jit_info(self.scene._commit(self.device_), out, C.cast(text, C.c_void_p), len(text)))
+        _lib.check(_lib.load().rpt_scan_jit_structure(self.scene._commit(self.device_), C.cast(structure, C.c_void_p), len(structure)))
         shape, _, reason = text.value.decode(errors="replace").partition("\n")
         return {"state": ("off", "idle", "active", "fallback", "out_of_scope")[int(out[0])], "cache": ("none", "memory", "disk", "miss")[int(out[1])],
                 "compile_ms": out[2] / 1000.0, "vgprs": int(out[3]), "scratch": int(out[4]), "launches": int(out[5]), "compiles": int(out[6]),
-                "aot_vgprs": int(out[7]), "shape": shape, "reason": reason}
+                "aot_vgprs": int(out[7]), "shape": shape, "reason": reason, "structure": structure.value.decode(errors="replace")}
 
 
 # ---- per-call hooks that need no scene (rpt_debug_bounce, rpt_debug_distance_pair, rpt_debug_material_f64, rpt_debug_material_bsdf_f64)

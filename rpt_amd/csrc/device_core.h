@@ -702,6 +702,90 @@ struct ScanShapeK {
 #else
 typedef ScanShapeRt ScanShapeK;
 #endif
+// What the code AROUND the scans knows about the scene before it reads a record -- the second constant block of the scan JIT
+// (DESIGN.md section 4, round 11): which lights there are and of what kind and shape, whether the small tables are staged in LDS, which
+// material kinds occur, the medium's kind, whether there is an HDRI, the box pairs' common slabs.  All of it is fixed at commit.
+// SceneStructRt: every question is answered from the record or the view at its place of use, as ever.  SceneStructK (builds with
+// -DRPT_SCENE_STRUCT=groups,n_lights,light word x 4,twin_lo x 4,twin_hi x 4,material mask,medium_kind,hdri,pair bits): constants, one
+// group of them per bit of `groups`, so that a build can take them singly; a group whose bit is clear answers as SceneStructRt does.
+// Record VALUES -- colours, transforms, boxes, light triangles, a mesh light's count and first -- stay data in both.  No constant of the
+// block is a floating-point operand: nothing the compiler could fold through an approximate instruction (rcp, rsq, sqrt).
+// A light word: bits 0-1 kind, 2-3 shape, 4 its LightXf has a transform, 5 twin_object >= 0, 6 the twin is a code range (lo <= hi).
+// (The group bits SS_*, kStructLights and kStructPairs: gpu_layout.h, shared with the host.)
+struct LightRt {   // one light of the light loop, known from its record
+    uint32_t i;
+    RPT_DEV uint32_t kind(const Light& L) const { return L.kind; }
+    RPT_DEV uint32_t shape(const Light& L) const { return L.shape; }
+    RPT_DEV bool has_twin(const Light& L) const { return L.twin_object >= 0; }
+    RPT_DEV bool has_range(const Light& L) const { return L.twin_lo <= L.twin_hi; }
+    RPT_DEV uint32_t twin_lo(const Light& L) const { return L.twin_lo; }
+    RPT_DEV uint32_t twin_hi(const Light& L) const { return L.twin_hi; }
+    template <class X> RPT_DEV bool has_xf(const X& x) const { return x.has_transform(); }
+};
+struct SceneStructRt {
+    static constexpr bool kLights = false;
+    typedef LightRt LightAt;
+    static RPT_DEV uint32_t light_count(uint32_t n_lights) { return n_lights; }
+    static RPT_DEV bool mat_staged(uint32_t obj, uint32_t n_staged) { return obj < n_staged; }
+    static RPT_DEV bool ltri_staged(uint32_t i, uint32_t n_staged) { return i < n_staged; }
+    static RPT_DEV bool is_mat(uint32_t kind, uint32_t which) { return kind == which; }
+    static RPT_DEV bool mat_has_colour(uint32_t kind) { return kind <= 1u; }
+    static RPT_DEV bool fog_by_height(uint32_t medium_kind) { return medium_kind == 1u; }
+    static RPT_DEV bool has_hdri(uint32_t hdri_w) { return hdri_w != 0u; }
+    static RPT_DEV uint32_t pair_shared(uint32_t, uint32_t word) { return word; }
+};
+#ifdef RPT_SCENE_STRUCT
+struct SceneStructK;
+struct LightK {   // light i of the light loop, known from the block (the loop is unrolled: i is a constant in every copy of its body)
+    uint32_t i;
+    template <uint32_t AT> RPT_DEV constexpr uint32_t word() const;
+    RPT_DEV constexpr uint32_t kind(const Light&) const { return word<2u>() & 3u; }
+    RPT_DEV constexpr uint32_t shape(const Light&) const { return (word<2u>() >> 2) & 3u; }
+    RPT_DEV constexpr bool has_twin(const Light&) const { return ((word<2u>() >> 5) & 1u) != 0u; }
+    RPT_DEV constexpr bool has_range(const Light&) const { return ((word<2u>() >> 6) & 1u) != 0u; }
+    RPT_DEV constexpr uint32_t twin_lo(const Light&) const { return word<6u>(); }
+    RPT_DEV constexpr uint32_t twin_hi(const Light&) const { return word<10u>(); }
+    template <class X> RPT_DEV constexpr bool has_xf(const X&) const { return ((word<2u>() >> 4) & 1u) != 0u; }
+};
+struct SceneStructK {
+    static constexpr uint64_t k[18] = {RPT_SCENE_STRUCT};
+    static constexpr uint32_t groups = uint32_t(k[0]), mats = uint32_t(k[14]);
+    static constexpr bool kLights = (groups & SS_LIGHTS) != 0u;
+    static_assert(!kLights || k[1] <= kStructLights, "the block describes at most kStructLights lights");
+    typedef tt::conditional_t<kLights, LightK, LightRt> LightAt;
+    static RPT_DEV constexpr uint32_t light_count(uint32_t n_lights) { return kLights ? uint32_t(k[1]) : n_lights; }
+    static RPT_DEV constexpr bool mat_staged(uint32_t obj, uint32_t n_staged) { return (groups & SS_TABLES) ? true : obj < n_staged; }
+    static RPT_DEV constexpr bool ltri_staged(uint32_t i, uint32_t n_staged) { return (groups & SS_TABLES) ? true : i < n_staged; }
+    static RPT_DEV constexpr bool is_mat(uint32_t kind, uint32_t which) {
+        if (!(groups & SS_MATS)) return kind == which;
+        return !((mats >> which) & 1u) ? false : (mats == (1u << which) ? true : kind == which);
+    }
+    static RPT_DEV constexpr bool mat_has_colour(uint32_t kind) {
+        if (!(groups & SS_MATS)) return kind <= 1u;
+        return !(mats & ~3u) ? true : (!(mats & 3u) ? false : kind <= 1u);
+    }
+    static RPT_DEV constexpr bool fog_by_height(uint32_t medium_kind) { return (groups & SS_SMALL) ? k[15] == 1u : medium_kind == 1u; }
+    // Only the ABSENCE of an HDRI is a constant (the lookup is not compiled).  With its presence a constant too, the lookup loses the branch
+    // around it and the compiler contracts its bilinear sums (a * b + c * d: either product can go into the fma) the other way round: frames
+    // one ulp off the AOT kernel's in a fifth of the pixels (profiles/r11/scan_jit_structure.txt).  A scene with an HDRI asks the view, as ever.
+    static RPT_DEV constexpr bool has_hdri(uint32_t hdri_w) { return ((groups & SS_SMALL) && k[16] == 0u) ? false : hdri_w != 0u; }
+    static RPT_DEV constexpr uint32_t pair_shared(uint32_t i, uint32_t word) { return (groups & SS_PAIRS) ? uint32_t(k[17] >> (3u * (i >> 1))) & 7u : word; }
+};
+template <uint32_t AT>
+RPT_DEV constexpr uint32_t LightK::word() const {   // k[AT + i], by constant indices only
+    return uint32_t(i == 0u ? SceneStructK::k[AT] : i == 1u ? SceneStructK::k[AT + 1u] : i == 2u ? SceneStructK::k[AT + 2u] : SceneStructK::k[AT + 3u]);
+}
+#else
+typedef SceneStructRt SceneStructK;
+#endif
+// The common-slab bits of the box pair that begins at record i: the block's where the scan takes the JIT's constants, else `word`.
+template <class SHAPE>
+RPT_DEV uint32_t scan_pair_shared(uint32_t i, uint32_t word) {
+#if defined(RPT_SCAN_SHAPE) && defined(RPT_SCENE_STRUCT)
+    if constexpr (tt::is_same_v<SHAPE, ScanShapeK>) return SceneStructK::pair_shared(i, word);
+#endif
+    return word;
+}
 template <bool MASKED = false, bool MONO = false, bool TAIL = false, bool SHADOW = false, class SHAPE = ScanShapeRt>
 RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbest, uint32_t& code, uint64_t mask = ~0ull,
                         bool* tail_skipped = nullptr, ShadowTwin twin = ShadowTwin{0u, 1u, 0u}, bool* best_is_twin = nullptr) {
@@ -815,7 +899,7 @@ RPT_DEV void scan_prims(const SceneView& scene, V o, V d, float tmin, float& tbe
             if (!MASKED)
                 for (; i + 1u < sh.n_aabb(); i += 2u) {
                     const AabbScan b0 = uload(&sc.aabb[i]), b1 = uload(&sc.aabb[i + 1u]);
-                    aabb_pair_closer(b0, b1, __float_as_uint(b0.hi.w), o, inv, tmin, tbest, i,   // hi.w: the slabs they have in common
+                    aabb_pair_closer(b0, b1, scan_pair_shared<SHAPE>(i, __float_as_uint(b0.hi.w)), o, inv, tmin, tbest, i,   // hi.w: the slabs they have in common
                                      [&](bool ok, float t, uint32_t k) { acc(ok, t, (K_AABB << 28) | k, twin_at(tw, k)); });
                 }
             for (; i < sh.n_aabb(); i++) {
@@ -1220,11 +1304,12 @@ struct LdsTables {
     const F4* ltris = nullptr;   // [n_ltris] LightTri records
     uint32_t n_ltris = 0;
 };
-static constexpr uint32_t kLdsMats = 32, kLdsLtris = 8;   // 32 x 32 B + 8 x 96 B = 1.75 KB per block
+// (kLdsMats = 32, kLdsLtris = 8: gpu_layout.h; 32 x 32 B + 8 x 96 B = 1.75 KB per block)
+template <class ST = SceneStructRt>   // (ST: what is known about the scene beforehand, here and below -- SceneStructRt / SceneStructK)
 RPT_DEV Mat load_mat(const SceneView& scene_, uint32_t obj, const LdsTables& tab = LdsTables{}) {
     const auto& sc = *kernarg_scene();   // (see kernarg_scene)
     Material m;
-    if (obj < tab.n_mats) {   // wave-uniform in effect: either every object's material is staged or none
+    if (ST::mat_staged(obj, tab.n_mats)) {   // wave-uniform in effect: either every object's material is staged or none
         m.albedo_emit = tab.mats[2u * obj];
         m.params = tab.mats[2u * obj + 1u];
     } else {
@@ -1232,8 +1317,10 @@ RPT_DEV Mat load_mat(const SceneView& scene_, uint32_t obj, const LdsTables& tab
     }
     return Mat{xyz(m.albedo_emit), m.albedo_emit.w, __float_as_uint(m.params.x), m.params.y, m.params.z};
 }
-RPT_DEV V mat_color(const Mat& m) { return (m.kind <= 1u) ? m.albedo : mk(0.f, 0.f, 0.f); }   // src/material.rs:107
-RPT_DEV float mat_emit(const Mat& m) { return (m.kind <= 1u) ? m.emit : 0.f; }                // src/material.rs:100
+template <class ST = SceneStructRt>
+RPT_DEV V mat_color(const Mat& m) { return ST::mat_has_colour(m.kind) ? m.albedo : mk(0.f, 0.f, 0.f); }   // src/material.rs:107
+template <class ST = SceneStructRt>
+RPT_DEV float mat_emit(const Mat& m) { return ST::mat_has_colour(m.kind) ? m.emit : 0.f; }                // src/material.rs:100
 
 // Rotation taking +Y onto `b` applied to v (nalgebra rotation_between(+Y, b)): axis k =
 // normalize(Y x b), angle acos(b.y).  `pi_fallback_x`: Lambertian's (0,1,1e-8) retry
@@ -1260,8 +1347,9 @@ RPT_DEV V rotate_from_y(V b, V v, bool pi_fallback_x) {
 RPT_DEV V reflect_neg(V w, V n) { return fma3(2.f * dot(n, w), n, -w); }  // -glm::reflect_vec(w, n)
 
 // Material::sample_f, src/material.rs:166-263.  Returns false for None (total internal reflection).
+template <class ST = SceneStructRt>
 RPT_DEV bool sample_f(const Mat& m, V n, V wo, Rng& rng, V& wi, float& pdf) {
-    if (m.kind == M_LAMBERTIAN) {
+    if (ST::is_mat(m.kind, M_LAMBERTIAN)) {
         float r1 = rng.uniform(), r2 = rng.uniform();
         float ct = sqrt1(r2);             // cos(acos(sqrt(r2)))
         float st = sqrt1(1.f - r2);
@@ -1269,7 +1357,7 @@ RPT_DEV bool sample_f(const Mat& m, V n, V wo, Rng& rng, V& wi, float& pdf) {
         V dir = mk(st * __builtin_amdgcn_cosf(r1), ct, st * __builtin_amdgcn_sinf(r1));  // phi = 2 pi r1
         wi = normalize(rotate_from_y(n, dir, true));
         return true;
-    } else if (m.kind == M_PHONG) {
+    } else if (ST::is_mat(m.kind, M_PHONG)) {
         float r1 = rng.uniform(), r2 = rng.uniform();
         float ct = __powf(r2, rcp(m.shin + 1.f));
         float st = sqrt1(fmaxf(1.f - ct * ct, 0.f));
@@ -1278,7 +1366,7 @@ RPT_DEV bool sample_f(const Mat& m, V n, V wo, Rng& rng, V& wi, float& pdf) {
         V refl = reflect_neg(wo, n);
         wi = normalize(rotate_from_y(normalize(refl), dir, false));
         return true;
-    } else if (m.kind == M_MIRROR) {
+    } else if (ST::is_mat(m.kind, M_MIRROR)) {
         wi = reflect_neg(wo, normalize(n));
         pdf = 1.f;
         return true;
@@ -1306,11 +1394,12 @@ RPT_DEV bool sample_f(const Mat& m, V n, V wo, Rng& rng, V& wi, float& pdf) {
     }
 }
 // Material::bsdf, src/material.rs:266-289.
+template <class ST = SceneStructRt>
 RPT_DEV V bsdf(const Mat& m, V n, V wo, V wi) {
     float nwi = dot(n, wi), nwo = dot(n, wo);
     if (__builtin_signbit(nwi) || __builtin_signbit(nwo)) return mk(0.f, 0.f, 0.f);
-    if (m.kind == M_LAMBERTIAN) return kInvPi * m.albedo;
-    if (m.kind == M_PHONG) {
+    if (ST::is_mat(m.kind, M_LAMBERTIAN)) return kInvPi * m.albedo;
+    if (ST::is_mat(m.kind, M_PHONG)) {
         V r = -normalize(fma3(-2.f * dot(n, wi), n, wi));
         float c = fminf(fmaxf(dot(r, wo), 0.f), 1.f);
         // The shininess behind an opaque copy: its two terms below are invariant in the render kernels' light loop, and hoisted out
@@ -1358,18 +1447,18 @@ template <> struct LightXfRows<false> {
     RPT_DEV bool has_transform() const { return p->nrm[1].w != 0.f; }
 };
 // One leaf shape of a Light::Object (Sphere/Cube/Mesh::sample under Transformed::sample, src/shape.rs:140-151).
-template <bool UNIFORM>
+template <bool UNIFORM, class ST = SceneStructRt, class LD = LightRt>   // (LD: what is known about this light beforehand -- LightRt / LightK)
 RPT_DEV void sample_light_leaf(const SceneView& scene_, uint32_t shape, uint32_t first, uint32_t count, const LightXf* xp,
-                               V pos, Rng& rng, V& v, V& n, float& p, const LdsTables& tab = LdsTables{}) {
+                               V pos, Rng& rng, V& v, V& n, float& p, const LdsTables& tab = LdsTables{}, LD ld = LD{}) {
     const auto& sc = *kernarg_scene();   // (see kernarg_scene)
     V vl, nl;
     const LightXfRows<UNIFORM> x(xp);
-    const bool xf = x.has_transform();
+    const bool xf = ld.has_xf(x);
     const bool mesh = shape == LS_MESH;
     if (mesh) {
         uint32_t idx = rng.index(count);
         LightTri tr;
-        if (first + idx < tab.n_ltris) {
+        if (ST::ltri_staged(first + idx, tab.n_ltris)) {
             const F4* q = tab.ltris + 6u * (first + idx);
             tr.v1 = q[0]; tr.v2 = q[1]; tr.v3 = q[2]; tr.n1 = q[3]; tr.n2 = q[4]; tr.n3 = q[5];
         } else {
@@ -1436,12 +1525,12 @@ RPT_DEV void sample_light_leaf(const SceneView& scene_, uint32_t shape, uint32_t
 }
 // Shape::sample of a Light::Object.  A KdTree group (src/kdtree.rs:141-146) samples a uniformly chosen child and
 // divides its pdf by the child count, nested groups repeat that: every lane descends to its own leaf.
-template <bool GROUPS>
+template <bool GROUPS, class ST = SceneStructRt, class LD = LightRt>
 RPT_DEV void sample_light_shape(const SceneView& scene_, const Light& L, V pos, Rng& rng, V& v, V& n, float& p,
-                                const LdsTables& tab = LdsTables{}) {
+                                const LdsTables& tab = LdsTables{}, LD ld = LD{}) {
     const auto& sc = *kernarg_scene();   // (see kernarg_scene)
     if (!GROUPS || L.shape != LS_GROUP) {  // wave-uniform
-        sample_light_leaf<true>(scene_, L.shape, L.first, L.count, &sc.lxf[L.xf], pos, rng, v, n, p, tab);
+        sample_light_leaf<true, ST, LD>(scene_, ld.shape(L), L.first, L.count, &sc.lxf[L.xf], pos, rng, v, n, p, tab, ld);
         return;
     }
     uint32_t shape = LS_GROUP, first = L.first, count = L.count, xfi = 0;
@@ -1452,15 +1541,15 @@ RPT_DEV void sample_light_shape(const SceneView& scene_, const Light& L, V pos, 
         const LightPart part = sc.lparts[first + idx];
         shape = part.shape; first = part.first; count = part.count; xfi = part.xf;
     }
-    sample_light_leaf<false>(scene_, shape, first, count, &sc.lxf[xfi], pos, rng, v, n, p, tab);
+    sample_light_leaf<false, ST>(scene_, shape, first, count, &sc.lxf[xfi], pos, rng, v, n, p, tab);
     p *= pick;
 }
-template <bool GROUPS>
+template <bool GROUPS, class ST = SceneStructRt, class LD = LightRt>
 RPT_DEV void illuminate_object(const SceneView& sc, const Light& L, V pos, Rng& rng, V& intensity, V& wi,
-                               float& dist, const LdsTables& tab = LdsTables{}) {
+                               float& dist, const LdsTables& tab = LdsTables{}, LD ld = LD{}) {
     V v, n;
     float p;
-    sample_light_shape<GROUPS>(sc, L, pos, rng, v, n, p, tab);
+    sample_light_shape<GROUPS, ST, LD>(sc, L, pos, rng, v, n, p, tab, ld);
     V disp = v - pos;
     float len2 = dot(disp, disp);
     float ilen = rsq(len2);
@@ -1473,9 +1562,10 @@ RPT_DEV void illuminate_object(const SceneView& sc, const Light& L, V pos, Rng& 
 
 // ------------------------------------------------------------------ environment
 // Environment::get_color, src/environment.rs:72-77; Hdri::get_color / bilinear_sample :25-52.
+template <class ST = SceneStructRt>
 RPT_DEV V env_color(const SceneView& scene_, V dir) {
     const auto& sc = *kernarg_scene();   // (see kernarg_scene)
-    if (sc.hdri_w == 0) return mk(sc.env[0], sc.env[1], sc.env[2]);
+    if (!ST::has_hdri(sc.hdri_w)) return mk(sc.env[0], sc.env[1], sc.env[2]);
     const V d = normalize(dir);
     const float azimuth = atan2f(d.z, d.x) + kPi;
     const float polar = acosf(fminf(fmaxf(d.y, -1.f), 1.f));

@@ -239,6 +239,12 @@ struct SceneView {
     uint32_t n_scan_groups, scan_cull, scan_pad2_[2];
 };
 static const uint32_t kMaxScanGroups = 4;
+// Tables the render kernels stage in LDS when they fit (device_core.h, LdsTables): materials, light triangles.
+static constexpr uint32_t kLdsMats = 32, kLdsLtris = 8;
+// The scan JIT's structure block (device_core.h, SceneStructK; rpt_capi.cpp, scan_struct_of): one bit per group of constants.
+enum : uint32_t { SS_LIGHTS = 1u, SS_TABLES = 2u, SS_MATS = 4u, SS_SMALL = 8u, SS_PAIRS = 16u, SS_ALL = 31u };
+static constexpr uint32_t kStructLights = 4u;   // lights the block describes; a scene with more reads them from the view (SS_LIGHTS clear)
+static constexpr uint32_t kStructPairs = 21u;   // box pairs, three bits each in one 64-bit word (more: SS_PAIRS clear)
 
 struct CameraG {
     float eye[3], ddir[3], right[3], up[3];  // ddir = cot(fov/2) * direction

@@ -106,6 +106,23 @@ std::string scan_jit_key(const std::string& program, const std::vector<std::pair
 bool scan_jit_compile(const ScanShape& shape, const std::vector<std::pair<std::string, std::string>>& sources, std::vector<char>* code,
                       std::string* lowered, double* ms, std::string* why);
 bool scan_jit_resources(const std::vector<char>& code, int* vgprs, int* scratch);
+// What the code around the scans knows beforehand (device_core.h, SceneStructK): the second constant block of the program.  `groups`: the
+// SS_* bits of the groups of constants in effect; the fields of a group that is not are zero, so that scenes which differ only there
+// share a code object.  Filled at commit from the records as they are uploaded; record values are not part of it.
+struct SceneStruct {
+    uint32_t groups, n_lights;
+    uint32_t light[4], twin_lo[4], twin_hi[4];   // light word (bits 0-1 kind, 2-3 shape, 4 has a transform, 5 has a twin, 6 the twin is a code range)
+    uint32_t mats;                                // bit k: some object's material is of kind k
+    uint32_t medium_kind, hdri;
+    uint64_t pairs;                               // three common-slab bits per pair of boxes, pair 0 lowest
+};
+uint32_t scan_struct_default_groups();   // the groups a commit takes: the default, or RPT_SCAN_STRUCT_GROUPS (a mask; measurements)
+SceneStruct scan_struct_of(uint32_t groups, const std::vector<rptg::Light>& lights, const std::vector<rptg::LightXf>& lxf, size_t n_ltris,
+                           const std::vector<rptg::Material>& mats, const std::vector<rptg::AabbScan>& aabb, uint32_t medium_kind, bool hdri);
+std::string scan_struct_string(const SceneStruct& t);   // "groups=<names>;lights=...;mats=...;medium_kind=..;hdri=..;pairs=..": what rpt_scan_jit_structure reports
+std::string scan_jit_program(const ScanShape& h, const SceneStruct& t);   // the shape block, the structure block, #include "kernels.hip" and the instantiation's name
+bool scan_jit_compile(const ScanShape& shape, const SceneStruct* structure, const std::vector<std::pair<std::string, std::string>>& sources,
+                      std::vector<char>* code, std::string* lowered, double* ms, std::string* why);
 bool scan_jit_cache_read(const std::string& path, std::vector<char>* code, std::string* lowered, std::string* why);
 bool scan_jit_cache_write(const std::string& dir, const std::string& path, const std::vector<char>& code, const std::string& lowered);
 // A scene's state of it (rpt_scan_jit_info).
@@ -113,6 +130,7 @@ struct ScanJit {
     int state = 1, cache = 0;   // RPT_SCAN_JIT_IDLE, RPT_SCAN_JIT_CACHE_NONE
     bool probed = false;
     ScanShape shape{};
+    SceneStruct structure{};   // set by the commit
     std::string shape_text, reason, key, compiler;
     std::vector<std::pair<std::string, std::string>> sources;
     double compile_ms = 0;

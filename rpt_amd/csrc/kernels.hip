@@ -188,14 +188,14 @@ RPT_DEV void stage_distance(Rng& rng, float inv_sigma_t, float& dmed, float& t) 
 }
 // The event at a medium point or a surface hit: position, what shading needs, emission (src/renderer.rs:207-216,
 // 243-255, 289-299).
-template <bool COUNT, bool MONO = false>
+template <bool COUNT, bool MONO = false, class ST = SceneStructRt>
 RPT_DEV void stage_event(const RenderArgs& a, const LdsTables& tab, V ro, V rd, uint32_t depth, bool medium, float dmed, float t,
                          uint32_t code, uint32_t inst, V& x, V& n, V& mcol, Mat& mat, V& E) {
     const SceneView& sc = a.sc;
     if (medium) {
         SECT(5);
         x = fma3(dmed, rd, ro);
-        bool hi = sc.medium_kind == 1u && x.y > 250.f;
+        bool hi = ST::fog_by_height(sc.medium_kind) && x.y > 250.f;
         mcol = hi ? mk(sc.medium_color_hi[0], sc.medium_color_hi[1], sc.medium_color_hi[2])
                   : mk(sc.medium_color[0], sc.medium_color[1], sc.medium_color[2]);
         E = (depth == 0) ? sc.medium_emission * mcol : mk(0, 0, 0);
@@ -203,9 +203,9 @@ RPT_DEV void stage_event(const RenderArgs& a, const LdsTables& tab, V ro, V rd, 
         uint32_t obj;
         SECT(6);
         finalize_hit<MONO>(sc, ro, rd, ray_tmin(ro), t, code, inst, n, obj);
-        mat = load_mat(sc, obj, tab);
+        mat = load_mat<ST>(sc, obj, tab);
         x = fma3(t, rd, ro);
-        E = (depth == 0) ? mat_emit(mat) * mat_color(mat) : mk(0, 0, 0);
+        E = (depth == 0) ? mat_emit<ST>(mat) * mat_color<ST>(mat) : mk(0, 0, 0);
     }
 }
 // The shadow test of an object light and its term of E (src/renderer.rs:347-353, 395-404).  Reference: contributes
@@ -213,13 +213,13 @@ RPT_DEV void stage_event(const RenderArgs& a, const LdsTables& tab, V ro, V rd, 
 // belongs to the scene object that IS this light, at the sampled distance (rel. tol 1e-3).
 // PIN_RD (the scan flavours): wo is formed behind an opaque copy of rd, or it is formed ahead of the light loop and holds three registers
 // across the shadow scan -- one more spill in kernels that sit at their 80-register limit.
-template <bool PIN_RD = false>
+template <bool PIN_RD = false, class ST = SceneStructRt>
 RPT_DEV void stage_light_add(const SceneView& sc, float albedo_med, V rd, bool medium, V I, V wi, V n, V mcol, const Mat& mat, V& E) {
     if (medium) {
         E = fma3(albedo_med * sc.medium_phase, I * mcol, E);
     } else {
         if constexpr (PIN_RD) asm volatile("" : "+v"(rd.x), "+v"(rd.y), "+v"(rd.z));
-        V f = bsdf(mat, n, -normalize(rd), wi);   // (wo is only needed at surface events: derived where used)
+        V f = bsdf<ST>(mat, n, -normalize(rd), wi);   // (wo is only needed at surface events: derived where used)
         E = fma3(dot(wi, n), f * I, E);
     }
 }
@@ -234,23 +234,23 @@ RPT_DEV void stage_light_term(const SceneView& sc, const Light& L, float albedo_
 // A light that the commit marked (Light::color.w; option "shadow_scan") asks the scan's shadow form for its one bit; every other
 // light -- a group light, a twin that is a shell face or a monomial surface, the option off -- runs the closest-hit scan and
 // stage_light_term's test, as before.  Wave-uniform choice.  `ts`: the closest hit's t (the end of the interval on a miss).
-template <bool MONO = false, class SHAPE = ScanShapeRt>
-RPT_DEV bool scan_light_visible(const SceneView& sc, const Light& L, V x, V wi, float dist, float& ts) {
+template <bool MONO = false, class SHAPE = ScanShapeRt, class LD = LightRt>
+RPT_DEV bool scan_light_visible(const SceneView& sc, const Light& L, V x, V wi, float dist, float& ts, LD ld = LD{}) {
     ts = dist * (1.f + 1e-3f);
     uint32_t cs = CODE_MISS;
     if (__float_as_uint(L.color.w) != 0u) {
         bool twin = false;
         scan_prims<false, MONO, false, true, SHAPE>(sc, x, wi, ray_tmin(x), ts, cs, ~0ull, nullptr,
-                                             ShadowTwin{L.twin_lo >> 28, L.twin_lo & 0x0FFFFFFFu, L.twin_hi - L.twin_lo}, &twin);
+                                             ShadowTwin{ld.twin_lo(L) >> 28, ld.twin_lo(L) & 0x0FFFFFFFu, ld.twin_hi(L) - ld.twin_lo(L)}, &twin);
         return twin && ts >= dist * (1.f - 1e-3f);
     }
     scan_prims<false, MONO, false, false, SHAPE>(sc, x, wi, ray_tmin(x), ts, cs);
-    const bool twin = (L.twin_lo <= L.twin_hi) ? (cs >= L.twin_lo && cs <= L.twin_hi)
+    const bool twin = ld.has_range(L) ? (cs >= ld.twin_lo(L) && cs <= ld.twin_hi(L))
                                                : (cs != CODE_MISS && code_object<MONO>(sc, cs, 0u) == uint32_t(L.twin_object));
     return cs != CODE_MISS && ts >= dist * (1.f - 1e-3f) && twin;
 }
 // Continue or end: Russian roulette / max_bounces, phase or BSDF sample, path weight (src/renderer.rs:222-232, 262-281, 301-313)
-template <bool MEDIUM, bool COUNT>
+template <bool MEDIUM, bool COUNT, class ST = SceneStructRt>
 RPT_DEV bool stage_bounce(const RenderArgs& a, float albedo_med, V rd, uint32_t depth, bool medium, V n, V mcol, const Mat& mat,
                           Rng& rng, V& wi, V& k) {
     bool bounce;
@@ -270,9 +270,9 @@ RPT_DEV bool stage_bounce(const RenderArgs& a, float albedo_med, V rd, uint32_t 
             float pdf;
             SECT(13);
             const V wo = -normalize(rd);
-            bounce = sample_f(mat, n, wo, rng, wi, pdf);
+            bounce = sample_f<ST>(mat, n, wo, rng, wi, pdf);
             if (bounce) {
-                V f = bsdf(mat, n, wo, wi);
+                V f = bsdf<ST>(mat, n, wo, wi);
                 float wgt = fabsf(dot(wi, n)) * rcp(MEDIUM ? pdf * 0.8f : pdf);
                 k = wgt * f;
             }
@@ -301,6 +301,8 @@ void render_kernel(const RenderArgs a) {
     // The scan flavours without group lights, monomial surfaces or counters take the scene's record counts as constants where the
     // build gives them (ScanShapeK); every other flavour, and every build without them, reads them from the view.
     using Shape = tt::conditional_t<BVH == 0 && !COUNT && !GROUPS && DETACH == 0 && !MONO, ScanShapeK, ScanShapeRt>;
+    // ... and what the code around the scans knows about the scene (SceneStructK), under the same condition.
+    using Struct = tt::conditional_t<BVH == 0 && !COUNT && !GROUPS && DETACH == 0 && !MONO, SceneStructK, SceneStructRt>;
     extern __shared__ uint32_t dyn_lds[];
     const SceneView& sc = a.sc;
     uint32_t* stk = BVH ? (dyn_lds + threadIdx.x) : nullptr;
@@ -1285,7 +1287,7 @@ void render_kernel(const RenderArgs a) {
         if (!ev_medium && !ev_surface) {  // miss: environment (src/renderer.rs:198-206, 288)
             SECTK(4);
             if constexpr (BVH == 0) {
-                const V v = fma3(ldv(S_Q, Q), env_color(sc, rd), ldv(S_P, P));
+                const V v = fma3(ldv(S_Q, Q), env_color<Struct>(sc, rd), ldv(S_P, P));
                 acc_add(MEDIUM ? v : vmin(v, ldv(S_RC, Rc)));   // in a medium Rc stays +inf (no firefly clamp, src/renderer.rs:229-232)
             } else {
                 acc_add(vmin(fma3(Q, env_color(sc, rd), P), Rc));
@@ -1296,27 +1298,32 @@ void render_kernel(const RenderArgs a) {
 
         V x, n = mk(0, 1, 0), mcol = mk(0, 0, 0), E;
         Mat mat = Mat{mk(0, 0, 0), 0.f, 0u, 0.f, 0.f};
-        stage_event<COUNT, MONO>(a, tab, ro, rd, depth, ev_medium, dmed, t, code, inst, x, n, mcol, mat, E);
+        stage_event<COUNT, MONO, Struct>(a, tab, ro, rd, depth, ev_medium, dmed, t, code, inst, x, n, mcol, mat, E);
 
         // ---- next-event estimation: sample_lights / sample_lights_for_media
         //      (src/renderer.rs:362-409 / 325-359); lights in scene order fix the draw order.
-        for (uint32_t li = 0; li < sc.n_lights; li++) {
+        //      `ld`: what is known about light li before its record is read (LightRt: nothing; LightK: its words of the structure block).
+#ifdef RPT_SCENE_STRUCT   // (a build with the block: one copy of the body per light it describes, each with its light's constants)
+#pragma unroll(Struct::kLights ? kStructLights : 1u)
+#endif
+        for (uint32_t li = 0; li < Struct::light_count(sc.n_lights); li++) {
+            const typename Struct::LightAt ld{li};
             const Light L = uload(&sc.lights[li]);
-            if (L.kind == L_AMBIENT) {
-                E = fma3(xyz(L.color), ev_medium ? mcol : mat_color(mat), E);
-            } else if (L.kind == L_OBJECT) {
+            if (ld.kind(L) == L_AMBIENT) {
+                E = fma3(xyz(L.color), ev_medium ? mcol : mat_color<Struct>(mat), E);
+            } else if (ld.kind(L) == L_OBJECT) {
                 V I, wi;
                 float dist;
                 SECTK(7);
-                illuminate_object<GROUPS>(sc, L, x, rng, I, wi, dist, tab);
-                if (L.twin_object >= 0) {
+                illuminate_object<GROUPS, Struct>(sc, L, x, rng, I, wi, dist, tab, ld);
+                if (ld.has_twin(L)) {
                     SECTK(8);
                     if constexpr (BVH == 0) {
                         float ts;
-                        const bool visible = scan_light_visible<MONO, Shape>(sc, L, x, wi, dist, ts);
+                        const bool visible = scan_light_visible<MONO, Shape>(sc, L, x, wi, dist, ts, ld);
                         if (COUNT) c_rays++;
                         SECTK(9);
-                        if (visible) stage_light_add<true>(sc, albedo_med, rd, ev_medium, I, wi, n, mcol, mat, E);
+                        if (visible) stage_light_add<true, Struct>(sc, albedo_med, rd, ev_medium, I, wi, n, mcol, mat, E);
                     } else {
                         float ts = dist * (1.f + 1e-3f);
                         uint32_t cs = CODE_MISS, is = 0;
@@ -1336,7 +1343,7 @@ void render_kernel(const RenderArgs a) {
 
         // ---- continue or end the path
         V wi = mk(0, 0, 1), k = mk(0, 0, 0);
-        const bool cont = stage_bounce<MEDIUM, COUNT>(a, albedo_med, rd, depth, ev_medium, n, mcol, mat, rng, wi, k);
+        const bool cont = stage_bounce<MEDIUM, COUNT, Struct>(a, albedo_med, rd, depth, ev_medium, n, mcol, mat, rng, wi, k);
         SECTK(14);
         if constexpr (BVH == 0) {
             const V q = ldv(S_Q, Q);

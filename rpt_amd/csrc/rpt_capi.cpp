@@ -1609,6 +1609,7 @@ struct Flattener {
         v.hdri_h = s->hdri_h;
         s->prims_per_ray = sph.size() + cub.size() + pln.size() + tri.size() + aabb.size() + rect.size() + (has_shell ? 1 : 0);
         s->light_records = lights;
+        s->jit.structure = rpti::scan_struct_of(rpti::scan_struct_default_groups(), lights, lxf, ltris.size(), mats, aabb, v.medium_kind, s->hdri_w != 0);
         s->twins_scanned = true;
         s->n_twin_lights = 0;
         for (const Light& L : lights) {
@@ -2515,6 +2516,90 @@ std::string scan_jit_kernel_name(const ScanShape& h) {
 std::string scan_jit_program(const ScanShape& h) {
     return "#define RPT_SCAN_SHAPE " + scan_shape_constants(h) + "\n#include \"kernels.hip\"\n";
 }
+// ---- the structure block
+// The groups that passed the acceptance rule on C3 (profiles/r11/scan_jit_structure.txt).  SS_SMALL (the medium's kind, no HDRI) gains
+// 0.09 - 0.11 ms of 15.1, within three times the run-to-run range: it stays a switch.
+static constexpr uint32_t kStructDefaultGroups = SS_ALL & ~SS_SMALL;
+uint32_t scan_struct_default_groups() {
+    const char* env = std::getenv("RPT_SCAN_STRUCT_GROUPS");
+    if (!env || !*env) return kStructDefaultGroups;
+    char* end = nullptr;
+    const unsigned long v = std::strtoul(env, &end, 0);
+    return (end && *end == 0) ? uint32_t(v) & SS_ALL : kStructDefaultGroups;
+}
+SceneStruct scan_struct_of(uint32_t groups, const std::vector<Light>& lights, const std::vector<LightXf>& lxf, size_t n_ltris,
+                           const std::vector<Material>& mats, const std::vector<AabbScan>& aabb, uint32_t medium_kind, bool hdri) {
+    SceneStruct t{};
+    groups &= SS_ALL;
+    if (lights.size() > kStructLights) groups &= ~SS_LIGHTS;                     // the light loop reads them from the view
+    if (mats.size() > kLdsMats || n_ltris > kLdsLtris) groups &= ~SS_TABLES;     // a table stays in global memory
+    if (aabb.size() / 2 > kStructPairs) groups &= ~SS_PAIRS;
+    for (const Light& L : lights)   // (a group light is outside the JIT's scope altogether: scan_shape_of)
+        if (L.kind == L_OBJECT && (L.shape == LS_GROUP || L.xf >= lxf.size())) groups &= ~SS_LIGHTS;
+    t.groups = groups;
+    if (groups & SS_LIGHTS) {
+        t.n_lights = uint32_t(lights.size());
+        for (size_t i = 0; i < lights.size(); i++) {
+            const Light& L = lights[i];
+            uint32_t w = L.kind & 3u;
+            if (L.kind == L_OBJECT) {
+                const bool range = L.twin_lo <= L.twin_hi;
+                w |= (L.shape & 3u) << 2 | (lxf[L.xf].nrm[1].w != 0.f ? 16u : 0u) | (L.twin_object >= 0 ? 32u : 0u) | (range ? 64u : 0u);
+                if (range) { t.twin_lo[i] = L.twin_lo; t.twin_hi[i] = L.twin_hi; }
+            }
+            t.light[i] = w;
+        }
+    }
+    if (groups & SS_MATS)
+        for (const Material& m : mats) t.mats |= 1u << (bits_u(m.params.x) & 3u);
+    if (groups & SS_SMALL) { t.medium_kind = medium_kind; t.hdri = hdri ? 1u : 0u; }
+    if (groups & SS_PAIRS)
+        for (size_t i = 0; i + 1 < aabb.size(); i += 2) t.pairs |= uint64_t(bits_u(aabb[i].hi.w) & 7u) << (3 * (i / 2));
+    return t;
+}
+// The constants in SceneStructK's order (device_core.h), as they stand behind "#define RPT_SCENE_STRUCT".
+std::string scan_struct_constants(const SceneStruct& t) {
+    std::string o = std::to_string(t.groups) + "," + std::to_string(t.n_lights);
+    for (const uint32_t* f : {t.light, t.twin_lo, t.twin_hi})
+        for (int i = 0; i < 4; i++) o += "," + std::to_string(f[i]) + "u";
+    char b[64];
+    std::snprintf(b, sizeof b, ",%u,%u,%u,0x%llxull", t.mats, t.medium_kind, t.hdri, (unsigned long long)t.pairs);
+    return o + b;
+}
+std::string scan_struct_string(const SceneStruct& t) {
+    static const char* const group_names[5] = {"lights", "tables", "mats", "small", "pairs"};
+    static const char* const kinds[4] = {"point", "ambient", "directional", "object"};
+    static const char* const shapes[4] = {"sphere", "cube", "group", "mesh"};
+    std::string o = "groups=";
+    for (int g = 0; g < 5; g++)
+        if (t.groups & (1u << g)) o += std::string(o.back() == '=' ? "" : "+") + group_names[g];
+    if (!t.groups) o += "none";
+    o += ";lights=";
+    if (!(t.groups & SS_LIGHTS)) o += "view";
+    else {
+        o += std::to_string(t.n_lights);
+        for (uint32_t i = 0; i < t.n_lights; i++) {
+            const uint32_t w = t.light[i];
+            o += std::string(i ? "|" : ":") + kinds[w & 3u];
+            if ((w & 3u) != L_OBJECT) continue;
+            o += std::string("/") + shapes[(w >> 2) & 3u] + ((w & 16u) ? "/xf" : "") + ((w & 32u) ? "/twin" : "");
+            char b[48];
+            std::snprintf(b, sizeof b, "/%x-%x", t.twin_lo[i], t.twin_hi[i]);
+            if (w & 64u) o += b;
+        }
+    }
+    char b[96];
+    if (t.groups & SS_MATS) { std::snprintf(b, sizeof b, ";mats=0x%x", t.mats); o += b; } else o += ";mats=view";
+    if (t.groups & SS_SMALL) { std::snprintf(b, sizeof b, ";medium_kind=%u;hdri=%u", t.medium_kind, t.hdri); o += b; } else o += ";medium_kind=view;hdri=view";
+    if (t.groups & SS_PAIRS) { std::snprintf(b, sizeof b, ";pairs=0x%llx", (unsigned long long)t.pairs); o += b; } else o += ";pairs=view";
+    return o;
+}
+std::string scan_jit_program(const ScanShape& h, const SceneStruct& t) {
+    // The last line names the instantiation: the medium is part of the shape and of the kernel's name but of neither block, and the cache
+    // key is taken over this text -- a scene in fog and one without, alike in every count, must not share a code object.
+    return "#define RPT_SCAN_SHAPE " + scan_shape_constants(h) + "\n#define RPT_SCENE_STRUCT " + scan_struct_constants(t) + "\n#include \"kernels.hip\"\n// " +
+           scan_jit_kernel_name(h) + "\n";
+}
 const std::vector<std::string>& scan_jit_options() {   // the library's own device flags (__graft_entry__.FLAGS)
     static const std::vector<std::string> o = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize"};
     return o;
@@ -2714,10 +2799,15 @@ bool scan_jit_cache_write(const std::string& dir, const std::string& path, const
 // One compile, in this process.  `rtc` null: the library is opened here (tests/host).
 bool scan_jit_compile(const ScanShape& shape, const std::vector<std::pair<std::string, std::string>>& sources, std::vector<char>* code,
                       std::string* lowered, double* ms, std::string* why) {
+    return scan_jit_compile(shape, nullptr, sources, code, lowered, ms, why);
+}
+// ... `structure` null: the shape block alone.
+bool scan_jit_compile(const ScanShape& shape, const SceneStruct* structure, const std::vector<std::pair<std::string, std::string>>& sources,
+                      std::vector<char>* code, std::string* lowered, double* ms, std::string* why) {
     std::string w;
     const Hiprtc* rtc = hiprtc_open(&w);
     if (!rtc) { *why = w; return false; }
-    const std::string program = scan_jit_program(shape), name = scan_jit_kernel_name(shape);
+    const std::string program = structure ? scan_jit_program(shape, *structure) : scan_jit_program(shape), name = scan_jit_kernel_name(shape);
     std::vector<const char*> texts, names, opts;
     for (auto& f : sources) { names.push_back(f.first.c_str()); texts.push_back(f.second.c_str()); }
     for (auto& o : scan_jit_options()) opts.push_back(o.c_str());
@@ -2766,7 +2856,7 @@ static hipFunction_t scan_jit_function(rpt_scene* s, const RenderArgs& a) {
         const Hiprtc* rtc = hiprtc_open(&why);
         if (!rtc) return give_up(RPT_SCAN_JIT_FALLBACK, why);
         if (!scan_jit_sources(jit_source_dir(), &j.sources, &why)) return give_up(RPT_SCAN_JIT_FALLBACK, why);
-        j.key = scan_jit_key(scan_jit_program(shape), j.sources, scan_jit_options(), rtc->major, rtc->minor);
+        j.key = scan_jit_key(scan_jit_program(shape, j.structure), j.sources, scan_jit_options(), rtc->major, rtc->minor);
         j.compiler = "hiprtc " + std::to_string(rtc->major) + "." + std::to_string(rtc->minor) + " (" + rtc->path + ")";
         int aot_scratch = 0;
         if (scan_render_info(shape.medium != 0, &j.aot_vgprs, &aot_scratch, &j.lds) != hipSuccess || j.aot_vgprs <= 0)
@@ -2798,7 +2888,7 @@ static hipFunction_t scan_jit_function(rpt_scene* s, const RenderArgs& a) {
         JitObject o;
         std::string why;
         g_jit_compiles++;
-        if (!scan_jit_compile(j.shape, j.sources, &o.code, &o.lowered, &o.compile_ms, &why)) o.rejected = why;
+        if (!scan_jit_compile(j.shape, &j.structure, j.sources, &o.code, &o.lowered, &o.compile_ms, &why)) o.rejected = why;
         else if (!scan_jit_resources(o.code, &o.vgprs, &o.scratch)) o.rejected = "no resource note in the code object";
         else if (!path.empty()) (void)scan_jit_cache_write(dir, path, o.code, o.lowered);   // (an unwritable directory: memory only)
         it = g_jit_objects.emplace(j.key, std::move(o)).first;
@@ -4064,6 +4154,17 @@ int rpt_scan_jit_info(rpt_scene* s, int64_t out[8], char* text, uint64_t text_ca
         std::memcpy(text, t.data(), n);
         text[n] = 0;
     }
+    return RPT_OK;
+}
+int rpt_scan_jit_structure(rpt_scene* s, char* text, uint64_t text_capacity) {
+    if (!s || !text || !text_capacity) return fail(RPT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(RPT_ERR_STATE, "rpt_scene_commit must be called first");
+    std::string why;
+    rpti::ScanShape h;
+    const std::string t = rpti::scan_shape_of(s->view, &h, &why) ? rpti::scan_struct_string(s->jit.structure) : std::string();   // (outside the scope: empty, as the shape)
+    const size_t n = std::min<size_t>(t.size(), size_t(text_capacity) - 1);
+    std::memcpy(text, t.data(), n);
+    text[n] = 0;
     return RPT_OK;
 }
 int rpt_scan_jit_forget(void) {
