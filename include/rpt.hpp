@@ -592,6 +592,20 @@ class Temporal {
         if (rpt_temporal_accumulate_device(h_, &params, &c, d_rgb, d_var, d_normal, d_depth, d_out, d_out_var, d_out_len, hip_stream) != RPT_OK)
             throw Error(rpt_last_error());
     }
+    // rpt_temporal_preview_device: what accumulate_device would write in the listed 32 x 32 tiles (d_tiles: a device list of n_tiles
+    // distinct ids; nullptr with 0: every tile); nothing of the accumulator changes and a pending motion table stays set.
+    void preview_device(const rpt_temporal_params& params, const Camera& camera, const void* d_rgb, const void* d_var, const void* d_normal,
+                        const void* d_depth, const void* d_tiles, uint32_t n_tiles, void* d_out, void* d_out_var = nullptr, void* d_out_len = nullptr,
+                        void* hip_stream = nullptr) {
+        const rpt_camera c = camera.desc();
+        if (rpt_temporal_preview_device(h_, &params, &c, d_rgb, d_var, d_normal, d_depth, d_tiles, n_tiles, d_out, d_out_var, d_out_len, hip_stream) != RPT_OK)
+            throw Error(rpt_last_error());
+    }
+    // rpt_temporal_tile_errors_device: Buffer::tile_errors_device's error of the listed tiles with the pixel's terms taken from planes
+    void tile_errors_device(const void* d_rgb, const void* d_var, double floor, const void* d_tiles, uint32_t n_tiles, void* d_err,
+                            void* hip_stream = nullptr) const {
+        if (rpt_temporal_tile_errors_device(h_, d_rgb, d_var, floor, d_tiles, n_tiles, d_err, hip_stream) != RPT_OK) throw Error(rpt_last_error());
+    }
     // rpt_temporal_frame_image: the buffer's mean and variance -> accumulate -> (with a denoiser: the a-trous filter with the
     // accumulated variance) -> color_bytes; the feature planes are device pointers.
     RgbImage frame_image(const rpt_temporal_params& params, const Camera& camera, const Buffer& buffer, const void* d_albedo,
@@ -738,6 +752,19 @@ class Renderer {
         rpt_render_params rp{p_.width, p_.height, p_.exposure_value, p_.max_bounces, p_.shard_rank, p_.shard_count};
         std::array<uint64_t, 4> stats{};
         check(rpt_render_adaptive(handle_, &cam, &rp, &params, p_.seed, buffer.raw(), stats.data()));
+        return stats;
+    }
+    // rpt_render_adaptive_temporal: render_adaptive with a tile's error taken from the preview of `temporal`'s accumulation of the frame
+    // so far, batch k at sample_offset + k spp_per_batch; nothing is accumulated (Temporal::frame_image finishes the frame).
+    std::array<uint64_t, 4> render_adaptive_temporal(const rpt_adaptive_params& params, Buffer& buffer, Temporal& temporal,
+                                                     const rpt_temporal_params& temporal_params, const void* d_normal, const void* d_depth,
+                                                     uint32_t sample_offset = 0) {
+        commit();
+        rpt_camera cam = camera_.desc();
+        rpt_render_params rp{p_.width, p_.height, p_.exposure_value, p_.max_bounces, p_.shard_rank, p_.shard_count};
+        std::array<uint64_t, 4> stats{};
+        check(rpt_render_adaptive_temporal(handle_, &cam, &rp, &params, p_.seed, sample_offset, buffer.raw(), temporal.raw(), &temporal_params, d_normal,
+                                           d_depth, stats.data()));
         return stats;
     }
 

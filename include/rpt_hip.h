@@ -570,6 +570,60 @@ int rpt_buffer_refine_tiles(rpt_buffer*, const rpt_adaptive_params*, void* d_til
 int rpt_render_adaptive(rpt_scene*, const rpt_camera*, const rpt_render_params*, const rpt_adaptive_params*,
                         uint64_t seed, rpt_buffer*, uint64_t stats[4] /* rounds, tile-batches rendered, tiles at max_batches, tiles */);
 
+/* ---- adaptive sampling over a sequence: the loop above aimed at the error of the ACCUMULATED frame (an addition) ----
+ * In a sequence the picture that is shown is the accumulation's: its variance is (1 - a)^2 hv + a^2 v_in, and with a long history
+ * the frame's own variance counts for little of it.  Three calls let the adaptive loop see that: a preview of the accumulation, the
+ * tile errors of planes, and the loop that uses both.  Tiles are the buffer's 32 x 32 tiles, ids ty * tiles_x + tx.
+ *
+ * rpt_temporal_preview_device: for the in-image pixels of the listed tiles, steps 1 - 5 of rpt_temporal_accumulate_device exactly as
+ * defined above, the motion path and (with RPT_TEMPORAL_CLIP) the clipping step included -- the same kernel body, the same fp64
+ * operations in the same order; the clipping window still reads rgb and depth of pixels in tiles that are not listed.  Step 6 does
+ * not happen: no history record is written, the records do not swap, the stored camera record and rpt_temporal_frames are unchanged,
+ * and a pending one-shot motion table is read but NOT consumed (the next accumulating call still consumes it; a host table is
+ * uploaded once, by the first call that reads it, on that call's stream behind the predecessor's event, as promised above).  On an
+ * accumulator that holds no frame: out = rgb, out_v = v_in, len = 1.0.  d_tiles is a DEVICE list of n_tiles distinct uint32 ids; an id
+ * out of range is skipped; NULL with n_tiles == 0 means every tile; a list with n_tiles == 0 writes nothing.  Pixels outside the listed
+ * tiles are not written in any output.  The argument checks, their order and the NULL rules are rpt_temporal_accumulate_device's; in
+ * addition d_tiles == NULL with n_tiles > 0 is RPT_ERR_INVALID (after the planes' checks, before the handle's), and so is a list
+ * longer than tiles_x * tiles_y (after the handle's).  A preview is ordered like every other call of the accumulator, through the
+ * same event: it waits for its predecessor and its successor waits for it, whatever their streams.
+ *
+ * rpt_temporal_tile_errors_device: E_t of the tile errors above for each listed tile (NULL with 0: every tile), with the pixel's terms
+ * taken from planes: y = (rgb_0 + rgb_1) + rgb_2;  a_j = var[p] / (y y + floor floor);  slots outside the image hold +0.0; the 1024
+ * terms reduced by halving strides 512 .. 1; the result divided by double(in-image pixels).  Only the listed tiles' entries of d_err
+ * (tiles_x * tiles_y doubles) are written; an id out of range is skipped.  The frame size is the accumulator's, of which nothing else
+ * is read: the call is NOT ordered with the accumulator's other calls (order it on its stream).  floor finite and > 0, then the
+ * pointers, then the list (as for the preview): RPT_ERR_INVALID.  On the planes rpt_buffer_mean_device wrote, the result is
+ * rpt_buffer_tile_errors_device's of that buffer, bit for bit.
+ *
+ * rpt_render_adaptive_temporal: rpt_render_adaptive with the tile errors taken from the preview, on the default stream, synchronous.
+ * Checks, all before any device call and in this order: rpt_render_adaptive's (NULL arguments, the adaptive parameters with
+ * min_batches >= 2; then sample_offset + max_batches spp_per_batch must fit 32 bits; not sharded, the buffer's size and device); the
+ * temporal parameters' and planes' (d_depth always, d_normal read only with normal_tol > 0), the NULL accumulator; buffer and
+ * accumulator of one device and one size (RPT_ERR_INVALID); an empty buffer (RPT_ERR_STATE).
+ * Batches k < min_batches are full-frame rpt_render_into_buffer calls at sample_offset + k spp_per_batch.  The active list starts as
+ * every tile.  Round k >= min_batches: (1) rpt_buffer_mean_device; (2) the preview of those two planes over the active list;
+ * (3) the tile errors of the preview's out / out_v over the active list; (4) the selection among the active list: a listed tile is
+ * selected iff E_t > threshold threshold (false for NaN) and n_t < max_batches, the ids stay ascending, and their number comes back
+ * through the round's one 4-byte read-back; (5) stop if nothing is selected; (6) otherwise a tile-list render of spp_per_batch samples
+ * at sample_offset + k spp_per_batch, added to the listed tiles, which are the next round's active list.
+ * A tile that left the active list is not evaluated again.  Without RPT_TEMPORAL_CLIP a pixel's preview depends on its own tile's
+ * samples alone, so the accumulation that follows the loop returns in every tile exactly the out / out_v / len of that tile's last
+ * preview (a tile that ended at max_batches got its last batch after its last preview: there the accumulation equals a preview
+ * taken after the loop).  With clipping, a neighbour's later samples can move the window of a finished tile's edge pixels: its final error may
+ * differ slightly from the one it stopped at.
+ * The loop does NOT accumulate: history, frame count and pending motion table are as before the call; the caller finishes the frame
+ * with rpt_temporal_frame_image or rpt_temporal_accumulate_device.  On an accumulator without a frame and with sample_offset 0 the
+ * buffer and the stats are bit-identical to rpt_render_adaptive's.  stats as for rpt_render_adaptive. */
+int rpt_temporal_preview_device(rpt_temporal*, const rpt_temporal_params*, const rpt_camera*, const void* d_rgb, const void* d_var,
+                                const void* d_normal, const void* d_depth, const void* d_tiles, uint32_t n_tiles, void* d_out_rgb,
+                                void* d_out_var, void* d_out_len, void* hip_stream);
+int rpt_temporal_tile_errors_device(rpt_temporal*, const void* d_rgb, const void* d_var, double floor, const void* d_tiles, uint32_t n_tiles,
+                                    void* d_err /* tiles_x*tiles_y doubles */, void* hip_stream);
+int rpt_render_adaptive_temporal(rpt_scene*, const rpt_camera*, const rpt_render_params*, const rpt_adaptive_params*, uint64_t seed,
+                                 uint32_t sample_offset, rpt_buffer*, rpt_temporal*, const rpt_temporal_params*, const void* d_normal,
+                                 const void* d_depth, uint64_t stats[4]);
+
 /* ---- photon mapping (next tier: src/photon.rs; config C4 = photon_point_query_beam_render) ----
  * `enum PhotonRenderKind` (src/photon.rs:631-639): point-point (photon_map_render), beam-point
  * (photon_point_query_beam_render, config C4) and beam-beam (photon_beam_query_beam_render). */

@@ -174,6 +174,12 @@ SYMBOLS = [
     ("rpt_buffer_refine_tiles", C.c_int, [_P, C.POINTER(AdaptiveParams), _P, C.POINTER(C.c_uint32), _P, _P]),
     ("rpt_render_adaptive", C.c_int,
      [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    ("rpt_temporal_preview_device", C.c_int,
+     [_P, C.POINTER(TemporalParams), C.POINTER(CameraDesc), _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
+    ("rpt_temporal_tile_errors_device", C.c_int, [_P, _P, _P, C.c_double, _P, C.c_uint32, _P, _P]),
+    ("rpt_render_adaptive_temporal", C.c_int,
+     [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.c_uint64, C.c_uint32, _P, _P,
+      C.POINTER(TemporalParams), _P, _P, C.POINTER(C.c_uint64)]),
     ("rpt_photon_map_build", C.c_int, [_P, C.c_uint64, C.c_int32, C.c_double, C.c_uint64]),
     ("rpt_photon_shoot", C.c_int,
      [_P, C.c_uint64, C.c_int32, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),

@@ -1007,6 +1007,86 @@ class TemporalAccumulator:
             self._h, C.byref(params.desc()), C.byref(camera_desc(camera, _lib.CameraDesc)),
             *[C.c_void_p(p or None) for p in (d_rgb, d_var, d_normal, d_depth, d_out, d_out_var, d_out_len)], C.c_void_p(stream_ptr)))
 
+    # ---- the accumulation without its side effects, over a tile list (rpt_temporal_preview_device, an addition)
+    @property
+    def tiles(self):
+        """(tiles_x, tiles_y): the frame in 32 x 32 tiles; a tile id is ty * tiles_x + tx."""
+        return (self.width + 31) // 32, (self.height + 31) // 32
+
+    def _tile_list(self, tiles, what):
+        """`tiles`: None (every tile) or a sequence of distinct ids -> (what keeps the upload alive, pointer, count)."""
+        if tiles is None:
+            return None, None, 0
+        import torch
+        ids = np.ascontiguousarray(tiles, dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= 1 << 32):
+            raise ValueError(f"{what}: a tile id does not fit 32 bits")
+        if np.unique(ids).size != ids.size:
+            raise ValueError(f"{what}: a tile id is listed twice")
+        if ids.size > self.tiles[0] * self.tiles[1]:
+            raise ValueError(f"{what}: {ids.size} tiles listed, the frame has {self.tiles[0] * self.tiles[1]}")
+        # (one spare entry: an empty list is still a list, not "every tile")
+        d = torch.from_numpy(np.concatenate([ids.astype(np.uint32), np.zeros(1, np.uint32)]).view(np.int32)).to(f"cuda:{self.device}")
+        return d, d.data_ptr(), int(ids.size)
+
+    def preview_device(self, camera, d_rgb, d_var, d_normal, d_depth, d_out, d_out_var=0, d_out_len=0, params=None, d_tiles=0, n_tiles=0,
+                       stream_ptr=0):
+        """rpt_temporal_preview_device: what accumulate_device would write to its outputs in the listed tiles (d_tiles: a device
+        array of n_tiles distinct uint32 ids; 0 with n_tiles 0: every tile), enqueued on stream_ptr.  Nothing of the accumulator
+        changes: no history is written, frames stays, a pending motion table stays set."""
+        params = params or TemporalParams()
+        _lib.check(_lib.load().rpt_temporal_preview_device(
+            self._h, C.byref(params.desc()), C.byref(camera_desc(camera, _lib.CameraDesc)),
+            *[C.c_void_p(p or None) for p in (d_rgb, d_var, d_normal, d_depth, d_tiles)], int(n_tiles),
+            *[C.c_void_p(p or None) for p in (d_out, d_out_var, d_out_len)], C.c_void_p(stream_ptr)))
+
+    def preview(self, camera, rgb, var, normal, depth, params=None, tiles=None, fill=np.nan):
+        """Host arrays as for accumulate -> (out, out_var, out_len) as accumulate(..., return_variance=True, return_length=True)
+        would return them in the tiles of `tiles` (None: every tile); pixels of other tiles hold `fill`.  Synchronous."""
+        params = params or TemporalParams()
+        n = self.width * self.height
+        dev = []
+        for name, a, size in (("rgb", rgb, 3 * n), ("var", var, n), ("normal", normal, 3 * n), ("depth", depth, 3 * n)):
+            if a is None:
+                if name in ("rgb", "depth"):
+                    raise ValueError(f"preview: {name} is required")
+                dev.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != size:
+                raise ValueError(f"preview: {name} has {a.size} values, the frame needs {size}")
+            dev.append(_device_copy(a, self.device))
+        keep, d_tiles, n_tiles = self._tile_list(tiles, "preview")
+        out = _device_copy(np.full(5 * n, fill, dtype=np.float64), self.device)
+        _sync(self.device)
+        self.preview_device(camera, *[d.data_ptr() if d is not None else 0 for d in dev], out.data_ptr(), out.data_ptr() + 24 * n,
+                            out.data_ptr() + 32 * n, params, d_tiles, n_tiles)
+        _sync(self.device)
+        host = out.cpu().numpy()
+        return (host[:3 * n].reshape(self.height, self.width, 3).copy(), host[3 * n:4 * n].reshape(self.height, self.width).copy(),
+                host[4 * n:].reshape(self.height, self.width).copy())
+
+    def tile_errors(self, rgb, var, floor, tiles=None, fill=np.nan):
+        """rpt_temporal_tile_errors_device -> (tiles_y, tiles_x) float64: DeviceBuffer.tile_errors' error with the pixel's mean and the
+        variance of that mean taken from the (h, w, 3) and (h, w) planes, for the tiles of `tiles` (None: every tile); the entries
+        of other tiles hold `fill`."""
+        floor = float(floor)
+        if not (floor > 0.0) or math.isinf(floor):
+            raise ValueError("tile_errors: floor must be finite and > 0")
+        n = self.width * self.height
+        rgb, var = np.ascontiguousarray(rgb, dtype=np.float64), np.ascontiguousarray(var, dtype=np.float64)
+        if rgb.size != 3 * n or var.size != n:
+            raise ValueError(f"tile_errors: the planes are not {self.height} x {self.width} x 3 and {self.height} x {self.width}")
+        tx, ty = self.tiles
+        d_rgb, d_var = _device_copy(rgb, self.device), _device_copy(var, self.device)
+        d_err = _device_copy(np.full(tx * ty, fill, dtype=np.float64), self.device)
+        keep, d_tiles, n_tiles = self._tile_list(tiles, "tile_errors")
+        _sync(self.device)
+        _lib.check(_lib.load().rpt_temporal_tile_errors_device(self._h, C.c_void_p(d_rgb.data_ptr()), C.c_void_p(d_var.data_ptr()), floor,
+                                                               C.c_void_p(d_tiles), n_tiles, C.c_void_p(d_err.data_ptr()), None))
+        _sync(self.device)
+        return d_err.cpu().numpy().reshape(ty, tx).copy()
+
     def set_motion(self, records):
         """rpt_temporal_set_motion: an (n, 24) array of motion records (temporal_motion_record), record i for the object with id
         i + 1, or None to clear.  One-shot: the next accumulate, accumulate_device or temporal_image consumes the table."""
@@ -1201,6 +1281,37 @@ class Renderer:
             C.byref(params.desc()), C.c_uint64(self.seed_), buffer._h, stats))
         return tuple(int(v) for v in stats)
 
+    def sample_adaptive_temporal(self, params, buffer, accumulator, camera_planes, temporal=None, sample_offset=None):
+        """rpt_render_adaptive_temporal (an addition) into an empty DeviceBuffer: sample_adaptive with a tile's error taken from the
+        preview of `accumulator`'s accumulation of the frame so far, so that params.threshold is the relative standard error of the
+        frame that is shown and tiles that their history carries stop early.  `camera_planes`: a dict with "depth" and, where
+        temporal.normal_tol > 0, "normal", as DeviceBuffer.temporal_image takes them.  Batch k uses the samples at
+        sample_offset + k * spp_per_batch (sample_offset None: the renderer's, which is advanced by max_batches * spp_per_batch).
+        Nothing is accumulated: DeviceBuffer.temporal_image finishes the frame.  -> sample_adaptive's four numbers."""
+        if not isinstance(params, AdaptiveParams):
+            raise ValueError("sample_adaptive_temporal: params must be an AdaptiveParams")
+        if not isinstance(buffer, DeviceBuffer):
+            raise ValueError("sample_adaptive_temporal: the buffer must be a DeviceBuffer")
+        if not isinstance(accumulator, TemporalAccumulator):
+            raise ValueError("sample_adaptive_temporal: the accumulator must be a TemporalAccumulator")
+        if temporal is not None and not isinstance(temporal, TemporalParams):
+            raise ValueError("sample_adaptive_temporal: temporal must be a TemporalParams or None")
+        if self.shard_count_ != 1:
+            raise ValueError("sample_adaptive_temporal: an adaptive render is not sharded")
+        temporal = temporal or TemporalParams()
+        offset = self._sample_offset if sample_offset is None else int(sample_offset)
+        if offset < 0 or offset + params.max_batches * params.spp_per_batch >= 1 << 32:
+            raise ValueError("sample_adaptive_temporal: sample_offset + max_batches * spp_per_batch must fit 32 bits")
+        keep, ptrs = buffer._plane_pointers({k: v for k, v in camera_planes.items() if k != "albedo"}, "sample_adaptive_temporal")
+        stats = (C.c_uint64 * 4)()
+        _lib.check(_lib.load().rpt_render_adaptive_temporal(
+            self.scene._commit(self.device_), C.byref(camera_desc(self.camera, _lib.CameraDesc)), C.byref(self._params()),
+            C.byref(params.desc()), C.c_uint64(self.seed_), offset, buffer._h, accumulator._h, C.byref(temporal.desc()), ptrs[1], ptrs[2],
+            stats))
+        if sample_offset is None:
+            self._sample_offset += params.max_batches * params.spp_per_batch
+        return tuple(int(v) for v in stats)
+
     def render_adaptive(self, params=None, denoise=None):
         """sample_adaptive into a fresh DeviceBuffer -> (image, tile_batches): (h, w, 3) uint8 and the (tiles_y, tiles_x) batches each
         tile ended with.  The image is DeviceBuffer.image() (filter() applies), or with denoise=DenoiseParams(..)
@@ -1305,7 +1416,7 @@ class Renderer:
         buffer.close()
         return img
 
-    def render_sequence(self, cameras, batches=4, temporal=None, denoise=None, scenes=None):
+    def render_sequence(self, cameras, batches=4, temporal=None, denoise=None, scenes=None, adaptive=None, return_tile_batches=False):
         """An addition: a generator of one (h, w, 3) uint8 frame per camera of `cameras`, for a camera that moves over this scene
         or, with `scenes` (one Scene per camera, as the reference builds one per frame: the same number of objects with the same
         base shape kinds in the same order, else ValueError), over objects that move: frame f renders scenes[f], committed when its
@@ -1315,12 +1426,22 @@ class Renderer:
         streams per frame) into a DeviceBuffer, the feature planes of the same camera samples, then DeviceBuffer.temporal_image
         with one TemporalAccumulator for the sequence: mean and variance, accumulation over the previous frames (`temporal`: a
         TemporalParams or None for the defaults), with denoise=DenoiseParams(..) the a-trous filter, color_bytes.  Everything but
-        the bytes stays on the device; filter() is not applied; self.camera is left as it was.  Not for sharded renders."""
+        the bytes stays on the device; filter() is not applied; self.camera is left as it was.  Not for sharded renders.
+        With adaptive=AdaptiveParams(..) frame f is sampled by sample_adaptive_temporal against the sequence's accumulator instead:
+        its batches at the sample offsets f * max_batches * spp_per_batch .., the feature planes those of the first
+        min_batches * spp_per_batch samples at that offset (as render_adaptive takes them), the motion table set before the loop
+        and consumed by temporal_image after it; num_samples and `batches` are not read.  With return_tile_batches=True (adaptive
+        only) each frame comes as (image, tile_batches), the (tiles_y, tiles_x) batches its tiles ended with."""
+        if adaptive is not None and not isinstance(adaptive, AdaptiveParams):
+            raise ValueError("render_sequence: adaptive must be an AdaptiveParams or None")
+        if return_tile_batches and adaptive is None:
+            raise ValueError("render_sequence: return_tile_batches needs adaptive")
         batches = int(batches)
-        if batches < 2:
-            raise ValueError("render_sequence: the variance of the mean needs at least 2 batches")
-        if self.num_samples_ < batches:
-            raise ValueError("render_sequence: num_samples must be at least the number of batches")
+        if adaptive is None:
+            if batches < 2:
+                raise ValueError("render_sequence: the variance of the mean needs at least 2 batches")
+            if self.num_samples_ < batches:
+                raise ValueError("render_sequence: num_samples must be at least the number of batches")
         if self.shard_count_ != 1:
             raise ValueError("render_sequence: a sharded frame is assembled first; rank 0 accumulates it")
         if temporal is not None and not isinstance(temporal, TemporalParams):
@@ -1328,7 +1449,10 @@ class Renderer:
         if denoise is not None and not isinstance(denoise, DenoiseParams):
             raise ValueError("render_sequence: denoise must be a DenoiseParams or None")
         cameras = list(cameras)
-        if len(cameras) * self.num_samples_ >= 1 << 32:
+        if adaptive is not None:
+            if len(cameras) * adaptive.max_batches * adaptive.spp_per_batch >= 1 << 32:
+                raise ValueError("render_sequence: frames * max_batches * spp_per_batch must fit 32 bits")
+        elif len(cameras) * self.num_samples_ >= 1 << 32:
             raise ValueError("render_sequence: frames * num_samples must fit 32 bits")
         if scenes is not None:
             scenes = list(scenes)
@@ -1339,9 +1463,9 @@ class Renderer:
             kinds = [[o.shape.base().KIND for o in sc.objects] for sc in scenes]
             if any(k != kinds[0] for k in kinds[1:]):
                 raise ValueError("render_sequence: every scene must hold the same base shape kinds in the same order")
-        return self._render_sequence(cameras, batches, temporal or TemporalParams(), denoise, scenes)
+        return self._render_sequence(cameras, batches, temporal or TemporalParams(), denoise, scenes, adaptive, bool(return_tile_batches))
 
-    def _render_sequence(self, cameras, batches, temporal, denoise, scenes=None):
+    def _render_sequence(self, cameras, batches, temporal, denoise, scenes=None, adaptive=None, return_tile_batches=False):
         accumulator = TemporalAccumulator(self.width_, self.height_, self.device_)
         denoiser = Denoiser(self.width_, self.height_, self.device_) if denoise is not None else None
         n = self.width_ * self.height_ * 3
@@ -1360,14 +1484,22 @@ class Renderer:
                                                          for c, p in zip(scenes[f].objects, scenes[f - 1].objects)])
                                                if scenes[f].objects else None)
                 buffer = DeviceBuffer(self.width_, self.height_, None, self.device_)
-                self.features_device(self.num_samples_, *ptrs, sample_offset=f * self.num_samples_)
-                self._sample_offset = f * self.num_samples_
-                for k in range(batches):
-                    self.sample(base + (1 if k < extra else 0), buffer)
+                counts = None
+                if adaptive is not None:
+                    offset = f * adaptive.max_batches * adaptive.spp_per_batch
+                    self.features_device(adaptive.min_batches * adaptive.spp_per_batch, *ptrs, sample_offset=offset)
+                    self.sample_adaptive_temporal(adaptive, buffer, accumulator, {"normal": ptrs[1], "depth": ptrs[2]}, temporal, sample_offset=offset)
+                    if return_tile_batches:
+                        counts = buffer.tile_batches()
+                else:
+                    self.features_device(self.num_samples_, *ptrs, sample_offset=f * self.num_samples_)
+                    self._sample_offset = f * self.num_samples_
+                    for k in range(batches):
+                        self.sample(base + (1 if k < extra else 0), buffer)
                 img = buffer.temporal_image(accumulator, cam, dict(zip(("albedo", "normal", "depth"), ptrs)), temporal, denoiser, denoise)
                 buffer.close()
                 self.camera, self.scene = own, own_scene
-                yield img
+                yield (img, counts) if return_tile_batches else img
         finally:
             self.camera, self.scene = own, own_scene
             accumulator.close()

@@ -8,6 +8,9 @@
 //                                   the read-outs of a buffer with extra batches: a pixel's count is n_batches + extra[its tile].
 //   tile_errors_kernel              one block per tile: the per-pixel terms of include/rpt_hip.h, reduced by halving strides.
 //   tile_select_kernel              one block: the ids of the tiles still above the threshold, ascending, and their number.
+//   plane_tile_errors_kernel, tile_select_list_kernel
+//                                   the same two over a tile list, the pixel's terms from planes (rpt_temporal_tile_errors_device and
+//                                   the rounds of rpt_render_adaptive_temporal).
 // The error and the mean are an order of fp64 operations, every one rounded on its own (contraction off, IEEE division, no
 // atomics): tests/adaptive_ref.py restates them in numpy and the kernels' output is compared with it bit for bit.  The three
 // kernels that repeat an expression of kernels.hip (add, image, variance) are compiled as that file is, so that a tile batch puts
@@ -165,7 +168,87 @@ __global__ __launch_bounds__(256) void tile_select_kernel(const TileBufferView b
     if (l == 0) *n_out = base;
 }
 
+// rpt_temporal_tile_errors_device: tile_errors_kernel's tree with the pixel's terms taken from planes, one block per listed tile
+// (tiles null: block b is tile b).  On the planes buffer_mean(_tiles)_kernel wrote, y and v are the values tile_errors_kernel forms
+// in registers, so the result is the same bits.
+__global__ __launch_bounds__(256) void plane_tile_errors_kernel(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t tiles_y, double floor2,
+                                                                const double* __restrict__ rgb, const double* __restrict__ var,
+                                                                const uint32_t* __restrict__ tiles, double* __restrict__ err) {
+    __shared__ double part[256];
+    const uint32_t tile = tiles ? tiles[blockIdx.x] : blockIdx.x, l = threadIdx.x;
+    if (tile >= tiles_x * tiles_y) return;                    // an id from a list: checked before it indexes anything (the whole block leaves)
+    double a[4];
+    for (uint32_t k = 0; k < 4; k++) {
+        size_t p;
+        a[k] = 0.0;
+        if (!tile_slot_pixel(tile, l + 256u * k, tiles_x, width, height, p)) continue;
+        const double y = (rgb[3 * p] + rgb[3 * p + 1]) + rgb[3 * p + 2];
+        a[k] = var[p] / (y * y + floor2);
+    }
+    part[l] = (a[0] + a[2]) + (a[1] + a[3]);
+    __syncthreads();
+    for (uint32_t s = 128; s >= 1; s >>= 1) {
+        if (l < s) part[l] = part[l] + part[l + s];
+        __syncthreads();
+    }
+    if (l == 0) {
+        const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+        const uint32_t w = min(32u, width - tx * 32u), h = min(32u, height - ty * 32u);
+        err[tile] = part[0] / double(w * h);
+    }
+}
+
+// tile_select_kernel among a list (in null: among every tile): position i of `in` is flagged by its tile's error and count, the
+// flagged ids keep their order.  `out` may be `in`: a chunk's ids are read before the chunk's barrier and written behind it, to
+// positions <= their own, and no later chunk's position is written.
+__global__ __launch_bounds__(256) void tile_select_list_kernel(const TileBufferView b, double threshold2, uint32_t max_batches,
+                                                               const double* __restrict__ err, const uint32_t* in, uint32_t n_in,
+                                                               uint32_t* out, uint32_t* __restrict__ n_out) {
+    __shared__ uint32_t scan[256];
+    const uint32_t l = threadIdx.x, n_tiles = b.tiles_x * b.tiles_y;
+    const uint32_t n = in ? n_in : n_tiles;
+    uint32_t base = 0;
+    for (uint32_t first = 0; first < n; first += 256u) {
+        const uint32_t i = first + l;
+        uint32_t flag = 0, tile = 0;
+        if (i < n) {
+            tile = in ? in[i] : i;
+            if (tile < n_tiles) {
+                const uint32_t n_t = b.n_batches + (b.extra ? b.extra[tile] : 0u);
+                flag = (err[tile] > threshold2 && n_t < max_batches) ? 1u : 0u;   // (false for a NaN error)
+            }
+        }
+        scan[l] = flag;
+        __syncthreads();
+        for (uint32_t s = 1; s < 256u; s <<= 1) {
+            const uint32_t add = l >= s ? scan[l - s] : 0u;
+            __syncthreads();
+            scan[l] += add;
+            __syncthreads();
+        }
+        if (flag) out[base + scan[l] - 1u] = tile;               // (base + scan <= positions seen so far <= n: the list's capacity)
+        base += scan[255];
+        __syncthreads();
+    }
+    if (l == 0) *n_out = base;
+}
+
 }  // namespace
+
+hipError_t launch_plane_tile_errors(uint32_t width, uint32_t height, double floor, const double* d_rgb, const double* d_var, const uint32_t* d_tiles,
+                                    uint32_t n_tiles, double* d_err, hipStream_t st) {
+    const uint32_t tiles_x = (width + 31u) / 32u, tiles_y = (height + 31u) / 32u;
+    const uint32_t blocks = d_tiles ? n_tiles : tiles_x * tiles_y;
+    if (!blocks) return hipSuccess;
+    hipLaunchKernelGGL(plane_tile_errors_kernel, dim3(blocks), dim3(256), 0, st, width, height, tiles_x, tiles_y, floor * floor, d_rgb, d_var, d_tiles,
+                       d_err);
+    return hipGetLastError();
+}
+hipError_t launch_tile_select_list(const TileBufferView& b, double threshold2, uint32_t max_batches, const double* d_err, const uint32_t* d_tiles_in,
+                                   uint32_t n_in, uint32_t* d_tiles_out, uint32_t* d_n_out, hipStream_t st) {
+    hipLaunchKernelGGL(tile_select_list_kernel, dim3(1), dim3(256), 0, st, b, threshold2, max_batches, d_err, d_tiles_in, n_in, d_tiles_out, d_n_out);
+    return hipGetLastError();
+}
 
 hipError_t launch_buffer_add_tiles(const TileBufferView& b, const double* d_batch, double* d_sum, double* d_sumsq, uint32_t* d_extra,
                                    const uint32_t* d_tiles, uint32_t n_tiles, hipStream_t st) {

@@ -153,6 +153,10 @@ static constexpr uint32_t kTemporalMotionDoubles = 24;   // RPT_TEMPORAL_MOTION_
 // (Weak: reached from rpt_temporal_accumulate* / rpt_temporal_frame_image alone, which report RPT_ERR_UNSUPPORTED where no kernel
 // library is linked.)
 __attribute__((weak)) hipError_t launch_temporal_accumulate(const TemporalArgs& a, hipStream_t stream);
+// rpt_temporal_preview_device: steps 1 - 5 of the same kernel over the in-image pixels of the listed 32 x 32 tiles (d_tiles null: over
+// the frame); hist_out is not written.  A list with no entries launches nothing; one longer than the frame's tiles is
+// hipErrorInvalidValue.  (Weak, like the launcher above.)
+__attribute__((weak)) hipError_t launch_temporal_preview(const TemporalArgs& a, const uint32_t* d_tiles, uint32_t n_tiles, hipStream_t stream);
 // rpt_temporal_set_motion's table on its way to the device: `bytes` from host memory to d_table, enqueued on `stream` (the host
 // array may be reused as soon as the call returns).  (Weak, like the launcher above.)
 __attribute__((weak)) hipError_t launch_temporal_motion_upload(void* d_table, const double* records, size_t bytes, hipStream_t stream);
@@ -180,6 +184,14 @@ __attribute__((weak)) hipError_t launch_tile_errors(const TileBufferView& b, dou
                                                     double* d_err, hipStream_t st);
 __attribute__((weak)) hipError_t launch_tile_select(const TileBufferView& b, double threshold2, uint32_t max_batches, const double* d_err,
                                                     uint32_t* d_tiles_out, uint32_t* d_n_out, hipStream_t st);
+// rpt_temporal_tile_errors_device: err[t] of the listed tiles (d_tiles null: of every tile) with the pixel's terms from the planes
+// rgb and var; an id out of range is skipped.  Then launch_tile_select among a list (d_tiles_in null: among every tile), the
+// selected ids in the list's order; d_tiles_out may be d_tiles_in.  (Weak, like the two above.)
+__attribute__((weak)) hipError_t launch_plane_tile_errors(uint32_t width, uint32_t height, double floor, const double* d_rgb, const double* d_var,
+                                                          const uint32_t* d_tiles, uint32_t n_tiles, double* d_err, hipStream_t st);
+__attribute__((weak)) hipError_t launch_tile_select_list(const TileBufferView& b, double threshold2, uint32_t max_batches, const double* d_err,
+                                                         const uint32_t* d_tiles_in, uint32_t n_in, uint32_t* d_tiles_out, uint32_t* d_n_out,
+                                                         hipStream_t st);
 hipError_t launch_debug_rng(uint64_t seed_mixed, uint32_t pixel, uint32_t sample, uint32_t n, uint32_t* d_out,
                             hipStream_t stream);
 hipError_t launch_debug_sample_f(const Material& m, uint64_t n, const float* d_n, const float* d_wo,

@@ -3554,7 +3554,8 @@ struct rpt_temporal {
     rpti::DevMem d_frame;              // rpt_temporal_frame_image: mean, variance, accumulated frame and variance, filtered frame
     rpti::Event done;                  // recorded after the kernel of a call: the next call waits for it, whatever its stream
     bool used = false;
-    // The one-shot motion table of the next call that passes its checks (motion_set: 0 none, 1 host records, 2 the caller's device table).
+    // The one-shot motion table of the next call that passes its checks (motion_set: 0 none, 1 host records, 2 the caller's device table, 3 host
+    // records that a preview has already uploaded to d_motion).
     int motion_set = 0;
     uint32_t n_motion = 0;
     std::vector<double> motion_host;   // rpt_temporal_set_motion's copy, uploaded by the consuming call on its stream
@@ -3676,7 +3677,8 @@ int rpt_temporal_set_clip(rpt_temporal* t, uint32_t radius, double gamma, uint32
 }
 // What rpt_temporal_* refuse before any device call; the call's camera record to *rec.
 static int check_temporal(const rpt_temporal* t, const rpt_temporal_params* prm, const rpt_camera* cam, const void* rgb, const void* var,
-                          const void* normal, const void* depth, const void* out, const void* out_var, const void* out_len, TemporalCam* rec) {
+                          const void* normal, const void* depth, const void* out, const void* out_var, const void* out_len, TemporalCam* rec,
+                          bool null_tile_list = false /* a preview's d_tiles == NULL with n_tiles > 0 */) {
     if (!prm) return fail(RPT_ERR_INVALID, "null temporal parameters");
     if (prm->max_history < 1 || prm->max_history > 4096) return fail(RPT_ERR_INVALID, "max_history must be 1..4096");
     if (prm->flags & ~(RPT_TEMPORAL_MATCH_ID | RPT_TEMPORAL_CLIP)) return fail(RPT_ERR_INVALID, "unknown temporal flag");
@@ -3693,14 +3695,20 @@ static int check_temporal(const rpt_temporal* t, const rpt_temporal_params* prm,
         for (const void* in : {rgb, var, normal, depth})
             if (o && o == in) return fail(RPT_ERR_INVALID, "an output must not be one of the inputs");
     if (out == out_var || out == out_len || (out_var && out_var == out_len)) return fail(RPT_ERR_INVALID, "the outputs must differ");
+    if (null_tile_list) return fail(RPT_ERR_INVALID, "null tile list");
     // (with RPT_TEMPORAL_CLIP the call would read its three settings from the accumulator: the refusal names the flag that needs them)
     if (!t) return fail(RPT_ERR_INVALID, (prm->flags & RPT_TEMPORAL_CLIP) ? "null accumulator: the flag RPT_TEMPORAL_CLIP reads its settings from it" : "null accumulator");
     return RPT_OK;
 }
-// (The arguments have passed check_temporal.)
+// (The arguments have passed check_temporal.)  preview: rpt_temporal_preview_device over d_tiles / n_tiles -- ordered through the same
+// event, the same arguments, the same table, but nothing of the accumulator's changes: no record is written, the records do not swap,
+// the camera record and the frame count stay, and the motion table stays set.  A host table is uploaded by the first call that reads
+// it, preview or not (motion_set 1 -> 3: "host records, already in d_motion"); the calls behind it wait for that call's event.
 static int run_temporal(rpt_temporal* t, const rpt_temporal_params* prm, const TemporalCam& rec, const double* d_rgb, const double* d_var,
-                        const double* d_normal, const double* d_depth, double* d_out, double* d_out_var, double* d_out_len, hipStream_t st) {
+                        const double* d_normal, const double* d_depth, double* d_out, double* d_out_var, double* d_out_len, hipStream_t st,
+                        bool preview = false, const uint32_t* d_tiles = nullptr, uint32_t n_tiles = 0) {
     if (!launch_temporal_accumulate) return fail(RPT_ERR_UNSUPPORTED, "rpt_temporal_accumulate: built without the kernels");
+    if (preview && !launch_temporal_preview) return fail(RPT_ERR_UNSUPPORTED, "rpt_temporal_preview_device: built without the kernels");
     HIP_TRY(hipSetDevice(t->device));
     if (t->used) HIP_TRY(hipStreamWaitEvent(st, t->done.get(), 0));
     t->used = true;
@@ -3728,10 +3736,18 @@ static int run_temporal(rpt_temporal* t, const rpt_temporal_params* prm, const T
             return fail(RPT_ERR_DEVICE, std::string("the motion table's upload: ") + hipGetErrorString(e));
         }
         a.motion = t->d_motion.get<double>();
+        t->motion_set = 3;
     } else if (t->motion_set == 2) {
         a.motion = t->motion_dev;
+    } else if (t->motion_set == 3) {
+        a.motion = t->d_motion.get<double>();
     }
     a.n_motion = a.motion ? t->n_motion : 0u;
+    if (preview) {
+        HIP_TRY(launch_temporal_preview(a, d_tiles, n_tiles, st));
+        HIP_TRY(hipEventRecord(t->done.get(), st));
+        return RPT_OK;
+    }
     t->motion_set = 0;                 // one-shot: the table describes this frame's motion only
     HIP_TRY(launch_temporal_accumulate(a, st));
     HIP_TRY(hipEventRecord(t->done.get(), st));
@@ -3748,6 +3764,98 @@ int rpt_temporal_accumulate_device(rpt_temporal* t, const rpt_temporal_params* p
     return run_temporal(t, prm, rec, static_cast<const double*>(d_rgb), static_cast<const double*>(d_var), static_cast<const double*>(d_normal),
                         static_cast<const double*>(d_depth), static_cast<double*>(d_out_rgb), static_cast<double*>(d_out_var),
                         static_cast<double*>(d_out_len), static_cast<hipStream_t>(hip_stream));
+}
+int rpt_temporal_preview_device(rpt_temporal* t, const rpt_temporal_params* prm, const rpt_camera* cam, const void* d_rgb, const void* d_var,
+                                const void* d_normal, const void* d_depth, const void* d_tiles, uint32_t n_tiles, void* d_out_rgb, void* d_out_var,
+                                void* d_out_len, void* hip_stream) {
+    TemporalCam rec;
+    if (int rc = check_temporal(t, prm, cam, d_rgb, d_var, d_normal, d_depth, d_out_rgb, d_out_var, d_out_len, &rec, !d_tiles && n_tiles)) return rc;
+    if (d_tiles && n_tiles > ((t->width + 31u) / 32u) * ((t->height + 31u) / 32u))
+        return fail(RPT_ERR_INVALID, "rpt_temporal_preview_device: more tiles listed than the frame has (the ids of a list are distinct)");
+    return run_temporal(t, prm, rec, static_cast<const double*>(d_rgb), static_cast<const double*>(d_var), static_cast<const double*>(d_normal),
+                        static_cast<const double*>(d_depth), static_cast<double*>(d_out_rgb), static_cast<double*>(d_out_var),
+                        static_cast<double*>(d_out_len), static_cast<hipStream_t>(hip_stream), true, static_cast<const uint32_t*>(d_tiles), n_tiles);
+}
+int rpt_temporal_tile_errors_device(rpt_temporal* t, const void* d_rgb, const void* d_var, double floor, const void* d_tiles, uint32_t n_tiles,
+                                    void* d_err, void* hip_stream) {
+    if (!(floor > 0.0) || std::isinf(floor)) return fail(RPT_ERR_INVALID, "floor must be finite and > 0");
+    if (!t || !d_rgb || !d_var || !d_err) return fail(RPT_ERR_INVALID, "null argument");
+    if (!d_tiles && n_tiles) return fail(RPT_ERR_INVALID, "null tile list");
+    if (d_tiles && n_tiles > ((t->width + 31u) / 32u) * ((t->height + 31u) / 32u))
+        return fail(RPT_ERR_INVALID, "rpt_temporal_tile_errors_device: more tiles listed than the frame has (the ids of a list are distinct)");
+    if (!launch_plane_tile_errors) return fail(RPT_ERR_UNSUPPORTED, "rpt_temporal_tile_errors_device: built without the kernels");
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(launch_plane_tile_errors(t->width, t->height, floor, static_cast<const double*>(d_rgb), static_cast<const double*>(d_var),
+                                     static_cast<const uint32_t*>(d_tiles), n_tiles, static_cast<double*>(d_err), static_cast<hipStream_t>(hip_stream)));
+    return RPT_OK;
+}
+int rpt_render_adaptive_temporal(rpt_scene* s, const rpt_camera* cam, const rpt_render_params* prm, const rpt_adaptive_params* p, uint64_t seed,
+                                 uint32_t sample_offset, rpt_buffer* b, rpt_temporal* t, const rpt_temporal_params* tprm, const void* d_normal,
+                                 const void* d_depth, uint64_t stats[4]) {
+    if (!s || !cam || !prm) return fail(RPT_ERR_INVALID, "null argument");
+    if (int rc = check_adaptive(p)) return rc;
+    if (uint64_t(sample_offset) + uint64_t(p->max_batches) * p->spp_per_batch > 0xFFFFFFFFull)
+        return fail(RPT_ERR_INVALID, "sample_offset + max_batches * spp_per_batch must fit 32 bits");
+    if (prm->shard_count > 1) return fail(RPT_ERR_INVALID, "an adaptive render is not sharded");
+    if (!b) return fail(RPT_ERR_INVALID, "null buffer");
+    if (prm->width != b->width || prm->height != b->height) return fail(RPT_ERR_INVALID, "Invalid sample dimension");  // buffer.rs:33-36
+    if (s->committed && s->device != b->device) return fail(RPT_ERR_INVALID, "buffer and scene live on different devices");
+    // (the frame, its variance and the preview come from the buffer and the accumulator: placeholders that are no plane of the
+    // caller's.  The accumulation reads the normal plane only where its test is on.)
+    TemporalCam rec;
+    const void* const t_normal = tprm && tprm->normal_tol > 0.0 ? d_normal : nullptr;
+    if (int rc = check_temporal(t, tprm, cam, &rec, nullptr, t_normal, d_depth, b, nullptr, nullptr, &rec)) return rc;
+    if (b->device != t->device) return fail(RPT_ERR_INVALID, "buffer and accumulator live on different devices");
+    if (b->width != t->width || b->height != t->height) return fail(RPT_ERR_INVALID, "buffer and accumulator have different sizes");
+    if (b->n_batches || b->d_extra) return fail(RPT_ERR_STATE, "rpt_render_adaptive_temporal needs an empty buffer");
+    if (!launch_buffer_mean || !launch_temporal_preview || !launch_plane_tile_errors || !launch_tile_select_list)
+        return fail(RPT_ERR_UNSUPPORTED, "rpt_render_adaptive_temporal: built without the kernels");
+    for (uint32_t k = 0; k < p->min_batches; k++)
+        if (int rc = rpt_render_into_buffer(s, cam, prm, p->spp_per_batch, seed, sample_offset + k * p->spp_per_batch, b)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipDeviceSynchronize());  // the planes may have been written on other streams
+    const size_t n = size_t(b->width) * b->height;
+    HIP_TRY(b->d_active.reserve(size_t(b->n_tiles()) * 4));
+    HIP_TRY(b->d_tile_err.reserve(size_t(b->n_tiles()) * 8 + 8));
+    HIP_TRY(t->d_frame.reserve(11 * n * 8));  // (rpt_temporal_frame_image's size: the frame's last call will ask for it)
+    uint32_t* const d_active = b->d_active.get<uint32_t>();
+    double* const err = b->d_tile_err.get<double>();
+    uint32_t* const d_count = reinterpret_cast<uint32_t*>(err + b->n_tiles());
+    double* const mean = t->d_frame.get<double>();
+    double* const var = mean + 3 * n;
+    double* const acc = mean + 4 * n;
+    double* const acc_var = mean + 7 * n;
+    uint64_t rounds = 0, tile_batches = uint64_t(p->min_batches) * b->n_tiles();
+    // The active list starts as every tile (a null list) and only shrinks: a tile that left it is not evaluated again.
+    const uint32_t* list = nullptr;
+    uint32_t n_active = 0;
+    for (uint32_t k = p->min_batches; k < p->max_batches; k++) {
+        if (int rc = rpt_buffer_mean_device(b, mean, var, nullptr)) return rc;
+        if (int rc = run_temporal(t, tprm, rec, mean, var, static_cast<const double*>(t_normal), static_cast<const double*>(d_depth), acc, acc_var,
+                                  nullptr, nullptr, true, list, n_active))
+            return rc;
+        HIP_TRY(launch_plane_tile_errors(b->width, b->height, p->floor, acc, acc_var, list, n_active, err, nullptr));
+        HIP_TRY(launch_tile_select_list(b->view(), p->threshold * p->threshold, p->max_batches, err, list, n_active, d_active, d_count, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));   // the one synchronisation and the one read-back of a round, 4 bytes
+        HIP_TRY(hipMemcpy(&n_active, d_count, 4, hipMemcpyDeviceToHost));
+        list = d_active;
+        if (n_active == 0) break;
+        if (int rc = rpt_render_sample_tiles_device(s, cam, prm, p->spp_per_batch, seed, sample_offset + k * p->spp_per_batch, d_active, n_active,
+                                                    b->d_stage.get(), nullptr))
+            return rc;
+        if (int rc = rpt_buffer_add_samples_tiles_device(b, b->d_stage.get(), d_active, n_active, nullptr)) return rc;
+        rounds++;
+        tile_batches += n_active;
+    }
+    if (stats) {
+        std::vector<uint32_t> nb(b->n_tiles());
+        if (int rc = rpt_buffer_tile_batches(b, nb.data(), nb.size())) return rc;
+        stats[0] = rounds;
+        stats[1] = tile_batches;
+        stats[2] = uint64_t(std::count(nb.begin(), nb.end(), p->max_batches));
+        stats[3] = b->n_tiles();
+    }
+    return RPT_OK;
 }
 int rpt_temporal_accumulate(rpt_temporal* t, const rpt_temporal_params* prm, const rpt_camera* cam, const double* rgb, const double* var,
                             const double* normal, const double* depth, double* out_rgb, double* out_var, double* out_len) {

@@ -15,6 +15,8 @@
 // parts into one comparison -- in LDS; a pixel that took history then sums its window from LDS in the definition's order.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/rpt_hip.h"
 #include "kernels.h"
 
@@ -48,9 +50,28 @@ __device__ __forceinline__ double clip_min(double a, double b) { return (a <= b 
 // neighbouring pixels that nearly always see one or two ids, so the 21 loads of its lanes fall on the same few cache lines.
 // CLIP: flag RPT_TEMPORAL_CLIP.  The key of a halo cell is NaN where the cell lies outside the image or its colour is not finite,
 // else its id with MATCH_ID and 0.0 without; a cell counts iff key == (MATCH_ID ? the pixel's id : 0.0), which is false for NaN.
-template <bool MOTION, bool CLIP>
-__global__ __launch_bounds__(256) void temporal_accumulate_kernel(const TemporalArgs a) {
-    const uint32_t x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
+// PREVIEW: rpt_temporal_preview_device, steps 1 - 5 alone: the same kernel -- one body, so the two cannot differ by a bit -- whose
+// argument carries a tile list and which writes no record.  With a list the grid is four blocks per listed 32 x 32 tile, block b the
+// quadrant b & 3 (row-major) of tile tiles[b >> 2]; an id out of range and a quadrant outside the image are left by the whole block
+// before anything else (no lane of it reaches the halo's barrier).  Without a list: the frame's ordinary grid.
+struct TemporalPreviewArgs : TemporalArgs {
+    const uint32_t* tiles;                               // [gridDim.x / 4] or null
+    uint32_t tiles_x, tiles_y;
+};
+template <bool MOTION, bool CLIP, bool PREVIEW = false>
+__global__ __launch_bounds__(256) void temporal_accumulate_kernel(const std::conditional_t<PREVIEW, TemporalPreviewArgs, TemporalArgs> a) {
+    uint32_t bx = blockIdx.x, by = blockIdx.y;           // the block's place in the frame's grid of 16 x 16 pixel blocks
+    if constexpr (PREVIEW) {
+        if (a.tiles) {
+            const uint32_t tile = a.tiles[blockIdx.x >> 2], q = blockIdx.x & 3u;
+            if (tile >= a.tiles_x * a.tiles_y) return;
+            const uint32_t ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+            bx = 2u * tx + (q & 1u);
+            by = 2u * ty + (q >> 1);
+            if (bx * kTile >= a.width || by * kTile >= a.height) return;
+        }
+    }
+    const uint32_t x = bx * kTile + threadIdx.x, y = by * kTile + threadIdx.y;
     __shared__ double halo[CLIP ? 2 : 1][CLIP ? kHaloSide : 1][CLIP ? kHaloPitch : 1];
     if constexpr (CLIP) {
         // every thread of the block, the ones outside the image included, stages and reaches the barrier
@@ -58,7 +79,7 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const Temporal
         const bool match = a.flags & RPT_TEMPORAL_MATCH_ID;
         for (uint32_t i = threadIdx.y * kTile + threadIdx.x; i < side * side; i += kTile * kTile) {
             const uint32_t cy = i / side, cx = i - cy * side;
-            const uint32_t gx = blockIdx.x * kTile + cx - r, gy = blockIdx.y * kTile + cy - r;   // (left of / above the image wraps to a large value)
+            const uint32_t gx = bx * kTile + cx - r, gy = by * kTile + cy - r;   // (left of / above the image wraps to a large value)
             double c0 = 0.0, c1 = 0.0, c2 = 0.0, key = __builtin_nan("");
             if (gx < a.width && gy < a.height) {
                 const size_t g = size_t(gy) * a.width + gx;
@@ -206,6 +227,7 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const Temporal
     a.out_rgb[3 * p + 2] = out.c[2];
     if (a.out_var) a.out_var[p] = out.v;
     if (a.out_len) a.out_len[p] = len;
+    if constexpr (PREVIEW) return;
     // 6: the new record; a miss or a value that is not finite carries no history
     const bool keep = hit && finite(out.c[0]) && finite(out.c[1]) && finite(out.c[2]) && finite(out.v);
     out.len = keep ? len : 0.0;
@@ -230,6 +252,29 @@ hipError_t launch_temporal_accumulate(const TemporalArgs& a, hipStream_t stream)
         hipLaunchKernelGGL((temporal_accumulate_kernel<true, false>), grid, block, 0, stream, a);
     } else {
         hipLaunchKernelGGL((temporal_accumulate_kernel<false, false>), grid, block, 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_temporal_preview(const TemporalArgs& args, const uint32_t* d_tiles, uint32_t n_tiles, hipStream_t stream) {
+    if (!args.width || !args.height || (d_tiles && !n_tiles)) return hipSuccess;
+    TemporalPreviewArgs a{};
+    static_cast<TemporalArgs&>(a) = args;
+    a.tiles = d_tiles;
+    a.tiles_x = (a.width + 31u) / 32u;
+    a.tiles_y = (a.height + 31u) / 32u;
+    if (d_tiles && n_tiles > a.tiles_x * a.tiles_y) return hipErrorInvalidValue;   // (distinct ids: a longer list cannot be; 4 n_tiles < 2^23)
+    const dim3 grid = d_tiles ? dim3(4u * n_tiles) : dim3((a.width + kTile - 1) / kTile, (a.height + kTile - 1) / kTile), block(kTile, kTile);
+    if (a.flags & RPT_TEMPORAL_CLIP) {
+        if (a.clip_radius < 1 || a.clip_radius > kTemporalClipMaxRadius) return hipErrorInvalidValue;   // the halo would not hold the window
+        if (a.motion)
+            hipLaunchKernelGGL((temporal_accumulate_kernel<true, true, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((temporal_accumulate_kernel<false, true, true>), grid, block, 0, stream, a);
+    } else if (a.motion) {
+        hipLaunchKernelGGL((temporal_accumulate_kernel<true, false, true>), grid, block, 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((temporal_accumulate_kernel<false, false, true>), grid, block, 0, stream, a);
     }
     return hipGetLastError();
 }
