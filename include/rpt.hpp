@@ -141,6 +141,16 @@ class Shape {
         return d;
     }
 
+    // MonomialSurface::closest_point / closest_point_precise (monomial_surface.rs:126-178) of the bare surface: the closest of 201 /
+    // 20,001 curve samples, a host function whose arithmetic rpt_hip.h states.
+    Vec3 closest_point(Vec3 p, bool precise = false) const {
+        if (kind != RPT_SHAPE_MONOMIAL || has_transform) throw Error("closest_point: not a bare monomial surface");
+        Vec3 out{};
+        check(rpt_monomial_closest_point(plane_normal[0], p.data(), precise ? 1 : 0, out.data()));
+        return out;
+    }
+    Vec3 closest_point_precise(Vec3 p) const { return closest_point(p, true); }
+
   private:
     mutable std::vector<rpt_shape_desc> child_descs_;
     Shape wrap(const Mat4& t) const {
@@ -877,5 +887,140 @@ inline void Renderer::sample_sharded(uint32_t iterations, Comm& comm, void* d_fr
     sample_offset_ += iterations;
     comm.gather(p_.width, p_.height, d_frame, d_frame, hip_stream);
 }
+
+// ---- src/ode/: ParticleState, the ParticleSystem trait and its three systems (rpt_particles_*; rpt_hip.h states the arithmetic).
+struct ParticleState {
+    std::vector<Vec3> pos, vel;
+    size_t size() const { return pos.size(); }
+};
+inline ParticleState operator+(const ParticleState& a, const ParticleState& b) {
+    ParticleState r = a;
+    for (size_t i = 0; i < r.pos.size(); i++)
+        for (int k = 0; k < 3; k++) {
+            r.pos[i][k] = a.pos[i][k] + b.pos[i][k];
+            r.vel[i][k] = a.vel[i][k] + b.vel[i][k];
+        }
+    return r;
+}
+inline ParticleState operator*(const ParticleState& a, double f) {
+    ParticleState r = a;
+    for (size_t i = 0; i < r.pos.size(); i++)
+        for (int k = 0; k < 3; k++) {
+            r.pos[i][k] = a.pos[i][k] * f;
+            r.vel[i][k] = a.vel[i][k] * f;
+        }
+    return r;
+}
+inline ParticleState operator/(const ParticleState& a, double f) {
+    ParticleState r = a;
+    for (size_t i = 0; i < r.pos.size(); i++)
+        for (int k = 0; k < 3; k++) {
+            r.pos[i][k] = a.pos[i][k] / f;
+            r.vel[i][k] = a.vel[i][k] / f;
+        }
+    return r;
+}
+// The open trait: a system of the caller's own overrides time_derivative and integrates on the host, with the operation order of
+// rpt_hip.h (k1 .. k4, ((k1 + k2 2) + k3 2) + k4, the reference's time loop).  Compile without fp contraction to get its bits.
+class ParticleSystem {
+  public:
+    virtual ~ParticleSystem() = default;
+    virtual ParticleState time_derivative(const ParticleState& state) const = 0;
+    virtual void rk4_integrate(ParticleState& state, double time, double step) const {
+        auto one = [&](double h) {
+            const ParticleState k1 = time_derivative(state);
+            const ParticleState k2 = time_derivative(state + k1 * (h / 2.0));
+            const ParticleState k3 = time_derivative(state + k2 * (h / 2.0));
+            const ParticleState k4 = time_derivative(state + k3 * h);
+            state = state + (((k1 + k2 * 2.0) + k3 * 2.0) + k4) * (h / 6.0);
+        };
+        while (time > step) {
+            one(step);
+            time = time - step;
+        }
+        one(time);
+    }
+};
+// A system's state on a device (rpt_particles): the calls of one simulator are ordered whatever their streams.
+class ParticleSimulator {
+  public:
+    ParticleSimulator(const rpt_particles_params& prm, const ParticleState& state, int device = 0) : n_(prm.n) {
+        h_ = rpt_particles_create(device, &prm);
+        if (!h_) throw Error(rpt_last_error());
+        set_state(state);
+    }
+    ParticleSimulator(const ParticleSimulator&) = delete;
+    ParticleSimulator& operator=(const ParticleSimulator&) = delete;
+    ~ParticleSimulator() { rpt_particles_destroy(h_); }
+    void set_state(const ParticleState& s) {
+        if (s.pos.size() != n_ || s.vel.size() != n_) throw Error("ParticleSimulator: the state has another number of particles");
+        check(rpt_particles_set_state(h_, s.pos[0].data(), s.vel[0].data()));   // (std::array<double, 3>: n x 3 contiguous doubles)
+    }
+    ParticleState state() const {
+        ParticleState s{std::vector<Vec3>(n_), std::vector<Vec3>(n_)};
+        check(rpt_particles_state(h_, s.pos[0].data(), s.vel[0].data()));
+        return s;
+    }
+    void integrate(double time, double step, void* hip_stream = nullptr) { check(rpt_particles_integrate(h_, time, step, hip_stream)); }
+    std::vector<Vec3> display_positions() const {
+        std::vector<Vec3> out(n_);
+        check(rpt_particles_display_positions(h_, out[0].data()));
+        return out;
+    }
+    std::array<uint64_t, 8> counters() const {
+        std::array<uint64_t, 8> c{};
+        check(rpt_particles_counters(h_, c.data()));
+        return c;
+    }
+    rpt_particles* raw() const { return h_; }
+
+  private:
+    rpt_particles* h_ = nullptr;
+    uint32_t n_ = 0;
+};
+// The three systems of particle_system.rs.  rk4_integrate goes through a handle on `device` (device < 0: the host function).
+class BuiltinParticleSystem : public ParticleSystem {
+  public:
+    int device = 0;
+    rpt_particles_params params(size_t n) const { return {kind_, uint32_t(n), radius_, height_}; }
+    ParticleState time_derivative(const ParticleState& s) const override {
+        ParticleState d{std::vector<Vec3>(s.size()), std::vector<Vec3>(s.size())};
+        const rpt_particles_params prm = params(s.size());
+        check(rpt_particles_derivative_host(&prm, s.size() ? s.pos[0].data() : nullptr, s.size() ? s.vel[0].data() : nullptr,
+                                            s.size() ? d.pos[0].data() : nullptr, s.size() ? d.vel[0].data() : nullptr, nullptr));
+        return d;
+    }
+    void rk4_integrate(ParticleState& s, double time, double step) const override {
+        const rpt_particles_params prm = params(s.size());
+        if (device < 0) {
+            uint64_t c[8];
+            check(rpt_particles_integrate_host(&prm, s.size() ? s.pos[0].data() : nullptr, s.size() ? s.vel[0].data() : nullptr, time, step, c));
+            return;
+        }
+        ParticleSimulator sim(prm, s, device);
+        sim.integrate(time, step);
+        s = sim.state();
+    }
+
+  protected:
+    BuiltinParticleSystem(int kind, double radius, double height) : kind_(kind), radius_(radius), height_(height) {}
+    int32_t kind_;
+    double radius_, height_;
+};
+struct SimpleCircleSystem : BuiltinParticleSystem {
+    SimpleCircleSystem() : BuiltinParticleSystem(RPT_PARTICLES_CIRCLE, 0.0, 0.0) {}
+};
+struct SolidGravitySystem : BuiltinParticleSystem {
+    SolidGravitySystem() : BuiltinParticleSystem(RPT_PARTICLES_GRAVITY, 0.0, 0.0) {}
+};
+struct MarblesSystem : BuiltinParticleSystem {
+    explicit MarblesSystem(double radius, double height = 2.0) : BuiltinParticleSystem(RPT_PARTICLES_MARBLES, radius, height) {}
+    std::vector<Vec3> display_positions(const std::vector<Vec3>& pos) const {   // marbles.rs:77-83 (a host function)
+        std::vector<Vec3> out(pos.size());
+        const rpt_particles_params prm = params(pos.size());
+        check(rpt_particles_display_positions_host(&prm, pos.empty() ? nullptr : pos[0].data(), out.empty() ? nullptr : out[0].data()));
+        return out;
+    }
+};
 
 }  // namespace rpt

@@ -624,6 +624,86 @@ int rpt_render_adaptive_temporal(rpt_scene*, const rpt_camera*, const rpt_render
                                  uint32_t sample_offset, rpt_buffer*, rpt_temporal*, const rpt_temporal_params*, const void* d_normal,
                                  const void* d_depth, uint64_t stats[4]);
 
+/* ---- particle systems (src/ode/particle_system.rs, particle_state.rs; MonomialSurface::closest_point*, src/shape/
+ * monomial_surface.rs:126-178; the display positions of examples/marbles.rs:76-88) ----
+ * The second of the two sequences the temporal code exists for, examples/marbles.rs, advances 25 marbles by rk4_integrate(state,
+ * 1/16, 1/10000) per frame.  A handle holds one system's state (pos, vel: n x 3 doubles each) on a device and integrates it there.
+ * The arithmetic is DEFINED here as an order of fp64 operations, each rounded on its own: no contraction, IEEE division, the
+ * correctly rounded square root.  tests/particles_ref.py restates it in numpy and the device's state is compared bit for bit.  Juxtaposition
+ * is a product; every bracket is a rounded operation; vector operations are componentwise.
+ *
+ *   length(v) = sqrt((v0 v0 + v1 v1) + v2 v2);  dot(a, b) = (a0 b0 + a1 b1) + a2 b2;  normalize(v)_k = v_k / length(v) (a division per
+ *   component);  x.powi(4) = (x x)(x x), powi(3) = (x x) x, powi(2) = x x, powi(1) = x;  len.powi(-2) = 1.0 / (len len);
+ *   len.powi(-5) = 1.0 / (len ((len len)(len len)));  max(a, b) = a if a >= b or b is NaN, else b (f64::max: the operand that is not NaN).
+ *
+ * closest_point(height, P) with n = 100, closest_point_precise with n = 10000:
+ *   1. If length(P) < 1e-12: the result is P.
+ *   2. px = sqrt(P0 P0 + P2 P2) (NOT the reference's f64::hypot: within an ulp of it where nothing over- or underflows, and numpy can
+ *      restate it);  py = P1.
+ *   3. For i = -n..n ascending:  xf = double(i) / double(n);  yc = height ((xf xf)(xf xf));  d = (px - xf)(px - xf) + (py - yc)(py - yc).
+ *      The winner is the first candidate with d < best, scanning upward from best = 1e18 (strict: of equal distances the lowest i wins;
+ *      a NaN distance or one >= 1e18 never wins).  If nothing wins, xf = -1.0.
+ *   4. ux = P0 / px;  uz = P2 / px;  X = xf ux;  Z = xf uz;  s = X X + Z Z;  the result is (X, height (s s), Z).
+ *      On the axis (px = 0, P1 != 0) that is NaN by IEEE rules, as in the reference.  Nothing is special-cased.
+ *
+ * RPT_PARTICLES_MARBLES, MarblesSystem{radius r}: the derivative of (pos, vel) is (vel, acc), with, for particle p, acc_p from (0, -1, 0):
+ *   pair terms, over the partners q != p in ASCENDING order (the order in which the reference's loop, i ascending and j < i, touches
+ *   particle p's accumulator):
+ *     q < p:  d = pos_p - pos_q;  q > p:  d = pos_q - pos_p.   len = length(d);  dir_k = d_k / len.
+ *     If len < 2.0 r:  c = (2.0 r - len) / r;  f_k = ((-dir_k) 5.0) c;  q < p: acc_p -= f;  q > p: acc_p += f;  then acc_p -= vel_p 0.5.
+ *     (Coincident marbles: NaN, as IEEE says.)
+ *   surface:  C = closest_point(height, pos_p);  v = pos_p - C;  L = length(v);  nrm_k = v_k / L;  ratio = (r - L) / r;  nv = dot(vel_p, nrm).
+ *     If -0.1 < ratio && ratio < 0.0 ("band"):  acc_p -= (30.0 nrm_k)((nv nv) nv).  Else if ratio >= 0.0 ("push"):  acc_p += (100.0 nrm_k) ratio.
+ *     NaN takes neither branch.
+ *   table:  n = (0, 1, 0);  ratio = ((r - 0.06) - pos_p.y) / r;  nv = ((vel0 0.0 + vel1 1.0) + vel2 0.0).  Only if length(pos_p) > 0.1:
+ *     band:  acc_p -= (20.0 n_k) nv;  push:  acc_p += (300000.0 n_k) ratio  -- on all three components, literally as written.
+ *   air:  acc_p -= vel_p / 5.0.
+ *   `height` is a parameter (the reference: 2.0); the exponent is the reference's hard-wired 4.
+ * RPT_PARTICLES_GRAVITY, SolidGravitySystem: acc_p from (0, 0, 0); partners in the same order and with the same d, len and dir;
+ *   s = 1.0 / (len len) - 0.0001 (1.0 / (len ((len len)(len len))));  f_k = dir_k s;  q < p: acc_p -= f;  q > p: acc_p += f.  (vel, acc).
+ * RPT_PARTICLES_CIRCLE, SimpleCircleSystem: the derivative is ((-pos.y, pos.x, 0.0), (0, 0, 0)).
+ *
+ * rk4_integrate(state, time, step).  One step of size h, on all six values of every particle alike:
+ *   k1 = f(S);  k2 = f(S + k1 (h / 2.0));  k3 = f(S + k2 (h / 2.0));  k4 = f(S + k3 h);  S = S + (((k1 + k2 2.0) + k3 2.0) + k4)(h / 6.0).
+ * The time loop is  t = time; while (t > step) { one(step); t = t - step; } one(t);  -- in fp64 (1/16, 1/10000) is 624 steps of `step` and one
+ * of 9.999999999924044e-05.  The host runs this loop for the step sequence and the device executes exactly that sequence, in launches
+ * of at most 256 steps chained on the caller's stream (a shared machine never sees a long kernel: 256 steps of 256 particles take 0.1 s).
+ *
+ * Display positions (MARBLES only):  C = closest_point_precise(pos);  v = pos - C;  if length(v) < r 1.05:  pos = C + (normalize(v) r) 1.05;
+ * then pos.y = max(pos.y, r - 0.06).
+ *
+ * Arguments, all checked before any device call and the parameters before the handle: n is 1..256; radius and height are finite, radius > 0
+ * for MARBLES; time is finite and >= 0, step finite and > 0; a step sequence of more than 2^20 steps is RPT_ERR_INVALID;
+ * rpt_particles_display_positions on a system that is not MARBLES is RPT_ERR_UNSUPPORTED.  State values that are not finite are
+ * accepted: NaN propagates as defined.  The calls of one handle are ordered whatever their streams; handles share nothing with scenes
+ * or with each other.  rpt_particles_integrate is asynchronous; the calls that move data to or from the host are synchronous.
+ * Counters: 0 derivative evaluations, 1 pair contacts (len < 2r, once per pair and evaluation), 2 surface band, 3 surface push, 4 table
+ * band, 5 table push, 6 kernel launches, 7 zero.  0..5 are part of the definition; the host functions report them with 6 = 7 = 0. */
+#define RPT_PARTICLES_CIRCLE 0
+#define RPT_PARTICLES_GRAVITY 1
+#define RPT_PARTICLES_MARBLES 2
+typedef struct rpt_particles_params {
+    int32_t kind;    /* RPT_PARTICLES_* */
+    uint32_t n;      /* 1..256 particles */
+    double radius;   /* MARBLES: > 0; otherwise unused */
+    double height;   /* MARBLES: the glass, y = height (x^2 + z^2)^2; otherwise unused */
+} rpt_particles_params;
+typedef struct rpt_particles rpt_particles;
+rpt_particles* rpt_particles_create(int device, const rpt_particles_params*);   /* the state starts as zeros */
+void rpt_particles_destroy(rpt_particles*);
+int rpt_particles_set_state(rpt_particles*, const double* pos, const double* vel /* NULL = zeros */);   /* host, n*3 each, copied */
+int rpt_particles_state(rpt_particles*, double* pos, double* vel);                                      /* synchronous; either may be NULL */
+int rpt_particles_state_device(rpt_particles*, void** d_pos, void** d_vel);                             /* the handle's own arrays */
+int rpt_particles_integrate(rpt_particles*, double time, double step, void* hip_stream);                /* asynchronous */
+int rpt_particles_display_positions(rpt_particles*, double* out /* host n*3 */);                        /* MARBLES only, synchronous */
+int rpt_particles_counters(rpt_particles*, uint64_t out[8]);
+/* Pure host functions, no device is touched: the same text run serially. */
+int rpt_monomial_closest_point(double height, const double p[3], int precise, double out[3]);
+int rpt_particles_derivative_host(const rpt_particles_params*, const double* pos, const double* vel, double* dpos, double* dvel,
+                                  uint64_t counters[8] /* or NULL */);
+int rpt_particles_integrate_host(const rpt_particles_params*, double* pos, double* vel, double time, double step, uint64_t counters[8]);
+int rpt_particles_display_positions_host(const rpt_particles_params*, const double* pos, double* out);
+
 /* ---- photon mapping (next tier: src/photon.rs; config C4 = photon_point_query_beam_render) ----
  * `enum PhotonRenderKind` (src/photon.rs:631-639): point-point (photon_map_render), beam-point
  * (photon_point_query_beam_render, config C4) and beam-beam (photon_beam_query_beam_render). */

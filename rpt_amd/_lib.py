@@ -84,6 +84,15 @@ class TemporalParams(C.Structure):
     ]
 
 
+class ParticlesParams(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("n", C.c_uint32),
+        ("radius", C.c_double),
+        ("height", C.c_double),
+    ]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [
         ("spp_per_batch", C.c_uint32),
@@ -180,6 +189,18 @@ SYMBOLS = [
     ("rpt_render_adaptive_temporal", C.c_int,
      [_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.c_uint64, C.c_uint32, _P, _P,
       C.POINTER(TemporalParams), _P, _P, C.POINTER(C.c_uint64)]),
+    ("rpt_particles_create", _P, [C.c_int, C.POINTER(ParticlesParams)]),
+    ("rpt_particles_destroy", None, [_P]),
+    ("rpt_particles_set_state", C.c_int, [_P, _P, _P]),
+    ("rpt_particles_state", C.c_int, [_P, _P, _P]),
+    ("rpt_particles_state_device", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("rpt_particles_integrate", C.c_int, [_P, C.c_double, C.c_double, _P]),
+    ("rpt_particles_display_positions", C.c_int, [_P, _P]),
+    ("rpt_particles_counters", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("rpt_monomial_closest_point", C.c_int, [C.c_double, _D3, C.c_int, _D3]),
+    ("rpt_particles_derivative_host", C.c_int, [C.POINTER(ParticlesParams), _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    ("rpt_particles_integrate_host", C.c_int, [C.POINTER(ParticlesParams), _P, _P, C.c_double, C.c_double, C.POINTER(C.c_uint64)]),
+    ("rpt_particles_display_positions_host", C.c_int, [C.POINTER(ParticlesParams), _P, _P]),
     ("rpt_photon_map_build", C.c_int, [_P, C.c_uint64, C.c_int32, C.c_double, C.c_uint64]),
     ("rpt_photon_shoot", C.c_int,
      [_P, C.c_uint64, C.c_int32, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),

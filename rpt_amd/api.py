@@ -188,6 +188,21 @@ class MonomialSurface(Shape):
         self.height = float(height)
         self.exp = float(exp)
 
+    def _closest(self, point, precise):
+        p = (C.c_double * 3)(*[float(x) for x in point])
+        out = (C.c_double * 3)()
+        _lib.check(_lib.load().rpt_monomial_closest_point(self.height, p, precise, out))
+        return np.array(out[:], dtype=np.float64)
+
+    def closest_point(self, point):
+        """The closest of the 201 curve samples xf = -1, -0.99 .. 1 to `point`, rotated back about the axis
+        (monomial_surface.rs:126-151; the exponent is 4, as there).  A host function: include/rpt_hip.h states its arithmetic."""
+        return self._closest(point, 0)
+
+    def closest_point_precise(self, point):
+        """... of 20,001 samples (monomial_surface.rs:154-178)."""
+        return self._closest(point, 1)
+
 
 class Triangle:
     """shape/mesh.rs:9-39."""

@@ -329,3 +329,54 @@ CONFIGS = {
     "C5": mesh_in_fog,
     "C5G": mesh_among_spheres,   # not a BASELINE configuration: C5's mesh inside a kd-tree group (scene tree + parked mesh walks)
 }
+
+
+MARBLES_RADIUS = 0.15
+
+
+def marbles_initial(n=25, seed=123):
+    """The start of examples/marbles.rs:36-48 as a ParticleState: marble i at ((i / 5) / 5 - 0.375, y_i, (i % 5) / 5 - 0.375), at
+    rest, y_i uniform in [4, 6).  The heights come from numpy.random.default_rng(seed): the stream of the reference's
+    StdRng::seed_from_u64(123) is not reproducible here, so the marbles fall from other heights than the example's."""
+    from .ode import ParticleState
+    rng = np.random.default_rng(seed)
+    pos = [[(i // 5) / 5.0 - 0.375, rng.uniform(4.0, 6.0), (i % 5) / 5.0 - 0.375] for i in range(n)]
+    return ParticleState(np.array(pos, dtype=np.float64).reshape(-1, 3))
+
+
+def marbles(positions, env=(0.6, 0.65, 0.7), glass=None):
+    """examples/marbles.rs:57-105 (800x600x2000, max_bounces(9) there): one frame of the sequence, marbles of radius 0.15 drawn at
+    `positions` (the display positions of the state: ParticleSimulator.display_positions) in the example's five colours, the clear
+    glass, the sphere light, the floor polygon and the focused camera.  The example downloads an HDRI (ballroom_8k.hdr); a constant
+    environment `env` stands in for it, as in monomial_glass.  `glass`: the glass's shape -- None for the analytic
+    monomial_surface(2, 4), or a mesh loaded with io.load_obj, as the example does with its monomial.obj.  Not in CONFIGS."""
+    r = MARBLES_RADIUS
+    scene = Scene()
+    scene.environment = Environment.Color(vec3(*env))
+    scene.add(Light.Object(Object(sphere().scale(vec3(1.5, 1.5, 1.5)).translate(vec3(0.0, 5.0, 0.0)))
+                           .material(Material.light(hex_color(0xFFFFFF), 15.0))))
+    scene.add(Object(monomial_surface(2.0, 4.0) if glass is None else glass).material(Material.clear(1.5, 0.0001)))
+    colors = [0x264653, 0x2A9D8F, 0xE9C46A, 0xF4A261, 0xE76F51]
+    for i, pos in enumerate(np.asarray(positions, dtype=np.float64).reshape(-1, 3)):
+        scene.add(Object(sphere().scale(vec3(r, r, r)).translate(vec3(*pos))).material(Material.specular(hex_color(colors[i % len(colors)]), 0.1)))
+    scene.add(Object(polygon([vec3(20.0, -0.06, 20.0), vec3(20.0, -0.06, -20.0), vec3(-20.0, -0.06, -20.0), vec3(-20.0, -0.06, 20.0)]))
+              .material(Material.diffuse(hex_color(0xAAAAAA))))
+    camera = Camera.look_at(vec3(0.0, 1.0, 6.0), vec3(0.0, 1.0, 0.0), vec3(0.0, 1.0, 0.0), math.pi / 4.0).focus(vec3(0.0, 1.0, 0.0), 0.02)
+    return scene, camera, {"width": 800, "height": 600, "spp": 2000, "max_bounces": 9}
+
+
+def marbles_sequence(frames, device=0, state=None, **kw):
+    """A generator of (scene, camera) for `frames` frames of examples/marbles.rs: frame f shows the state after f advances of
+    rk4_integrate(state, 1/16, 1/10000) on the device (one ParticleSimulator for the sequence), from `state` (default:
+    marbles_initial()); `kw` goes to marbles().  The scenes go into Renderer.render_sequence(cameras, scenes=...), which builds the
+    motion records from the objects' matrices."""
+    from .ode import MarblesSystem, ParticleSimulator
+    sim = ParticleSimulator(MarblesSystem(MARBLES_RADIUS), marbles_initial() if state is None else state, device=device)
+    try:
+        for f in range(frames):
+            scene, camera, _ = marbles(sim.display_positions(), **kw)
+            if f + 1 < frames:
+                sim.integrate(1.0 / 16.0, 1.0 / 10000.0)   # (asynchronous: the caller renders this frame meanwhile)
+            yield scene, camera
+    finally:
+        sim.close()
