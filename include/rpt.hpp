@@ -978,6 +978,71 @@ class ParticleSimulator {
     rpt_particles* h_ = nullptr;
     uint32_t n_ = 0;
 };
+// Many independent systems on a device, integrated in one launch (rpt_particles_batch): system i of `prm` with state i of `states`.
+// Every system comes out with the bits it would have alone; the calls of one ensemble are ordered whatever their streams.
+class ParticleEnsemble {
+  public:
+    ParticleEnsemble(const std::vector<rpt_particles_params>& prm, const std::vector<ParticleState>& states, int device = 0) {
+        if (prm.size() != states.size()) throw Error("ParticleEnsemble: as many states as systems");
+        first_.push_back(0);
+        for (size_t i = 0; i < prm.size(); i++) {
+            if (states[i].pos.size() != prm[i].n || states[i].vel.size() != prm[i].n) throw Error("ParticleEnsemble: a state has another number of particles");
+            first_.push_back(first_.back() + prm[i].n);
+        }
+        h_ = rpt_particles_batch_create(device, prm.data(), uint32_t(prm.size()));
+        if (!h_) throw Error(rpt_last_error());
+        std::vector<Vec3> pos, vel;
+        for (const ParticleState& s : states) {
+            pos.insert(pos.end(), s.pos.begin(), s.pos.end());
+            vel.insert(vel.end(), s.vel.begin(), s.vel.end());
+        }
+        const int rc = rpt_particles_batch_set_state(h_, pos[0].data(), vel[0].data());
+        if (rc != RPT_OK) {
+            rpt_particles_batch_destroy(h_);
+            check(rc);
+        }
+    }
+    ParticleEnsemble(const ParticleEnsemble&) = delete;
+    ParticleEnsemble& operator=(const ParticleEnsemble&) = delete;
+    ~ParticleEnsemble() { rpt_particles_batch_destroy(h_); }
+    size_t size() const { return first_.size() - 1; }
+    void set_state(size_t i, const ParticleState& s) {
+        if (i >= size()) throw Error("ParticleEnsemble: system index out of range");
+        if (s.pos.size() != first_[i + 1] - first_[i] || s.vel.size() != s.pos.size()) throw Error("ParticleEnsemble: the state has another number of particles");
+        check(rpt_particles_batch_set_system_state(h_, uint32_t(i), s.pos[0].data(), s.vel[0].data()));
+    }
+    std::vector<ParticleState> states() const {
+        std::vector<Vec3> pos(first_.back()), vel(first_.back());
+        check(rpt_particles_batch_state(h_, pos[0].data(), vel[0].data()));
+        std::vector<ParticleState> out;
+        for (size_t i = 0; i < size(); i++)
+            out.push_back({std::vector<Vec3>(pos.begin() + first_[i], pos.begin() + first_[i + 1]), std::vector<Vec3>(vel.begin() + first_[i], vel.begin() + first_[i + 1])});
+        return out;
+    }
+    void integrate(double time, double step, void* hip_stream = nullptr) { check(rpt_particles_batch_integrate(h_, time, step, hip_stream)); }
+    std::vector<std::vector<Vec3>> display_positions() const {
+        std::vector<Vec3> all(first_.back());
+        check(rpt_particles_batch_display_positions(h_, all[0].data()));
+        std::vector<std::vector<Vec3>> out;
+        for (size_t i = 0; i < size(); i++) out.emplace_back(all.begin() + first_[i], all.begin() + first_[i + 1]);
+        return out;
+    }
+    std::vector<std::array<uint64_t, 8>> counters() const {
+        std::vector<std::array<uint64_t, 8>> c(size());
+        check(rpt_particles_batch_counters(h_, c[0].data()));
+        return c;
+    }
+    std::array<uint64_t, 8> info() const {   // resident blocks, rounds, steps per launch, LDS bytes, largest n, particles, block, lanes
+        std::array<uint64_t, 8> c{};
+        check(rpt_particles_batch_info(h_, c.data()));
+        return c;
+    }
+    rpt_particles_batch* raw() const { return h_; }
+
+  private:
+    rpt_particles_batch* h_ = nullptr;
+    std::vector<size_t> first_;
+};
 // The three systems of particle_system.rs.  rk4_integrate goes through a handle on `device` (device < 0: the host function).
 class BuiltinParticleSystem : public ParticleSystem {
   public:

@@ -704,6 +704,42 @@ int rpt_particles_derivative_host(const rpt_particles_params*, const double* pos
 int rpt_particles_integrate_host(const rpt_particles_params*, double* pos, double* vel, double time, double step, uint64_t counters[8]);
 int rpt_particles_display_positions_host(const rpt_particles_params*, const double* pos, double* out);
 
+/* ---- particle ensembles: many independent systems in one launch ----
+ * A batch holds n_systems systems (1..4096, a stated limit as 256 is for n) of any kinds, sizes and parameters on one device: their
+ * states concatenated in system order (pos, vel: sum(n) x 3 doubles each; system s starts at particle first[s] = n_0 + .. + n_(s-1))
+ * and eight counters per system.  rpt_particles_batch_integrate advances every system by the same (time, step).  The result of system
+ * s -- state, display positions, counters 0..5 at out[8 s ..] -- is DEFINED as that of rpt_particles_integrate_host (and
+ * rpt_particles_display_positions_host) on that system alone, by the text above: the systems do not interact, and the device compares
+ * bit for bit, whatever else is in the batch.
+ *
+ * On the device one workgroup integrates one system, block s of a launch system s, with local memory sized for the batch's largest n,
+ * so that blocks of small systems share a compute unit.  R = compute units x blocks per compute unit (the occupancy query for the
+ * kernel and the local memory actually launched) blocks run at once; a batch of more runs in rounds = ceil(n_systems / R) rounds, and a
+ * launch lasts rounds x steps.  The host runs the time loop above for the step sequence and the device executes exactly that sequence in
+ * launches of L = max(1, floor(256 / (rounds x 2))) steps; only the last launch carries the remainder step.  (The factor 2 is what blocks
+ * that share a compute unit were measured to cost each other in the longest launch -- 1.98, four blocks of 256 particles on a compute
+ * unit -- rounded up to a power of two: DESIGN.md section 4, "Ensembles".)  Counter 6 of every system is the number of kernel launches of the batch's calls so far, 7 is zero.
+ * rpt_particles_batch_info: out[0] = R, 1 = rounds, 2 = L, 3 = bytes of dynamic local memory per block, 4 = the largest n, 5 = sum(n),
+ * 6 = threads per block, 7 = lanes per particle in the closest-point scan (6 and 7: tuning, no effect on results).
+ *
+ * Arguments, all checked before any device call and the parameters before the handle: params is not NULL; n_systems is 1..4096; then
+ * every system's parameters as rpt_particles_create checks them, in system order -- the first bad one is named in rpt_last_error
+ * ("system 17: ..."); time and step as rpt_particles_integrate checks them; rpt_particles_batch_set_system_state's system is
+ * < n_systems; rpt_particles_batch_display_positions on a batch in which any system is not MARBLES is RPT_ERR_UNSUPPORTED.  The calls of
+ * one batch are ordered whatever their streams; batches share nothing with handles, scenes or each other.
+ * rpt_particles_batch_integrate is asynchronous; the calls that move data to or from the host are synchronous. */
+typedef struct rpt_particles_batch rpt_particles_batch;
+rpt_particles_batch* rpt_particles_batch_create(int device, const rpt_particles_params* params /* [n_systems] */, uint32_t n_systems);
+void rpt_particles_batch_destroy(rpt_particles_batch*);
+int rpt_particles_batch_set_state(rpt_particles_batch*, const double* pos, const double* vel /* NULL = zeros */);   /* concatenated, sum(n) x 3 */
+int rpt_particles_batch_set_system_state(rpt_particles_batch*, uint32_t system, const double* pos, const double* vel /* NULL = zeros */);
+int rpt_particles_batch_state(rpt_particles_batch*, double* pos, double* vel);                    /* synchronous; either may be NULL */
+int rpt_particles_batch_state_device(rpt_particles_batch*, void** d_pos, void** d_vel, void** d_first /* uint32 first[n_systems] */);
+int rpt_particles_batch_integrate(rpt_particles_batch*, double time, double step, void* hip_stream);   /* asynchronous, one step sequence for all */
+int rpt_particles_batch_display_positions(rpt_particles_batch*, double* out /* host sum(n) x 3 */);    /* every system MARBLES, synchronous */
+int rpt_particles_batch_counters(rpt_particles_batch*, uint64_t* out /* n_systems x 8 */);
+int rpt_particles_batch_info(rpt_particles_batch*, uint64_t out[8]);
+
 /* ---- photon mapping (next tier: src/photon.rs; config C4 = photon_point_query_beam_render) ----
  * `enum PhotonRenderKind` (src/photon.rs:631-639): point-point (photon_map_render), beam-point
  * (photon_point_query_beam_render, config C4) and beam-beam (photon_beam_query_beam_render). */

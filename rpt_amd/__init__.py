@@ -8,7 +8,7 @@ from .api import *  # noqa: F401,F403
 from .api import __all__ as _api_all
 from . import scenes  # noqa: F401
 from .io import load_obj, load_obj_with_mtl, load_stl  # noqa: F401
-from .ode import MarblesSystem, ParticleSimulator, ParticleState, ParticleSystem, SimpleCircleSystem, SolidGravitySystem  # noqa: F401
+from .ode import MarblesSystem, ParticleEnsemble, ParticleSimulator, ParticleState, ParticleSystem, SimpleCircleSystem, SolidGravitySystem  # noqa: F401
 
 __all__ = list(_api_all) + ["scenes", "load_obj", "load_obj_with_mtl", "load_stl", "ParticleState", "ParticleSystem",
-                               "SimpleCircleSystem", "SolidGravitySystem", "MarblesSystem", "ParticleSimulator"]
+                               "SimpleCircleSystem", "SolidGravitySystem", "MarblesSystem", "ParticleSimulator", "ParticleEnsemble"]

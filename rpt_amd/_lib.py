@@ -197,6 +197,16 @@ SYMBOLS = [
     ("rpt_particles_integrate", C.c_int, [_P, C.c_double, C.c_double, _P]),
     ("rpt_particles_display_positions", C.c_int, [_P, _P]),
     ("rpt_particles_counters", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("rpt_particles_batch_create", _P, [C.c_int, C.POINTER(ParticlesParams), C.c_uint32]),
+    ("rpt_particles_batch_destroy", None, [_P]),
+    ("rpt_particles_batch_set_state", C.c_int, [_P, _P, _P]),
+    ("rpt_particles_batch_set_system_state", C.c_int, [_P, C.c_uint32, _P, _P]),
+    ("rpt_particles_batch_state", C.c_int, [_P, _P, _P]),
+    ("rpt_particles_batch_state_device", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("rpt_particles_batch_integrate", C.c_int, [_P, C.c_double, C.c_double, _P]),
+    ("rpt_particles_batch_display_positions", C.c_int, [_P, _P]),
+    ("rpt_particles_batch_counters", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("rpt_particles_batch_info", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("rpt_monomial_closest_point", C.c_int, [C.c_double, _D3, C.c_int, _D3]),
     ("rpt_particles_derivative_host", C.c_int, [C.POINTER(ParticlesParams), _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
     ("rpt_particles_integrate_host", C.c_int, [C.POINTER(ParticlesParams), _P, _P, C.c_double, C.c_double, C.POINTER(C.c_uint64)]),

@@ -18,6 +18,9 @@
 //   3. surface, table and air terms, lane p again.
 // No grid-wide synchronisation, no spin wait.  The six counters are summed per lane, added up in LDS at the end of a launch and
 // written by six lanes with ordinary stores.  A launch is at most 256 steps (rpt_particles.cpp cuts the sequence).
+//
+// rpt_particles_batch_*: the same body (integrate_system) with a grid of n_systems workgroups, block b on system b of a device
+// table, and the per-system LDS arrays dynamic, sized for the batch's largest n.
 #include <hip/hip_runtime.h>
 
 #include "../../include/rpt_hip.h"
@@ -51,17 +54,28 @@ __device__ __forceinline__ Key key_reduce(Key k) {
     return k;
 }
 
+// What one workgroup does for one system: the body of both kernels, so that a system of a batch cannot differ from a system
+// alone.  `lds` is where the per-system arrays lie (static in the single kernel, carved out of dynamic LDS in the batched one);
+// `staged` is uniform over the block and picks where the pair forces are computed, never their values.
+struct SystemLds {
+    double* pos;        // [3 n]: the stage positions
+    double* win;        // [n]: the winning xf of each particle's scan
+    double *xf, *yc;    // [kCand]
+    unsigned* cnt;      // [6]
+    double* f;          // staged: the force of pair (hi, lo) at pair_slot(hi, lo)
+    uint32_t* pair;     // ... hi << 16 | lo, and bit 31: the two touch (MARBLES; written per evaluation)
+};
 template <int BLOCK, int LANES>
-__global__ __launch_bounds__(BLOCK) void particles_integrate_kernel(const ParticlesArgs a) {
+__device__ __forceinline__ void integrate_system(const ParticlesArgs& a, const bool staged, const SystemLds lds) {
     static_assert(BLOCK >= int(kMaxParticles) && BLOCK % 64 == 0 && LANES <= 64 && (LANES & (LANES - 1)) == 0, "a lane per particle; a group within a wave");
-    __shared__ double s_pos[3 * kMaxParticles];   // the stage positions
-    __shared__ double s_win[kMaxParticles];       // the winning xf of each particle's scan
-    __shared__ double s_xf[kCand], s_yc[kCand];
-    __shared__ unsigned s_cnt[6];
-    __shared__ double s_f[3 * kPairSlots];        // n <= kStagedMaxN: the force of pair (hi, lo) at pair_slot(hi, lo)
-    __shared__ uint32_t s_pair[kPairSlots];       // ... hi << 16 | lo, and bit 31: the two touch (MARBLES; written per evaluation)
+    double* const s_pos = lds.pos;
+    double* const s_win = lds.win;
+    double* const s_xf = lds.xf;
+    double* const s_yc = lds.yc;
+    unsigned* const s_cnt = lds.cnt;
+    double* const s_f = lds.f;
+    uint32_t* const s_pair = lds.pair;
     const uint32_t t = threadIdx.x, n = a.n;
-    const bool staged = n <= kStagedMaxN && a.kind != RPT_PARTICLES_CIRCLE;
     const uint32_t n_pairs = n * (n - 1u) / 2u;
     if (staged && t < n)
         for (uint32_t lo = 0; lo < t; lo++) s_pair[pair_slot(t, lo)] = t << 16 | lo;
@@ -187,9 +201,50 @@ __global__ __launch_bounds__(BLOCK) void particles_integrate_kernel(const Partic
     if (t < 6) a.counters[t] = a.counters[t] + uint64_t(s_cnt[t]);
 }
 
+template <int BLOCK, int LANES>
+__global__ __launch_bounds__(BLOCK) void particles_integrate_kernel(const ParticlesArgs a) {
+    __shared__ double s_pos[3 * kMaxParticles];
+    __shared__ double s_win[kMaxParticles];
+    __shared__ double s_xf[kCand], s_yc[kCand];
+    __shared__ unsigned s_cnt[6];
+    __shared__ double s_f[3 * kPairSlots];        // n <= kStagedMaxN
+    __shared__ uint32_t s_pair[kPairSlots];
+    integrate_system<BLOCK, LANES>(a, a.n <= kStagedMaxN && a.kind != RPT_PARTICLES_CIRCLE, SystemLds{s_pos, s_win, s_xf, s_yc, s_cnt, s_f, s_pair});
+}
+
+// The batched form: block b integrates system b of the table.  The per-system arrays are dynamic LDS sized for the batch's largest
+// n (particles_batch_lds), so blocks of small systems co-reside up to the CU's wave limit; pair forces are staged when that n is at
+// most kStagedMaxN, for every system of the batch alike.  Blocks share nothing: no grid-wide synchronisation, no spin wait, no
+// atomics on state, and system b's counters at counters[8 b ..] get the same plain stores.
+template <int BLOCK, int LANES>
+__global__ __launch_bounds__(BLOCK) void particles_batch_integrate_kernel(const ParticlesBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_batch[];
+    const uint32_t sys = blockIdx.x;
+    if (sys >= b.n_systems) return;   // (uniform over the block)
+    const ParticlesSystemRecord rec = b.table[sys];
+    const ParticlesBatchLds l = particles_batch_lds(b.n_max);
+    ParticlesArgs a;
+    a.kind = rec.kind;
+    a.n = rec.n;
+    a.radius = rec.radius;
+    a.height = rec.height;
+    a.pos = b.pos + 3 * size_t(rec.first);
+    a.vel = b.vel + 3 * size_t(rec.first);
+    a.counters = b.counters + 8 * size_t(sys);
+    a.n_steps = b.n_steps;
+    a.tail = b.tail;
+    a.h = b.h;
+    a.h_tail = b.h_tail;
+    integrate_system<BLOCK, LANES>(a, b.n_max <= kStagedMaxN && rec.kind != RPT_PARTICLES_CIRCLE,
+                                   SystemLds{reinterpret_cast<double*>(s_batch + l.pos), reinterpret_cast<double*>(s_batch + l.win),
+                                             reinterpret_cast<double*>(s_batch + l.xf), reinterpret_cast<double*>(s_batch + l.yc),
+                                             reinterpret_cast<unsigned*>(s_batch + l.cnt), reinterpret_cast<double*>(s_batch + l.f),
+                                             reinterpret_cast<uint32_t*>(s_batch + l.pair)});
+}
+
 // The display positions: closest_point_precise recomputes its 20,001 candidates, the whole workgroup on one particle at a time.
 constexpr int kDisplayBlock = 256;
-__global__ __launch_bounds__(kDisplayBlock) void particles_display_kernel(const ParticlesArgs a, double* __restrict__ out) {
+__device__ __forceinline__ void display_system(const ParticlesArgs& a, double* __restrict__ out) {
     constexpr int kWaves = kDisplayBlock / 64;
     __shared__ double s_d[kWaves];
     __shared__ int s_i[kWaves];
@@ -230,6 +285,20 @@ __global__ __launch_bounds__(kDisplayBlock) void particles_display_kernel(const 
         for (int k = 0; k < 3; k++) out[3 * t + k] = D[k];
     }
 }
+__global__ __launch_bounds__(kDisplayBlock) void particles_display_kernel(const ParticlesArgs a, double* __restrict__ out) { display_system(a, out); }
+// ... and of a batch: block b shows system b of the table (every system MARBLES: the host checks)
+__global__ __launch_bounds__(kDisplayBlock) void particles_batch_display_kernel(const ParticlesBatchArgs b, double* __restrict__ out) {
+    const uint32_t sys = blockIdx.x;
+    if (sys >= b.n_systems) return;
+    const ParticlesSystemRecord rec = b.table[sys];
+    ParticlesArgs a{};
+    a.kind = rec.kind;
+    a.n = rec.n;
+    a.radius = rec.radius;
+    a.height = rec.height;
+    a.pos = b.pos + 3 * size_t(rec.first);
+    display_system(a, out + 3 * size_t(rec.first));
+}
 
 template <int BLOCK>
 hipError_t launch_block(const ParticlesArgs& a, uint32_t lanes, hipStream_t stream) {
@@ -241,6 +310,28 @@ hipError_t launch_block(const ParticlesArgs& a, uint32_t lanes, hipStream_t stre
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+// The batched instantiations, by (block, lanes): one table for the launch and for the occupancy query, so that R is asked of the
+// kernel that runs.
+using BatchKernel = void (*)(const ParticlesBatchArgs);
+template <int BLOCK>
+BatchKernel batch_kernel_of(uint32_t lanes) {
+    switch (lanes) {
+    case 8: return particles_batch_integrate_kernel<BLOCK, 8>;
+    case 16: return particles_batch_integrate_kernel<BLOCK, 16>;
+    case 32: return particles_batch_integrate_kernel<BLOCK, 32>;
+    case 64: return particles_batch_integrate_kernel<BLOCK, 64>;
+    default: return nullptr;
+    }
+}
+BatchKernel batch_kernel(uint32_t block, uint32_t lanes) {
+    switch (block) {
+    case 256: return batch_kernel_of<256>(lanes);
+    case 512: return batch_kernel_of<512>(lanes);
+    case 1024: return batch_kernel_of<1024>(lanes);
+    default: return nullptr;
+    }
 }
 }  // namespace
 
@@ -258,6 +349,35 @@ hipError_t launch_particles_display(const ParticlesArgs& a, double* d_out, hipSt
     if (a.n < 1 || a.n > kMaxParticles) return hipErrorInvalidValue;
     hipLaunchKernelGGL(particles_display_kernel, dim3(1), dim3(kDisplayBlock), 0, stream, a, d_out);
     return hipGetLastError();
+}
+
+hipError_t launch_particles_batch_integrate(const ParticlesBatchArgs& a, uint32_t block, uint32_t lanes, hipStream_t stream) {
+    const BatchKernel k = batch_kernel(block, lanes);
+    if (!k || !a.table || !a.pos || !a.vel || !a.counters || a.n_systems < 1 || a.n_systems > kBatchMaxSystems || a.n_max < 1 || a.n_max > kMaxParticles ||
+        a.n_steps < 1 || a.n_steps > kMaxLaunchSteps || a.lds_pad > kBatchMaxLds ||
+        particles_batch_lds(a.n_max).bytes + a.lds_pad > kBatchMaxLds)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, dim3(a.n_systems), dim3(block), particles_batch_lds(a.n_max).bytes + a.lds_pad, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_particles_batch_display(const ParticlesBatchArgs& a, double* d_out, hipStream_t stream) {
+    if (!a.table || !a.pos || !d_out || a.n_systems < 1 || a.n_systems > kBatchMaxSystems) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(particles_batch_display_kernel, dim3(a.n_systems), dim3(kDisplayBlock), 0, stream, a, d_out);
+    return hipGetLastError();
+}
+
+hipError_t particles_batch_resident_blocks(int device, uint32_t block, uint32_t lanes, uint32_t n_max, uint32_t lds_pad, uint32_t* resident) {
+    const BatchKernel k = batch_kernel(block, lanes);
+    if (!k || !resident || n_max < 1 || n_max > kMaxParticles || lds_pad > kBatchMaxLds || particles_batch_lds(n_max).bytes + lds_pad > kBatchMaxLds)
+        return hipErrorInvalidValue;
+    int per_cu = 0, cus = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k), int(block), particles_batch_lds(n_max).bytes + lds_pad);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    if (e != hipSuccess) return e;
+    if (per_cu < 1 || cus < 1) return hipErrorInvalidValue;
+    *resident = uint32_t(per_cu) * uint32_t(cus);
+    return hipSuccess;
 }
 
 }  // namespace rptg

@@ -1,7 +1,9 @@
 // rpt_particles.cpp — the host half of rpt_particles_* and the pure host functions next to them (include/rpt_hip.h, "particle
 // systems").  The arithmetic is particles_core.h's, the text the kernel compiles: rpt_particles_integrate_host is that text run
 // serially.  A handle owns its state arrays and counters on one device and shares nothing with scenes or with other handles; its
-// calls are ordered, whatever their streams, through one event, as the accumulators' are.
+// calls are ordered, whatever their streams, through one event, as the accumulators' are.  A batch (rpt_particles_batch) is the same
+// for many systems at once: concatenated state arrays, a device table with one record per system, one event, and a launch length
+// that shrinks with the number of rounds the device needs for the batch's blocks.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -171,6 +173,211 @@ int rpt_particles_counters(rpt_particles* h, uint64_t out[8]) {
     RPTI_HIP_TRY(hipMemcpy(out, h->d_cnt.get(), 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     out[6] = h->launches;
     out[7] = 0;
+    return RPT_OK;
+}
+
+}  // extern "C"
+
+// ---- ensembles: many independent systems, one workgroup each, in one launch (include/rpt_hip.h, "particle ensembles")
+struct rpt_particles_batch {
+    int device = 0;
+    std::vector<ParticlesSystemRecord> table;   // the host's copy of the device table
+    uint32_t total = 0, n_max = 0;              // particles of all systems; the largest system
+    bool all_marbles = true;
+    rpti::DevMem d_pos, d_vel, d_disp, d_cnt, d_table, d_first;
+    rpti::Event done;                           // as rpt_particles::done
+    bool used = false;
+    uint64_t launches = 0;
+    uint32_t block = kBatchDefaultBlock, lanes = kBatchDefaultLanes;   // the sweep at n_systems = R; RPT_PARTICLES_TUNE overrides them
+    uint32_t lds_pad = 0;                       // RPT_PARTICLES_TUNE="block,lanes,pad": extra dynamic LDS per block, to measure what sizing it to the batch buys
+    uint32_t resident = 0;                      // R of the launch rule, for this instantiation and this dynamic LDS
+};
+
+static ParticlesBatchArgs batch_args(rpt_particles_batch* b) {
+    ParticlesBatchArgs a{};
+    a.table = b->d_table.get<ParticlesSystemRecord>();
+    a.n_systems = uint32_t(b->table.size());
+    a.n_max = b->n_max;
+    a.pos = b->d_pos.get<double>();
+    a.vel = b->d_vel.get<double>();
+    a.counters = b->d_cnt.get<uint64_t>();
+    a.lds_pad = b->lds_pad;
+    return a;
+}
+// rounds = ceil(n_systems / R); a launch lasts rounds x steps, so it gets 256 / (rounds x kBatchLaunchScale) steps, at least one
+static uint32_t batch_rounds(const rpt_particles_batch* b) { return uint32_t((b->table.size() + b->resident - 1) / b->resident); }
+static uint32_t batch_launch_steps(const rpt_particles_batch* b) {
+    const uint32_t l = rptp::kMaxLaunchSteps / (batch_rounds(b) * kBatchLaunchScale);
+    return l < 1 ? 1 : l;
+}
+static int settle(rpt_particles_batch* b) {
+    RPTI_HIP_TRY(hipSetDevice(b->device));
+    if (b->used) RPTI_HIP_TRY(hipEventSynchronize(b->done.get()));
+    return RPT_OK;
+}
+
+extern "C" {
+rpt_particles_batch* rpt_particles_batch_create(int device, const rpt_particles_params* params, uint32_t n_systems) {
+    if (!params) { fail(RPT_ERR_INVALID, "null particle parameters"); return nullptr; }
+    if (n_systems < 1 || n_systems > kBatchMaxSystems) { fail(RPT_ERR_INVALID, "the number of systems must be 1..4096"); return nullptr; }
+    for (uint32_t s = 0; s < n_systems; s++)
+        if (check_params(params + s) != RPT_OK) {
+            fail(RPT_ERR_INVALID, "system " + std::to_string(s) + ": " + rpt_last_error());
+            return nullptr;
+        }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { fail(RPT_ERR_INVALID, "device index out of range"); return nullptr; }
+    if (!launch_particles_batch_integrate || !particles_batch_resident_blocks) { fail(RPT_ERR_UNSUPPORTED, "rpt_particles_batch_create: built without the kernels"); return nullptr; }
+    auto* b = new rpt_particles_batch();
+    b->device = device;
+    b->table.resize(n_systems);
+    std::vector<uint32_t> first(n_systems);
+    for (uint32_t s = 0; s < n_systems; s++) {
+        b->table[s] = ParticlesSystemRecord{params[s].kind, params[s].n, b->total, 0u, params[s].radius, params[s].height};
+        first[s] = b->total;
+        b->total += params[s].n;
+        if (params[s].n > b->n_max) b->n_max = params[s].n;
+        if (params[s].kind != RPT_PARTICLES_MARBLES) b->all_marbles = false;
+    }
+    if (const char* tune = std::getenv("RPT_PARTICLES_TUNE")) {
+        unsigned bl = 0, l = 0, pad = 0;
+        if (std::sscanf(tune, "%u,%u,%u", &bl, &l, &pad) >= 2 && (bl == 256 || bl == 512 || bl == 1024) && (l == 8 || l == 16 || l == 32 || l == 64)) {
+            b->block = bl;
+            b->lanes = l;
+            b->lds_pad = (pad + 15u) & ~15u;
+            if (b->lds_pad > kBatchMaxLds || particles_batch_lds(b->n_max).bytes + b->lds_pad > kBatchMaxLds) b->lds_pad = 0;
+        }
+    }
+    const size_t bytes = size_t(b->total) * 3 * sizeof(double), cnt_bytes = size_t(n_systems) * 8 * sizeof(uint64_t);
+    const size_t table_bytes = size_t(n_systems) * sizeof(ParticlesSystemRecord), first_bytes = size_t(n_systems) * sizeof(uint32_t);
+    const bool ok = hipSetDevice(device) == hipSuccess && b->d_pos.reserve(bytes) == hipSuccess && b->d_vel.reserve(bytes) == hipSuccess &&
+                    b->d_disp.reserve(bytes) == hipSuccess && b->d_cnt.reserve(cnt_bytes) == hipSuccess && b->d_table.reserve(table_bytes) == hipSuccess &&
+                    b->d_first.reserve(first_bytes) == hipSuccess && hipMemset(b->d_pos.get(), 0, bytes) == hipSuccess &&
+                    hipMemset(b->d_vel.get(), 0, bytes) == hipSuccess && hipMemset(b->d_cnt.get(), 0, cnt_bytes) == hipSuccess &&
+                    hipMemcpy(b->d_table.get(), b->table.data(), table_bytes, hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(b->d_first.get(), first.data(), first_bytes, hipMemcpyHostToDevice) == hipSuccess &&
+                    b->done.create(hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        fail(RPT_ERR_DEVICE, "rpt_particles_batch_create: device allocation failed");
+        rpt_particles_batch_destroy(b);
+        return nullptr;
+    }
+    if (particles_batch_resident_blocks(device, b->block, b->lanes, b->n_max, b->lds_pad, &b->resident) != hipSuccess || b->resident < 1) {
+        fail(RPT_ERR_DEVICE, "rpt_particles_batch_create: the occupancy query failed");
+        rpt_particles_batch_destroy(b);
+        return nullptr;
+    }
+    return b;
+}
+void rpt_particles_batch_destroy(rpt_particles_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    delete b;
+}
+int rpt_particles_batch_set_state(rpt_particles_batch* b, const double* pos, const double* vel) {
+    if (!pos) return fail(RPT_ERR_INVALID, "null positions");
+    if (!b) return fail(RPT_ERR_INVALID, "null particle ensemble");
+    if (int rc = settle(b)) return rc;
+    const size_t bytes = size_t(b->total) * 3 * sizeof(double);
+    RPTI_HIP_TRY(hipMemcpy(b->d_pos.get(), pos, bytes, hipMemcpyHostToDevice));
+    if (vel)
+        RPTI_HIP_TRY(hipMemcpy(b->d_vel.get(), vel, bytes, hipMemcpyHostToDevice));
+    else
+        RPTI_HIP_TRY(hipMemset(b->d_vel.get(), 0, bytes));
+    return RPT_OK;
+}
+int rpt_particles_batch_set_system_state(rpt_particles_batch* b, uint32_t system, const double* pos, const double* vel) {
+    if (!pos) return fail(RPT_ERR_INVALID, "null positions");
+    if (!b) return fail(RPT_ERR_INVALID, "null particle ensemble");
+    if (system >= b->table.size()) return fail(RPT_ERR_INVALID, "system index out of range");
+    if (int rc = settle(b)) return rc;
+    const ParticlesSystemRecord& r = b->table[system];
+    const size_t bytes = size_t(r.n) * 3 * sizeof(double), at = size_t(r.first) * 3;
+    RPTI_HIP_TRY(hipMemcpy(b->d_pos.get<double>() + at, pos, bytes, hipMemcpyHostToDevice));
+    if (vel)
+        RPTI_HIP_TRY(hipMemcpy(b->d_vel.get<double>() + at, vel, bytes, hipMemcpyHostToDevice));
+    else
+        RPTI_HIP_TRY(hipMemset(b->d_vel.get<double>() + at, 0, bytes));
+    return RPT_OK;
+}
+int rpt_particles_batch_state(rpt_particles_batch* b, double* pos, double* vel) {
+    if (!pos && !vel) return fail(RPT_ERR_INVALID, "null outputs");
+    if (!b) return fail(RPT_ERR_INVALID, "null particle ensemble");
+    if (int rc = settle(b)) return rc;
+    const size_t bytes = size_t(b->total) * 3 * sizeof(double);
+    if (pos) RPTI_HIP_TRY(hipMemcpy(pos, b->d_pos.get(), bytes, hipMemcpyDeviceToHost));
+    if (vel) RPTI_HIP_TRY(hipMemcpy(vel, b->d_vel.get(), bytes, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+int rpt_particles_batch_state_device(rpt_particles_batch* b, void** d_pos, void** d_vel, void** d_first) {
+    if (!d_pos && !d_vel && !d_first) return fail(RPT_ERR_INVALID, "null outputs");
+    if (!b) return fail(RPT_ERR_INVALID, "null particle ensemble");
+    if (d_pos) *d_pos = b->d_pos.get();
+    if (d_vel) *d_vel = b->d_vel.get();
+    if (d_first) *d_first = b->d_first.get();
+    return RPT_OK;
+}
+int rpt_particles_batch_integrate(rpt_particles_batch* b, double time, double step, void* hip_stream) {
+    uint64_t n_full = 0;
+    double last = 0.0;
+    if (int rc = check_time(time, step, &n_full, &last)) return rc;
+    if (!b) return fail(RPT_ERR_INVALID, "null particle ensemble");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    RPTI_HIP_TRY(hipSetDevice(b->device));
+    if (b->used) RPTI_HIP_TRY(hipStreamWaitEvent(st, b->done.get(), 0));
+    b->used = true;
+    ParticlesBatchArgs a = batch_args(b);
+    a.h = step;
+    a.h_tail = last;
+    // the same step sequence as the single handle's, in launches of L steps: only the last launch carries the tail step
+    const uint32_t L = batch_launch_steps(b);
+    hipError_t e = hipSuccess;
+    for (uint64_t left = n_full + 1; left > 0 && e == hipSuccess;) {
+        const uint32_t m = uint32_t(left < L ? left : L);
+        a.n_steps = m;
+        a.tail = left == m ? 1u : 0u;
+        e = launch_particles_batch_integrate(a, b->block, b->lanes, st);
+        if (e == hipSuccess) b->launches++;
+        left -= m;
+    }
+    const hipError_t er = hipEventRecord(b->done.get(), st);   // (after a failed launch too, as rpt_particles_integrate)
+    RPTI_HIP_TRY(e);
+    RPTI_HIP_TRY(er);
+    return RPT_OK;
+}
+int rpt_particles_batch_display_positions(rpt_particles_batch* b, double* out) {
+    if (!out) return fail(RPT_ERR_INVALID, "null output");
+    if (!b) return fail(RPT_ERR_INVALID, "null particle ensemble");
+    if (!b->all_marbles) return fail(RPT_ERR_UNSUPPORTED, "display positions are defined for marbles systems only");
+    if (!launch_particles_batch_display) return fail(RPT_ERR_UNSUPPORTED, "rpt_particles_batch_display_positions: built without the kernels");
+    if (int rc = settle(b)) return rc;
+    RPTI_HIP_TRY(launch_particles_batch_display(batch_args(b), b->d_disp.get<double>(), nullptr));
+    b->launches++;
+    RPTI_HIP_TRY(hipMemcpy(out, b->d_disp.get(), size_t(b->total) * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+int rpt_particles_batch_counters(rpt_particles_batch* b, uint64_t* out) {
+    if (!out) return fail(RPT_ERR_INVALID, "null output");
+    if (!b) return fail(RPT_ERR_INVALID, "null particle ensemble");
+    if (int rc = settle(b)) return rc;
+    RPTI_HIP_TRY(hipMemcpy(out, b->d_cnt.get(), b->table.size() * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < b->table.size(); s++) {
+        out[8 * s + 6] = b->launches;
+        out[8 * s + 7] = 0;
+    }
+    return RPT_OK;
+}
+int rpt_particles_batch_info(rpt_particles_batch* b, uint64_t out[8]) {
+    if (!out) return fail(RPT_ERR_INVALID, "null output");
+    if (!b) return fail(RPT_ERR_INVALID, "null particle ensemble");
+    out[0] = b->resident;
+    out[1] = batch_rounds(b);
+    out[2] = batch_launch_steps(b);
+    out[3] = particles_batch_lds(b->n_max).bytes + b->lds_pad;
+    out[4] = b->n_max;
+    out[5] = b->total;
+    out[6] = b->block;
+    out[7] = b->lanes;
     return RPT_OK;
 }
 

@@ -1,7 +1,7 @@
 """The reference's src/ode/: ParticleState, the ParticleSystem trait's three systems and their RK4 integration, over the
 rpt_particles_* entry points of include/rpt_hip.h, which states the arithmetic as an order of fp64 operations.  With a device the
 integration runs in a HIP kernel (one workgroup, the time loop inside); `device=None` runs the same text serially on the host.
-The two give the same bits."""
+The two give the same bits.  ParticleEnsemble integrates many independent systems in one launch, a workgroup each."""
 import ctypes as C
 
 import numpy as np
@@ -146,6 +146,90 @@ class ParticleSimulator:
     def close(self):
         if self._h:
             _lib.load().rpt_particles_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ParticleEnsemble:
+    """Many independent systems on a device, integrated in one launch, one workgroup each (rpt_particles_batch).  `systems` and
+    `states` are lists of equal length: system i (a MarblesSystem, SolidGravitySystem or SimpleCircleSystem, of any size and
+    parameters) with its ParticleState.  Every system comes out with the bits it would have alone; the calls of one ensemble are
+    ordered whatever their streams."""
+
+    def __init__(self, systems, states, device=0):
+        systems, states = list(systems), list(states)
+        if len(systems) != len(states):
+            raise ValueError(f"{len(systems)} systems but {len(states)} states")
+        self.systems = systems
+        self.sizes = [len(s) for s in states]
+        self.first = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
+        prm = (ParticlesParams * max(1, len(systems)))(*[sy.params(n) for sy, n in zip(systems, self.sizes)])
+        self._h = _lib.load().rpt_particles_batch_create(int(device), prm, len(systems))
+        if not self._h:
+            _lib.check(-1)
+        pos = np.concatenate([_arr(s.pos) for s in states])
+        vel = np.concatenate([_arr(s.vel) for s in states])
+        _lib.check(_lib.load().rpt_particles_batch_set_state(self._h, _vp(pos), _vp(vel)))
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def _split(self, a):
+        return [a[self.first[i]:self.first[i + 1]].copy() for i in range(len(self.sizes))]
+
+    def set_state(self, i, state):
+        """Replaces system i's state (ordered behind what the ensemble has queued)."""
+        if not 0 <= i < len(self.sizes):
+            raise IndexError(f"system {i} of {len(self.sizes)}")
+        pos, vel = _arr(state.pos, self.sizes[i]), _arr(state.vel, self.sizes[i])
+        _lib.check(_lib.load().rpt_particles_batch_set_system_state(self._h, int(i), _vp(pos), _vp(vel)))
+
+    def states(self):
+        """A list of ParticleState, one per system; synchronous."""
+        total = int(self.first[-1])
+        pos, vel = np.zeros((total, 3)), np.zeros((total, 3))
+        _lib.check(_lib.load().rpt_particles_batch_state(self._h, _vp(pos), _vp(vel)))
+        return [ParticleState(p, v) for p, v in zip(self._split(pos), self._split(vel))]
+
+    def state_device(self):
+        """The device addresses of the concatenated position and velocity arrays and of the uint32 first-particle indices."""
+        p, v, f = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(_lib.load().rpt_particles_batch_state_device(self._h, C.byref(p), C.byref(v), C.byref(f)))
+        return p.value, v.value, f.value
+
+    def integrate(self, time, step, stream=None):
+        """Advances every system by `time` in steps of `step`.  Asynchronous, on `stream` (a hipStream_t as an integer; None: the
+        default stream)."""
+        _lib.check(_lib.load().rpt_particles_batch_integrate(self._h, float(time), float(step), C.c_void_p(stream)))
+
+    def display_positions(self):
+        """A list of (n_i, 3) arrays: where marbles.rs draws each system's marbles (every system a MarblesSystem)."""
+        out = np.zeros((int(self.first[-1]), 3))
+        _lib.check(_lib.load().rpt_particles_batch_display_positions(self._h, _vp(out)))
+        return self._split(out)
+
+    def counters(self):
+        """One list of eight per system: ParticleSimulator.counters' slots, launches counted for the ensemble."""
+        out = (C.c_uint64 * (8 * len(self.sizes)))()
+        _lib.check(_lib.load().rpt_particles_batch_counters(self._h, out))
+        return [[int(x) for x in out[8 * i:8 * i + 8]] for i in range(len(self.sizes))]
+
+    def info(self):
+        """Resident blocks R, rounds, steps per launch, dynamic LDS bytes per block, the largest n, the number of particles, and the
+        tuning (threads per block, lanes per particle)."""
+        out = (C.c_uint64 * 8)()
+        _lib.check(_lib.load().rpt_particles_batch_info(self._h, out))
+        keys = ("resident_blocks", "rounds", "launch_steps", "lds_bytes", "n_max", "particles", "block", "lanes")
+        return dict(zip(keys, (int(x) for x in out)))
+
+    def close(self):
+        if self._h:
+            _lib.load().rpt_particles_batch_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -380,3 +380,64 @@ def marbles_sequence(frames, device=0, state=None, **kw):
             yield scene, camera
     finally:
         sim.close()
+
+
+def marbles_field(positions, offsets, env=(0.6, 0.65, 0.7), glass=None):
+    """marbles() with one glass and its marbles per entry: glass g, translated by offsets[g] = (x, z), with marbles of radius 0.15
+    drawn at positions[g] (world coordinates: a system's display positions moved by its glass's offset), all over the one floor and
+    under the one light, which hangs over the middle of the field; the camera looks at the middle from far enough to see every glass.
+    The shapes are the light, then per glass the glass and its marbles, then the floor: the same shapes in the same order for every
+    frame of a sequence.  Not in CONFIGS."""
+    r = MARBLES_RADIUS
+    offsets = np.asarray(offsets, dtype=np.float64).reshape(-1, 2)
+    if len(positions) != len(offsets):
+        raise ValueError(f"{len(positions)} sets of marbles but {len(offsets)} glasses")
+    lo, hi = offsets.min(axis=0), offsets.max(axis=0)
+    cx, cz = (float(v) for v in (lo + hi) / 2.0)
+    extent = float(np.max(hi - lo)) / 2.0
+    scene = Scene()
+    scene.environment = Environment.Color(vec3(*env))
+    scene.add(Light.Object(Object(sphere().scale(vec3(1.5, 1.5, 1.5)).translate(vec3(cx, 5.0 + extent, cz)))
+                           .material(Material.light(hex_color(0xFFFFFF), 15.0))))
+    colors = [0x264653, 0x2A9D8F, 0xE9C46A, 0xF4A261, 0xE76F51]
+    for (ox, oz), marbles_at in zip(offsets, positions):
+        shape = monomial_surface(2.0, 4.0) if glass is None else glass
+        scene.add(Object(shape.translate(vec3(float(ox), 0.0, float(oz)))).material(Material.clear(1.5, 0.0001)))
+        for i, pos in enumerate(np.asarray(marbles_at, dtype=np.float64).reshape(-1, 3)):
+            scene.add(Object(sphere().scale(vec3(r, r, r)).translate(vec3(*pos))).material(Material.specular(hex_color(colors[i % len(colors)]), 0.1)))
+    far = 20.0 + extent
+    scene.add(Object(polygon([vec3(cx + far, -0.06, cz + far), vec3(cx + far, -0.06, cz - far), vec3(cx - far, -0.06, cz - far), vec3(cx - far, -0.06, cz + far)]))
+              .material(Material.diffuse(hex_color(0xAAAAAA))))
+    eye = vec3(cx, 1.0 + 1.5 * extent, cz + 6.0 + 2.5 * extent)
+    camera = Camera.look_at(eye, vec3(cx, 1.0, cz), vec3(0.0, 1.0, 0.0), math.pi / 4.0).focus(vec3(cx, 1.0, cz), 0.02)
+    return scene, camera, {"width": 800, "height": 600, "spp": 2000, "max_bounces": 9}
+
+
+def marbles_field_offsets(grid=(2, 2), spacing=3.0):
+    """The (x, z) offsets of a grid of grid[0] x grid[1] glasses `spacing` apart, centred on the origin, x varying slowest."""
+    gx, gz = grid
+    return np.array([[(i - (gx - 1) / 2.0) * spacing, (j - (gz - 1) / 2.0) * spacing] for i in range(gx) for j in range(gz)], dtype=np.float64).reshape(-1, 2)
+
+
+def marbles_field_sequence(frames, grid=(2, 2), spacing=3.0, time=1.0 / 16.0, step=1.0 / 10000.0, device=0, states=None, **kw):
+    """A generator of (scene, camera) for `frames` frames of a field of grid[0] x grid[1] glasses `spacing` apart, as
+    marbles_sequence is for one: frame f shows every glass's marbles after f advances of rk4_integrate(state, time, step), all
+    glasses in one ParticleEnsemble on the device, a system per glass in the glass's own coordinates (its display positions are
+    moved by the glass's offset).  `states`: one ParticleState per glass (default: marbles_initial(seed=123 + g)); `kw` goes to
+    marbles_field().  The next frame's integration is queued before a frame is yielded."""
+    from .ode import MarblesSystem, ParticleEnsemble
+    offsets = marbles_field_offsets(grid, spacing)
+    if states is None:
+        states = [marbles_initial(seed=123 + g) for g in range(len(offsets))]
+    if len(states) != len(offsets):
+        raise ValueError(f"{len(states)} states for {len(offsets)} glasses")
+    sim = ParticleEnsemble([MarblesSystem(MARBLES_RADIUS)] * len(offsets), states, device=device)
+    try:
+        for f in range(frames):
+            shown = [p + np.array([ox, 0.0, oz]) for p, (ox, oz) in zip(sim.display_positions(), offsets)]
+            scene, camera, _ = marbles_field(shown, offsets, **kw)
+            if f + 1 < frames:
+                sim.integrate(time, step)   # (asynchronous: the caller renders this frame meanwhile)
+            yield scene, camera
+    finally:
+        sim.close()
