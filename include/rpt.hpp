@@ -457,6 +457,11 @@ class Buffer {
     // rpt_buffer_denoised_image (an addition): mean -> Denoiser -> color_bytes, no box filter; the feature planes are device pointers.
     RgbImage denoised_image(class Denoiser& denoiser, const rpt_denoise_params& params, const void* d_albedo, const void* d_normal,
                             const void* d_depth) const;
+    // rpt_buffer_upsampled_image (an addition): this buffer holds the LOW-resolution batches; mean -> (with a denoiser of this
+    // buffer's size: the a-trous filter at the low resolution) -> guided upsampling -> color_bytes.  d_lo[3] / d_hi[3]: the albedo,
+    // normal and depth planes of the low and of the full resolution (device pointers, each or null as `params` allows).
+    RgbImage upsampled_image(const rpt_upsample_params& params, const void* const d_lo[3], const void* const d_hi[3],
+                             class Denoiser* denoiser = nullptr, const rpt_denoise_params* denoise = nullptr) const;
     // Adaptive sampling by tile (rpt_hip.h, an addition).  One batch for the listed 32 x 32 tiles alone (device frame, device list
     // of distinct tile ids), and the batches each tile holds: tiles_x * tiles_y values, row-major.
     void add_samples_tiles_device(const void* d_rgb, const void* d_tiles, uint32_t n_tiles, void* hip_stream = nullptr) {
@@ -532,6 +537,57 @@ inline RgbImage Buffer::denoised_image(Denoiser& denoiser, const rpt_denoise_par
     if (rpt_buffer_denoised_image(h_, denoiser.raw(), &params, d_albedo, d_normal, d_depth, img.data.data()) != RPT_OK) throw Error(rpt_last_error());
     return img;
 }
+inline RgbImage Buffer::upsampled_image(const rpt_upsample_params& params, const void* const d_lo[3], const void* const d_hi[3], Denoiser* denoiser,
+                                        const rpt_denoise_params* denoise) const {
+    const uint32_t s = params.scale >= 2 && params.scale <= 4 ? params.scale : 1;   // (a bad scale: the call below refuses it)
+    RgbImage img{width * s, height * s, std::vector<uint8_t>(size_t(width) * s * height * s * 3)};
+    const rpt_denoise_params dflt = Denoiser::default_params();
+    if (rpt_buffer_upsampled_image(h_, denoiser ? denoiser->raw() : nullptr, denoise ? denoise : &dflt, &params, d_lo[0], d_lo[1], d_lo[2], d_hi[0],
+                                   d_hi[1], d_hi[2], img.data.data()) != RPT_OK)
+        throw Error(rpt_last_error());
+    return img;
+}
+// Guided upsampling (rpt_upsample*, an addition): a frame rendered at (w, h) and its variance taken to (s w, s h) under the feature
+// planes of both sizes.  Stateless: thin wrappers of the C entry points.
+struct Upsample {
+    // s = 2, bilinear 2 x 2 taps, demodulation and id match on, sigma_normal 1 ("Guided upsampling"), depth term
+    // off (it is in scene units per low-resolution pixel)
+    static rpt_upsample_params default_params() { return {2, 1, RPT_UPSAMPLE_DEMODULATE | RPT_UPSAMPLE_MATCH_ID, 0, 1.0, 0.0}; }
+    // device pointers on the current device; d_lo[3] / d_hi[3]: albedo, normal, depth, each or null as `params` allows
+    static void run_device(const rpt_upsample_params& params, uint32_t lo_width, uint32_t lo_height, const void* d_lo_rgb, const void* d_lo_var,
+                           const void* const d_lo[3], const void* const d_hi[3], void* d_out, void* d_out_var = nullptr, void* hip_stream = nullptr) {
+        if (rpt_upsample_device(&params, lo_width, lo_height, d_lo_rgb, d_lo_var, d_lo[0], d_lo[1], d_lo[2], d_hi[0], d_hi[1], d_hi[2], d_out, d_out_var,
+                                hip_stream) != RPT_OK)
+            throw Error(rpt_last_error());
+    }
+    // host arrays; an empty vector is a null plane
+    static std::vector<double> run(const rpt_upsample_params& params, uint32_t lo_width, uint32_t lo_height, const std::vector<double>& lo_rgb,
+                                   const std::vector<double>& lo_var, const std::vector<double> (&lo)[3], const std::vector<double> (&hi)[3],
+                                   std::vector<double>* out_var = nullptr, int device = 0) {
+        if (params.scale < 2 || params.scale > 4) throw Error("scale must be 2, 3 or 4");   // (before anything is sized by it)
+        const uint64_t W = uint64_t(lo_width) * params.scale, H = uint64_t(lo_height) * params.scale;
+        if (W >= (1ull << 32) || H >= (1ull << 32) || W * H >= (1ull << 31)) throw Error("the full-resolution frame is too large");
+        const size_t n = size_t(lo_width) * lo_height, N = n * params.scale * params.scale;
+        auto ptr = [&](const std::vector<double>& v, size_t want) -> const double* {
+            if (v.empty()) return nullptr;
+            if (v.size() != want) throw Error("Invalid plane dimension");
+            return v.data();
+        };
+        std::vector<double> out(N * 3);
+        if (out_var) out_var->assign(N, 0.0);
+        if (rpt_upsample(device, &params, lo_width, lo_height, ptr(lo_rgb, n * 3), ptr(lo_var, n), ptr(lo[0], n * 3), ptr(lo[1], n * 3), ptr(lo[2], n * 3),
+                         ptr(hi[0], N * 3), ptr(hi[1], N * 3), ptr(hi[2], N * 3), out.data(), out_var ? out_var->data() : nullptr) != RPT_OK)
+            throw Error(rpt_last_error());
+        return out;
+    }
+    // rpt_image_bytes_device: color_bytes of a device plane, only the bytes come back
+    static RgbImage image_bytes_device(const void* d_rgb, uint32_t width, uint32_t height, void* hip_stream = nullptr) {
+        if (uint64_t(width) * height >= (1ull << 31)) throw Error("bad image size");   // (before anything is sized by it)
+        RgbImage img{width, height, std::vector<uint8_t>(size_t(width) * height * 3)};
+        if (rpt_image_bytes_device(d_rgb, width, height, img.data.data(), hip_stream) != RPT_OK) throw Error(rpt_last_error());
+        return img;
+    }
+};
 // Temporal accumulation with reprojection (rpt_temporal_*, an addition): owns the history of a frame sequence of one size on one
 // device.  For a camera that moves over a scene whose objects keep their places and indices.
 class Temporal {

@@ -372,6 +372,72 @@ int rpt_buffer_mean_device(rpt_buffer*, void* d_rgb, void* d_var, void* hip_stre
 int rpt_buffer_denoised_image(rpt_buffer*, rpt_denoiser*, const rpt_denoise_params*, const void* d_albedo, const void* d_normal,
                               const void* d_depth, uint8_t* out_rgb8);
 
+/* ---- guided upsampling on the device (an addition: the reference renders every pixel it shows) ----
+ * A joint-bilateral upsampling: a frame rendered at (w, h) and the variance of its mean are taken to (W, H) = (s w, s h), steered by
+ * the first-hit feature planes of BOTH sizes (rpt_render_features* of the same camera: the reference's pixel-to-ray map,
+ * src/renderer.rs:173-181, is scale-consistent, so pixel (i, j) of the small render integrates exactly over the full-size pixels
+ * s i .. s i + s - 1, s j .. s j + s - 1).  Texture and geometry edges come from the full-size planes; only the lighting is interpolated.
+ *
+ * Defined, like the denoiser, as an order of fp64 operations, each rounded on its own (no fused multiply-add, IEEE division, no
+ * atomics): the result is a function of the arguments alone, whatever the tiling or the stream.  Every array is fp64, row-major,
+ * y = 0 at the top.  Low resolution (w x h): lo_rgb[h][w][3]; lo_var[h][w] or NULL; lo_albedo, lo_normal, lo_depth in the format
+ * rpt_render_features writes, each or NULL.  Full resolution: hi_albedo, hi_normal, hi_depth, each or NULL.  Outputs: out_rgb[H][W][3],
+ * out_var[H][W] or NULL.  scale s in {2, 3, 4}; radius r in {1, 2} (2 r taps per axis); flags RPT_UPSAMPLE_*; a term is on iff its sigma
+ * > 0.  A term or flag whose plane is NULL on either side is RPT_ERR_INVALID: sigma_normal > 0 needs both normal planes,
+ * sigma_depth > 0 and RPT_UPSAMPLE_MATCH_ID both depth planes, RPT_UPSAMPLE_DEMODULATE both albedo planes.
+ *   Full-resolution pixel p = (X, Y):
+ *     den_p,k = (DEMODULATE and hi_albedo_p,k > 0.0) ? hi_albedo_p,k : 1.0 (false for NaN); for a low-resolution pixel q, den_q,k is
+ *       the same rule on lo_albedo;  c_q,k = lo_rgb_q,k / den_q,k;  v_q = lo_var ? lo_var[q] : 0.0.
+ *     Position, in integers: tx = 2 X + 1 - s (signed);  i0 = floor(tx / (2 s)) (floor division, may be -1);
+ *       fx = double(tx - 2 s i0) / double(2 s);  the same for ty, j0, fy: the pixel's centre in low-resolution pixel-centre coordinates.
+ *     a_n = 1.0 / sigma_normal;  a_z = 1.0 / (sigma_depth double(s)).
+ *     For dy = 1-r .. r (outer), dx = 1-r .. r (inner), q = (i0 + dx, j0 + dy); taps outside the low-resolution image are skipped.
+ *       g_dx = 1.0 - |fx - double(dx)| / double(r), likewise g_dy; the tap is skipped unless g_dx > 0.0 and g_dy > 0.0 (r = 1: the
+ *       bilinear 2 x 2).
+ *       x = +0.0, then the enabled terms in the order normal, depth:
+ *         normal: e_k = (lo_normal_q,k - hi_normal_p,k) a_n;   x = x + ((e0 e0 + e1 e1) + e2 e2)
+ *         depth:  e = (lo_depth_q[0] - hi_depth_p[0]) a_z;     x = x + e e
+ *       The tap is skipped unless x < 4.0 and, with MATCH_ID, lo_depth_q[2] == hi_depth_p[2] (NaN fails every test).
+ *       t = 1.0 - x 0.25;  t2 = t t;  wgt = (t2 t2) (g_dy g_dx): the denoiser's stand-in for exp(-x).
+ *       Wsum += wgt;  C_k += wgt c_q,k;  V += (wgt wgt) v_q, all from +0.0.
+ *     If Wsum > 0.0: c_k = C_k / Wsum and v = V / (Wsum Wsum); otherwise the pixel falls back to its own footprint q = (X / s, Y / s)
+ *     (integer division): c = c_q, v = v_q.
+ *     out_rgb_k = c_k den_p,k;  out_var = v.
+ * Checks, in this order and all before any device call, each RPT_ERR_INVALID: null parameters; scale; radius; unknown flag; a sigma
+ * that is not finite and >= 0; a zero size; s w or s h not below 2^32, or W H not below 2^31; null lo_rgb or out_rgb; the planes of
+ * sigma_normal, sigma_depth, DEMODULATE, MATCH_ID (in that order, the low-resolution one first); an output that is one of the inputs
+ * or the other output; (rpt_upsample) the device index. */
+#define RPT_UPSAMPLE_DEMODULATE 1u
+#define RPT_UPSAMPLE_MATCH_ID 2u
+typedef struct rpt_upsample_params {
+    uint32_t scale;    /* s in {2, 3, 4} */
+    uint32_t radius;   /* r in {1, 2}: taps per axis = 2 r */
+    uint32_t flags;    /* RPT_UPSAMPLE_* */
+    uint32_t _pad;
+    double sigma_normal, sigma_depth;   /* a term is on iff its sigma > 0 */
+} rpt_upsample_params;
+/* Stateless and asynchronous, on the current device (as rpt_frame_pack_device): DEVICE pointers, hip_stream a hipStream_t (NULL =
+ * default stream); one out-of-place pass, no scratch.  The outputs must not alias the inputs. */
+int rpt_upsample_device(const rpt_upsample_params*, uint32_t lo_width, uint32_t lo_height, const void* d_lo_rgb, const void* d_lo_var,
+                        const void* d_lo_albedo, const void* d_lo_normal, const void* d_lo_depth, const void* d_hi_albedo,
+                        const void* d_hi_normal, const void* d_hi_depth, void* d_out_rgb, void* d_out_var, void* hip_stream);
+/* The same with host pointers on device `device`, synchronous. */
+int rpt_upsample(int device, const rpt_upsample_params*, uint32_t lo_width, uint32_t lo_height, const double* lo_rgb, const double* lo_var,
+                 const double* lo_albedo, const double* lo_normal, const double* lo_depth, const double* hi_albedo,
+                 const double* hi_normal, const double* hi_depth, double* out_rgb, double* out_var);
+/* color_bytes (src/color.rs:18-24) of a DEVICE plane of width*height*3 doubles on the current device, enqueued on hip_stream and
+ * waited for: only the width*height*3 bytes come back, to host memory.  What ends a pipeline composed from device entry points.
+ * RPT_ERR_INVALID: a null pointer, a zero size, width*height not below 2^31. */
+int rpt_image_bytes_device(const void* d_rgb, uint32_t width, uint32_t height, uint8_t* out_rgb8_host, void* hip_stream);
+/* mean -> (with a denoiser of the buffer's size: the a-trous filter at the low resolution, on the low-resolution planes) -> upsample ->
+ * color_bytes; synchronous, only (s w)(s h)*3 bytes come back.  `lo` holds the low-resolution batches; the planes are DEVICE
+ * pointers (each or NULL, as the parameters allow).  Checks in this order: null buffer or output; the upsampling's (above); with a
+ * denoiser the denoiser's, then devices and sizes; RPT_ERR_STATE with fewer than 2 batches.  Without a denoiser the denoise parameters
+ * are ignored. */
+int rpt_buffer_upsampled_image(rpt_buffer* lo, rpt_denoiser* lo_denoiser_or_null, const rpt_denoise_params*, const rpt_upsample_params*,
+                               const void* d_lo_albedo, const void* d_lo_normal, const void* d_lo_depth, const void* d_hi_albedo,
+                               const void* d_hi_normal, const void* d_hi_depth, uint8_t* out_rgb8);
+
 /* ---- temporal accumulation with reprojection (an addition with no counterpart in the reference, whose frame sequences --
  * examples/simple_video.rs, marbles.rs -- render every frame from nothing) ----
  * For a camera that moves over a scene whose objects keep their indices: a frame's pixel is blended with what the previous

@@ -75,6 +75,17 @@ class DenoiseParams(C.Structure):
     ]
 
 
+class UpsampleParams(C.Structure):
+    _fields_ = [
+        ("scale", C.c_uint32),
+        ("radius", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("sigma_normal", C.c_double),
+        ("sigma_depth", C.c_double),
+    ]
+
+
 class TemporalParams(C.Structure):
     _fields_ = [
         ("max_history", C.c_uint32),
@@ -163,6 +174,10 @@ SYMBOLS = [
     ("rpt_denoise", C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P]),
     ("rpt_buffer_mean_device", C.c_int, [_P, _P, _P, _P]),
     ("rpt_buffer_denoised_image", C.c_int, [_P, _P, C.POINTER(DenoiseParams), _P, _P, _P, _P]),
+    ("rpt_upsample_device", C.c_int, [C.POINTER(UpsampleParams), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("rpt_upsample", C.c_int, [C.c_int, C.POINTER(UpsampleParams), C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("rpt_image_bytes_device", C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    ("rpt_buffer_upsampled_image", C.c_int, [_P, _P, C.POINTER(DenoiseParams), C.POINTER(UpsampleParams), _P, _P, _P, _P, _P, _P, _P]),
     ("rpt_temporal_camera_record", C.c_int, [C.POINTER(CameraDesc), _D3]),
     ("rpt_temporal_create", _P, [C.c_int, C.c_uint32, C.c_uint32]),
     ("rpt_temporal_destroy", None, [_P]),

@@ -62,6 +62,7 @@ __all__ = [
     "MonomialSurface", "sphere", "cube", "plane", "polygon", "monomial_surface", "Material", "Object", "Light", "Medium", "Environment",
     "Scene", "Camera", "Filter", "Buffer", "DeviceBuffer", "Renderer", "RptError", "DenoiseParams", "Denoiser", "AdaptiveParams",
     "TemporalParams", "TemporalAccumulator", "temporal_camera_record", "temporal_motion_record",
+    "UpsampleParams", "upsample", "upsample_device", "image_bytes_device",
 ]
 
 
@@ -761,9 +762,10 @@ class DeviceBuffer:
         _sync(self.device)
         return d_ids.cpu().numpy().view(np.uint32)[:n.value].copy(), d_err.cpu().numpy().reshape(ty, tx).copy()
 
-    def _plane_pointers(self, planes, what):
+    def _plane_pointers(self, planes, what, scale=1):
         """`planes`: a dict with any of "albedo", "normal", "depth", each an (h, w, 3) array as Renderer.features_array returns it or a
-        device pointer (int) as Renderer.features_device filled it -> (what keeps the uploads alive, the three pointers)."""
+        device pointer (int) as Renderer.features_device filled it -> (what keeps the uploads alive, the three pointers).  scale:
+        the planes are that many times the buffer's size on each axis."""
         unknown = set(planes) - {"albedo", "normal", "depth"}
         if unknown:
             raise ValueError(f"{what}: unknown planes {sorted(unknown)}")
@@ -774,8 +776,8 @@ class DeviceBuffer:
                 ptrs.append(C.c_void_p(v or None))
                 continue
             a = np.ascontiguousarray(v, dtype=np.float64)
-            if a.size != self.width * self.height * 3:
-                raise ValueError(f"{what}: plane {k} is not {self.height} x {self.width} x 3")
+            if a.size != scale * self.width * scale * self.height * 3:
+                raise ValueError(f"{what}: plane {k} is not {scale * self.height} x {scale * self.width} x 3")
             keep.append(_device_copy(a, self.device))
             ptrs.append(C.c_void_p(keep[-1].data_ptr()))
         _sync(self.device)
@@ -789,6 +791,25 @@ class DeviceBuffer:
         keep, ptrs = self._plane_pointers(planes, "denoised_image")
         out = np.empty((self.height, self.width, 3), dtype=np.uint8)
         _lib.check(_lib.load().rpt_buffer_denoised_image(self._h, denoiser._h, C.byref(params.desc()), *ptrs, _vp(out)))
+        return out
+
+    def upsampled_image(self, planes, hi_planes, params=None, denoiser=None, denoise=None):
+        """rpt_buffer_upsampled_image: this buffer holds the LOW-resolution batches; mean -> (with `denoiser`, of this buffer's size:
+        the a-trous filter at the low resolution, parameters `denoise`) -> guided upsampling -> color_bytes ->
+        (s h, s w, 3) uint8.  `planes`: the low-resolution feature planes as for denoised_image; `hi_planes`: the same dict for the
+        full-resolution ones, arrays of (s h, s w, 3) or device pointers."""
+        params = params or UpsampleParams()
+        if denoiser is not None:
+            denoise = denoise or DenoiseParams()
+        s = params.scale
+        if s not in (2, 3, 4):
+            raise ValueError("upsampled_image: scale must be 2, 3 or 4")
+        keep, ptrs = self._plane_pointers(planes, "upsampled_image")
+        hi_keep, hi_ptrs = self._plane_pointers(hi_planes, "upsampled_image", s)
+        out = np.empty((s * self.height, s * self.width, 3), dtype=np.uint8)
+        _lib.check(_lib.load().rpt_buffer_upsampled_image(
+            self._h, denoiser._h if denoiser is not None else None, C.byref(denoise.desc()) if denoise is not None else None,
+            C.byref(params.desc()), *ptrs, *hi_ptrs, _vp(out)))
         return out
 
     def temporal_image(self, accumulator, camera, planes, temporal=None, denoiser=None, denoise=None):
@@ -930,6 +951,80 @@ class Denoiser:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------ guided upsampling (rpt_upsample*, an addition)
+class UpsampleParams:
+    """rpt_upsample_params: scale s in {2, 3, 4}, radius r in {1, 2} (2 r taps per axis); a term is on iff its sigma > 0.  The
+    defaults are those of tools/upsample_quality.py on the oracle's renders ("Guided upsampling"); sigma_depth
+    is off because it is in scene units per low-resolution pixel and no default is right for every scene.  On that grid
+    sigma_normal = 1 gives the figures of the term switched off at radius 1: it is the loosest setting that still has the term on.
+    Warning: demodulate=True can do worse than plain s x s replication on scenes whose materials have an albedo channel of 0
+    (saturated colours, black backgrounds): at an edge where the channel is 0 on one side only, the pixel is remodulated with 1
+    instead of 0 (cornell: RMS 26.27 levels against replication's 15.75, 14.62 with the id match alone at sigma_normal 0.5).  Pass demodulate=False there."""
+    DEMODULATE, MATCH_ID = 1, 2
+
+    def __init__(self, scale=2, radius=1, demodulate=True, match_id=True, sigma_normal=1.0, sigma_depth=0.0):
+        self.scale, self.radius = int(scale), int(radius)
+        self.demodulate, self.match_id = bool(demodulate), bool(match_id)
+        self.sigma_normal, self.sigma_depth = float(sigma_normal), float(sigma_depth)
+
+    @property
+    def flags(self):
+        return (self.DEMODULATE if self.demodulate else 0) | (self.MATCH_ID if self.match_id else 0)
+
+    def desc(self):
+        return _lib.UpsampleParams(self.scale, self.radius, self.flags, 0, self.sigma_normal, self.sigma_depth)
+
+
+def upsample(lo_rgb, lo_var=None, lo_albedo=None, lo_normal=None, lo_depth=None, hi_albedo=None, hi_normal=None, hi_depth=None, params=None,
+             return_variance=False, device=0):
+    """rpt_upsample.  Host arrays: lo_rgb (h, w, 3), lo_var (h, w), the low-resolution planes (h, w, 3), the full-resolution ones
+    (s h, s w, 3); any but lo_rgb may be None where `params` does not need it -> the (s h, s w, 3) frame, with return_variance the
+    (s h, s w) variance as well."""
+    params = params or UpsampleParams()
+    lo_rgb = np.ascontiguousarray(lo_rgb, dtype=np.float64)
+    if lo_rgb.ndim != 3 or lo_rgb.shape[2] != 3:
+        raise ValueError("upsample: lo_rgb must be (h, w, 3)")
+    h, w = lo_rgb.shape[:2]
+    n, s = w * h, params.scale
+    if s not in (2, 3, 4):
+        raise ValueError("upsample: scale must be 2, 3 or 4")
+    arrays = [lo_rgb]
+    for name, a, size in (("lo_var", lo_var, n), ("lo_albedo", lo_albedo, 3 * n), ("lo_normal", lo_normal, 3 * n), ("lo_depth", lo_depth, 3 * n),
+                          ("hi_albedo", hi_albedo, 3 * n * s * s), ("hi_normal", hi_normal, 3 * n * s * s), ("hi_depth", hi_depth, 3 * n * s * s)):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != size:
+                raise ValueError(f"upsample: {name} has {a.size} values, the frame needs {size}")
+        arrays.append(a)
+    out = np.empty((s * h, s * w, 3), dtype=np.float64)
+    out_var = np.empty((s * h, s * w), dtype=np.float64) if return_variance else None
+    _lib.check(_lib.load().rpt_upsample(int(device), C.byref(params.desc()), w, h, *[_vp(a) if a is not None else None for a in arrays],
+                                        _vp(out), _vp(out_var) if return_variance else None))
+    return (out, out_var) if return_variance else out
+
+
+def upsample_device(lo_width, lo_height, d_lo_rgb, d_lo_var, d_lo_albedo, d_lo_normal, d_lo_depth, d_hi_albedo, d_hi_normal, d_hi_depth,
+                    d_out, d_out_var=0, params=None, stream_ptr=0):
+    """rpt_upsample_device: asynchronous and stateless, device pointers on the current device (0 / None: a null plane), enqueued on
+    stream_ptr."""
+    params = params or UpsampleParams()
+    _lib.check(_lib.load().rpt_upsample_device(
+        C.byref(params.desc()), int(lo_width), int(lo_height),
+        *[C.c_void_p(p or None) for p in (d_lo_rgb, d_lo_var, d_lo_albedo, d_lo_normal, d_lo_depth, d_hi_albedo, d_hi_normal, d_hi_depth,
+                                          d_out, d_out_var)], C.c_void_p(stream_ptr)))
+
+
+def image_bytes_device(d_rgb, width, height, stream_ptr=0):
+    """rpt_image_bytes_device: color_bytes of a device plane of width*height*3 doubles, enqueued on stream_ptr and waited for ->
+    (h, w, 3) uint8.  What ends a pipeline composed from device entry points."""
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0:
+        raise ValueError("image_bytes_device: empty image")
+    out = np.empty((height, width, 3), dtype=np.uint8)
+    _lib.check(_lib.load().rpt_image_bytes_device(C.c_void_p(d_rgb or None), width, height, _vp(out), C.c_void_p(stream_ptr)))
+    return out
 
 
 # ------------------------------------------------------------------ temporal accumulation (rpt_temporal_*, an addition)
@@ -1431,7 +1526,118 @@ class Renderer:
         buffer.close()
         return img
 
-    def render_sequence(self, cameras, batches=4, temporal=None, denoise=None, scenes=None, adaptive=None, return_tile_batches=False):
+    def _low(self, scale, what):
+        """This renderer at 1 / scale of its size: the same scene, camera, seed and settings (the reference's pixel-to-ray map is
+        scale-consistent: a low-resolution pixel integrates over scale x scale full-resolution ones)."""
+        if scale not in (2, 3, 4):
+            raise ValueError(f"{what}: scale must be 2, 3 or 4")
+        if self.width_ % scale or self.height_ % scale or self.width_ < scale or self.height_ < scale:
+            raise ValueError(f"{what}: width and height must be multiples of the scale {scale}")
+        import copy
+        lo = copy.copy(self)
+        lo.width_, lo.height_ = self.width_ // scale, self.height_ // scale
+        return lo
+
+    def render_upsampled(self, params=None, batches=4, denoise=None, guide_samples=1):
+        """An addition: the frame rendered at (width / s, height / s) and rebuilt at full size.  num_samples in `batches` batches
+        (as render_denoised) at the low resolution with the same camera into a DeviceBuffer, the low-resolution feature planes of
+        the same camera samples, the full-resolution planes of `guide_samples` samples, then DeviceBuffer.upsampled_image
+        (`params`: an UpsampleParams or None for the defaults; denoise=DenoiseParams(..): the a-trous filter at the low resolution
+        first) -> (h, w, 3) uint8.  width and height must be multiples of params.scale.  Everything but the bytes stays on the
+        device; filter() is not applied.  Not for sharded renders."""
+        params = params or UpsampleParams()
+        if not isinstance(params, UpsampleParams):
+            raise ValueError("render_upsampled: params must be an UpsampleParams or None")
+        if denoise is not None and not isinstance(denoise, DenoiseParams):
+            raise ValueError("render_upsampled: denoise must be a DenoiseParams or None")
+        batches, guide_samples = int(batches), int(guide_samples)
+        if batches < 2:
+            raise ValueError("render_upsampled: the variance of the mean needs at least 2 batches")
+        if self.num_samples_ < batches:
+            raise ValueError("render_upsampled: num_samples must be at least the number of batches")
+        if guide_samples < 1:
+            raise ValueError("render_upsampled: guide_samples must be at least 1")
+        if self.shard_count_ != 1:
+            raise ValueError("render_upsampled: a sharded frame is assembled first; rank 0 upsamples it")
+        lo = self._low(params.scale, "render_upsampled")
+        buffer, denoiser = DeviceBuffer(lo.width_, lo.height_, None, self.device_), None
+        try:
+            if denoise is not None:
+                denoiser = Denoiser(lo.width_, lo.height_, self.device_)
+            n, big = lo.width_ * lo.height_ * 3, self.width_ * self.height_ * 3
+            planes = _device_zeros(3 * n + 3 * big, self.device_)
+            _sync(self.device_)
+            ptrs = [planes.data_ptr() + 8 * n * k for k in range(3)]
+            hi_ptrs = [planes.data_ptr() + 8 * (3 * n + big * k) for k in range(3)]
+            lo.features_device(self.num_samples_, *ptrs, sample_offset=0)
+            self.features_device(guide_samples, *hi_ptrs, sample_offset=0)
+            lo._sample_offset = 0
+            base, extra = divmod(self.num_samples_, batches)
+            for k in range(batches):
+                lo.sample(base + (1 if k < extra else 0), buffer)
+            names = ("albedo", "normal", "depth")
+            return buffer.upsampled_image(dict(zip(names, ptrs)), dict(zip(names, hi_ptrs)), params, denoiser, denoise)
+        finally:
+            if denoiser is not None:
+                denoiser.close()
+            buffer.close()
+
+    def _upsampled_sequence(self, cameras, batches, temporal, denoise, scenes, upsample, guide_samples):
+        """render_sequence with upsample=: composed from the device entry points on the default stream."""
+        lo = self._low(upsample.scale, "render_sequence")
+        accumulator, denoiser = TemporalAccumulator(self.width_, self.height_, self.device_), None
+        own, own_scene = self.camera, self.scene
+        try:
+            if denoise is not None:
+                denoiser = Denoiser(self.width_, self.height_, self.device_)
+            n, big = lo.width_ * lo.height_, self.width_ * self.height_
+            # low resolution: mean 3 n, variance n, planes 9 n; full resolution: planes 9, upsampled 3 + 1, accumulated 3 + 1, filtered 3
+            mem = _device_zeros(13 * n + 20 * big, self.device_)
+            _sync(self.device_)
+            at = lambda k: mem.data_ptr() + 8 * k  # noqa: E731
+            mean, var = at(0), at(3 * n)
+            ptrs = [at(4 * n + 3 * n * k) for k in range(3)]
+            hi_ptrs = [at(13 * n + 3 * big * k) for k in range(3)]
+            up, up_var, acc, acc_var, out = (at(13 * n + big * k) for k in (9, 12, 13, 16, 17))
+            base, extra = divmod(self.num_samples_, batches)
+            for f, cam in enumerate(cameras):
+                self.camera = lo.camera = cam
+                if scenes is not None:
+                    self.scene = lo.scene = scenes[f]
+                    if f > 0:
+                        accumulator.set_motion(np.stack([temporal_motion_record(c.shape.matrix(), p.shape.matrix())
+                                                         for c, p in zip(scenes[f].objects, scenes[f - 1].objects)])
+                                               if scenes[f].objects else None)
+                buffer = DeviceBuffer(lo.width_, lo.height_, None, self.device_)
+                try:
+                    lo.features_device(self.num_samples_, *ptrs, sample_offset=f * self.num_samples_)
+                    self.features_device(guide_samples, *hi_ptrs, sample_offset=f * self.num_samples_)
+                    lo._sample_offset = f * self.num_samples_
+                    for k in range(batches):
+                        lo.sample(base + (1 if k < extra else 0), buffer)
+                    _sync(self.device_)                          # batches and planes may have been written on other streams
+                    buffer.mean_device(mean, var)
+                    _sync(self.device_)                          # (the buffer goes away below: its sums have been read)
+                finally:
+                    buffer.close()
+                upsample_device(lo.width_, lo.height_, mean, var, *ptrs, *hi_ptrs, up, up_var, params=upsample)
+                accumulator.accumulate_device(cam, up, up_var, hi_ptrs[1] if temporal.normal_tol > 0.0 else 0, hi_ptrs[2], acc, acc_var,
+                                              params=temporal)
+                last = acc
+                if denoiser is not None:
+                    denoiser.denoise_device(acc, acc_var, *hi_ptrs, out, params=denoise)
+                    last = out
+                img = image_bytes_device(last, self.width_, self.height_)
+                self.camera, self.scene = own, own_scene
+                yield img
+        finally:
+            self.camera, self.scene = own, own_scene
+            accumulator.close()
+            if denoiser is not None:
+                denoiser.close()
+
+    def render_sequence(self, cameras, batches=4, temporal=None, denoise=None, scenes=None, adaptive=None, return_tile_batches=False,
+                        upsample=None, guide_samples=1):
         """An addition: a generator of one (h, w, 3) uint8 frame per camera of `cameras`, for a camera that moves over this scene
         or, with `scenes` (one Scene per camera, as the reference builds one per frame: the same number of objects with the same
         base shape kinds in the same order, else ValueError), over objects that move: frame f renders scenes[f], committed when its
@@ -1446,7 +1652,20 @@ class Renderer:
         its batches at the sample offsets f * max_batches * spp_per_batch .., the feature planes those of the first
         min_batches * spp_per_batch samples at that offset (as render_adaptive takes them), the motion table set before the loop
         and consumed by temporal_image after it; num_samples and `batches` are not read.  With return_tile_batches=True (adaptive
-        only) each frame comes as (image, tile_batches), the (tiles_y, tiles_x) batches its tiles ended with."""
+        only) each frame comes as (image, tile_batches), the (tiles_y, tiles_x) batches its tiles ended with.
+        With upsample=UpsampleParams(..) frame f is rendered at (width / s, height / s) (width and height multiples of s, else
+        ValueError): its low-resolution mean and variance are upsampled under the low-resolution planes of the same camera samples
+        and the full-resolution planes of `guide_samples` samples, then accumulate_device, the optional filter and
+        image_bytes_device run at full resolution, where the depth and normal planes and the motion table are.  Not together
+        with `adaptive` (ValueError)."""
+        if upsample is not None:
+            if not isinstance(upsample, UpsampleParams):
+                raise ValueError("render_sequence: upsample must be an UpsampleParams or None")
+            if adaptive is not None:
+                raise ValueError("render_sequence: adaptive sampling is not combined with upsampling")
+            if int(guide_samples) < 1:
+                raise ValueError("render_sequence: guide_samples must be at least 1")
+            self._low(upsample.scale, "render_sequence")
         if adaptive is not None and not isinstance(adaptive, AdaptiveParams):
             raise ValueError("render_sequence: adaptive must be an AdaptiveParams or None")
         if return_tile_batches and adaptive is None:
@@ -1478,6 +1697,8 @@ class Renderer:
             kinds = [[o.shape.base().KIND for o in sc.objects] for sc in scenes]
             if any(k != kinds[0] for k in kinds[1:]):
                 raise ValueError("render_sequence: every scene must hold the same base shape kinds in the same order")
+        if upsample is not None:
+            return self._upsampled_sequence(cameras, batches, temporal or TemporalParams(), denoise, scenes, upsample, int(guide_samples))
         return self._render_sequence(cameras, batches, temporal or TemporalParams(), denoise, scenes, adaptive, bool(return_tile_batches))
 
     def _render_sequence(self, cameras, batches, temporal, denoise, scenes=None, adaptive=None, return_tile_batches=False):

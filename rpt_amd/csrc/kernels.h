@@ -126,6 +126,19 @@ static constexpr uint32_t kDenoiseMaxStagedStep = 2;   // the largest step whose
 __attribute__((weak)) hipError_t launch_buffer_mean(uint32_t n_pixels, uint32_t n_batches, const double* d_sum, const double* d_sumsq,
                                                     double* d_rgb, double* d_var /* or null */, hipStream_t st);
 __attribute__((weak)) hipError_t launch_color_bytes(uint64_t n_values, const double* d_rgb, uint8_t* d_out, hipStream_t st);
+// rpt_upsample* (upsample.hip): the guided upsampling of include/rpt_hip.h, one kernel, one lane per full-resolution pixel, the taps
+// gathered from the low-resolution planes.  width x height is the LOW resolution; the outputs are scale times as large on each axis.
+struct UpsampleArgs {
+    uint32_t width, height, scale, radius;
+    uint32_t flags, terms;                               // RPT_UPSAMPLE_*; bit 0 normal, 1 depth
+    double a_n, a_z;                                     // 1 / sigma_normal, 1 / (sigma_depth * double(scale))
+    const double *lo_rgb, *lo_var, *lo_albedo, *lo_normal, *lo_depth;   // all but lo_rgb: or null
+    const double *hi_albedo, *hi_normal, *hi_depth;      // or null
+    double *out_rgb, *out_var;                           // out_var: or null
+};
+// (Weak: reached from rpt_upsample* and rpt_buffer_upsampled_image alone, which report RPT_ERR_UNSUPPORTED where no kernel library is
+// linked.)
+__attribute__((weak)) hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t stream);
 // rpt_temporal_* (temporal.hip): the accumulation of include/rpt_hip.h, one kernel, one lane per pixel.  The history is one record of
 // kTemporalRecDoubles doubles per pixel (c rgb, v, len, n xyz, z, id); a call reads the old records of its four taps and writes the new
 // ones elsewhere.  The two camera records are rpt_temporal_camera_record's 13 doubles.

@@ -3522,6 +3522,155 @@ int rpt_buffer_denoised_image(rpt_buffer* b, rpt_denoiser* d, const rpt_denoise_
     return RPT_OK;
 }
 
+// ---------------------------------------------------------------------------- guided upsampling (upsample.hip)
+// What rpt_upsample* refuse before any device call, in the order include/rpt_hip.h states.
+static int check_upsample(const rpt_upsample_params* prm, uint32_t w, uint32_t h, const void* lo_rgb, const void* lo_var, const void* lo_albedo,
+                          const void* lo_normal, const void* lo_depth, const void* hi_albedo, const void* hi_normal, const void* hi_depth,
+                          const void* out, const void* out_var) {
+    if (!prm) return fail(RPT_ERR_INVALID, "null upsample parameters");
+    if (prm->scale < 2 || prm->scale > 4) return fail(RPT_ERR_INVALID, "scale must be 2, 3 or 4");
+    if (prm->radius < 1 || prm->radius > 2) return fail(RPT_ERR_INVALID, "radius must be 1 or 2");
+    if (prm->flags & ~(RPT_UPSAMPLE_DEMODULATE | RPT_UPSAMPLE_MATCH_ID)) return fail(RPT_ERR_INVALID, "unknown upsample flag");
+    for (double sg : {prm->sigma_normal, prm->sigma_depth})
+        if (!(sg >= 0.0) || std::isinf(sg)) return fail(RPT_ERR_INVALID, "a sigma must be finite and >= 0 (0: the term is off)");
+    if (w == 0 || h == 0) return fail(RPT_ERR_INVALID, "empty low-resolution frame");
+    const uint64_t W = uint64_t(w) * prm->scale, H = uint64_t(h) * prm->scale;
+    if (W >= (1ull << 32) || H >= (1ull << 32) || W * H >= (1ull << 31)) return fail(RPT_ERR_INVALID, "the full-resolution frame is too large");
+    if (!lo_rgb || !out) return fail(RPT_ERR_INVALID, "null frame");
+    if (prm->sigma_normal > 0.0 && !lo_normal) return fail(RPT_ERR_INVALID, "sigma_normal > 0 needs the low-resolution normal plane");
+    if (prm->sigma_normal > 0.0 && !hi_normal) return fail(RPT_ERR_INVALID, "sigma_normal > 0 needs the full-resolution normal plane");
+    if (prm->sigma_depth > 0.0 && !lo_depth) return fail(RPT_ERR_INVALID, "sigma_depth > 0 needs the low-resolution depth plane");
+    if (prm->sigma_depth > 0.0 && !hi_depth) return fail(RPT_ERR_INVALID, "sigma_depth > 0 needs the full-resolution depth plane");
+    if ((prm->flags & RPT_UPSAMPLE_DEMODULATE) && !lo_albedo) return fail(RPT_ERR_INVALID, "RPT_UPSAMPLE_DEMODULATE needs the low-resolution albedo plane");
+    if ((prm->flags & RPT_UPSAMPLE_DEMODULATE) && !hi_albedo) return fail(RPT_ERR_INVALID, "RPT_UPSAMPLE_DEMODULATE needs the full-resolution albedo plane");
+    if ((prm->flags & RPT_UPSAMPLE_MATCH_ID) && !lo_depth) return fail(RPT_ERR_INVALID, "RPT_UPSAMPLE_MATCH_ID needs the low-resolution depth plane");
+    if ((prm->flags & RPT_UPSAMPLE_MATCH_ID) && !hi_depth) return fail(RPT_ERR_INVALID, "RPT_UPSAMPLE_MATCH_ID needs the full-resolution depth plane");
+    for (const void* o : {out, out_var})
+        for (const void* in : {lo_rgb, lo_var, lo_albedo, lo_normal, lo_depth, hi_albedo, hi_normal, hi_depth})
+            if (o && o == in) return fail(RPT_ERR_INVALID, "an output must not be one of the inputs");
+    if (out == out_var) return fail(RPT_ERR_INVALID, "out_rgb and out_var must differ");
+    return RPT_OK;
+}
+// The launch of a checked call: the planes a term or flag that is off would read are not handed on.
+static int run_upsample(const rpt_upsample_params* prm, uint32_t w, uint32_t h, const void* lo_rgb, const void* lo_var, const void* lo_albedo,
+                        const void* lo_normal, const void* lo_depth, const void* hi_albedo, const void* hi_normal, const void* hi_depth, void* out,
+                        void* out_var, hipStream_t st) {
+    if (!launch_upsample) return fail(RPT_ERR_UNSUPPORTED, "rpt_upsample: built without the kernels");
+    UpsampleArgs a{};
+    a.width = w; a.height = h; a.scale = prm->scale; a.radius = prm->radius; a.flags = prm->flags;
+    a.terms = (prm->sigma_normal > 0.0 ? 1u : 0u) | (prm->sigma_depth > 0.0 ? 2u : 0u);
+    a.a_n = 1.0 / prm->sigma_normal;
+    a.a_z = 1.0 / (prm->sigma_depth * double(prm->scale));
+    const bool demod = prm->flags & RPT_UPSAMPLE_DEMODULATE, depth = (a.terms & 2u) || (prm->flags & RPT_UPSAMPLE_MATCH_ID);
+    a.lo_rgb = static_cast<const double*>(lo_rgb);
+    a.lo_var = static_cast<const double*>(lo_var);
+    a.lo_albedo = demod ? static_cast<const double*>(lo_albedo) : nullptr;
+    a.hi_albedo = demod ? static_cast<const double*>(hi_albedo) : nullptr;
+    a.lo_normal = (a.terms & 1u) ? static_cast<const double*>(lo_normal) : nullptr;
+    a.hi_normal = (a.terms & 1u) ? static_cast<const double*>(hi_normal) : nullptr;
+    a.lo_depth = depth ? static_cast<const double*>(lo_depth) : nullptr;
+    a.hi_depth = depth ? static_cast<const double*>(hi_depth) : nullptr;
+    a.out_rgb = static_cast<double*>(out);
+    a.out_var = static_cast<double*>(out_var);
+    HIP_TRY(launch_upsample(a, st));
+    return RPT_OK;
+}
+int rpt_upsample_device(const rpt_upsample_params* prm, uint32_t lo_width, uint32_t lo_height, const void* d_lo_rgb, const void* d_lo_var,
+                        const void* d_lo_albedo, const void* d_lo_normal, const void* d_lo_depth, const void* d_hi_albedo,
+                        const void* d_hi_normal, const void* d_hi_depth, void* d_out_rgb, void* d_out_var, void* hip_stream) {
+    if (int rc = check_upsample(prm, lo_width, lo_height, d_lo_rgb, d_lo_var, d_lo_albedo, d_lo_normal, d_lo_depth, d_hi_albedo, d_hi_normal,
+                                d_hi_depth, d_out_rgb, d_out_var))
+        return rc;
+    return run_upsample(prm, lo_width, lo_height, d_lo_rgb, d_lo_var, d_lo_albedo, d_lo_normal, d_lo_depth, d_hi_albedo, d_hi_normal, d_hi_depth,
+                        d_out_rgb, d_out_var, static_cast<hipStream_t>(hip_stream));
+}
+int rpt_upsample(int device, const rpt_upsample_params* prm, uint32_t lo_width, uint32_t lo_height, const double* lo_rgb, const double* lo_var,
+                 const double* lo_albedo, const double* lo_normal, const double* lo_depth, const double* hi_albedo, const double* hi_normal,
+                 const double* hi_depth, double* out_rgb, double* out_var) {
+    if (int rc = check_upsample(prm, lo_width, lo_height, lo_rgb, lo_var, lo_albedo, lo_normal, lo_depth, hi_albedo, hi_normal, hi_depth, out_rgb,
+                                out_var))
+        return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(RPT_ERR_INVALID, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    const size_t n = size_t(lo_width) * lo_height, N = n * prm->scale * prm->scale;
+    // low resolution: rgb, albedo, normal, depth 3 n each, var n; full resolution: albedo, normal, depth, out 3 N each, out_var N
+    rpti::DevMem mem;
+    HIP_TRY(mem.reserve((13 * n + 13 * N) * 8));
+    double* const base = mem.get<double>();
+    const double* const ins[8] = {lo_rgb, lo_albedo, lo_normal, lo_depth, lo_var, hi_albedo, hi_normal, hi_depth};
+    const size_t at[8] = {0, 3 * n, 6 * n, 9 * n, 12 * n, 13 * n, 13 * n + 3 * N, 13 * n + 6 * N};
+    const size_t len[8] = {3 * n, 3 * n, 3 * n, 3 * n, n, 3 * N, 3 * N, 3 * N};
+    double* dev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 8; k++)
+        if (ins[k]) {
+            dev[k] = base + at[k];
+            HIP_TRY(hipMemcpy(dev[k], ins[k], len[k] * 8, hipMemcpyHostToDevice));
+        }
+    double* const d_out = base + 13 * n + 9 * N;
+    double* const d_out_var = out_var ? base + 13 * n + 12 * N : nullptr;
+    if (int rc = run_upsample(prm, lo_width, lo_height, dev[0], dev[4], dev[1], dev[2], dev[3], dev[5], dev[6], dev[7], d_out, d_out_var, nullptr))
+        return rc;
+    HIP_TRY(hipMemcpy(out_rgb, d_out, 3 * N * 8, hipMemcpyDeviceToHost));
+    if (out_var) HIP_TRY(hipMemcpy(out_var, d_out_var, N * 8, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+int rpt_image_bytes_device(const void* d_rgb, uint32_t width, uint32_t height, uint8_t* out_rgb8_host, void* hip_stream) {
+    if (!d_rgb || !out_rgb8_host) return fail(RPT_ERR_INVALID, "null argument");
+    if (width == 0 || height == 0 || uint64_t(width) * height >= (1ull << 31)) return fail(RPT_ERR_INVALID, "bad image size");
+    if (!launch_color_bytes) return fail(RPT_ERR_UNSUPPORTED, "rpt_image_bytes_device: built without the kernels");
+    const size_t n = size_t(width) * height;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    rpti::DevMem img;
+    HIP_TRY(img.reserve(3 * n));
+    HIP_TRY(launch_color_bytes(3 * n, static_cast<const double*>(d_rgb), img.get<uint8_t>(), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(out_rgb8_host, img.get(), 3 * n, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+int rpt_buffer_upsampled_image(rpt_buffer* b, rpt_denoiser* d, const rpt_denoise_params* dprm, const rpt_upsample_params* prm,
+                               const void* d_lo_albedo, const void* d_lo_normal, const void* d_lo_depth, const void* d_hi_albedo,
+                               const void* d_hi_normal, const void* d_hi_depth, uint8_t* out_rgb8) {
+    if (!b || !out_rgb8) return fail(RPT_ERR_INVALID, "null argument");
+    // (the frame and its variance come from the buffer: placeholders that are no plane of the caller's)
+    if (int rc = check_upsample(prm, b->width, b->height, b, nullptr, d_lo_albedo, d_lo_normal, d_lo_depth, d_hi_albedo, d_hi_normal, d_hi_depth,
+                                out_rgb8, nullptr))
+        return rc;
+    if (d) {
+        if (int rc = check_denoise(d, dprm, b, dprm && dprm->sigma_color > 0.0 ? d : nullptr, d_lo_albedo, d_lo_normal, d_lo_depth, out_rgb8, nullptr))
+            return rc;
+        if (b->device != d->device) return fail(RPT_ERR_INVALID, "buffer and denoiser live on different devices");
+        if (b->width != d->width || b->height != d->height) return fail(RPT_ERR_INVALID, "buffer and denoiser have different sizes");
+    }
+    if (b->n_batches < 2) return fail(RPT_ERR_STATE, "the variance of the mean needs at least 2 batches");
+    if (!launch_buffer_mean || !launch_color_bytes || !launch_upsample)
+        return fail(RPT_ERR_UNSUPPORTED, "rpt_buffer_upsampled_image: built without the kernels");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipDeviceSynchronize());  // batches and planes may have been written on other streams
+    const size_t n = size_t(b->width) * b->height, N = n * prm->scale * prm->scale;
+    // mean 3 n, variance n, filtered mean 3 n (with a denoiser), the full-resolution frame 3 N, then its 3 N bytes
+    HIP_TRY(b->d_up.reserve((7 * n + 3 * N) * 8 + 3 * N));
+    double* const mean = b->d_up.get<double>();
+    double* const var = mean + 3 * n;
+    double* const up = mean + 7 * n;
+    uint8_t* const img = reinterpret_cast<uint8_t*>(up + 3 * N);
+    const double* lo = mean;
+    if (int rc = rpt_buffer_mean_device(b, mean, var, nullptr)) return rc;
+    if (d) {
+        if (int rc = run_denoise(d, dprm, mean, var, static_cast<const double*>(d_lo_albedo), static_cast<const double*>(d_lo_normal),
+                                 static_cast<const double*>(d_lo_depth), mean + 4 * n, nullptr, nullptr))
+            return rc;
+        lo = mean + 4 * n;
+    }
+    // (no variance is asked for, so none is read)
+    if (int rc = run_upsample(prm, b->width, b->height, lo, nullptr, d_lo_albedo, d_lo_normal, d_lo_depth, d_hi_albedo, d_hi_normal, d_hi_depth,
+                              up, nullptr, nullptr))
+        return rc;
+    HIP_TRY(launch_color_bytes(3 * N, up, img, nullptr));
+    HIP_TRY(hipMemcpy(out_rgb8, img, 3 * N, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
 // ---------------------------------------------------------------------------- temporal accumulation (temporal.hip)
 int rpt_temporal_camera_record(const rpt_camera* cam, double out[13]) {
     if (!cam || !out) return fail(RPT_ERR_INVALID, "null argument");

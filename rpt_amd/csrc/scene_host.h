@@ -181,6 +181,7 @@ struct rpt_buffer {
     uint32_t width = 0, height = 0, radius = 0, n_batches = 0;
     rpti::DevMem d_sum, d_sumsq, d_stage;  // stage: one batch / per-pixel variances
     rpti::DevMem d_img;
+    rpti::DevMem d_up;                     // rpt_buffer_upsampled_image: mean, variance, filtered mean, the full-resolution frame and its bytes
     // Adaptive sampling by tile (adaptive.hip): allocated at the first tile batch / the first refinement.
     rpti::DevMem d_extra;                  // extra batches per 32 x 32 tile (u32); a pixel holds n_batches + extra[its tile]
     rpti::DevMem d_tile_err, d_active;     // rpt_buffer_refine_tiles' errors when the caller keeps none, its count; rpt_render_adaptive's list
