@@ -269,6 +269,8 @@ int rpt_scene_render_chunking(rpt_scene*, uint32_t iterations, uint32_t* chunk_s
  * 8x8 pixel block once per work item and test them with one photon per lane, default 1; 0 walks the tree per
  * sample), "photon_parts" (work items per 8x8 pixel block and sample chunk of the photon camera pass: the block's
  * rows in 1, 2, 4 or 8 strips, default 4; changes the fp32 order of a pixel's beam sum, nothing else),
+ * "photon_keep_counts" 0/1 (default 0; 1: the per-photon record counts of a shooting pass are kept with the map for
+ * rpt_debug_photon_chain_counts -- a test hook; without it the shooting pass allocates and launches exactly what it did),
  * "photon_coop_gather" 0/1 (surface estimate of the photon camera pass: the wave collects the candidates of a
  * pixel's samples together and every lane picks its K nearest from that list, default 1; 0 searches per lane),
  * "photon_skip" (diagnostic bit mask that switches parts of the photon camera pass off), "defer_lanes" / "defer_stop" (scenes whose meshes
@@ -951,6 +953,10 @@ int rpt_debug_exclusive_scan2(uint64_t n, const uint32_t* a, const uint32_t* b, 
 /* Reference-epsilon mode: the surface photons' positions as the shooting pass holds them (fp64, 3 per photon, shooting order -- the
  * order of rpt_photon_map_download(which = 0)); capacity in photons. */
 int rpt_debug_photon_positions64(rpt_scene*, double* out, uint64_t capacity);
+/* Scenes with the option "photon_keep_counts" = 1: the record counts of every photon of the last shooting pass (rpt_photon_shoot: of
+ * this rank's photons; rpt_photon_map_build: of all), in shooting order; which = 0 surface, 1 volume; capacity in photons.  Their
+ * exclusive prefix sums index each photon's first record in the shooting-order arrays.  RPT_ERR_STATE when nothing was kept. */
+int rpt_debug_photon_chain_counts(rpt_scene*, int32_t which, uint32_t* out, uint64_t capacity);
 /* ... and what the last camera pass (its last slice) handed from the k-nearest selection to the fp64 surface estimate:
  * dims = {owned pixel slots, gather_size + 2, samples}; out[slot][row][sample], rows: photon indices (sorted order), their number,
  * the squared distance of the farthest (float bits).  out may be null (dims only). */

@@ -102,6 +102,12 @@ def lib():
         L.orc_photon_map_from_photons.restype = P
         L.orc_photon_map_from_photons.argtypes = [C.c_uint64, C.c_int, C.c_double, C.c_uint64, C.c_uint64, P, C.c_uint64, P, C.c_uint64]
         L.orc_photon_map_free.argtypes = [P]
+        L.orc_photon_chains.restype = P
+        L.orc_photon_chains.argtypes = [P, C.c_uint64, C.c_uint64, C.c_uint64, P, C.c_int, C.c_double, C.c_uint64, C.c_int, C.c_double,
+                                        C.c_uint64, C.c_int]
+        L.orc_photon_chains_free.argtypes = [P]
+        L.orc_photon_chains_totals.argtypes = [P, P]
+        L.orc_photon_chains_get.argtypes = [P, P, P, P, P, P, P, P]
         L.orc_photon_map_get.restype = C.c_uint64
         L.orc_photon_map_get.argtypes = [P, C.c_int, P]
         L.orc_photon_render.argtypes = [P, P, C.POINTER(CameraDesc), C.POINTER(Params), C.c_uint32, C.c_uint64,
@@ -284,6 +290,29 @@ class OracleScene:
     def photon_map(self, photon_count, kind, watts, gather_size=50, gather_size_volume=50, seed=0, robust=0):
         """Renderer::photon_render's shooting + map build (src/photon.rs:655-704)."""
         return OraclePhotonMap(self, photon_count, kind, watts, gather_size, gather_size_volume, seed, robust)
+
+    CHAIN_ROW = 12
+
+    def photon_chains(self, photon_count, kind, watts, seed=0, robust=0, first=0, n=None, indices=None, amp=0.0, cloud_seed=0, verts=False):
+        """orc_photon_chains: photons [first, first + n) (or `indices`) of a photon_count map, chain by chain, no map built.  -> dict:
+        ns, nv (records per photon; volume after thinning), sig (u64 signature of the chain's decisions), surface, volume ((., 10) as
+        OraclePhotonMap.photons lays them out), and with verts: nrows and rows ((., 12), see ChainTrace in rpt_oracle.cpp)."""
+        L = lib()
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint64)
+        m = int(n if idx is None else idx.size)
+        h = L.orc_photon_chains(self.h, int(photon_count), int(first), m, None if idx is None else idx.ctypes.data_as(C.c_void_p), int(kind),
+                                float(watts), int(seed), int(robust), float(amp), int(cloud_seed), int(bool(verts)))
+        if not h:
+            raise ValueError("Only found non-object lights while photon mapping")
+        try:
+            tot = np.zeros(3, dtype=np.uint64)
+            L.orc_photon_chains_totals(h, tot.ctypes.data_as(C.c_void_p))
+            out = {"ns": np.zeros(m, np.uint32), "nv": np.zeros(m, np.uint32), "nrows": np.zeros(m, np.uint32), "sig": np.zeros(m, np.uint64),
+                   "surface": np.zeros((int(tot[0]), 10)), "volume": np.zeros((int(tot[1]), 10)), "rows": np.zeros((int(tot[2]), self.CHAIN_ROW))}
+            L.orc_photon_chains_get(h, *[out[k].ctypes.data_as(C.c_void_p) for k in ("ns", "nv", "nrows", "sig", "surface", "volume", "rows")])
+        finally:
+            L.orc_photon_chains_free(h)
+        return out
 
     def close(self):
         if self.h:

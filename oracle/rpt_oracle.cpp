@@ -1144,9 +1144,40 @@ enum PhotonKind { PK_PHOTON_MAP = 0, PK_POINT_BEAM = 1, PK_BEAM_BEAM = 2 };  // 
 
 // trace_photon, src/photon.rs:803-946.  The recursion is a tail call (nothing but list
 // concatenation follows it), so it is a loop here; photons are stored in path order.
-static void trace_photon(const Renderer& r, Ray ray, V3 power, Rng& rng, PhotonList& out) {
+// ChainTrace (orc_photon_chains): what a chain decided, vertex by vertex, and optionally a small seeded displacement of every
+// vertex's ray.  A row of `verts` (CHAIN_ROW doubles): 0 event (0 miss, 1 volume, 2 surface, 3 emission), 1 object index (surface) or
+// the side of y = 250 (volume), 2 what ended the chain there (0 nothing, 1 absorbed at 0.7, 2 sample_f None, 3 medium roulette, 4 escape),
+// 3 length of the segment that ends at the vertex, 4 max |origin| of that segment's ray, 5 record stored (0 none, 1 surface, 2 volume;
+// before thinning), 6 material kind, 7 wi.n (emission: sine of the polar angle), 8 |n|_1, 9 / 10 / 11 per material -- Phong: the lobe
+// cosine, shininess; glass: ni / nt, Snell's k = 1 - (ni / nt)^2 (1 - ci^2), refracted (1) or reflected (0); emission: the local z of a
+// sphere sample (1 otherwise), sqrt(n.x^2 + n.z^2) of the emitter's normal, |v| of the sampled point.  Beam-beam thinning turns the 2 of
+// slot 5 into 4 for a volume vertex whose record is not kept.
+static const int CHAIN_ROW = 12;
+struct ChainTrace {
+    double amp = 0.0;
+    Rng jit{0, 0, 0};
+    uint64_t sig = 0x243F6A8885A308D3ULL;
+    std::vector<double>* verts = nullptr;
+    size_t thin_row = 0;
+    void jitter(Ray& ray) {
+        if (!(amp > 0.0)) return;
+        double s = amp * (1.0 + std::fmax(std::fabs(ray.origin.x), std::fmax(std::fabs(ray.origin.y), std::fabs(ray.origin.z))));
+        double a = jit.range(-1.0, 1.0), b = jit.range(-1.0, 1.0), c = jit.range(-1.0, 1.0);
+        ray.origin = ray.origin + s * V3(a, b, c);
+        a = jit.range(-1.0, 1.0); b = jit.range(-1.0, 1.0); c = jit.range(-1.0, 1.0);
+        ray.dir = ray.dir + amp * V3(a, b, c);
+    }
+    void vertex(const double (&row)[CHAIN_ROW], int cw_sign) {
+        uint64_t w = uint64_t(row[0]) | uint64_t(int64_t(row[1]) + 1) << 8 | uint64_t(row[2]) << 40 | uint64_t(cw_sign + 1) << 44;
+        sig = mix64(sig ^ (w + 0x9E3779B97F4A7C15ULL));
+        if (verts) verts->insert(verts->end(), row, row + CHAIN_ROW);
+    }
+};
+static void trace_photon(const Renderer& r, Ray ray, V3 power, Rng& rng, PhotonList& out, ChainTrace* tr = nullptr) {
     const Scene& scene = r.scene;
     for (;;) {
+        if (tr) tr->jitter(ray);
+        const double seg_o = std::fmax(std::fabs(ray.origin.x), std::fmax(std::fabs(ray.origin.y), std::fabs(ray.origin.z)));
         V3 wo = -normalize(ray.dir);
         HitRecord h;
         int oi;
@@ -1159,6 +1190,7 @@ static void trace_photon(const Renderer& r, Ray ray, V3 power, Rng& rng, PhotonL
             medium->sample_d(ray, rng, d, pdf_d, cdf_d);
             in_volume = !hit || d < h.time;
         } else if (!hit) {
+            if (tr) tr->vertex({0, -1, 4, 0, seg_o, 0, 0, 0, 0, 0, 0, 0}, 0);
             return;
         }
         if (in_volume) {  // trace_in_volume :879-914
@@ -1168,7 +1200,10 @@ static void trace_photon(const Renderer& r, Ray ray, V3 power, Rng& rng, PhotonL
             V3 attenuated = cmul(power, medium_color) * scat / extinction;
             double rr_prob = scat / extinction;
             out.volume.push_back(Photon{collision, wo, power, ray.origin});
-            if (rng.uniform() < rr_prob) {
+            const bool scatters = rng.uniform() < rr_prob;
+            if (tr) tr->vertex({1, double(medium->kind == COLORED_GLOWING_FOG && collision.y > 250.0), scatters ? 0.0 : 3.0,
+                                d * length(ray.dir), seg_o, 2, 0, 0, 0, 0, 0, 0}, 0);
+            if (scatters) {
                 V3 wi;
                 double ph_p;
                 medium->sample_ph(wo, rng, wi, ph_p);
@@ -1182,21 +1217,45 @@ static void trace_photon(const Renderer& r, Ray ray, V3 power, Rng& rng, PhotonL
         V3 world_pos = ray.at(h.time);
         const Material& material = scene.objects[oi].material;
         const double p_d = (0.7 + 0.7 + 0.7) / (0.7 + 0.7 + 0.7 + 0.0) * 0.7;
-        if (!(rng.uniform() < p_d)) return;  // absorbed: no photon is stored
+        const double seg_len = h.time * length(ray.dir);
+        if (!(rng.uniform() < p_d)) {  // absorbed: no photon is stored
+            if (tr) tr->vertex({2, double(oi), 1, seg_len, seg_o, 0, double(material.kind), 0, 0, 0, 0, 0}, 0);
+            return;
+        }
         V3 wi;
         double pdf;
-        if (!sample_f(material, h.normal, wo, rng, wi, pdf)) return;  // total internal reflection: no photons
+        if (!sample_f(material, h.normal, wo, rng, wi, pdf)) {  // total internal reflection: no photons
+            if (tr) tr->vertex({2, double(oi), 2, seg_len, seg_o, 0, double(material.kind), 0, 0, 0, 0, 0}, 0);
+            return;
+        }
         V3 f = bsdf(material, h.normal, wo, wi);
         double cosine_term = dot(wi, h.normal) > 0.0 ? dot(wi, h.normal) : 1.0;
         V3 attenuated = cmul(power, f) * cosine_term / pdf / p_d;
         bool is_mirror = material.kind == MIRROR || material.kind == TRANSMISSIVE;  // material.rs:135-141
+        if (tr) {
+            const V3& n = h.normal;
+            const double cw = dot(wi, n);
+            double a1 = 0.0, a2 = 0.0, a3 = 0.0;
+            if (material.kind == PHONG) {
+                a1 = dot(wi, normalize(-reflect_vec(wo, n)));
+                a2 = material.shininess;
+            } else if (material.kind == TRANSMISSIVE) {
+                const bool inside = dot(n, wo) < 0.0;
+                const double ci = std::fmin(std::fmax(dot(wo, inside ? -n : n), 0.0), 1.0), eta = inside ? material.ior : 1.0 / material.ior;
+                a1 = eta;
+                a2 = 1.0 - eta * eta * (1.0 - ci * ci);
+                a3 = dot(wi, n) * dot(wo, n) < 0.0 ? 1.0 : 0.0;
+            }
+            tr->vertex({2, double(oi), 0, seg_len, seg_o, is_mirror ? 0.0 : 1.0, double(material.kind), cw,
+                        std::fabs(n.x) + std::fabs(n.y) + std::fabs(n.z), a1, a2, a3}, cw > 0.0 ? 1 : -1);
+        }
         if (!is_mirror) out.surface.push_back(Photon{world_pos, wo, power, world_pos});  // `ray` is shadowed by the new ray at :842-846
         power = attenuated;
         ray = Ray{world_pos, wi};
     }
 }
 // shoot_photon, src/photon.rs:724-799 (first Light::Object only, as written)
-static bool shoot_photon(const Renderer& r, double power, Rng& rng, Rng& thin, int kind, PhotonList& out) {
+static bool shoot_photon(const Renderer& r, double power, Rng& rng, Rng& thin, int kind, PhotonList& out, ChainTrace* tr = nullptr) {
     for (const Light& light : r.scene.lights) {
         if (light.kind != L_OBJECT) continue;
         SurfSample s = light.object.shape->sample(V3(0, 0, 0), rng);
@@ -1207,14 +1266,30 @@ static bool shoot_photon(const Renderer& r, double power, Rng& rng, Rng& thin, i
         V3 direction = rotation_between_apply(V3(0, 1, 0), s.n, dir, ok);
         if (!ok) direction = rotation_between_apply(V3(0, 1, 0.00000001), s.n, dir, ok);
         PhotonList mine;
-        trace_photon(r, Ray{s.v, direction}, power * light.object.material.color(), rng, mine);
+        const size_t row0 = tr && tr->verts ? tr->verts->size() : 0;
+        if (tr) {
+            double z = 1.0;
+            if (auto* t = dynamic_cast<const Transformed*>(light.object.shape.get()))
+                if (dynamic_cast<const Sphere*>(t->shape.get()))
+                    z = dot(mul(t->inverse_transform, s.v, 1.0), normalize(mul(t->inverse_transform, V3(0, 0, 0), 1.0)));
+            tr->vertex({3, -1, 0, 0, std::fmax(std::fabs(s.v.x), std::fmax(std::fabs(s.v.y), std::fabs(s.v.z))), 0, 0, std::sin(theta),
+                        std::fabs(s.n.x) + std::fabs(s.n.y) + std::fabs(s.n.z), z, std::sqrt(s.n.x * s.n.x + s.n.z * s.n.z), length(s.v)}, 0);
+        }
+        trace_photon(r, Ray{s.v, direction}, power * light.object.material.color(), rng, mine, tr);
         for (const Photon& p : mine.surface) out.surface.push_back(p);
         for (Photon p : mine.volume) {
             if (kind == PK_BEAM_BEAM) {  // :779-787 thinning (iid Bernoulli draws; taken from a side stream in path order)
                 const double thresh = 0.001;
-                if (thin.uniform() < thresh) {
+                const bool keep = thin.uniform() < thresh;
+                if (keep) {
                     p.power = p.power / thresh;
                     out.volume.push_back(p);
+                }
+                if (tr && tr->verts) {  // the rows of the volume vertices come in path order, as the photons of `mine` do
+                    size_t& at = tr->thin_row;
+                    for (at = std::max(at, row0); (*tr->verts)[at + 5] != 2.0; at += CHAIN_ROW) {}
+                    if (!keep) (*tr->verts)[at + 5] = 4.0;
+                    at += CHAIN_ROW;
                 }
             } else {
                 out.volume.push_back(p);
@@ -1961,6 +2036,72 @@ orc_photon_map* orc_photon_map_build(orc_scene* s, uint64_t photon_count, int ki
     return m;
 }
 void orc_photon_map_free(orc_photon_map* m) { delete m; }
+// Test hook: the chains of n photons of a `photon_count` map, one by one, with orc_photon_map_build's streams and power and no map.
+// Photon j is indices[j], or first + j when indices is null.  amp > 0: every vertex's ray is displaced (origin by amp (1 + max|o|) xi,
+// direction by amp xi, xi uniform in [-1, 1]^3 from a generator keyed by (cloud_seed, photon index)); the chain's own streams are
+// untouched, and amp = 0 gives orc_photon_map_build's lists bit for bit.  The result is owned by the handle: per photon the record
+// counts (volume: after thinning), a signature of the chain's decisions and its number of ChainTrace rows; the records in the layout of
+// orc_photon_map_get; the rows themselves when want_verts.
+struct orc_photon_chains_t {
+    std::vector<uint32_t> ns, nv, nrows;
+    std::vector<uint64_t> sig;
+    std::vector<double> verts;
+    PhotonList list;
+    int kind = 0;
+};
+orc_photon_chains_t* orc_photon_chains(orc_scene* s, uint64_t photon_count, uint64_t first, uint64_t n, const uint64_t* indices, int kind,
+                                       double watts, uint64_t seed, int robust, double amp, uint64_t cloud_seed, int want_verts) {
+    RenderParams rp{1, 1, 0.0, 0, robust};
+    Renderer r{s->scene, Camera{}, rp};
+    auto* c = new orc_photon_chains_t();
+    c->kind = kind;
+    const double power = watts / double(photon_count);
+    for (uint64_t j = 0; j < n; j++) {
+        const uint64_t i = indices ? indices[j] : first + j;
+        Rng rng(seed, uint32_t(i), 0x80000000u + uint32_t(i >> 32));
+        Rng thin(seed, uint32_t(i), 0xC0000000u + uint32_t(i >> 32));
+        ChainTrace tr;
+        tr.amp = amp;
+        tr.jit = Rng(cloud_seed ^ 0x636C6F7564ULL, uint32_t(i), 0x20000000u + uint32_t(i >> 32));
+        tr.verts = want_verts ? &c->verts : nullptr;
+        const size_t s0 = c->list.surface.size(), v0 = c->list.volume.size(), r0 = c->verts.size();
+        if (!shoot_photon(r, power, rng, thin, kind, c->list, &tr)) {
+            delete c;
+            return nullptr;
+        }
+        c->ns.push_back(uint32_t(c->list.surface.size() - s0));
+        c->nv.push_back(uint32_t(c->list.volume.size() - v0));
+        c->nrows.push_back(uint32_t((c->verts.size() - r0) / CHAIN_ROW));
+        c->sig.push_back(mix64(tr.sig ^ (uint64_t(c->ns.back()) << 32 | c->nv.back())));
+    }
+    return c;
+}
+void orc_photon_chains_free(orc_photon_chains_t* c) { delete c; }
+// totals[3]: surface records, volume records, rows
+void orc_photon_chains_totals(orc_photon_chains_t* c, uint64_t* totals) {
+    totals[0] = c->list.surface.size(); totals[1] = c->list.volume.size(); totals[2] = c->verts.size() / CHAIN_ROW;
+}
+void orc_photon_chains_get(orc_photon_chains_t* c, uint32_t* ns, uint32_t* nv, uint32_t* nrows, uint64_t* sig, double* surface, double* volume,
+                           double* verts) {
+    std::copy(c->ns.begin(), c->ns.end(), ns);
+    std::copy(c->nv.begin(), c->nv.end(), nv);
+    std::copy(c->nrows.begin(), c->nrows.end(), nrows);
+    std::copy(c->sig.begin(), c->sig.end(), sig);
+    std::copy(c->verts.begin(), c->verts.end(), verts);
+    for (int which = 0; which < 2; which++) {
+        const std::vector<Photon>& v = which == 0 ? c->list.surface : c->list.volume;
+        double* out = which == 0 ? surface : volume;
+        const bool beam = which == 1 && c->kind == PK_BEAM_BEAM;
+        for (size_t i = 0; i < v.size(); i++) {
+            double* o = out + i * 10;
+            const V3& dd = beam ? v[i].starting_position : v[i].direction;
+            o[0] = v[i].position.x; o[1] = v[i].position.y; o[2] = v[i].position.z;
+            o[3] = dd.x; o[4] = dd.y; o[5] = dd.z;
+            o[6] = v[i].power.x; o[7] = v[i].power.y; o[8] = v[i].power.z;
+            o[9] = 0.0;
+        }
+    }
+}
 // Test hook: the maps of PhotonMap::new (src/photon.rs:181-311) over photon lists handed in -- n * 10 doubles each, laid out as
 // orc_photon_map_get writes them (position, direction or start of the beam, power, unused) -- instead of lists this oracle shot: lets
 // a camera pass be compared on the very photons of another implementation's shooting pass.

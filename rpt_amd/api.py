@@ -1840,6 +1840,16 @@ class Renderer:
         _lib.check(_lib.load().rpt_debug_photon_positions64(self.scene._handle, out.ctypes.data_as(C.c_void_p), n))
         return out
 
+    def photon_chain_counts(self, n):
+        """Test hook (scene option "photon_keep_counts" = 1): (surface, volume) record counts of the n photons of the last shooting
+        pass, u32, in shooting order."""
+        out = []
+        for which in (0, 1):
+            a = np.zeros(int(n), dtype=np.uint32)
+            _lib.check(_lib.load().rpt_debug_photon_chain_counts(self.scene._handle, which, a.ctypes.data_as(C.c_void_p), int(n)))
+            out.append(a)
+        return out[0], out[1]
+
     def photon_selections(self):
         """Reference-epsilon mode, test hook: the last camera pass's per-sample selections, (pixel slots, gather_size + 2, samples) u32."""
         lib = _lib.load()

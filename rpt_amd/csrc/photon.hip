@@ -2081,6 +2081,9 @@ struct PhotonMapDev {
     PoolMem<double> d_slab64;
     uint64_t emit_dims[3] = {0, 0, 0};   // of the last slice: owned pixel slots, gather_size + 2, samples
     int shoot_blocks = 0, surf64_blocks = 0;   // grids of the last shooting pass and of the last fp64 surface pass (rpt_photon_map_stats)
+    // scene option "photon_keep_counts": the last shooting pass's records per photon (rpt_debug_photon_chain_counts)
+    PoolMem<uint32_t> kept_cnt_s, kept_cnt_v;
+    uint64_t n_kept = 0;
     void release_raw() {
         raw_s.reset();
         raw_v.reset();
@@ -2283,6 +2286,9 @@ static int shoot_range(rpt_scene* s, PhotonMapDev* pm, uint64_t photon_count, ui
     }
     pm->release_raw();
     pm->pos64.reset();
+    pm->kept_cnt_s.reset();
+    pm->kept_cnt_v.reset();
+    pm->n_kept = 0;
     if (n == 0) return RPT_OK;
     PoolMem<uint32_t> cnt_s, cnt_v, off_s, off_v;
     PoolMem<unsigned long long> queue, d_tot;
@@ -2345,6 +2351,11 @@ static int shoot_range(rpt_scene* s, PhotonMapDev* pm, uint64_t photon_count, ui
         uint32_t mismatch = 0;
         RPTI_HIP_TRY(hipMemcpy(&mismatch, d_mismatch.get(), 4, hipMemcpyDeviceToHost));
         if (mismatch) return rpti::fail(RPT_ERR_DEVICE, "photon shooting: write pass did not retrace the count pass");
+    }
+    if (s->opt.photon_keep_counts) {
+        pm->kept_cnt_s = std::move(cnt_s);
+        pm->kept_cnt_v = std::move(cnt_v);
+        pm->n_kept = n;
     }
     return RPT_OK;
 }
@@ -2685,6 +2696,17 @@ int rpt_debug_photon_positions64(rpt_scene* s, double* out, uint64_t capacity) {
     if (pm->surf.n && !pm->pos64.get()) return rpti::fail(RPT_ERR_STATE, "this photon map was not shot in the reference-epsilon mode");
     if (capacity < pm->surf.n) return rpti::fail(RPT_ERR_INVALID, "output buffer too small");
     if (pm->surf.n) RPTI_HIP_TRY(hipMemcpy(out, pm->pos64.get(), size_t(pm->surf.n) * 24u, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+int rpt_debug_photon_chain_counts(rpt_scene* s, int32_t which, uint32_t* out, uint64_t capacity) {
+    if (!s || !out) return rpti::fail(RPT_ERR_INVALID, "null argument");
+    if (which != 0 && which != 1) return rpti::fail(RPT_ERR_INVALID, "which must be 0 (surface) or 1 (volume)");
+    auto* pm = static_cast<PhotonMapDev*>(s->photon);
+    if (!pm || !pm->n_kept) return rpti::fail(RPT_ERR_STATE, "no record counts kept: set the scene option photon_keep_counts before the shooting pass");
+    if (capacity < pm->n_kept) return rpti::fail(RPT_ERR_INVALID, "output buffer too small");
+    RPTI_HIP_TRY(hipSetDevice(pm->device));
+    RPTI_HIP_TRY(hipMemcpy(out, (which == 0 ? pm->kept_cnt_s : pm->kept_cnt_v).get(), size_t(pm->n_kept) * 4u, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 

@@ -75,6 +75,7 @@ static int set_option_in(rpt_options& o, const char* name, int64_t value) {
     else if (s == "photon_skip") o.photon_skip = value;
     else if (s == "photon_block_lists") o.photon_block_lists = value;
     else if (s == "photon_parts") o.photon_parts = value;
+    else if (s == "photon_keep_counts") { if (value < 0 || value > 1) return fail(RPT_ERR_INVALID, "photon_keep_counts must be 0 or 1"); o.photon_keep_counts = value; }
     else if (s == "photon_split") {
 #ifndef RPT_EXPERIMENTS
         if (value != 0) return fail(RPT_ERR_UNSUPPORTED, "photon_split: a rejected prototype, built with -DRPT_EXPERIMENTS only");

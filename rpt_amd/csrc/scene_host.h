@@ -32,6 +32,7 @@ struct rpt_options {
                                     // code, for every light whose twin is one range of scanned records (read by rpt_scene_commit; 0: the closest-hit scan)
     int64_t photon_skip = 0;
     int64_t photon_block_lists = 1;
+    int64_t photon_keep_counts = 0; // 1: the shooting pass's per-photon record counts outlive it (rpt_debug_photon_chain_counts; a test hook)
     int64_t photon_coop_gather = 1; // surface gather of a pixel's samples by the wave together (0: one search per lane)
     int64_t photon_split = 0;       // camera pass of the beam kinds in a medium: volume estimate and surface estimate as two launches (no scratch in
                                     // either, but 112 ms instead of 95 on C4: in one kernel the LDS-bound and the VALU-bound estimate overlap)

@@ -1,9 +1,11 @@
 """Photon mapping in the reference-epsilon mode (option "epsilon_policy" = 1): the shooting pass and the surface estimate's
 visibility rays run in fp64 with rpt's own epsilons (kernels_f64.hip: t_min = 1e-12, a gathered photon counts unless
 `len > hit.time`, src/photon.rs:357-361); maps, k-nearest selection and volume estimates are the fp32 machinery's.  Checked against
-the oracle's literal restatement (robust = 0).  The comparison is statistical where photon chains are concerned: whether a photon
-meets the surface it has just left again is decided by the last bits of its ray, and the device's libm and the host's differ there,
-so the two maps hold different photons wherever a chain met such a self-intersection."""
+the oracle's literal restatement (robust = 0).  On the Cornell-sized scenes of this module (coordinates up to 559) the comparison is
+statistical where photon chains are concerned: whether a photon meets the surface it has just left again is decided by the last bits
+of its ray (1e-14 x 559 exceeds the reference's 1e-12), and the device's libm and the host's differ there, so the two maps hold
+different photons wherever a chain met such a self-intersection.  On a room of unit extent nearly every chain is decided, and there
+the shooting pass is compared chain by chain: tests/test_gpu_photon_chains.py (the rule: tests/photon_chain_ref.py)."""
 import json
 import os
 
