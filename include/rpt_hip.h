@@ -829,7 +829,14 @@ int rpt_photon_map_build(rpt_scene*, uint64_t photon_count, int32_t kind, double
  *      (the gathered ones; they are read, not kept).  Invalidates the pointers of step 2.
  * The records may be any photons.  The volume map of kinds RPT_PHOTON_MAP and RPT_PHOTON_POINT_BEAM is searched with a stack of 64
  * pending nodes per lane: a map whose k-nearest tree has more than 64 inner nodes on a path (thousands of coincident photons next
- * to far outliers; a shot map has about 15) is refused with RPT_ERR_UNSUPPORTED, the depth in the message -- by both builds. */
+ * to far outliers; a shot map has about 15) is refused with RPT_ERR_UNSUPPORTED, the depth in the message -- by both builds.
+ * A record is twelve floats.  Surface records, and volume records of kinds RPT_PHOTON_MAP and RPT_PHOTON_POINT_BEAM:
+ *   position xyz, 0;  direction xyz, 0;  power rgb, 0     (the build of kind 1 computes each volume photon's gather radius itself).
+ * Volume records of kind RPT_PHOTON_BEAM_BEAM are beams:
+ *   end xyz, radius;  start xyz, 0;  power rgb, 0
+ * The beam's radius is read from the record: the camera pass uses it for the beam's own box and for the kernel's support (the shooting
+ * pass writes the reference's constant 3 there, src/photon.rs:250-305).  Degenerate beams behave as in the reference: one of length 0
+ * has no box and adds nothing; one whose line passes exactly through the eye makes every pixel NaN whose ray hits its box. */
 #define RPT_PHOTON_RECORD_BYTES 48
 int rpt_photon_shoot(rpt_scene*, uint64_t photon_count, int32_t kind, double watts, uint64_t seed,
                      uint32_t shard_rank, uint32_t shard_count, uint64_t n_out[2]);

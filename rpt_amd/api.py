@@ -1816,7 +1816,9 @@ class Renderer:
         return int(ptr.value or 0), int(n.value)
 
     def photon_map_from_records(self, photon_count, kind, d_surface, n_surface, d_volume, n_volume):
-        """rpt_photon_map_from_records: build the maps from (gathered) device record arrays."""
+        """rpt_photon_map_from_records: build the maps from (gathered) device record arrays of 48 bytes per record: position, 0;
+        direction, 0; power, 0 -- the volume records of kind 2 (beam x beam) are end, radius; start, 0; power, 0, and the beam's
+        radius is read from the record."""
         h = self.scene._commit(self.device_)
         _lib.check(_lib.load().rpt_photon_map_from_records(h, int(photon_count), int(kind), C.c_void_p(d_surface),
                                                            int(n_surface), C.c_void_p(d_volume), int(n_volume)))

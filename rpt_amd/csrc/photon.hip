@@ -1069,7 +1069,8 @@ RPT_DEV V volume_estimate_sample_lanes(QueryK q, bool active, V ro, V rd, bool h
         const V bc = fma3(beam_t, bdir, bstart);
         const V dq = qc - bc;
         const float dist = sqrt1(dot(dq, dq));
-        const bool ok = !(hit && tq >= t) && beam_t >= 0.f && beam_t <= beam_len && dist < radius;
+        // (the reference's tests are rejections: a NaN -- a beam whose line holds the eye, l x b = 0 -- passes them all and is added)
+        const bool ok = !(hit && tq >= t) && !(beam_t < 0.f || beam_t > beam_len) && !(dist >= radius);
         if (ok) {
             c_acc++;
             const float inv_sin = rsq(fmaxf(0.f, 1.f - dd * dd));
@@ -1081,8 +1082,10 @@ RPT_DEV V volume_estimate_sample_lanes(QueryK q, bool active, V ro, V rd, bool h
     };
     if (KIND == RPT_PHOTON_BEAM_BEAM) {
         if (!beam_walk_packet<false>(q.v_nodes, q.v_ph, q.n_v, active, ro, rd, wstack, stage, q.overflow,
-                                     [](const PhotonRec& ph, const V&) { return ph; }, visit_beam))
+                                     [](const PhotonRec& ph, const V&) { return ph; }, visit_beam)) {
+            diag_add(q.r.counters, 20, 1ull);
             beam_walk_batch(q.v_nodes, q.v_ph, q.n_v, active, ro, rd, wstack, stage, q.overflow, prep_none, visit_beam);
+        }
     } else {
         if (!beam_walk_packet<true>(q.v_nodes, q.v_ph, q.n_v, active, ro, rd, wstack, stage, q.overflow, prep_packet, visit_packet))
             beam_walk_batch(q.v_nodes, q.v_ph, q.n_v, active, ro, rd, wstack, stage, q.overflow, prep_point, visit);
@@ -1958,7 +1961,8 @@ __global__ __launch_bounds__(256, RPT_MIN_WAVES_QUERY) void photon_query_kernel(
     // Diagnostic counters (counters build; added where they occur, diag_add): [0] camera samples, [5] / [6] photon spheres visited /
     // accepted; the wave-level surface gather: [8] trips with a gather, [9] photon terms without a visibility scan, [10] steps of
     // the ball walks, [11] candidates, [12] overfull walks, [13] / [14] selection steps / list updates, [15] / [16] candidates looked
-    // at / photon terms of the second pass, [17] new anchors, [18] / [19] trips / lanes that searched one by one; [23] trips in which
+    // at / photon terms of the second pass, [17] new anchors, [18] / [19] trips / lanes that searched one by one; [20] trips of the
+    // beam x beam estimate whose rays formed no packet (lanes with different origins: a thin lens) and took beam_walk_batch; [23] trips in which
     // two layouts of the wave's LDS region were live at once (must stay 0); [24..33] clock
     // ticks (100 MHz) per part of a pixel, summed over the waves.
 }

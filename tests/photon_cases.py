@@ -9,12 +9,18 @@ Scenes (y is up; every surface is Lambertian; the camera is a pinhole):
   B   a closed room [-2, 2] x [0, 4] x [-2, 2] of six polygons with an inner cube, the camera inside: the room shell;
   C   A with the floor as a `plane`;
   D   a bumpy_torus(40, 24) mesh over the floor of A: the mesh has a tree, the BVH kernel flavours run;
-  Am, Bm   A and B in a homogeneous isotropic medium.
+  E   A with the veil of `veil_triangles()` between the eye and the floor (used as Ed);
+  L   A seen through a thin lens (aperture 0.1, focused on the origin): the samples of a pixel start at different points (used as Lm);
+  Am, Bm   A and B in a homogeneous isotropic medium;
+  Ad, Wd   A and W in a denser one (sigma_t = 0.14): the sampled distance of the point x point estimate (mean 7) falls before the
+           first hit (4 to 6 away) for about half of the pixels; in the fog of Am (sigma_t = 0.07, mean 14) it rarely does.
 
 `family(name)` is a Case: scene, gather size K, surface and volume photon lists ((n, 10): position, direction, power, 0) and the
 frames ((width, height, sample), ...) it is rendered at.  The surface families: control, few-*, dense, duplicates, pairs, line, outlier,
 far, visibility, room, K-*, plane, torus, deep.  The volume families (beam x point map, kind 1): v-control, v-room, v-n1 .. v-n9,
-v-coincident, v-behind, v-camera, v-block; `deep_volume()` is the deep comb as volume photons.  `radii_sets()` are position sets that
+v-coincident, v-behind, v-camera, v-block; `deep_volume()` is the deep comb as volume photons.  The families of the other two kinds of map carry their kind (`Case.kind`): p-* are
+point x point maps (kind 0, volume gather size `Case.Kv`), b-* beam x beam maps (kind 2), whose volume list is (n, 10): end, start,
+power, radius and whose records come from `beam_records`.  `radii_sets()` are position sets that
 only go through the 10-NN radius kernel.  `restated(name)` / `answers(name, w, h, sample)` compute a family's reference once per process.
 
 `tree_depth(positions)` emulates the map build far enough to count the inner nodes on the deepest path of the k-nearest tree:
@@ -23,6 +29,7 @@ import functools
 
 import numpy as np
 
+from tests.photon_ref import word_uniform
 from rpt_amd import Camera, Material, Medium, Mesh, Object, Scene, cube, plane, polygon, scenes, vec3
 
 LEAF_MAX = 8            # kKnnLeaf
@@ -33,6 +40,9 @@ FLOOR = 2.0
 WALL_X, WALL_HALF = 0.3, 0.01
 CUBE_AT, CUBE_SIZE = np.array([0.6, 0.4, -0.5]), 0.8
 FOG = (0.02, 0.05)
+FOG_DENSE = (0.04, 0.1)
+EYE = np.array([0.0, 2.5, 4.5])      # the camera of every scene but B
+ORACLE_BEAM_RADIUS = 3.0             # the reference's constant: only beams of this radius can be pinned to the oracle
 
 
 def f32(a):
@@ -62,7 +72,7 @@ def scene(name):
     floor_m = Material.diffuse(vec3(0.75, 0.6, 0.45))
     grey = Material.diffuse(vec3(0.5, 0.55, 0.6))
     lamp = Material.light(vec3(1.0, 1.0, 1.0), 10.0)
-    base = name.rstrip("m")
+    base = name.rstrip("md")
     if base == "B":
         s, h = FLOOR, 4.0
         mid = (0.0, 2.0, 0.0)
@@ -82,13 +92,19 @@ def scene(name):
             sc.add(Object(_floor()).material(floor_m))
         if base == "W":
             sc.add(Object(cube().scale(vec3(2.0 * WALL_HALF, 1.0, 2.0)).translate(vec3(WALL_X, 0.5, 0.0))).material(grey))
+        if base == "E":
+            sc.add(Object(Mesh(veil_triangles())).material(grey))
         if base == "D":
             mesh = Mesh(scenes.bumpy_torus(40, 24))
             sc.add(Object(mesh.scale(vec3(2.0, 2.0, 2.0)).translate(vec3(0.0, 0.5, 0.0))).material(grey))
         sc.add((_light(3.0), lamp))
         cam = Camera.look_at(vec3(0.0, 2.5, 4.5), vec3(0.0, 0.0, 0.0), vec3(0.0, 1.0, 0.0), 0.55)
+        if base == "L":
+            cam.focus(vec3(0.0, 0.0, 0.0), 0.1)
     if name.endswith("m"):
         sc.add(Medium.homogeneous_isotropic(*FOG))
+    if name.endswith("d"):
+        sc.add(Medium.homogeneous_isotropic(*FOG_DENSE))
     return sc, cam
 
 
@@ -116,6 +132,24 @@ def records(ph):
     ph = np.asarray(ph, dtype=np.float64).reshape(-1, 10)
     out = np.zeros((len(ph), 12), dtype=np.float32)
     out[:, 0:3], out[:, 4:7], out[:, 8:11] = ph[:, 0:3], ph[:, 3:6], ph[:, 6:9]
+    return out
+
+
+def beams(start, end, radius, rng, power=None):
+    """(n, 10) beam list: end, start, power in [0.1, 1]^3 (seeded), radius; all rounded to fp32."""
+    start, end = np.asarray(start, dtype=np.float64).reshape(-1, 3), np.asarray(end, dtype=np.float64).reshape(-1, 3)
+    n = len(start)
+    out = np.zeros((n, 10))
+    out[:, :3], out[:, 3:6], out[:, 9] = end, start, radius
+    out[:, 6:9] = rng.uniform(0.1, 1.0, (n, 3)) if power is None else power
+    return f32(out)
+
+
+def beam_records(bm):
+    """The library's 48-byte records of a beam list: (n, 12) float32 (end, radius; start, 0; power, 0)."""
+    bm = np.asarray(bm, dtype=np.float64).reshape(-1, 10)
+    out = np.zeros((len(bm), 12), dtype=np.float32)
+    out[:, 0:3], out[:, 3], out[:, 4:7], out[:, 8:11] = bm[:, 0:3], bm[:, 9], bm[:, 3:6], bm[:, 6:9]
     return out
 
 
@@ -192,14 +226,17 @@ def tree_depth(pos, leaf_max=LEAF_MAX):
 
 # ------------------------------------------------------------------ families
 class Case:
-    def __init__(self, name, scene_name, K, surface, volume=None, frames=((24, 24, 0),), note=""):
-        self.name, self.scene_name, self.K = name, scene_name, K
+    def __init__(self, name, scene_name, K, surface, volume=None, frames=((24, 24, 0),), note="", kind=1, Kv=3):
+        self.name, self.scene_name, self.K, self.kind, self.Kv = name, scene_name, K, kind, Kv
         self.surface = np.asarray(surface, dtype=np.float64).reshape(-1, 10)
         self.volume = np.zeros((0, 10)) if volume is None else np.asarray(volume, dtype=np.float64).reshape(-1, 10)
         self.frames, self.note = tuple(frames), note
 
     def scene(self):
         return scene(self.scene_name)
+
+    def volume_records(self):
+        return beam_records(self.volume) if self.kind == 2 else records(self.volume)
 
 
 K0 = 12
@@ -325,9 +362,199 @@ def _volume_families():
     return fam
 
 
+# ------------------------------------------------------------------ point x point maps (kind 0) and beam x beam maps (kind 2)
+PIXEL_FRAME = (24, 24, 0)            # the frame whose camera rays the per-pixel constructions below are made for
+VEIL_STEP = 2                        # the veil of scene "Ed" stands before every second pixel
+
+
+@functools.lru_cache(maxsize=None)
+def _pixel_rays(scene_name="Am"):
+    from oracle.pyoracle import camera_rays
+    cam = scene(scene_name)[1]
+    w, h, s = PIXEL_FRAME
+    r = camera_rays(cam, w, h, sample=s, seed=0)
+    return r["o"], r["d"], r["next_word"]
+
+
+def _frame_of(d):
+    """Two unit vectors that complete each direction d to a right-handed orthogonal frame."""
+    a = np.where(np.abs(d[:, 1:2]) < 0.9, [[0.0, 1.0, 0.0]], [[1.0, 0.0, 0.0]])
+    e1 = np.cross(d, a)
+    e1 /= np.linalg.norm(e1, axis=1, keepdims=True)
+    return e1, np.cross(d, e1)
+
+
+def veil_triangles():
+    """One small triangle per chosen pixel of PIXEL_FRAME, facing the eye at the very distance the pixel's sample draws in the dense
+    fog, 0.4 pixel wide: the point x point estimate's branch d < t is undecided there on purpose.  -> (n, 6, 3)."""
+    o, d, word = _pixel_rays()
+    dist = -np.log(word_uniform(word)) / (FOG_DENSE[0] + FOG_DENSE[1])
+    pix = np.arange(0, len(o), VEIL_STEP)
+    # (not nearer than 1: a triangle 0.4 pixel wide a few thousandths from the eye is a handful of fp32 steps across at these
+    # coordinates -- the fp32 mesh is then another triangle than the fp64 one)
+    pix = pix[(dist[pix] >= 1.0) & (dist[pix] < 8.0)]
+    cam = scene("Am")[1]
+    size = 0.4 * np.tan(0.5 * cam.fov) / PIXEL_FRAME[0] * dist[pix]
+    e1, e2 = _frame_of(d[pix])
+    c = o[pix] + dist[pix, None] * d[pix]
+    tri = np.zeros((len(pix), 6, 3))
+    for k, a in enumerate((0.5, 0.5 + 2.0 / 3.0, 0.5 + 4.0 / 3.0)):
+        tri[:, k] = c + size[:, None] * (np.cos(np.pi * a) * e1 + np.sin(np.pi * a) * e2)
+        tri[:, 3 + k] = -d[pix]
+    return tri
+
+
+def _bb_point(o, d, start, end):
+    """The beam x beam estimate's geometry for one ray and one beam -> tq, beam_t, dist (src/photon.rs:503-593)."""
+    b = (end - start) / np.linalg.norm(end - start)
+    l = start - o
+    u = np.cross(l, b)
+    u /= np.linalg.norm(u)
+    n = np.cross(b, u)
+    n /= np.linalg.norm(n)
+    tq = (n @ l) / (n @ d)
+    qc = o + tq * d
+    bt = b @ (qc - start)
+    return tq, bt, np.linalg.norm(qc - (start + bt * b))
+
+
+def _point_families():
+    fam = []
+    rng = np.random.default_rng(4401)
+    floor = photons(lattice(rng, 20, 20), rng)
+    K, KV = 8, 8
+
+    def add(name, vol, scene_name="Ad", Kv=KV, frames=(PIXEL_FRAME,), note=""):
+        fam.append(Case(name, scene_name, K, floor, vol, frames=frames, note=note, kind=0, Kv=Kv))
+
+    rng = np.random.default_rng(4402)
+    g = np.stack(np.meshgrid(np.linspace(-1.8, 1.8, 12), np.linspace(0.2, 2.6, 8), np.linspace(-1.8, 2.5, 12), indexing="ij"), axis=-1).reshape(-1, 3)
+    control = photons(g + rng.uniform(-0.1, 0.1, g.shape), rng)
+    add("p-control", control, frames=BOTH, note="a jittered 3-D lattice in the fogged scene")
+    spread = control[::120]
+    for n in (0, 1, KV - 1, KV, KV + 1):
+        add(f"p-n{n}", spread[:n], note="an empty map gives 0 / 0 in the volume branch")
+    add("p-coincident", np.repeat(control[500:501], KV, axis=0), note="K coincident photons are the whole map: every distance ties")
+    sites = control[7::97][:6]
+    ties = [control[::3]] + [np.repeat(sites[i:i + 1], m, axis=0) for i, m in enumerate((2, 2, KV, KV, 3 * KV, 3 * KV))]
+    add("p-ties", np.concatenate(ties), note="groups of 2, K and 3K identical records: ties at the K-th distance")
+    for kv in (1, 56, 57, 100):
+        add(f"p-K{kv}", control, Kv=kv, note="57: the first gather with its lists in global memory")
+    rng = np.random.default_rng(4403)
+    ball = rng.normal(size=(1000, 3))
+    ball = np.array([0.3, 1.2, 1.0]) + 0.03 * ball / np.linalg.norm(ball, axis=1, keepdims=True) * rng.uniform(0.0, 1.0, (1000, 1)) ** (1.0 / 3.0)
+    add("p-clump", photons(np.concatenate([ball, control[::6, :3], [[1.0e4, 0.0, 0.0]]]), rng), note="a dense clump, a sparse lattice and one photon at 1e4")
+    rng = np.random.default_rng(4404)
+    wall = np.stack([WALL_X + rng.choice([-1.0, 1.0], 800) * rng.uniform(WALL_HALF + 0.002, 0.08, 800), rng.uniform(0.05, 0.95, 800),
+                     rng.uniform(-0.9, 0.9, 800)], axis=1)
+    add("p-wall", photons(np.concatenate([wall, control[::4, :3]]), rng), scene_name="Wd", note="photons on both sides of the thin wall: the volume gather has no visibility test")
+    rng = np.random.default_rng(4405)
+    behind = np.stack([rng.uniform(-1.0, 1.0, 300), rng.uniform(2.0, 3.5, 300), rng.uniform(4.6, 6.0, 300)], axis=1)
+    add("p-behind", photons(np.concatenate([behind, control[::4, :3]]), rng), note="photons behind the eye")
+    rng = np.random.default_rng(4406)
+    add("p-deep16", _comb_photons(rng, 16), note="the comb with 16 origin copies: 64 inner nodes on the deepest path, the deepest tree the walk holds")
+    add("p-edge", control, scene_name="Ed", note="a veil of triangles at the sampled distances: the branch d < t is undecided on purpose")
+    return fam
+
+
+def _beam_families():
+    fam = []
+    rng = np.random.default_rng(4501)
+    floor = photons(lattice(rng, 20, 20), rng)
+    K, R3 = 8, ORACLE_BEAM_RADIUS
+
+    def add(name, bm, frames=(PIXEL_FRAME,), note="", scene_name="Am"):
+        fam.append(Case(name, scene_name, K, floor, bm, frames=frames, note=note, kind=2))
+
+    rng = np.random.default_rng(4502)
+    n = 300
+    start = np.array([0.0, 3.0, 0.0]) + rng.uniform(-0.25, 0.25, (n, 3)) * [1.0, 0.0, 1.0]
+    dirs = rng.normal(size=(n, 3))
+    dirs[:, 1] = -np.abs(dirs[:, 1])
+    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+    end = start + dirs * rng.uniform(0.5, 3.0, (n, 1))
+    control = beams(start, end, R3, rng)
+    add("b-control", control, frames=BOTH, note="beams of the oracle's radius from under the light")
+    thin = control.copy()
+    thin[:, 9] = f32(rng.uniform(0.05, 0.3, n))
+    add("b-thin", thin, frames=BOTH, note="radii 0.05 .. 0.3 from the record: against the restatement only")
+    add("b-lens", control[:120], scene_name="Lm", note="a thin lens: with several samples per pixel the lanes' rays share no origin, "
+        "form no packet and take beam_walk_batch")
+    add("b-n0", control[:0])
+    add("b-n1", control[:1])
+    some = control[:60]
+    o, d, _ = _pixel_rays()
+    e1, e2 = _frame_of(d)
+    rng = np.random.default_rng(4503)
+    pix = rng.choice(len(o), 16, replace=False)
+    depth = rng.uniform(2.0, 4.0, 16)
+    on_ray = o[pix] + depth[:, None] * d[pix]
+    first = np.arange(16) < 8
+    s_ = np.where(first[:, None], on_ray, on_ray - 0.8 * e1[pix])
+    e_ = np.where(first[:, None], on_ray + 0.8 * e1[pix], on_ray)
+    add("b-ends", np.concatenate([beams(s_, e_, R3, rng), some]), note="beams that start (8) or end (8) on a pixel's own ray: beam_t at 0 and at the length")
+    rng = np.random.default_rng(4504)
+    pix = rng.choice(len(o), 12, replace=False)
+    s_, e_ = np.zeros((12, 3)), np.zeros((12, 3))
+    for i, p in enumerate(pix):
+        at = o[p] + rng.uniform(2.0, 4.0) * d[p]
+        lo_a, hi_a = 0.0, 6.0
+        for _ in range(80):                                  # the offset at which the reference's own dist equals the radius
+            mid = 0.5 * (lo_a + hi_a)
+            c = at + mid * e1[p]
+            if _bb_point(o[p], d[p], c - 2.0 * e2[p], c + 2.0 * e2[p])[2] < R3:
+                lo_a = mid
+            else:
+                hi_a = mid
+        c = at + lo_a * e1[p]
+        s_[i], e_[i] = c - 2.0 * e2[p], c + 2.0 * e2[p]
+    add("b-tangent", np.concatenate([beams(s_, e_, R3, rng), some]), note="beams at the radius from a pixel's own ray")
+    rng = np.random.default_rng(4505)
+
+    def seg(n, y0, y1):
+        a = np.stack([rng.uniform(-1.5, 1.5, n), rng.uniform(*y0, n), rng.uniform(-1.5, 1.5, n)], axis=1)
+        b = np.stack([a[:, 0] + rng.uniform(-0.8, 0.8, n), rng.uniform(*y1, n), a[:, 2] + rng.uniform(-0.8, 0.8, n)], axis=1)
+        return a, b
+
+    parts = [seg(60, (-1.5, -0.2), (-1.5, -0.2)), seg(60, (0.2, 0.8), (-0.8, -0.2)), seg(60, (0.3, 1.5), (0.3, 1.5))]
+    add("b-hit", beams(np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]), R3, rng),
+        note="beams beyond, across and in front of the floor")
+    rng = np.random.default_rng(4506)
+
+    def short(n, zlo, zhi):
+        a = np.stack([rng.uniform(-1.0, 1.0, n), rng.uniform(1.5, 3.5, n), rng.uniform(zlo, zhi, n)], axis=1)
+        v = rng.normal(size=(n, 3))
+        return a, a + v / np.linalg.norm(v, axis=1, keepdims=True) * rng.uniform(0.5, 1.0, (n, 1))
+
+    near, far = short(40, 4.8, 6.5), short(40, 9.5, 12.0)
+    add("b-behind", np.concatenate([beams(near[0], near[1], R3, rng), beams(far[0], far[1], R3, rng), some]),
+        note="beams behind the eye: 40 whose box holds the eye or reaches the forward ray, 40 whose box lies wholly behind")
+    rng = np.random.default_rng(4507)
+    axis = (np.zeros(3) - EYE) / np.linalg.norm(EYE)
+    pix = rng.choice(len(o), 9, replace=False)
+    s_, e_ = [], []
+    for i, ang in enumerate((1e-3, 1e-2, 1e-1) * 3 + (1e-3, 1e-2, 1e-1)):
+        dv = d[pix[i]] if i < 9 else axis
+        f1, f2 = _frame_of(dv[None])
+        b = dv + ang * f1[0]
+        at = EYE + 2.0 * dv + 0.1 * f2[0]
+        s_.append(at)
+        e_.append(at + 1.5 * b / np.linalg.norm(b))
+    add("b-parallel", np.concatenate([beams(s_, e_, R3, rng), some]), note="beams 1e-3, 1e-2 and 1e-1 rad from a pixel's ray (9) and from the view axis (3)")
+    rng = np.random.default_rng(4508)
+    a = np.stack([rng.uniform(-1.5, 1.5, 60), rng.uniform(0.2, 2.5, 60), rng.uniform(-1.5, 1.5, 60)], axis=1)
+    b = a.copy()
+    b[np.arange(60), np.arange(60) % 3] += rng.choice([-1.0, 1.0], 60) * rng.uniform(0.5, 2.0, 60)
+    add("b-axis", beams(a, b, R3, rng), note="axis-aligned beams: a box without extent beyond the ends, exact zeros in its widening")
+    add("b-long", np.concatenate([beams([[-500.0, 1.5, 0.3]], [[500.0, 1.2, -0.2]], R3, rng), control[:80]]), note="one beam of length 1000 among short ones")
+    add("b-len0", np.concatenate([beams([[0.2, 1.0, 0.5]], [[0.2, 1.0, 0.5]], R3, rng), some]), note="a beam of length 0")
+    add("b-eye", np.concatenate([beams([EYE + [0.0, 0.0, -2.0]], [EYE + [0.0, 0.0, -4.0]], R3, rng), some]), note="a beam whose line passes exactly through the eye")
+    return fam
+
+
 @functools.lru_cache(maxsize=None)
 def _families():
-    return {c.name: c for c in _surface_families() + _volume_families()}
+    return {c.name: c for c in _surface_families() + _volume_families() + _point_families() + _beam_families()}
 
 
 def family(name):
@@ -338,14 +565,20 @@ SURFACE_NAMES = ("control", "few-0", "few-1", "few-5", "few-11", "few-12", "dens
                  "visibility", "room", "K-1", "K-56", "K-57", "K-200", "plane", "torus", "deep")
 VOLUME_NAMES = ("v-control", "v-room") + tuple(f"v-n{n}" for n in range(1, 10)) + ("v-coincident", "v-behind", "v-camera", "v-block")
 NAMES = SURFACE_NAMES + VOLUME_NAMES
-UNDECIDED_ON_PURPOSE = ("pairs",)
+POINT_NAMES = ("p-control", "p-n0", "p-n1", "p-n7", "p-n8", "p-n9", "p-coincident", "p-ties", "p-K1", "p-K56", "p-K57", "p-K100", "p-clump",
+               "p-wall", "p-behind", "p-deep16", "p-edge")
+BEAM_NAMES = ("b-control", "b-thin", "b-lens", "b-n0", "b-n1", "b-ends", "b-tangent", "b-hit", "b-behind", "b-parallel", "b-axis", "b-long",
+              "b-len0", "b-eye")
+BEAM_NOT_PINNED = ("b-thin",)        # radii other than the oracle's constant
+UNDECIDED_ON_PURPOSE = ("pairs", "p-edge")
 
 
 @functools.lru_cache(maxsize=None)
-def deep_volume():
-    """The deep comb as volume photons (with a few floor photons): the radii and the point x point gather must be right or refused."""
+def deep_volume(kind=1):
+    """The deep comb as volume photons (with a few floor photons): the radii and the point x point gather must be right or refused.
+    kind 0: the same lists as a point x point map ("p-deep72" to `restated` and `answers`)."""
     rng = np.random.default_rng(4301)
-    return Case("v-deep", "Am", 8, photons(lattice(rng, 10, 10), rng), _comb_photons(rng))
+    return Case("v-deep" if kind == 1 else "p-deep72", "Am", 8, photons(lattice(rng, 10, 10), rng), _comb_photons(rng), kind=kind, Kv=3)
 
 
 @functools.lru_cache(maxsize=None)
@@ -362,9 +595,9 @@ def radii_sets():
 @functools.lru_cache(maxsize=None)
 def restated(name):
     from tests.photon_ref import Restated
-    c = deep_volume() if name == "v-deep" else family(name)
+    c = deep_volume() if name == "v-deep" else deep_volume(0) if name == "p-deep72" else family(name)
     sc, cam = c.scene()
-    return Restated(sc, cam, c.surface, c.volume, c.K)
+    return Restated(sc, cam, c.surface, c.volume, c.K, c.kind, c.Kv)
 
 
 @functools.lru_cache(maxsize=None)

@@ -45,6 +45,61 @@ beam_estimate_photon_lanes, volume_estimate_sample_lanes), stated here before an
             the unit direction); 6 u for r_i^2 (4 u from the radius kernel's distance, sqrt, the square, rcp); n_i contributing photons.
             The photon-per-lane form replaces exp(-sigma_t s) by exp(-sigma_t |c|) (1 + sigma_t (|c| - s)) and states "to fp32
             precision" (|c| - s <= r^2 / |c|): the model takes it at its word and has no term for it.
+
+The other two kinds of map (`Restated(kind=0)` and `Restated(kind=2)`; kind 1 above is unchanged).  Both are restated literally from
+the reference's loops, src/photon.rs:384-438 and :503-593, one camera ray at a time.
+
+  point x point (kind 0, RPT_PHOTON_MAP), in a medium: the sampled distance d = -ln(xi) / sigma_t, xi the uniform of the sample's own
+            stream right after the camera's draws (`camera_rays`' next_word; Medium::sample_d, the host test proves the stream and the
+            draw).  When d < t, or nothing is hit:
+              colour_medium * phase * sum_j P_j / ((4/3) pi r^3) / sigma_t * T(d) / (sigma_t T(d)),     T(s) = exp(-sigma_t s)
+            j over the `gather_size_volume` volume photons nearest to x = o + d dir (all of them when the map holds fewer), r the
+            largest of their distances; no visibility test.  Otherwise the surface estimate above times T(t) / T(d).  An empty
+            volume map gives 0 / 0.
+  beam x beam (kind 2, RPT_PHOTON_BEAM_BEAM): the volume list holds (end, start, power, radius).  Per beam, in the reference's
+            order: it is looked at only when the ray hits the beam's own box (min/max of the two ends, widened per axis by
+            radius * sqrt of the other two squared extents over their sum; t_far >= max(t_near, 0)) -- the only test that keeps
+            a beam behind the eye out; with b = unit(end - start), l = start - o, u = unit(l x b), n = unit(b x u):
+            tq = (n . l) / (n . d), left out when the ray hits and tq >= t; beam_t = b . (o + tq d - start), left out when
+            beam_t < 0 or beam_t > |end - start|; dist = |o + tq d - (start + beam_t b)|, left out when dist >= radius; else
+              sigma_t colour_medium P phase / sqrt(max(0, 1 - (d . b)^2)) T(tq) T(beam_t) (3 / pi) (1 - dist / radius)^2 / (2 radius)
+            and the surface estimate times T(t) is added as for kind 1.  The radius is the record's (the reference's is the
+            constant 3).  A comparison with NaN lets the beam through, as the reference's negated tests do.
+
+The cloud of a kind-0 ray also moves the sampled distance: member c uses d + A_d s_c, s_c = clamp(off_x + off_y + off_z, -1, 1) and
+A_d = FOG_K u max(1, -ln xi) / sigma_t, the bound that tests/test_gpu_device_samplers.py::test_medium_distance_matches_oracle states for
+-__logf(xi) / sigma_t (FOG_K = 8.32); the query point x = o + d dir is moved by AMP (1 + max|x|) off like a hit point, and the branch is
+taken with the moved d against the moved t.  Signatures gain: the branch and the multiset of the selected volume payloads (kind 0; in
+the volume branch the hit object is not part of it), the set of contributing beams (kind 2).
+
+The fp32 bounds of the two estimates, stated before any device value was looked at (photon.hip: gather_knn and the scale line of
+photon_query_kernel<..., RPT_PHOTON_MAP>; visit_beam in volume_estimate_sample_lanes):
+
+  point x point, volume branch   B_pp = |V| (Kv + 24) u
+            Kv u for the sum of Kv non-negative powers; 8 u for r^3 = max_d2 sqrt(max_d2) (4 u on a squared distance as above, times
+            3/2, sqrt, one product); 3 u for rcp((4/3) pi r^3) (the constant, the product, rcp); 2 u for rcp(sigma_t); 3 u for
+            T(d) rcp(sigma_t T(d)) -- __expf's own error cancels, both factors hold the same tr_d --; 5 u for the phase constant and
+            the four products of the scale line; 3 u for colour_medium, sum * colour and scale * (...).  Where x lies is the cloud's.
+            Ties: photons whose squared distance from x lies within 8 u (relative) of the K-th's cannot be told apart from it in
+            fp32 (the 4 u of each squared distance); when such a photon stays outside the selection the sum may hold any n of the
+            band in place of the n it holds here: B_pp grows by scale * (the largest change of the band's sum of powers, per
+            channel) and by 12 u |V| for r^3.  p-deep16 has such a band: 16 origin copies and two comb teeth 0.03 and 0.06 fp32
+            ulp nearer to a query 4.5 away.
+  point x point, surface branch  B_ps = B_s / T(d) + |V| (E_EXP max(1, sigma_t d) + 3 u)
+            B_s the surface bound above (T(t) included); __expf(-sigma_t d): E_EXP while the argument is below 1, growing with the
+            argument (its rounding and that of the product with log2 e are relative to it); rcp and two products.
+  beam x beam   B_bb = sum_i A_i [2 tmp_i dtmp_i + dtmp_i^2 + tmp_i^2 R_i]  +  |V_b| (n_i + 8) u,      A_i = term_i / tmp_i^2
+            L = |l|, h = |n . l| (the eye's distance from the beam's line), g = |qc - start|, qc = o + tq d:
+            eps_n  = 8 u (1 + L / h)            direction error of u and n: l x b cancels down to a vector of length h
+            dtq    = (L (eps_n + 3 u) + |tq| (eps_n + 3 u)) / |n . d| + 2 u |tq|        numerator, denominator, rcp and product
+            dqc    = dtq + 2 u (max|o| + |tq|)                                          fma3(tq, rd, ro)
+            dbt    = dqc + 8 u g                       beam_t: b carries 4 u (sqrt, rcp, product), the difference and the dot 4 u
+            ddist  = dqc + dbt + 4 u |beam_t| + u max|start| + 2 u dist                 bc = fma3(beam_t, b, start), |qc - bc|
+            dtmp_i = ddist / radius + 3 u                                               rcp(radius), product, 1 - ...
+            R_i    = sigma_t (dtq + dbt) + E_EXP (max(1, sigma_t |tq|) + max(1, sigma_t |beam_t|)) + 8 u / (1 - (d . b)^2) + 16 u
+            the two __expf as above; 1 - dd^2 cancels near parallel: dd carries 6 u absolute (b's 4 u, the dot), 1 - dd^2 twice
+            that plus its own roundings, rsq halves the relative error: at most 8 u / (1 - dd^2); 16 u for rsq, rcp(2 radius),
+            3 / pi, sigma_t, phase and the nine products of the weight line.
 """
 import itertools
 
@@ -57,6 +112,8 @@ U = 2.0 ** -24
 E_COS, E_BSDF, E_EXP = 1e-6, 1e-6, 2e-6
 N_SEEDED = 6
 KNN_RADIUS = 10
+TIE_POOL = 64           # how far beyond the K-th nearest a band of indistinguishable distances is followed
+FOG_K = 2 * 4.16        # tests/test_gpu_device_samplers.py: |dmed sigma_t + ln xi| <= FOG_K u max(1, -ln xi)
 
 
 def _offsets():
@@ -67,6 +124,12 @@ def _offsets():
 OFFS = _offsets()
 OFFS_MORE = np.concatenate([np.array([c for c in itertools.product((-1.0, 0.0, 1.0), repeat=3) if any(c)]),
                             np.random.default_rng(12).uniform(-1.0, 1.0, (32, 3))])
+
+
+def word_uniform(word):
+    """The oracle's uniform of one generator word: (2k + 1) 2^-24, k the word's top 23 bits (in (0, 1), exact in fp32)."""
+    w = np.asarray(word).astype(np.uint64)
+    return (((w >> np.uint64(9)) << np.uint64(1)) | np.uint64(1)).astype(np.float64) * 2.0 ** -24
 
 
 def knn_radii(pos, k=KNN_RADIUS):
@@ -84,11 +147,11 @@ def knn_radii(pos, k=KNN_RADIUS):
     return out
 
 
-def _payload_weights(ph, seed):
+def _payload_weights(ph, seed, cols=9):
     """One random 64-bit weight per distinct (position, direction, power): identical records share theirs."""
     if len(ph) == 0:
         return np.zeros(0, dtype=np.uint64)
-    _, inv = np.unique(ph[:, :9], axis=0, return_inverse=True)
+    _, inv = np.unique(ph[:, :cols], axis=0, return_inverse=True)
     inv = np.asarray(inv).reshape(-1)
     return np.random.default_rng(seed).integers(1, 2 ** 62, int(inv.max()) + 1, dtype=np.uint64)[inv]
 
@@ -134,12 +197,15 @@ class Answers:
 
 
 class Restated:
-    """The camera pass over the photon lists `surface` and `volume` ((n, 10): position, direction, power, -) in `scene`, gather size K."""
+    """The camera pass over the photon lists `surface` and `volume` ((n, 10): position, direction, power, -) in `scene`, gather size K.
+    kind: the PhotonRenderKind of the map -- 1 beam x point (the default), 0 point x point with the volume gather size Kv, 2 beam x
+    beam, whose volume list is (n, 10): end, start, power, radius."""
 
-    def __init__(self, scene, camera, surface, volume, K):
+    def __init__(self, scene, camera, surface, volume, K, kind=1, Kv=3):
         from oracle.pyoracle import OracleScene
         from rpt_amd import Material, Medium, hex_color
-        self.scene, self.camera, self.K = scene, camera, int(K)
+        self.scene, self.camera, self.K, self.kind, self.Kv = scene, camera, int(K), int(kind), int(Kv)
+        assert self.kind in (0, 1, 2)
         self.osc = OracleScene(scene)
         self.ps = np.ascontiguousarray(surface, dtype=np.float64).reshape(-1, 10)
         self.pv = np.ascontiguousarray(volume, dtype=np.float64).reshape(-1, 10)
@@ -151,8 +217,8 @@ class Restated:
             self.sigma_t = self.medium.absorption + self.medium.scattering
             self.phase = 1.0 / (4.0 * np.pi)
             self.mcol = np.asarray(hex_color(0xD2B48C), dtype=np.float64)
-        self.radius = knn_radii(self.pv[:, :3])
-        self.w_s, self.w_v = _payload_weights(self.ps, 5), _payload_weights(self.pv, 6)
+        self.radius = knn_radii(self.pv[:, :3]) if self.kind == 1 else self.pv[:, 9].copy()
+        self.w_s, self.w_v = _payload_weights(self.ps, 5), _payload_weights(self.pv, 6, 10 if self.kind == 2 else 9)
         self.albedo = np.array([o.material_.color() for o in scene.objects], dtype=np.float64).reshape(-1, 3)
         self.emission = np.array([o.material_.emittance() * np.asarray(o.material_.color()) for o in scene.objects], dtype=np.float64).reshape(-1, 3)
 
@@ -244,14 +310,139 @@ class Restated:
             sig[sl] = (ok * w_v[None, :]).sum(axis=1, dtype=np.uint64)
         return val, bound, sig
 
-    def evaluate(self, o, d, shift=None):
+    def _point_point(self, o, d, shift, dist, t, obj, nrm):
+        """Point x point estimate (kind 0 in a medium), src/photon.rs:384-438: the volume gather at o + dist d when dist < t or
+        nothing is hit, else the surface estimate times T(t) / T(dist)."""
+        q, m = len(o), len(self.pv)
+        hit = obj >= 0
+        dist = np.asarray(dist, dtype=np.float64).reshape(q)
+        moved = np.zeros(q, dtype=bool) if shift is None else (shift != 0).any(axis=1)
+        tt = np.where(hit, t, np.inf)
+        xs = o + np.where(hit, t, 0.0)[:, None] * d
+        if shift is not None:
+            xs = xs + (AMP * (1.0 + np.abs(xs).max(axis=1)))[:, None] * shift
+            tt = np.where(hit & moved, np.sqrt(((xs - o) ** 2).sum(axis=1)), tt)
+        vol = ~hit | (dist < tt)
+        val, bound, sig = np.zeros((q, 3)), np.zeros((q, 3)), np.zeros(q, dtype=np.uint64)
+        Td = np.exp(-self.sigma_t * dist)
+        rows = np.flatnonzero(vol)
+        if len(rows):
+            x = o[rows] + dist[rows, None] * d[rows]
+            if shift is not None:
+                x = x + (AMP * (1.0 + np.abs(x).max(axis=1)))[:, None] * shift[rows]
+            k = min(self.Kv, m)
+            if k == 0:
+                sum_p, r2, s = np.zeros((len(rows), 3)), np.zeros(len(rows)), np.zeros(len(rows), dtype=np.uint64)
+                tie = np.zeros((len(rows), 3))
+            else:
+                more = min(m, k + TIE_POOL)
+                sel, d2 = _nearest(self.pv[:, :3], x, more)
+                POW = self.pv[:, 6:9][sel]                                  # (q, more, 3) in the order (distance, index)
+                sum_p, r2, s = POW[:, :k].sum(axis=1), d2[:, k - 1], self.w_v[sel[:, :k]].sum(axis=1, dtype=np.uint64)
+                # photons whose squared distance is within 8 u of the K-th's cannot be told apart from it in fp32 (4 u each): the
+                # device's sum may hold any n_in of that band; per channel the largest and the smallest such sum
+                inside = np.arange(more)[None, :] < k
+                band = np.abs(d2 - r2[:, None]) <= 8.0 * U * r2[:, None]
+                n_in = (band & inside).sum(axis=1)
+                cur = np.where((band & inside)[..., None], POW, 0.0).sum(axis=1)
+                hi_p = -np.sort(np.where(band[..., None], -POW, 0.0), axis=1)        # descending, zeros last
+                lo_p = np.sort(np.where(band[..., None], POW, np.inf), axis=1)        # ascending, inf last
+                take = (np.arange(more)[None, :] < n_in[:, None])[..., None]
+                tie = np.maximum(np.where(take, hi_p, 0.0).sum(axis=1) - cur, cur - np.where(take, lo_p, 0.0).sum(axis=1))
+                tie = np.where((band & ~inside).any(axis=1)[:, None], tie, 0.0)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                scale = self.mcol * self.phase / ((4.0 / 3.0) * np.pi * r2 ** 1.5)[:, None] / self.sigma_t
+                scale = scale * Td[rows, None] / (self.sigma_t * Td[rows])[:, None]
+                v = sum_p * scale
+                b = np.abs(v) * ((k + 24) * U) + scale * tie + np.where(tie.any(axis=1), 12.0 * U, 0.0)[:, None] * np.abs(v)
+            val[rows], bound[rows] = v, np.where(np.isfinite(b), b, 0.0)
+            sig[rows] = np.uint64(0xD1B54A32D192ED03) + s * np.uint64(7)
+        rows = np.flatnonzero(~vol)
+        if len(rows):
+            wo = -d[rows] / np.sqrt((d[rows] ** 2).sum(axis=1))[:, None]
+            v, b, s = self._surface(xs[rows], nrm[rows], wo, obj[rows], tt[rows])
+            with np.errstate(divide="ignore", invalid="ignore"):
+                v = v / Td[rows, None]
+                b = b / Td[rows, None] + np.abs(v) * (E_EXP * np.maximum(1.0, self.sigma_t * dist[rows]) + 3.0 * U)[:, None]
+            val[rows], bound[rows] = v, np.where(np.isfinite(b), b, 0.0)
+            sig[rows] = (obj[rows].astype(np.int64) + 2).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15) + s
+        return val, bound, sig
+
+    def _beam_beam(self, o, d, hit, t):
+        """Beam x beam estimate along the rays (o, d), cut at t where `hit`: src/photon.rs:503-593 over the beams whose own box the ray
+        hits (impl Bounded for PhotonBeam, :74-104), the radius from the record."""
+        q, m = len(o), len(self.pv)
+        val, bound, sig = np.zeros((q, 3)), np.zeros((q, 3)), np.zeros(q, dtype=np.uint64)
+        if m == 0 or self.medium is None:
+            return val, bound, sig
+        E, S, POW, R = self.pv[:, 0:3], self.pv[:, 3:6], self.pv[:, 6:9], self.pv[:, 9]
+        omax = np.abs(o).max(axis=1)
+        smax = np.abs(S).max(axis=1)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            bvec = E - S
+            blen = np.sqrt((bvec ** 2).sum(axis=1))
+            bdir = bvec / blen[:, None]
+            c = (S - E) ** 2
+            tot = c[:, 0] + c[:, 1] + c[:, 2]
+            adj = np.sqrt(np.stack([c[:, 1] + c[:, 2], c[:, 0] + c[:, 2], c[:, 0] + c[:, 1]], axis=1) / tot[:, None]) * R[:, None]
+            lo, hi = np.minimum(S, E) - adj, np.maximum(S, E) + adj
+
+            def unit(v):
+                return v / np.sqrt((v ** 2).sum(axis=2))[..., None]
+
+            step = max(1, (1 << 18) // m)
+            for i0 in range(0, q, step):
+                sl = slice(i0, i0 + step)
+                oo, dd = o[sl, None, :], d[sl, None, :]
+                a1, a2 = (lo[None] - oo) / dd, (hi[None] - oo) / dd
+                tn = np.fmax(np.fmax(np.fmin(a1, a2)[..., 0], np.fmin(a1, a2)[..., 1]), np.fmin(a1, a2)[..., 2])
+                tf = np.fmin(np.fmin(np.fmax(a1, a2)[..., 0], np.fmax(a1, a2)[..., 1]), np.fmax(a1, a2)[..., 2])
+                box = tf >= np.fmax(tn, 0.0)
+                l = S[None] - oo
+                bd = np.broadcast_to(bdir[None], l.shape)
+                u = unit(np.cross(l, bd))
+                n = unit(np.cross(bd, u))
+                nl, nd = (n * l).sum(axis=2), (n * dd).sum(axis=2)
+                tq = nl / nd
+                qc = oo + tq[..., None] * dd
+                dot_db = (dd * bd).sum(axis=2)
+                inv_sin = 1.0 / np.sqrt(np.maximum(0.0, 1.0 - dot_db * dot_db))
+                rel = qc - S[None]
+                beam_t = (bd * rel).sum(axis=2)
+                dq = qc - (S[None] + beam_t[..., None] * bd)
+                dist = np.sqrt((dq ** 2).sum(axis=2))
+                ok = box & ~(hit[sl, None] & (tq >= t[sl, None])) & ~((beam_t < 0.0) | (beam_t > blen[None])) & ~(dist >= R[None])
+                tmp = 1.0 - dist / R[None]
+                A = (self.sigma_t * self.phase * inv_sin * np.exp(-self.sigma_t * tq) * np.exp(-self.sigma_t * beam_t) * (3.0 / np.pi)
+                     / (2.0 * R[None]))
+                w = np.where(ok, A * tmp * tmp, 0.0)
+                val[sl] = (w[..., None] * POW[None]).sum(axis=1) * self.mcol
+                L, h, g = np.sqrt((l ** 2).sum(axis=2)), np.abs(nl), np.sqrt((rel ** 2).sum(axis=2))
+                eps_n = 8.0 * U * (1.0 + L / h)
+                dtq = (L * (eps_n + 3.0 * U) + np.abs(tq) * (eps_n + 3.0 * U)) / np.abs(nd) + 2.0 * U * np.abs(tq)
+                dqc = dtq + 2.0 * U * (omax[sl, None] + np.abs(tq))
+                dbt = dqc + 8.0 * U * g
+                ddist = dqc + dbt + 4.0 * U * np.abs(beam_t) + U * smax[None] + 2.0 * U * dist
+                dtmp = ddist / R[None] + 3.0 * U
+                rr = (self.sigma_t * (dtq + dbt) + E_EXP * (np.maximum(1.0, self.sigma_t * np.abs(tq)) + np.maximum(1.0, self.sigma_t * np.abs(beam_t)))
+                      + 8.0 * U / (1.0 - dot_db * dot_db) + 16.0 * U)
+                wb = np.where(ok, np.abs(A) * (2.0 * np.abs(tmp) * dtmp + dtmp * dtmp + tmp * tmp * rr), 0.0)
+                b = (wb[..., None] * POW[None]).sum(axis=1) * self.mcol + np.abs(val[sl]) * ((ok.sum(axis=1) + 8) * U)[:, None]
+                bound[sl] = np.where(np.isfinite(b), b, 0.0)
+                sig[sl] = (ok * self.w_v[None, :]).sum(axis=1, dtype=np.uint64)
+        return val, bound, sig
+
+    def evaluate(self, o, d, shift=None, dist=None):
         """photon_estimate_indirect for the rays (o, d), each on its own; shift: (q, 3) displacement of the hit point in units of
-        AMP (1 + max|x|) (the cloud) -> value (q, 3), fp32 bound (q, 3), decision signature (q,)."""
+        AMP (1 + max|x|) (the cloud); dist (q,): the sampled medium distances of a kind-0 map, the cloud's move included
+        -> value (q, 3), fp32 bound (q, 3), decision signature (q,)."""
         o = np.ascontiguousarray(o, dtype=np.float64).reshape(-1, 3)
         d = np.ascontiguousarray(d, dtype=np.float64).reshape(-1, 3)
         q = len(o)
         t, obj, nrm = self.osc.intersect(o, d, robust=1)
         hit = obj >= 0
+        if self.kind == 0 and self.medium is not None:
+            return self._point_point(o, d, shift, dist, t, obj, nrm)
         val, bound = np.zeros((q, 3)), np.zeros((q, 3))
         sig = (obj.astype(np.int64) + 2).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
         rows = np.flatnonzero(hit)
@@ -271,7 +462,7 @@ class Restated:
             if len(miss):
                 val[miss] = self.osc.env_color(d[miss])
         else:
-            v, b, s = self._beam(o, d, hit, tt)
+            v, b, s = self._beam(o, d, hit, tt) if self.kind == 1 else self._beam_beam(o, d, hit, tt)
             val, bound = val + v, bound + b
             sig += s * np.uint64(7)
         return val, bound, sig
@@ -282,24 +473,36 @@ class Restated:
         r = camera_rays(self.camera, width, height, sample=sample, seed=seed)
         return r["o"], r["d"]
 
-    def _cloud(self, o, d, offs):
+    def distances(self, width, height, sample, seed=0):
+        """Medium::sample_d of every pixel's sample `sample` -> the distance (n,), its cloud amplitude A_d (n,): the uniform is the
+        stream's next draw after the camera's, (2k + 1) 2^-24 with k the word's top 23 bits."""
+        from oracle.pyoracle import camera_rays
+        mlog = -np.log(word_uniform(camera_rays(self.camera, width, height, sample=sample, seed=seed)["next_word"]))
+        return mlog / self.sigma_t, FOG_K * U * np.maximum(1.0, mlog) / self.sigma_t
+
+    def _cloud(self, o, d, offs, dist=None, amp_d=None):
         n, C = len(o), len(offs)
         oo = np.repeat(o, C, axis=0)
         dd = np.repeat(d, C, axis=0) + AMP * np.tile(offs, (n, 1))
         nz = np.tile((offs != 0).any(axis=1), n)
         dd[~nz] = np.repeat(d, C, axis=0)[~nz]                       # (the ray itself, bit for bit)
         dd[nz] /= np.sqrt((dd[nz] ** 2).sum(axis=1))[:, None]
-        val, bound, sig = self.evaluate(oo, dd, np.tile(offs, (n, 1)))
+        if dist is None:
+            val, bound, sig = self.evaluate(oo, dd, np.tile(offs, (n, 1)))
+        else:
+            ds = np.repeat(dist, C) + np.repeat(amp_d, C) * np.tile(np.clip(offs.sum(axis=1), -1.0, 1.0), n)
+            val, bound, sig = self.evaluate(oo, dd, np.tile(offs, (n, 1)), ds)
         return val.reshape(n, C, 3), bound.reshape(n, C, 3), sig.reshape(n, C)
 
     def sample(self, width, height, sample, seed=0):
         """Sample `sample` of every pixel -> Answers."""
         o, d = self.rays(width, height, sample, seed)
-        val, bound, sig = self._cloud(o, d, OFFS)
+        dist, amp_d = self.distances(width, height, sample, seed) if self.kind == 0 and self.medium is not None else (None, None)
+        val, bound, sig = self._cloud(o, d, OFFS, dist, amp_d)
         again = np.flatnonzero((sig != sig[:, :1]).any(axis=1))
         if len(again) == 0:
             return Answers(val, bound, sig)
-        v2, b2, s2 = self._cloud(o[again], d[again], OFFS_MORE)
+        v2, b2, s2 = self._cloud(o[again], d[again], OFFS_MORE, None if dist is None else dist[again], None if dist is None else amp_d[again])
         return Answers(val, bound, sig, again, np.concatenate([val[again], v2], axis=1), np.concatenate([bound[again], b2], axis=1),
                        np.concatenate([sig[again], s2], axis=1))
 
