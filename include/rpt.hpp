@@ -867,6 +867,30 @@ class Renderer {
         return out;
     }
 
+    // Moving spheres (rpt_hip.h, rpt_scene_set_movable_spheres; the committed scene is this renderer's, so the calls live here and not in
+    // Scene, which stays a description): `objects` are indices into scene.objects of spheres under translate(c) * scale(r, r, r).
+    // move_spheres: host centres (and offsets added to them, or none), synchronous; returns the motion table (scene.objects.size()
+    // x 24 doubles, identity for the objects that are not listed) when asked for one.  move_spheres_device: centres, offsets and
+    // motion table in device memory, asynchronous on hip_stream and ordered like a render of the scene.
+    void set_movable_spheres(const std::vector<uint32_t>& objects) {
+        commit();
+        check(rpt_scene_set_movable_spheres(handle_, objects.data(), uint32_t(objects.size())));
+    }
+    std::vector<double> move_spheres(const std::vector<Vec3>& centres, const std::vector<Vec3>* offsets = nullptr, bool motion = false) {
+        commit();
+        std::array<uint64_t, 8> info{};
+        check(rpt_scene_movable_info(handle_, info.data()));
+        if (centres.size() != info[1] || (offsets && offsets->size() != info[1])) throw Error("move_spheres: one centre (and offset) per movable sphere");
+        std::vector<double> table(motion ? scene_.objects.size() * 24 : 0);
+        check(rpt_scene_move_spheres(handle_, centres.empty() ? nullptr : centres[0].data(), offsets && !offsets->empty() ? (*offsets)[0].data() : nullptr,
+                                     motion ? table.data() : nullptr));
+        return table;
+    }
+    void move_spheres_device(const void* d_centres, const void* d_offsets = nullptr, void* d_motion = nullptr, void* hip_stream = nullptr) {
+        commit();
+        check(rpt_scene_move_spheres_device(handle_, d_centres, d_offsets, d_motion, hip_stream));
+    }
+
   private:
     void commit() {
         if (handle_) return;
@@ -1023,6 +1047,12 @@ class ParticleSimulator {
         check(rpt_particles_display_positions(h_, out[0].data()));
         return out;
     }
+    // The same positions left in the simulator's own device array (n x 3 doubles): asynchronous, ordered like integrate.
+    void* display_positions_device(void* hip_stream = nullptr) const {
+        void* d = nullptr;
+        check(rpt_particles_display_positions_device(h_, &d, hip_stream));
+        return d;
+    }
     std::array<uint64_t, 8> counters() const {
         std::array<uint64_t, 8> c{};
         check(rpt_particles_counters(h_, c.data()));
@@ -1082,6 +1112,12 @@ class ParticleEnsemble {
         std::vector<std::vector<Vec3>> out;
         for (size_t i = 0; i < size(); i++) out.emplace_back(all.begin() + first_[i], all.begin() + first_[i + 1]);
         return out;
+    }
+    // ... left in the ensemble's own device array (sum(n) x 3 doubles, the systems concatenated): asynchronous, ordered like integrate.
+    void* display_positions_device(void* hip_stream = nullptr) const {
+        void* d = nullptr;
+        check(rpt_particles_batch_display_positions_device(h_, &d, hip_stream));
+        return d;
     }
     std::vector<std::array<uint64_t, 8>> counters() const {
         std::vector<std::array<uint64_t, 8>> c(size());

@@ -764,6 +764,10 @@ int rpt_particles_state(rpt_particles*, double* pos, double* vel);              
 int rpt_particles_state_device(rpt_particles*, void** d_pos, void** d_vel);                             /* the handle's own arrays */
 int rpt_particles_integrate(rpt_particles*, double time, double step, void* hip_stream);                /* asynchronous */
 int rpt_particles_display_positions(rpt_particles*, double* out /* host n*3 */);                        /* MARBLES only, synchronous */
+/* The same positions left on the device: asynchronous on hip_stream and ordered like rpt_particles_integrate (behind the handle's
+ * earlier calls, ahead of its later ones, whatever their streams).  *d_out is the handle's own array of n*3 doubles, valid until the
+ * handle is destroyed and rewritten by the next display call of either kind. */
+int rpt_particles_display_positions_device(rpt_particles*, void** d_out, void* hip_stream);             /* MARBLES only, asynchronous */
 int rpt_particles_counters(rpt_particles*, uint64_t out[8]);
 /* Pure host functions, no device is touched: the same text run serially. */
 int rpt_monomial_closest_point(double height, const double p[3], int precise, double out[3]);
@@ -805,8 +809,83 @@ int rpt_particles_batch_state(rpt_particles_batch*, double* pos, double* vel);  
 int rpt_particles_batch_state_device(rpt_particles_batch*, void** d_pos, void** d_vel, void** d_first /* uint32 first[n_systems] */);
 int rpt_particles_batch_integrate(rpt_particles_batch*, double time, double step, void* hip_stream);   /* asynchronous, one step sequence for all */
 int rpt_particles_batch_display_positions(rpt_particles_batch*, double* out /* host sum(n) x 3 */);    /* every system MARBLES, synchronous */
+int rpt_particles_batch_display_positions_device(rpt_particles_batch*, void** d_out /* sum(n) x 3, the batch's own */, void* hip_stream);   /* as rpt_particles_display_positions_device */
 int rpt_particles_batch_counters(rpt_particles_batch*, uint64_t* out /* n_systems x 8 */);
 int rpt_particles_batch_info(rpt_particles_batch*, uint64_t out[8]);
+
+/* ---- moving spheres: a committed scene updated on the device (an addition; the reference rebuilds its Scene for every frame) ----
+ * rpt_scene_commit makes a scene immutable with one exception: spheres whose transform is translate(c) * scale(r, r, r) can be moved to
+ * new centres that lie in device memory, in both render modes, in scenes that are scanned and in scenes with a scene tree.  The radius
+ * stays.  Out of scope: every other transform, cubes, meshes, monomial surfaces, lights, members of groups, a tree rebuild.
+ *
+ * The records of a moved sphere are DEFINED as the ones a fresh commit of the scene with the matrix (r 0 0 cx | 0 r 0 cy | 0 0 r cz | 0 0 0 1),
+ * every zero +0.0, would upload, bit for bit: XfScan, XfShade and the pbox entry of the fp32 path; ObjRec::inv, ObjShade::nrm and the
+ * CullBox of the reference-epsilon mode (and the cull32 box of its group of 32 records); the motion record is
+ * rpt_temporal_motion_record(cur, prev) of the two matrices, so a sphere moved onto its own place (c == prev, component by component:
+ * -0.0 equals 0.0) gets the exact identity record.  rpt_amd/csrc/scene_update_core.h states the operations; rpt_sphere_records_host
+ * runs them once on the host (any output may be NULL; motion needs prev_centre, and is RPT_ERR_INVALID where
+ * rpt_temporal_motion_record would refuse the pair): scan = XfScan (12 floats), shade = XfShade (12 floats, the object id r0.w left 0),
+ * item_box = the sphere's own world box as the scene tree's build received it (lo, hi), pbox = the pbox entry (8 floats), inv =
+ * ObjRec::inv, nrm = ObjShade::nrm, cull = the 32 bytes of its CullBox.
+ *
+ * rpt_scene_set_movable_spheres(scene, objects, n): after the commit; a second call replaces the list: it waits for a queued move,
+ * and every sphere the earlier list has moved stays where it is -- a sphere that is listed again moves on from there (that centre is
+ * the previous centre of its next motion record), one that is dropped keeps its moved records, and a refit bounds it where it is.
+ * `objects` are indices of scene objects in rpt_scene_add_object order.  Refusals, in this order: a null scene, or a null list with
+ * n > 0 (RPT_ERR_INVALID); a scene that is not committed (RPT_ERR_STATE); then for every entry in list order: an index that is not an
+ * object's, or one listed before (RPT_ERR_INVALID); a group (RPT_ERR_UNSUPPORTED); any other shape that is not a sphere
+ * (RPT_ERR_INVALID); the twin of a Light::Object (RPT_ERR_UNSUPPORTED: the light's sampler would stay behind); no transform, a non-zero
+ * off-diagonal in the linear part, a diagonal that is not one value r, an r that is not finite and > 0, a bottom row other than
+ * 0 0 0 1, a centre that is not finite, an r whose motion record has a zero or non-finite determinant (RPT_ERR_INVALID each);
+ * then a library built without the kernels (RPT_ERR_UNSUPPORTED); last, for a scene with a scene tree: a leaf of the tree that holds
+ * more than two listed spheres (RPT_ERR_UNSUPPORTED: the builder makes leaves of two items, and larger ones only where it finds no
+ * split, as for spheres that coincide; list fewer of them or commit with a larger "scene_bvh_min"), and a tree that is not the one the
+ * commit recorded -- a child that does not follow its parent, a leaf that is no primitive list, more than 32 heights, record counts
+ * that are not the scene's (RPT_ERR_STATE: none of these can happen to a scene this library committed).  rpt_last_error names the object.
+ * From this call on the scene reports no scan bound and no scan groups (rpt_scan_cull_counters, rpt_scan_cull_groups: lo[0] > hi[0],
+ * n_groups = 0): diagnostics of the counters build that a moved sphere would make stale.  The scan JIT's scene shape stays valid (the
+ * y-rotation bits of this matrix form do not depend on r or c).
+ *
+ * rpt_scene_move_spheres_device(scene, d_centres, d_offsets, d_motion, stream): asynchronous, ordered like a render of the scene --
+ * behind every pass of the scene queued before it, on `stream`, ahead of every pass issued later, whatever their streams (renders,
+ * feature passes, photon passes and every hook that takes the scene: each waits for the last move before its first launch).  The centre
+ * of listed sphere k becomes d_centres[k] (n x 3 doubles), or d_centres[k] + d_offsets[k], one rounded add per component.  With
+ * d_motion (n_objects x 24 doubles, which the caller has filled with identity records) the rows of the listed objects are written:
+ * the motion from the centre of the previous call (or of the commit) to the new one.  Centres that are not finite give records that
+ * are not: nothing on the device checks them.  A photon map built before the call is stale: rpt_photon_render_sample* is RPT_ERR_STATE
+ * until rpt_photon_map_build or rpt_photon_map_from_records has run again.  Refusals: null scene (RPT_ERR_INVALID); not committed, no
+ * list set (RPT_ERR_STATE); with n > 0: null d_centres (RPT_ERR_INVALID), built without the kernels (RPT_ERR_UNSUPPORTED).
+ * rpt_scene_move_spheres is the host-array variant: it uploads, moves on the null stream, synchronises and downloads `motion`
+ * (n_objects x 24, identity for the objects that are not listed).
+ *
+ * Scene tree (fp32 records, more than "scene_bvh_min" bounded records): the topology stays, the boxes are refitted bottom-up -- an
+ * entry's bounds are the union of the own boxes of the items below it, and its box is those bounds under the padding the commit's
+ * builder applies (1e-6 of the larger magnitude + 1e-30 per axis), so a move onto the committed centres reproduces the committed
+ * boxes.  A refitted tree finds the hits a fresh commit finds; it is not the tree a fresh commit would build, and its quality decays
+ * as the spheres travel ("Moving spheres"): a caller who sees that commits again.  Option "refit_per_height" = 1
+ * runs the refit as one launch per height instead of one workgroup (same boxes).
+ *
+ * rpt_scene_movable_info: out[0] = a list is set, 1 = its length, 2 = scene-tree nodes refitted per move, 3 = their heights, 4 = cull32
+ * groups recomputed per move, 5 = moves so far, 6 = bytes of the tables on the device, 7 = 1 in the reference-epsilon mode.
+ * rpt_debug_scene_records downloads one array an update touches (synchronous; it waits for the device): *bytes is its size, `out` may be
+ * NULL to ask for that alone.  The reference-epsilon arrays of a scene committed without the mode are RPT_ERR_STATE. */
+enum { RPT_SCENE_RECORDS_SPH = 0, RPT_SCENE_RECORDS_SPH_SHADE = 1, RPT_SCENE_RECORDS_PBOX = 2,
+       RPT_SCENE_RECORDS_TREE_NODES = 3,     /* the scene tree's two-box nodes, 64 bytes each (none: 0 bytes) */
+       RPT_SCENE_RECORDS_RECS = 4, RPT_SCENE_RECORDS_SHADE = 5, RPT_SCENE_RECORDS_CULL = 6, RPT_SCENE_RECORDS_CULL32 = 7,
+       RPT_SCENE_RECORDS_TREE_RAW = 8,       /* per node 16 floats: the unpadded bounds of its two entries (lo, -, hi, -) x 2; a list must be set */
+       RPT_SCENE_RECORDS_TREE_ENTRIES = 9,   /* per entry 32 bytes: fixed lo, a, fixed hi, b (a = 0xFFFFFFFE: the union of node b's entries; else the fixed
+                                                box united with movable spheres a and b, 0xFFFFFFFF = none) */
+       RPT_SCENE_RECORDS_TREE_ORDER = 10,    /* the scene tree's local node numbers by height, children before parents */
+       RPT_SCENE_RECORDS_ITEM_BOXES = 11,    /* per listed sphere 8 floats: its own box (lo, -, hi, -) */
+       RPT_SCENE_RECORDS_TABLE = 12 };       /* per listed sphere 48 bytes: sphere record, object, fp64 record, 0 (uint32 each); radius; centre[3] */
+int rpt_sphere_records_host(double radius, const double centre[3], const double prev_centre[3] /* or NULL */, float scan[12], float shade[12],
+                            float item_box[6], float pbox[8], double inv[12], double nrm[9], void* cull /* 32 bytes */, double motion[24]);
+int rpt_scene_set_movable_spheres(rpt_scene*, const uint32_t* objects, uint32_t n);
+int rpt_scene_move_spheres_device(rpt_scene*, const void* d_centres /* n x 3 doubles */, const void* d_offsets /* n x 3 doubles or NULL */,
+                                  void* d_motion /* n_objects x 24 doubles or NULL */, void* hip_stream);
+int rpt_scene_move_spheres(rpt_scene*, const double* centres, const double* offsets_or_null, double* motion_or_null);
+int rpt_scene_movable_info(rpt_scene*, uint64_t out[8]);
+int rpt_debug_scene_records(rpt_scene*, uint32_t which, void* out, uint64_t capacity_bytes, uint64_t* bytes);
 
 /* ---- photon mapping (next tier: src/photon.rs; config C4 = photon_point_query_beam_render) ----
  * `enum PhotonRenderKind` (src/photon.rs:631-639): point-point (photon_map_render), beam-point

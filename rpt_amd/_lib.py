@@ -222,6 +222,14 @@ SYMBOLS = [
     ("rpt_particles_batch_display_positions", C.c_int, [_P, _P]),
     ("rpt_particles_batch_counters", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("rpt_particles_batch_info", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("rpt_particles_display_positions_device", C.c_int, [_P, C.POINTER(C.c_void_p), _P]),
+    ("rpt_particles_batch_display_positions_device", C.c_int, [_P, C.POINTER(C.c_void_p), _P]),
+    ("rpt_sphere_records_host", C.c_int, [C.c_double, _D3, _D3, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("rpt_scene_set_movable_spheres", C.c_int, [_P, _P, C.c_uint32]),
+    ("rpt_scene_move_spheres_device", C.c_int, [_P, _P, _P, _P, _P]),
+    ("rpt_scene_move_spheres", C.c_int, [_P, _P, _P, _P]),
+    ("rpt_scene_movable_info", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("rpt_debug_scene_records", C.c_int, [_P, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("rpt_monomial_closest_point", C.c_int, [C.c_double, _D3, C.c_int, _D3]),
     ("rpt_particles_derivative_host", C.c_int, [C.POINTER(ParticlesParams), _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
     ("rpt_particles_integrate_host", C.c_int, [C.POINTER(ParticlesParams), _P, _P, C.c_double, C.c_double, C.POINTER(C.c_uint64)]),

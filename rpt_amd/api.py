@@ -504,10 +504,72 @@ class Scene:
         _LIVE_SCENES.add(self)
         return h
 
+    # ---- moving spheres (rpt_hip.h, "moving spheres": an addition): the one change a committed scene takes
+    def set_movable_spheres(self, objects, device=0):
+        """rpt_scene_set_movable_spheres: `objects` are indices into self.objects of spheres under translate(c) * scale(r, r, r);
+        the scene is committed to `device` if it has not been.  A second call replaces the list.  self.objects keeps describing
+        the scene as it was committed."""
+        h = self._commit(self._device if self._handle is not None else device)
+        objects = np.ascontiguousarray(objects, dtype=np.uint32).reshape(-1)
+        _lib.check(_lib.load().rpt_scene_set_movable_spheres(h, _lib.vp(objects), len(objects)))
+        self._movable = objects.copy()
+        return self
+
+    def _movable_handle(self, what):
+        if self._handle is None or getattr(self, "_movable", None) is None:
+            raise RptError(f"{what}: set_movable_spheres must be called first")
+        return self._handle
+
+    def move_spheres(self, centres, offsets=None, motion=False):
+        """rpt_scene_move_spheres: listed sphere k moves to centres[k] (+ offsets[k], one rounded add per component); synchronous.
+        With motion=True returns the (len(self.objects), 24) motion table of the move: rpt_temporal_motion_record of each listed
+        sphere's new and previous matrix, identity for every other object."""
+        h = self._movable_handle("move_spheres")
+        n = len(self._movable)
+        centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1, 3)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1, 3)
+        if len(centres) != n or (offsets is not None and len(offsets) != n):
+            raise ValueError(f"move_spheres: {n} movable spheres, {len(centres)} centres")
+        table = np.zeros((len(self.objects), 24)) if motion else None
+        _lib.check(_lib.load().rpt_scene_move_spheres(h, _lib.vp(centres) if n else None, _lib.vp(offsets) if offsets is not None and n else None,
+                                                      _lib.vp(table) if motion and len(self.objects) else None))
+        return table
+
+    def move_spheres_device(self, d_centres, d_offsets=0, d_motion=0, stream_ptr=0):
+        """rpt_scene_move_spheres_device: centres (n x 3 doubles), offsets (or 0) and the motion table (len(self.objects) x 24
+        doubles that hold identity records, or 0) are device addresses; asynchronous on `stream_ptr` and ordered like a render of
+        the scene."""
+        h = self._movable_handle("move_spheres_device")
+        _lib.check(_lib.load().rpt_scene_move_spheres_device(h, C.c_void_p(d_centres or None), C.c_void_p(d_offsets or None), C.c_void_p(d_motion or None),
+                                                             C.c_void_p(stream_ptr or None)))
+
+    def movable_info(self):
+        """rpt_scene_movable_info as a dict."""
+        if self._handle is None:
+            raise RptError("movable_info: the scene is not committed")
+        out = (C.c_uint64 * 8)()
+        _lib.check(_lib.load().rpt_scene_movable_info(self._handle, out))
+        keys = ("set", "spheres", "tree_nodes", "tree_heights", "cull32_groups", "moves", "table_bytes", "epsilon")
+        return dict(zip(keys, (int(x) for x in out)))
+
+    def debug_records(self, which, dtype=np.uint8):
+        """rpt_debug_scene_records: one of the arrays an update touches (RPT_SCENE_RECORDS_*), downloaded, as a flat array of `dtype`."""
+        if self._handle is None:
+            raise RptError("debug_records: the scene is not committed")
+        lib = _lib.load()
+        n = C.c_uint64()
+        _lib.check(lib.rpt_debug_scene_records(self._handle, int(which), None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        if n.value:
+            _lib.check(lib.rpt_debug_scene_records(self._handle, int(which), _lib.vp(out), n.value, C.byref(n)))
+        return out.view(dtype)
+
     def close(self):
         if self._handle is not None:
             _lib.load().rpt_scene_destroy(self._handle)
             self._handle = None
+            self._movable = None
 
     def __del__(self):
         try:
@@ -1637,7 +1699,7 @@ class Renderer:
                 denoiser.close()
 
     def render_sequence(self, cameras, batches=4, temporal=None, denoise=None, scenes=None, adaptive=None, return_tile_batches=False,
-                        upsample=None, guide_samples=1):
+                        upsample=None, guide_samples=1, live=None):
         """An addition: a generator of one (h, w, 3) uint8 frame per camera of `cameras`, for a camera that moves over this scene
         or, with `scenes` (one Scene per camera, as the reference builds one per frame: the same number of objects with the same
         base shape kinds in the same order, else ValueError), over objects that move: frame f renders scenes[f], committed when its
@@ -1657,7 +1719,20 @@ class Renderer:
         ValueError): its low-resolution mean and variance are upsampled under the low-resolution planes of the same camera samples
         and the full-resolution planes of `guide_samples` samples, then accumulate_device, the optional filter and
         image_bytes_device run at full resolution, where the depth and normal planes and the motion table are.  Not together
-        with `adaptive` (ValueError)."""
+        with `adaptive` (ValueError).
+        With live=mover (not together with `scenes` or `upsample`: ValueError) the objects of this renderer's own scene move on the
+        device: mover.scene is this renderer's scene (else ValueError); before frame f > 0 the renderer calls mover.step(f), which moves the committed scene's spheres
+        (Scene.move_spheres_device) and returns the device address of the move's motion table, len(scene.objects) x 24 doubles
+        (or 0 for none), which goes to TemporalAccumulator.set_motion_device.  scenes.marbles_live builds such a mover; nothing is
+        read back and nothing is committed again."""
+        if live is not None:
+            if scenes is not None or upsample is not None:
+                raise ValueError("render_sequence: live is not combined with scenes or upsample")
+            if not callable(getattr(live, "step", None)):
+                raise ValueError("render_sequence: live must have a step(frame) method")
+            if getattr(live, "scene", None) is not self.scene:
+                raise ValueError("render_sequence: live.scene must be this renderer's scene (the mover moves what is rendered, and its "
+                                 "motion table has one row per object of that scene)")
         if upsample is not None:
             if not isinstance(upsample, UpsampleParams):
                 raise ValueError("render_sequence: upsample must be an UpsampleParams or None")
@@ -1699,9 +1774,9 @@ class Renderer:
                 raise ValueError("render_sequence: every scene must hold the same base shape kinds in the same order")
         if upsample is not None:
             return self._upsampled_sequence(cameras, batches, temporal or TemporalParams(), denoise, scenes, upsample, int(guide_samples))
-        return self._render_sequence(cameras, batches, temporal or TemporalParams(), denoise, scenes, adaptive, bool(return_tile_batches))
+        return self._render_sequence(cameras, batches, temporal or TemporalParams(), denoise, scenes, adaptive, bool(return_tile_batches), live)
 
-    def _render_sequence(self, cameras, batches, temporal, denoise, scenes=None, adaptive=None, return_tile_batches=False):
+    def _render_sequence(self, cameras, batches, temporal, denoise, scenes=None, adaptive=None, return_tile_batches=False, live=None):
         accumulator = TemporalAccumulator(self.width_, self.height_, self.device_)
         denoiser = Denoiser(self.width_, self.height_, self.device_) if denoise is not None else None
         n = self.width_ * self.height_ * 3
@@ -1719,6 +1794,10 @@ class Renderer:
                         accumulator.set_motion(np.stack([temporal_motion_record(c.shape.matrix(), p.shape.matrix())
                                                          for c, p in zip(scenes[f].objects, scenes[f - 1].objects)])
                                                if scenes[f].objects else None)
+                elif live is not None and f > 0:
+                    table = live.step(f)
+                    if table:
+                        accumulator.set_motion_device(table, len(self.scene.objects))
                 buffer = DeviceBuffer(self.width_, self.height_, None, self.device_)
                 counts = None
                 if adaptive is not None:

@@ -1942,6 +1942,7 @@ extern "C" int rpt_intersect_batch_f64(rpt_scene* s, uint64_t n, const double* o
     q.t = d_t.get<double>();
     q.obj = d_obj.get<int32_t>();
     q.nrm = d_nrm.get<double>();
+    if (int rc = rpti::wait_for_move(s, nullptr)) return rc;
     RPTI_HIP_TRY(rptg::launch_intersect_f64(q, nullptr));
     RPTI_HIP_TRY(hipMemcpy(t, d_t.get(), n * 8, hipMemcpyDeviceToHost));
     RPTI_HIP_TRY(hipMemcpy(object, d_obj.get(), n * 4, hipMemcpyDeviceToHost));
@@ -1959,6 +1960,7 @@ extern "C" int rpt_debug_light_sample_f64(rpt_scene* s, uint32_t light, uint64_t
     if (n == 0) return RPT_OK;
     if (n > 0xFFFFFFFFull) return rpti::fail(RPT_ERR_INVALID, "rpt_debug_light_sample_f64: the case number keys a 32-bit stream field");
     RPTI_HIP_TRY(hipSetDevice(s->device));
+    if (int rc = rpti::wait_for_move(s, nullptr)) return rc;   // (the hook launches on the null stream: behind the last move of the scene's spheres)
     rpti::DevMem d_pos, d_out;   // d_out: v, nrm, intensity, wi (3 n each), pdf, dist (n each), next_word (n dwords)
     RPTI_HIP_TRY(d_pos.reserve(n * 24));
     RPTI_HIP_TRY(d_out.reserve(n * (14 * 8 + 4)));
@@ -1993,6 +1995,7 @@ extern "C" int rpt_debug_env_color_f64(rpt_scene* s, uint64_t n, const double* d
     if (!s->dev.arena64) return rpti::fail(RPT_ERR_STATE, "rpt_debug_env_color_f64 needs a scene committed with epsilon_policy = 1");
     if (n == 0) return RPT_OK;
     RPTI_HIP_TRY(hipSetDevice(s->device));
+    if (int rc = rpti::wait_for_move(s, nullptr)) return rc;   // (the hook launches on the null stream: behind the last move of the scene's spheres)
     rpti::DevMem d_d, d_c;
     RPTI_HIP_TRY(d_d.reserve(n * 24));
     RPTI_HIP_TRY(d_c.reserve(n * 24));

@@ -2397,10 +2397,11 @@ static int photon_args_ok(rpt_scene* s, uint64_t photon_count, int32_t kind) {
     if (rpti::first_object_light(s) < 0)
         return rpti::fail(RPT_ERR_INVALID, "Only found non-object lights while photon mapping");  // the reference's panic
     RPTI_HIP_TRY(hipSetDevice(s->device));
-    return RPT_OK;
+    return rpti::wait_for_move(s, nullptr);   // (the shooting passes run on the null stream: behind the last move of the scene's spheres)
 }
 static PhotonMapDev* fresh_map(rpt_scene* s, uint64_t photon_count, int32_t kind) {
     void*& slot = s->photon;
+    s->photon_stale = false;   // the map under way is shot into the scene as it is now
     std::shared_ptr<DevPool> pool;
     if (slot) {
         // the old map's buffers go back to the pool and may be handed out at once: nothing may still be reading them
@@ -2531,6 +2532,9 @@ static int photon_render_impl(rpt_scene* s, const rpt_camera* cam, const rpt_ren
                               double* d_out, hipStream_t st, bool sync_counters, const EpsSlice* eps = nullptr) {
     auto* pm = s ? static_cast<PhotonMapDev*>(s->photon) : nullptr;
     if (!pm || !pm->built) return rpti::fail(RPT_ERR_STATE, "no photon map: call rpt_photon_map_build first");
+    if (s->photon_stale)
+        return rpti::fail(RPT_ERR_STATE, "the photon map is stale: the scene's spheres have moved since it was built (rpt_scene_move_spheres); rebuild the map "
+                                         "with rpt_photon_map_build or rpt_photon_map_from_records");
     const uint64_t gather_max = pm->kind == RPT_PHOTON_MAP ? std::max(gather_size, gather_size_volume) : gather_size;
     if (gather_max > kGatherMax) return rpti::fail(RPT_ERR_UNSUPPORTED, "gather sizes above 1024 are not supported");
     const bool gg = gather_max > kGatherLds;  // lists in global memory

@@ -112,6 +112,7 @@ static int set_option_in(rpt_options& o, const char* name, int64_t value) {
         o.denoise_stage = value;
     }
     else if (s == "scene_tree_meshes") o.scene_tree_meshes = value;
+    else if (s == "refit_per_height") { if (value < 0 || value > 1) return fail(RPT_ERR_INVALID, "refit_per_height must be 0 or 1"); o.refit_per_height = value; }
     else if (s == "scene_bvh_min") { if (value < 0) return fail(RPT_ERR_INVALID, "scene_bvh_min must be >= 0"); o.scene_bvh_min = value; }
     else return fail(RPT_ERR_INVALID, "unknown option: " + s);
     return RPT_OK;
@@ -528,6 +529,7 @@ static void release_device(rpt_scene* s) {
     s->dev = rpt_scene::Device{};
     if (s->photon) rpti::photon_release(s->photon);
     s->photon = nullptr;
+    s->photon_stale = false;
     s->committed = false;
     s->jit = rpti::ScanJit{};   // (the modules belong to the process, not to the scene)
 }
@@ -771,6 +773,9 @@ struct Flattener {
     std::vector<RectScan> rect;        // the scanned rectangles, sorted by axis
     std::vector<RectShade> rect_sh;    // ... their shade records, followed by shell_sh
     std::vector<uint32_t> pleaf;
+    // what a refit of the scene tree starts from (rpt_scene_set_movable_spheres): per entry of pleaf the box add_item received
+    // (lo, hi), and per child entry of every scene-tree node (2 x local node + side) the bounds of the items below it, unpadded
+    std::vector<float> pleaf_box, tree_raw;
     uint32_t top_root = 0;
     bool scene_bvh = false;
     bool mesh_deferred = false;   // the scene tree does not hold the meshes that have trees of their own
@@ -1303,9 +1308,27 @@ struct Flattener {
                     const uint32_t c0 = codes[items[c.left_or_first].idx];
                     if ((c0 >> 28) == K_BVHTRI) return meshes[c0 & 0x0FFFFFFFu].root;  // always alone in its leaf
                     const uint32_t first = uint32_t(pleaf.size());
-                    for (uint32_t i = 0; i < c.count; i++) pleaf.push_back(codes[items[c.left_or_first + i].idx]);
+                    for (uint32_t i = 0; i < c.count; i++) {
+                        const BTri& it = items[c.left_or_first + i];
+                        pleaf.push_back(codes[it.idx]);
+                        pleaf_box.insert(pleaf_box.end(), it.lo, it.lo + 3);
+                        pleaf_box.insert(pleaf_box.end(), it.hi, it.hi + 3);
+                    }
                     return BVH_LEAF | BVH_PRIMS | ((c.count - 1u) << 26) | first;
                 };
+                // the bounds of the items below every tmp node before BvhBuilder::build pads them (children follow their parents)
+                std::vector<PBox> raw(tmp.size());
+                for (size_t k = tmp.size(); k-- > 0;) {
+                    PBox& b = raw[k];
+                    for (int a = 0; a < 3; a++) { b.lo[a] = std::numeric_limits<float>::infinity(); b.hi[a] = -b.lo[a]; }
+                    const TmpNode& n = tmp[k];
+                    for (uint32_t i = 0; i < (n.count == 0 ? 2u : n.count); i++) {
+                        const float* lo = n.count == 0 ? raw[n.left_or_first + i].lo : items[n.left_or_first + i].lo;
+                        const float* hi = n.count == 0 ? raw[n.left_or_first + i].hi : items[n.left_or_first + i].hi;
+                        for (int a = 0; a < 3; a++) { b.lo[a] = std::min(b.lo[a], lo[a]); b.hi[a] = std::max(b.hi[a], hi[a]); }
+                    }
+                }
+                tree_raw.assign(size_t(n_inner) * 12, 0.f);
                 for (size_t k = 0; k < tmp.size(); k++) {
                     if (tmp[k].count != 0) continue;
                     BvhNode& w = local[remap[k]];
@@ -1317,6 +1340,10 @@ struct Flattener {
                     w.e0 = entry(l);
                     w.e1 = entry(l + 1);
                     w.pad0 = w.pad1 = 0;
+                    for (uint32_t side = 0; side < 2; side++) {
+                        float* r = &tree_raw[(size_t(remap[k]) * 2 + side) * 6];
+                        for (int a = 0; a < 3; a++) { r[a] = raw[l + side].lo[a]; r[3 + a] = raw[l + side].hi[a]; }
+                    }
                 }
                 nodes.insert(nodes.end(), local.begin(), local.end());
                 if (pleaf.size() >= BVH_INDEX_MASK) return fail(RPT_ERR_UNSUPPORTED, "too many primitives");
@@ -1636,6 +1663,8 @@ struct Flattener {
         }
         HIP_TRY(s->dev.d_counters.reserve(80 * sizeof(unsigned long long)));
         s->view.stack_overflows = s->dev.d_counters.get<unsigned long long>() + 7;
+        s->pleaf_box = std::move(pleaf_box);
+        s->tree_raw = std::move(tree_raw);
         s->device = device;
         s->committed = true;
         return RPT_OK;
@@ -2338,6 +2367,7 @@ extern "C++" int rpti::prepare_render(rpt_scene* s, hipStream_t st, const rpt_ca
     uint32_t shard_count = prm->shard_count == 0 ? 1 : prm->shard_count;
     if (prm->shard_rank >= shard_count) return fail(RPT_ERR_INVALID, "shard_rank >= shard_count");
     HIP_TRY(hipSetDevice(s->device));
+    if (int rc = rpti::wait_for_move(s, st)) return rc;   // (a scene whose spheres have moved: this pass reads what the move wrote)
 
     a.sc = s->view;
     a.cam = camera_g(cam);
@@ -4171,6 +4201,7 @@ int rpt_intersect_batch(rpt_scene* s, uint64_t n, const float* origins, const fl
     HIP_TRY(hook_scratch(d_obj, n * 4));
     HIP_TRY(hipMemcpy(d_o.get(), origins, n * 12, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_d.get(), dirs, n * 12, hipMemcpyHostToDevice));
+    if (int rc = rpti::wait_for_move(s, nullptr)) return rc;
     HIP_TRY(launch_intersect(s->view, n, d_o.get<float>(), d_d.get<float>(), d_t.get<float>(), d_obj.get<int32_t>(), d_n.get<float>(),
                              s->view.n_nodes != 0, nullptr));
     HIP_TRY(hipMemcpy(t, d_t.get(), n * 4, hipMemcpyDeviceToHost));
@@ -4196,6 +4227,7 @@ int rpt_intersect_segments(rpt_scene* s, uint64_t n, const float* origins, const
     HIP_TRY(hipMemcpy(d_o.get(), origins, n * 12, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_d.get(), dirs, n * 12, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_m.get(), t_max, n * 4, hipMemcpyHostToDevice));
+    if (int rc = rpti::wait_for_move(s, nullptr)) return rc;
     HIP_TRY(launch_intersect_segments(s->view, n, d_o.get<float>(), d_d.get<float>(), d_m.get<float>(), d_t.get<float>(), d_c.get<uint32_t>(), nullptr));
     HIP_TRY(hipMemcpy(t, d_t.get(), n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(code, d_c.get(), n * 4, hipMemcpyDeviceToHost));
@@ -4285,6 +4317,7 @@ int rpt_debug_light_sample(rpt_scene* s, uint32_t light, uint64_t n, const float
     if (n == 0) return RPT_OK;
     if (n > 0xFFFFFFFFull) return fail(RPT_ERR_INVALID, "rpt_debug_light_sample: the case number keys a 32-bit stream field");
     HIP_TRY(hipSetDevice(s->device));
+    if (int rc = rpti::wait_for_move(s, nullptr)) return rc;   // (the hook launches on the null stream: behind the last move of the scene's spheres)
     rpti::DevMem d_pos, d_out;   // d_out: v, nrm, intensity, wi (3 n each), pdf, dist, next_word (n each)
     HIP_TRY(hook_scratch(d_pos, n * 12));
     HIP_TRY(hook_scratch(d_out, n * 60));
@@ -4315,6 +4348,7 @@ int rpt_debug_env_color(rpt_scene* s, uint64_t n, const float* dirs, float* rgb)
     if (!launch_debug_env_color) return fail(RPT_ERR_UNSUPPORTED, "rpt_debug_env_color: built without the kernels");
     if (n == 0) return RPT_OK;
     HIP_TRY(hipSetDevice(s->device));
+    if (int rc = rpti::wait_for_move(s, nullptr)) return rc;   // (the hook launches on the null stream: behind the last move of the scene's spheres)
     rpti::DevMem d_d, d_c;
     HIP_TRY(hook_scratch(d_d, n * 12));
     HIP_TRY(hook_scratch(d_c, n * 12));
@@ -4332,6 +4366,7 @@ int rpt_debug_medium_distance(rpt_scene* s, uint64_t n, uint64_t seed, float* dm
     if (n == 0) return RPT_OK;
     if (n > 0xFFFFFFFFull) return fail(RPT_ERR_INVALID, "rpt_debug_medium_distance: the case number keys a 32-bit stream field");
     HIP_TRY(hipSetDevice(s->device));
+    if (int rc = rpti::wait_for_move(s, nullptr)) return rc;   // (the hook launches on the null stream: behind the last move of the scene's spheres)
     rpti::DevMem d_m, d_t;
     HIP_TRY(hook_scratch(d_m, n * 4));
     HIP_TRY(hook_scratch(d_t, n * 4));
@@ -4351,6 +4386,7 @@ int rpt_debug_shadow_test(rpt_scene* s, uint32_t light, uint64_t n, const float*
     if (!launch_debug_shadow_test) return fail(RPT_ERR_UNSUPPORTED, "rpt_debug_shadow_test: built without the kernels");
     if (n == 0) return RPT_OK;
     HIP_TRY(hipSetDevice(s->device));
+    if (int rc = rpti::wait_for_move(s, nullptr)) return rc;   // (the hook launches on the null stream: behind the last move of the scene's spheres)
     rpti::DevMem d_in, d_out;   // d_in: origins, dirs (3 n each), dist (n); d_out: flag, t (n each)
     HIP_TRY(hook_scratch(d_in, n * 28));
     HIP_TRY(hook_scratch(d_out, n * 8));

@@ -166,6 +166,30 @@ int rpt_particles_display_positions(rpt_particles* h, double* out) {
     RPTI_HIP_TRY(hipMemcpy(out, h->d_disp.get(), size_t(a.n) * 3 * sizeof(double), hipMemcpyDeviceToHost));
     return RPT_OK;
 }
+int rpt_particles_display_positions_device(rpt_particles* h, void** d_out, void* hip_stream) {
+    if (!d_out) return fail(RPT_ERR_INVALID, "null output");
+    if (!h) return fail(RPT_ERR_INVALID, "null particle system");
+    if (h->prm.kind != RPT_PARTICLES_MARBLES) return fail(RPT_ERR_UNSUPPORTED, "display positions are defined for a marbles system only");
+    if (!launch_particles_display) return fail(RPT_ERR_UNSUPPORTED, "rpt_particles_display_positions_device: built without the kernels");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    RPTI_HIP_TRY(hipSetDevice(h->device));
+    if (h->used) RPTI_HIP_TRY(hipStreamWaitEvent(st, h->done.get(), 0));
+    h->used = true;
+    ParticlesArgs a{};
+    a.kind = h->prm.kind;
+    a.n = h->prm.n;
+    a.radius = h->prm.radius;
+    a.height = h->prm.height;
+    a.pos = h->d_pos.get<double>();
+    a.vel = h->d_vel.get<double>();
+    const hipError_t e = launch_particles_display(a, h->d_disp.get<double>(), st);
+    if (e == hipSuccess) h->launches++;
+    const hipError_t er = hipEventRecord(h->done.get(), st);   // (after a failed launch too, as rpt_particles_integrate)
+    RPTI_HIP_TRY(e);
+    RPTI_HIP_TRY(er);
+    *d_out = h->d_disp.get();
+    return RPT_OK;
+}
 int rpt_particles_counters(rpt_particles* h, uint64_t out[8]) {
     if (!out) return fail(RPT_ERR_INVALID, "null output");
     if (!h) return fail(RPT_ERR_INVALID, "null particle system");
@@ -354,6 +378,23 @@ int rpt_particles_batch_display_positions(rpt_particles_batch* b, double* out) {
     RPTI_HIP_TRY(launch_particles_batch_display(batch_args(b), b->d_disp.get<double>(), nullptr));
     b->launches++;
     RPTI_HIP_TRY(hipMemcpy(out, b->d_disp.get(), size_t(b->total) * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+int rpt_particles_batch_display_positions_device(rpt_particles_batch* b, void** d_out, void* hip_stream) {
+    if (!d_out) return fail(RPT_ERR_INVALID, "null output");
+    if (!b) return fail(RPT_ERR_INVALID, "null particle ensemble");
+    if (!b->all_marbles) return fail(RPT_ERR_UNSUPPORTED, "display positions are defined for marbles systems only");
+    if (!launch_particles_batch_display) return fail(RPT_ERR_UNSUPPORTED, "rpt_particles_batch_display_positions_device: built without the kernels");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    RPTI_HIP_TRY(hipSetDevice(b->device));
+    if (b->used) RPTI_HIP_TRY(hipStreamWaitEvent(st, b->done.get(), 0));
+    b->used = true;
+    const hipError_t e = launch_particles_batch_display(batch_args(b), b->d_disp.get<double>(), st);
+    if (e == hipSuccess) b->launches++;
+    const hipError_t er = hipEventRecord(b->done.get(), st);
+    RPTI_HIP_TRY(e);
+    RPTI_HIP_TRY(er);
+    *d_out = b->d_disp.get();
     return RPT_OK;
 }
 int rpt_particles_batch_counters(rpt_particles_batch* b, uint64_t* out) {

@@ -2,6 +2,7 @@
 // options, the host scene store, rpt_scene and rpt_buffer, and the render machinery rpt_capi.cpp defines for the other two.
 // Not for kernels.h / kernels.hip: the scan JIT compiles those.
 #pragma once
+#include <array>
 #include <functional>
 #include <memory>
 #include <string>
@@ -55,6 +56,8 @@ struct rpt_options {
     int64_t scene_bvh_min = 64;     // bounded primitives + BVH meshes from which the scene-level BVH is built
     int64_t scene_tree_meshes = 0;  // 1: meshes with trees of their own are leaves of the scene tree (every query walks to completion);
                                     // 0: they stay outside it and their walks are parked as in scenes without a scene tree (read by rpt_scene_commit)
+    int64_t refit_per_height = 0;   // rpt_scene_move_spheres*: the scene tree's refit as one launch per height (1) instead of one workgroup that walks the
+                                    // heights with a barrier between two (0, the measured default: DESIGN.md section 4, "Moving spheres"); same boxes
     int64_t f64_cull = 1;           // reference-epsilon mode: 1 = a lane evaluates only the objects whose fp32 box its ray can reach (same bits), 0 = every object;
                                     // 2 = as 1, and the counters build keeps the search limits as well (its counters then describe the schedule, not the reference's work)
     int64_t f64_mesh_tree_min = 64; // reference-epsilon mode: triangles from which a mesh gets a candidate tree (read by rpt_scene_commit; 0 = never, 1 = every mesh;
@@ -148,6 +151,24 @@ struct rpt_scene {
         // "timing": an event triple (before render, after render, after resolve) per launch, in a ring; nothing waits
         // for them until rpt_get_timing / rpt_get_timing_mean is called
         std::vector<rpti::Event> evs;
+        // Movable spheres (rpt_scene_set_movable_spheres; rpt_scene_update.cpp): the tables of scene_update.h on the device, and the
+        // event recorded after the kernels of the last move -- every later pass of the scene on another stream waits for it
+        // (wait_for_move), as the move itself waits for the passes queued before it.
+        struct Movable {
+            bool set = false;
+            uint32_t n = 0;
+            std::vector<uint32_t> objects;          // as listed
+            rpti::DevMem d_table, d_item_box, d_groups, d_entries, d_raw, d_order, d_centres, d_offsets, d_motion;
+            uint32_t n_groups = 0, n_tree = 0, n_heights = 0;
+            std::vector<uint32_t> height_first;     // n_heights + 1 values
+            rpti::Event done;
+            bool used = false;                      // `done` has been recorded
+            hipStream_t stream = nullptr;           // ... on this stream
+            uint64_t moves = 0;
+        } mov;
+        // Where the spheres of an earlier list were when that list was replaced (by object): the next list starts from these
+        // centres, not from the committed matrices, whether it names the sphere again or leaves it where it was moved to.
+        std::unordered_map<uint32_t, std::array<double, 3>> moved_centres;
     } dev;
     int cur_set = 0;
     uint64_t last_counters[64] = {0};  // [0..7] counters, [8..63] diagnostic trip stamps
@@ -162,6 +183,10 @@ struct rpt_scene {
     uint64_t stats[16] = {0};
     rpti::ScanJit jit;   // the specialised render kernel of this scene, if any (option "scan_jit")
     void* photon = nullptr;  // PhotonMapDev*, owned by photon.hip
+    bool photon_stale = false;   // spheres have moved since the map was built (rpt_scene_move_spheres*): the camera pass refuses it
+    // The commit's record of its scene tree on the host, for a refit (rpt_scene_set_movable_spheres): per entry of pleaf the item's own
+    // box (lo, hi), per child entry of a scene-tree node (2 x local node + side) the bounds of the items below it before padding.
+    std::vector<float> pleaf_box, tree_raw;
     // reference-epsilon mode (option "epsilon_policy" = 1 at commit): the fp64 scene of kernels_f64.hip in dev.arena64
     rpt64::Scene view64{};
     double medium_color64[3] = {0, 0, 0}, medium_color_hi64[3] = {0, 0, 0};
@@ -231,6 +256,13 @@ struct PersistentLaunch {
 // Zeroes the queue / sharded frame, calls `launch` with a persistent grid, then resolves the slab into d_out.
 int run_persistent(rpt_scene* s, const rpt_render_params* prm, const rptg::RenderArgs& a, double* d_out, hipStream_t st, const PersistentLaunch& pl);
 int serialize_with_other_streams(rpt_scene* s, hipStream_t st);  // for launches with per-scene scratch outside the launch set
+// A pass that reads the scene's records on `st` follows the last move of its spheres (rpt_scene_move_spheres_device), whatever
+// stream that ran on.  Nothing to do for a scene that has not moved.
+inline int wait_for_move(rpt_scene* s, hipStream_t st) {
+    const auto& m = s->dev.mov;
+    if (m.used && m.stream != st) RPTI_HIP_TRY(hipStreamWaitEvent(st, m.done.get(), 0));
+    return RPT_OK;
+}
 int fetch_counters(rpt_scene* s, const rptg::RenderArgs& a);  // the fp32 kernels' counters, after the stream has been synchronised
 double* scratch_out(rpt_scene* s, size_t bytes);  // cached device frame for the host-buffer entry points
 // photon.hip

@@ -137,6 +137,13 @@ class ParticleSimulator:
         _lib.check(_lib.load().rpt_particles_display_positions(self._h, _vp(out)))
         return out
 
+    def display_positions_device(self, stream=None):
+        """The display positions left in the simulator's own device array: its address (n x 3 doubles, valid until close()).
+        Asynchronous on `stream`, ordered like integrate."""
+        d = C.c_void_p()
+        _lib.check(_lib.load().rpt_particles_display_positions_device(self._h, C.byref(d), C.c_void_p(stream)))
+        return d.value
+
     def counters(self):
         """Derivative evaluations, pair contacts, surface band / push, table band / push, launches, 0."""
         out = (C.c_uint64 * 8)()
@@ -212,6 +219,13 @@ class ParticleEnsemble:
         out = np.zeros((int(self.first[-1]), 3))
         _lib.check(_lib.load().rpt_particles_batch_display_positions(self._h, _vp(out)))
         return self._split(out)
+
+    def display_positions_device(self, stream=None):
+        """Every system's display positions left in the ensemble's own device array, the systems concatenated: its address
+        (sum(n) x 3 doubles, valid until close()).  Asynchronous on `stream`, ordered like integrate."""
+        d = C.c_void_p()
+        _lib.check(_lib.load().rpt_particles_batch_display_positions_device(self._h, C.byref(d), C.c_void_p(stream)))
+        return d.value
 
     def counters(self):
         """One list of eight per system: ParticleSimulator.counters' slots, launches counted for the ensemble."""

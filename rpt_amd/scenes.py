@@ -441,3 +441,71 @@ def marbles_field_sequence(frames, grid=(2, 2), spacing=3.0, time=1.0 / 16.0, st
             yield scene, camera
     finally:
         sim.close()
+
+
+class MarblesMover:
+    """What Renderer.render_sequence(cameras, live=...) drives: the marbles of a scene that was committed once follow a particle
+    simulation without leaving the device.  step(f) chains display_positions_device -> Scene.move_spheres_device (the motion table is
+    written by the same kernel) and queues the integration of the next frame, as the generators do; it returns the device address of
+    the motion table.  close() frees the simulation (the scene belongs to the caller)."""
+
+    def __init__(self, scene, sim, objects, frames, time, step, offsets=None, device=0):
+        from .api import _device_copy, _sync
+        identity = np.zeros(24)
+        identity[[0, 5, 10, 12, 16, 20]] = 1.0
+        self.scene, self.sim, self.frames, self.time, self.dt = scene, sim, int(frames), float(time), float(step)
+        scene.set_movable_spheres(objects, device)
+        self._offsets = _device_copy(offsets, device) if offsets is not None else None
+        self._table = _device_copy(np.tile(identity, (len(scene.objects), 1)), device)   # the kernel rewrites the listed rows
+        _sync(device)
+        if self.frames > 1:
+            sim.integrate(self.time, self.dt)   # (asynchronous: the caller renders frame 0 meanwhile)
+
+    def step(self, f):
+        d = self.sim.display_positions_device()
+        self.scene.move_spheres_device(d, self._offsets.data_ptr() if self._offsets is not None else 0, self._table.data_ptr())
+        if f + 1 < self.frames:
+            self.sim.integrate(self.time, self.dt)
+        return self._table.data_ptr()
+
+    def close(self):
+        self.sim.close()
+
+
+def marbles_live(frames, device=0, state=None, **kw):
+    """marbles_sequence without the per-frame scenes: (scene, camera, mover).  The scene is frame 0's, committed once to `device`;
+    Renderer(scene, camera).render_sequence(cameras, live=mover) renders the frames marbles_sequence(frames) would give, byte for
+    byte, with the marbles moved on the device.  mover.close() when done."""
+    from .ode import MarblesSystem, ParticleSimulator
+    sim = ParticleSimulator(MarblesSystem(MARBLES_RADIUS), marbles_initial() if state is None else state, device=device)
+    try:
+        scene, camera, _ = marbles(sim.display_positions(), **kw)
+        n = sim.n
+        return scene, camera, MarblesMover(scene, sim, np.arange(1, 1 + n), frames, 1.0 / 16.0, 1.0 / 10000.0, device=device)
+    except Exception:
+        sim.close()
+        raise
+
+
+def marbles_field_live(frames, grid=(2, 2), spacing=3.0, time=1.0 / 16.0, step=1.0 / 10000.0, device=0, states=None, **kw):
+    """marbles_field_sequence without the per-frame scenes, as marbles_live is for marbles_sequence: (scene, camera, mover).  The
+    glasses' offsets are added on the device, one rounded add per component, as the generator adds them in numpy."""
+    from .ode import MarblesSystem, ParticleEnsemble
+    offsets = marbles_field_offsets(grid, spacing)
+    if states is None:
+        states = [marbles_initial(seed=123 + g) for g in range(len(offsets))]
+    if len(states) != len(offsets):
+        raise ValueError(f"{len(states)} states for {len(offsets)} glasses")
+    sim = ParticleEnsemble([MarblesSystem(MARBLES_RADIUS)] * len(offsets), states, device=device)
+    try:
+        shown = [p + np.array([ox, 0.0, oz]) for p, (ox, oz) in zip(sim.display_positions(), offsets)]
+        scene, camera, _ = marbles_field(shown, offsets, **kw)
+        objects, shifts, at = [], [], 0   # objects: per glass the glass, then its marbles
+        for size, (ox, oz) in zip(sim.sizes, offsets):
+            objects += list(range(at + 1, at + 1 + size))
+            shifts += [[ox, 0.0, oz]] * size
+            at += 1 + size
+        return scene, camera, MarblesMover(scene, sim, np.array(objects), frames, time, step, offsets=np.array(shifts), device=device)
+    except Exception:
+        sim.close()
+        raise
