@@ -73,6 +73,8 @@ def lib():
         L.orc_render.argtypes = [P, C.POINTER(CameraDesc), C.POINTER(Params), C.c_uint32, C.c_uint64, C.c_uint32, P,
                                  C.c_int, C.POINTER(Counters), P, C.c_uint64]
         L.orc_intersect.argtypes = [P, C.c_uint64, P, P, C.c_int, P, P, P]
+        L.orc_render_paths.restype = C.c_uint64
+        L.orc_render_paths.argtypes = [P, C.POINTER(CameraDesc), C.POINTER(Params), C.c_uint64, C.c_uint32, P, C.c_int, P, P, C.c_uint64]
         L.orc_shape_intersect.argtypes = [C.POINTER(ShapeDesc), D, D, C.c_double, C.c_double, D, D, C.c_int]
         L.orc_mesh_kd_vs_brute.argtypes = [C.POINTER(ShapeDesc), C.c_uint64, P, P, P]
         L.orc_mesh_kd_vs_brute.restype = C.c_int64
@@ -223,6 +225,7 @@ class OracleScene:
             else:
                 L.orc_add_light(self.h, l.kind, _d3(l.color), _d3(l.vec if l.vec is not None else np.zeros(3)), None,
                                 None, -1)
+        self.n_lights = len(scene.lights)
         for m in scene.media:
             L.orc_add_medium(self.h, m.kind, m.absorption, m.scattering)
         if getattr(scene.environment, "hdri", None) is not None:
@@ -249,6 +252,29 @@ class OracleScene:
                      sample_offset, out.ctypes.data_as(C.c_void_p), threads, C.byref(cnt) if counters else None,
                      pl.ctypes.data_as(C.c_void_p) if pl is not None else None, npix)
         return (out, cnt.as_dict()) if counters else out
+
+    PATH_LEVELS = 16
+    PATH_END = ("miss", "roulette or max_bounces", "no sample")
+    PATH_MEDIUM_EVENT, PATH_FAR_MISS, PATH_OVERFLOW = 1, 2, 4
+    PATH_DTYPE = np.dtype([("sig", np.uint64), ("clamp", np.uint64), ("depth", np.uint32), ("end", np.uint32), ("flags", np.uint32),
+                           ("levels", np.uint32), ("d", np.float64, (16, 3)), ("k", np.float64, (16, 3))])
+
+    def render_paths(self, camera, width, height, max_bounces, seed=0, sample_offset=0, exposure_value=0.0, robust=0, threads=None):
+        """render(iterations=1) with what happened on each path (PathRecord in rpt_oracle.cpp) -> (h*w, 3) radiance of the streams
+        (seed, pixel, sample_offset), a structured array of PATH_DTYPE per pixel, and per light the number of vertices at which its
+        shadow test passed."""
+        from rpt_amd.api import camera_desc
+        p = Params(width, height, exposure_value, max_bounces, robust)
+        n = width * height
+        out = np.zeros((n, 3), dtype=np.float64)
+        rec = np.zeros(n, dtype=self.PATH_DTYPE)
+        lights = np.zeros(max(self.n_lights, 1), dtype=np.uint64)
+        if threads is None:
+            threads = os.cpu_count() or 1
+        size = lib().orc_render_paths(self.h, C.byref(camera_desc(camera, CameraDesc)), C.byref(p), C.c_uint64(seed), sample_offset,
+                                      _vp(out), threads, _vp(rec), _vp(lights), self.n_lights)
+        assert size == self.PATH_DTYPE.itemsize
+        return out, rec, lights[:self.n_lights]
 
     def intersect(self, origins, dirs, robust=0):
         o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)

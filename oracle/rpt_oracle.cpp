@@ -209,6 +209,61 @@ struct Counters {
 static thread_local Counters* tl_cnt = nullptr;
 #define CNT(field) do { if (tl_cnt) tl_cnt->field++; } while (0)
 
+// ------------------------------------------------------------------ what happened on a camera path (orc_render_paths)
+// One record per camera sample, written beside the radiance through a thread-local pointer as the counters are: trace_ray keeps its
+// text and its arithmetic, the REC_* lines only look on.  Level = num_bounces of the trace_ray call.
+//   depth   the deepest level reached
+//   end     how the last call ended: a miss, the roulette or the max_bounces rule, or a material that gave no sample
+//   sig     a hash of the vertex sequence: per vertex the object index (or "medium event" / "miss beyond the background distance" /
+//           "miss before it"), and per vertex the lights whose shadow test passed, in order
+//   clamp   3 bits per level (x, y, z from bit 3 * level): the channels in which fmin(indirect, FIREFLY_CLAMP) took the clamp
+//   flags   PATH_MEDIUM_EVENT, PATH_FAR_MISS, PATH_OVERFLOW (levels >= PATH_LEVELS were reached; d and k hold the first PATH_LEVELS only)
+//   d, k    per level: the radiance the call adds itself (emission, lights, or the environment on a miss) and the factor on what its
+//           recursive call returns (the weighing of unit radiance; 0 where the path ended), so that
+//           radiance(level) = d + min(k * radiance(level + 1), clamp) can be restated with another clamp.
+static const int PATH_LEVELS = 16;
+enum { PATH_END_MISS = 0, PATH_END_STOP = 1, PATH_END_NO_SAMPLE = 2 };
+enum { PATH_MEDIUM_EVENT = 1, PATH_FAR_MISS = 2, PATH_OVERFLOW = 4 };
+enum { PATH_V_MEDIUM = 0xFFFFFF01u, PATH_V_FAR_MISS = 0xFFFFFF02u, PATH_V_NEAR_MISS = 0xFFFFFF03u, PATH_V_LIGHT = 0xFFFF0000u };
+struct PathRecord {
+    uint64_t sig, clamp;
+    uint32_t depth, end, flags, levels;
+    double d[PATH_LEVELS][3], k[PATH_LEVELS][3];
+};
+struct PathRecorder {
+    PathRecord* rec = nullptr;          // the sample being traced
+    std::vector<uint64_t> light_pass;   // per light: vertices at which its shadow test passed
+    void begin(PathRecord* r) {
+        rec = r;
+        std::memset(r, 0, sizeof *r);
+        r->sig = 0xcbf29ce484222325ull;
+        r->end = PATH_END_STOP;
+    }
+    void mix(uint32_t what) { rec->sig = (rec->sig ^ what) * 0x100000001b3ull; }
+    void vertex(uint32_t level, uint32_t what) {
+        mix(what);
+        rec->depth = std::max(rec->depth, level);
+        rec->levels = std::max(rec->levels, level + 1);
+        rec->end = PATH_END_STOP;   // (until the call says otherwise)
+        if (what == PATH_V_MEDIUM) rec->flags |= PATH_MEDIUM_EVENT;
+        if (what == PATH_V_FAR_MISS) rec->flags |= PATH_FAR_MISS;
+        if (level >= uint32_t(PATH_LEVELS)) rec->flags |= PATH_OVERFLOW;
+    }
+    void light(size_t index) {
+        mix(PATH_V_LIGHT | uint32_t(index));
+        if (index < light_pass.size()) light_pass[index]++;
+    }
+    void set(double (*a)[3], uint32_t level, double x, double y, double z) {
+        if (level < uint32_t(PATH_LEVELS)) { a[level][0] = x; a[level][1] = y; a[level][2] = z; }
+    }
+    void clamped(uint32_t level, double x, double y, double z, double c) {
+        uint64_t m = uint64_t(!(x <= c)) | uint64_t(!(y <= c)) << 1 | uint64_t(!(z <= c)) << 2;
+        if (level < 21) rec->clamp |= m << (3 * level);
+    }
+};
+static thread_local PathRecorder* tl_rec = nullptr;
+#define REC(call) do { if (tl_rec && tl_rec->rec) tl_rec->call; } while (0)
+
 // ------------------------------------------------------------------ shape.rs
 struct Ray {  // src/shape.rs:50-72
     V3 origin, dir;
@@ -923,7 +978,10 @@ static Ray jittered_ray(const Camera& camera, double xn, double yn, double dim, 
 static bool bounce_surface_sample(const Material& material, const V3& normal, const V3& wo, double rr_p, uint32_t num_bounces,
                                   uint32_t max_bounces, Rng& rng, V3& wi, double& pdf, V3& f) {
     if (rr_p > 0.0 ? !(rng.uniform() < rr_p) : !(num_bounces < max_bounces)) return false;
-    if (!sample_f(material, normal, wo, rng, wi, pdf)) return false;
+    if (!sample_f(material, normal, wo, rng, wi, pdf)) {
+        REC(rec->end = PATH_END_NO_SAMPLE);
+        return false;
+    }
     f = bsdf(material, normal, wo, wi);
     return true;
 }
@@ -1001,6 +1059,7 @@ struct Renderer {
             pass = (obj == light.twin) && std::fabs(h.time - dist_to_light) <= 1e-3 * dist_to_light;
         }
         if (pass) CNT(shadow_pass);
+        if (pass) REC(light(size_t(&light - scene.lights.data())));
         return pass;
     }
     // src/renderer.rs:362-409
@@ -1058,16 +1117,29 @@ struct Renderer {
                 const double background_dist = 400.0;
                 surface_color = (d >= background_dist) ? scene.env_color(ray.dir) : V3(0, 0, 0);
                 max_dist = background_dist;
+                if (d >= background_dist) {
+                    REC(vertex(num_bounces, PATH_V_FAR_MISS));
+                    REC(rec->end = PATH_END_MISS);
+                    REC(set(tl_rec->rec->d, num_bounces, surface_color.x, surface_color.y, surface_color.z));
+                } else {
+                    REC(mix(PATH_V_NEAR_MISS));
+                }
             } else {
                 if (d >= h.time) {
                     V3 world_pos = ray.at(h.time);
                     const Material& material = scene.objects[oi].material;
+                    REC(vertex(num_bounces, uint32_t(oi)));
                     V3 color = (num_bounces == 0) ? material.color() * material.emittance() : V3(0, 0, 0);
                     color = color + sample_lights(material, world_pos, h.normal, wo, rng);
+                    REC(set(tl_rec->rec->d, num_bounces, color.x, color.y, color.z));
                     V3 wi, f;
                     double pdf;
                     if (bounce_surface_sample(material, h.normal, wo, rr_p, num_bounces, p.max_bounces, rng, wi, pdf, f)) {
                         Ray nr{world_pos, wi};
+                        if (tl_rec && tl_rec->rec) {
+                            V3 k = bounce_surface_weigh(f, pdf, rr_p, wi, h.normal, V3(1, 1, 1));
+                            tl_rec->set(tl_rec->rec->k, num_bounces, k.x, k.y, k.z);
+                        }
                         color = color + bounce_surface_weigh(f, pdf, rr_p, wi, h.normal, trace_ray(nr, num_bounces + 1, rng));
                     }
                     surface_color = color;
@@ -1078,12 +1150,18 @@ struct Renderer {
                 V3 collision = ray.at(d);
                 double emm = medium.emission(collision);
                 V3 medium_color = medium.color(collision);
+                REC(vertex(num_bounces, PATH_V_MEDIUM));
                 V3 color = (num_bounces == 0) ? emm * medium_color : V3(0, 0, 0);
                 color = color + sample_lights_for_media(medium, collision, wo, rng);
+                REC(set(tl_rec->rec->d, num_bounces, color.x, color.y, color.z));
                 V3 wi;
                 double ph_p;
                 if (bounce_medium_sample(medium, wo, rr_p, rng, wi, ph_p)) {
                     Ray nr{collision, wi};
+                    if (tl_rec && tl_rec->rec) {
+                        V3 k = bounce_medium_weigh(medium, collision, wo, wi, ph_p, rr_p, V3(1, 1, 1));
+                        tl_rec->set(tl_rec->rec->k, num_bounces, k.x, k.y, k.z);
+                    }
                     color = color + bounce_medium_weigh(medium, collision, wo, wi, ph_p, rr_p, trace_ray(nr, num_bounces + 1, rng));
                 }
                 return color;
@@ -1092,17 +1170,33 @@ struct Renderer {
         }
         HitRecord h;
         int oi;
-        if (!get_closest_hit(ray, h, oi)) return scene.env_color(ray.dir);
+        if (!get_closest_hit(ray, h, oi)) {
+            if (tl_rec && tl_rec->rec) {
+                V3 env = scene.env_color(ray.dir);
+                tl_rec->vertex(num_bounces, PATH_V_FAR_MISS);
+                tl_rec->rec->flags &= ~uint32_t(PATH_FAR_MISS);   // (the flag is for a scene with a medium)
+                tl_rec->rec->end = PATH_END_MISS;
+                tl_rec->set(tl_rec->rec->d, num_bounces, env.x, env.y, env.z);
+            }
+            return scene.env_color(ray.dir);
+        }
         V3 world_pos = ray.at(h.time);
         const Material& material = scene.objects[oi].material;
+        REC(vertex(num_bounces, uint32_t(oi)));
         V3 wo = -normalize(ray.dir);
         V3 color = (num_bounces == 0) ? material.color() * material.emittance() : V3(0, 0, 0);
         color = color + sample_lights(material, world_pos, h.normal, wo, rng);
+        REC(set(tl_rec->rec->d, num_bounces, color.x, color.y, color.z));
         V3 wi, f;
         double pdf;
         if (bounce_surface_sample(material, h.normal, wo, 0.0, num_bounces, p.max_bounces, rng, wi, pdf, f)) {
             Ray nr{world_pos, wi};
+            if (tl_rec && tl_rec->rec) {
+                V3 k = bounce_surface_weigh(f, pdf, 0.0, wi, h.normal, V3(1, 1, 1));
+                tl_rec->set(tl_rec->rec->k, num_bounces, k.x, k.y, k.z);
+            }
             V3 indirect = bounce_surface_weigh(f, pdf, 0.0, wi, h.normal, trace_ray(nr, num_bounces + 1, rng));
+            REC(clamped(num_bounces, indirect.x, indirect.y, indirect.z, FIREFLY_CLAMP));
             // f64::min returns the non-NaN operand (src/renderer.rs:311-313)
             color.x += std::fmin(indirect.x, FIREFLY_CLAMP);
             color.y += std::fmin(indirect.y, FIREFLY_CLAMP);
@@ -1777,6 +1871,44 @@ int orc_render(orc_scene* s, const orc_camera* cam, const orc_params* prm, uint3
                                  tot.vertices, tot.self_hits, tot.shadow_tests, tot.shadow_pass, tot.shadow_near};
     }
     return 0;
+}
+
+// orc_render with one iteration (pixel p of out_rgb is the radiance of stream (seed, p, sample_offset)) and, beside it, what happened
+// on each path: records[p] is a PathRecord (its size is returned, for the caller to check its own layout against) and light_pass[l]
+// (n_lights of them, may be null) counts the vertices at which light l passed its shadow test.  The radiance is orc_render's, bit for bit.
+uint64_t orc_render_paths(orc_scene* s, const orc_camera* cam, const orc_params* prm, uint64_t seed, uint32_t sample_offset,
+                          double* out_rgb, int threads, void* records, uint64_t* light_pass, uint64_t n_lights) {
+    RenderParams rp{prm->width, prm->height, prm->exposure_value, prm->max_bounces, prm->robust};
+    Renderer r{s->scene, make_camera(cam), rp};
+    if (threads < 1) threads = 1;
+    PathRecord* recs = static_cast<PathRecord*>(records);
+    std::vector<PathRecorder> recorders(threads);
+    for (auto& pr : recorders) pr.light_pass.assign(s->scene.lights.size(), 0);
+    std::atomic<uint32_t> next(0);
+    auto work = [&](int tid) {
+        tl_rec = &recorders[tid];
+        for (;;) {
+            uint32_t y = next.fetch_add(1);
+            if (y >= prm->height) break;
+            for (uint32_t x = 0; x < prm->width; x++) {
+                size_t i = size_t(y) * prm->width + x;
+                tl_rec->begin(&recs[i]);
+                V3 c = r.get_color(x, y, 1, seed, sample_offset);
+                out_rgb[3 * i] = c.x; out_rgb[3 * i + 1] = c.y; out_rgb[3 * i + 2] = c.z;
+            }
+        }
+        tl_rec->rec = nullptr;
+        tl_rec = nullptr;
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < threads; t++) pool.emplace_back(work, t);
+    work(0);
+    for (auto& t : pool) t.join();
+    for (uint64_t l = 0; light_pass && l < n_lights; l++) {
+        light_pass[l] = 0;
+        for (auto& pr : recorders) light_pass[l] += l < pr.light_pass.size() ? pr.light_pass[l] : 0;
+    }
+    return sizeof(PathRecord);
 }
 
 // get_closest_hit over n rays; t = +inf and obj = -1 on a miss.  robust selects the t_min policy.

@@ -634,3 +634,20 @@ def test_material_cases_flag_few_random_cases_and_only_named_structured_ones():
         for sample in mc.SAMPLES:
             flagged, cands = mc.lens_flags(w, h, sample)
             assert not flagged.any() and cands.max() > (1 if w * h > 1 else 0)
+
+
+# ---- the path recorder only looks on (orc_render_paths; tests/path_cloud.py)
+@pytest.mark.parametrize("fog", [None, "fog"])
+@pytest.mark.parametrize("robust", [0, 1])
+def test_path_records_leave_the_radiance_bit_identical(fog, robust):
+    from tests import path_cloud as pc
+    sc, cam, mb = pc.clamp(fog, torus=True)
+    orc = OracleScene(sc)
+    for off in (0, 3):
+        plain, cnt = orc.render(cam, 48, 48, 1, mb, seed=6, sample_offset=off, robust=robust, counters=True)
+        rad, rec, light_pass = orc.render_paths(cam, 48, 48, mb, seed=6, sample_offset=off, robust=robust, threads=3)
+        assert np.array_equal(rad.view(np.uint64), plain.view(np.uint64))
+        # and the record counts what the counters count: one level per trace_ray call, the shadow passes
+        assert light_pass.sum() == cnt["shadow_pass"] and cnt["samples"] == len(rec)
+        assert rec["levels"].sum() == cnt["vertices"]
+        assert (rec["clamp"] != 0).sum() >= (150 if fog is None else 0) and ((rec["clamp"] != 0).sum() == 0 or fog is None)
